@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of taper's training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, or self-spawned)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run, or self-spawned)
 
 A "step" is one pass of the hot path over one batch of synthetic MNIST-shaped
 input already resident in HBM: gather batch -> forward -> softmax cross-entropy
@@ -11,9 +11,16 @@ kernels of libtaper_hip.so through the C ABI).  Headline workload at N = 1 =
 BASELINE.json configs[1]: MLP 784-128-10, batch 64, Adam(1e-3, wd 1e-4); at N > 1 = configs[3]: the same MLP at
 128 rows per GPU (global 1024 at N = 8), with the single-GPU figure of the same per-GPU batch printed beside it.
 
-Prints ONE JSON line (rank 0) with the BASELINE metric plus `roofline` (the
-dominant kernel timed live with HIP events), `cpu_baseline` (the C restatement of the reference's CPU path, timed on
-this box's host cores) and, at N = 1, `workloads`: the other BASELINE configs (both CNNs at batch 256, the example
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line (rank 0) with the BASELINE metric
+(`value`, `ms_per_step` = milliseconds of one timed step); nothing else is measured.
+
+--dump-outputs DIR: after the timed steps, what the last of them computed -- the step's loss and hit count and every
+parameter after its Adam update, as float32 DIR/<name>.npy (rank 0).  The inputs are seeded: the same arguments give
+the same inputs, so two builds can be compared output for output.
+
+--full adds everything else to the line: `roofline` (the dominant kernel timed live with HIP events), `sustained`,
+the batch sweeps, `cpu_baseline` (the C restatement of the reference's CPU path, timed on the host's cores), the
+data-parallel figures and, at N = 1, `workloads`: the other BASELINE configs (both CNNs at batch 256, the example
 MLP, the 4096-wide Linear stack and the 4096^3 sgemm variants), each with its step time, per-kernel roofline
 fractions and its own CPU baseline.
 """
@@ -183,13 +190,15 @@ def replicas_identical(rdzv, model):
 
 
 # ---------------------------------------------------------------------------- the timed loop
-def run_steps(T, trainer, loader, steps):
-    """exactly `steps` graph-replayed steps; returns samples processed"""
+def run_steps(T, trainer, loader, steps, last=None):
+    """exactly `steps` graph-replayed steps; returns samples processed (`last`, a dict: the record of the final run_epoch call)"""
     done, samples = 0, 0
     while done < steps:
         ep = trainer.run_epoch(loader, T.Trainer.GRAPH, max_steps=min(steps - done, loader.num_batches()))
         done += ep["num_batches"]
         samples += ep["total_samples"]
+        if last is not None:
+            last.update(ep)
     return samples
 
 
@@ -1023,17 +1032,34 @@ def self_spawn(n):
     sys.exit(rc)
 
 
-def timed_run(T, dist, trainer, loader, steps):
+def timed_run(T, dist, trainer, loader, steps, last=None):
     """barrier + stream sync, exactly `steps` steps, barrier + stream sync; MAX over ranks, samples summed over ranks"""
     barrier_sync(dist, T)
     t0 = time.perf_counter()
-    samples = run_steps(T, trainer, loader, steps)
+    samples = run_steps(T, trainer, loader, steps, last)
     barrier_sync(dist, T)
     dt = time.perf_counter() - t0
     if dist is not None:
         dt = dist.all_reduce_max(dt)
         samples = int(dist.all_reduce_sum(samples))
     return samples, dt
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(T, model, last, out_dir):
+    """--dump-outputs: what the caller of the timed path holds after its last step -- that step's loss and hit count (run_epoch's
+    per-step log) and every parameter after its Adam update -- as float32 <out_dir>/<name>.npy (the models here are < 1 MB)"""
+    T.Device.sync()
+    arrays = {"loss": np.asarray(last["losses"][-1:], np.float32), "ncorrect": np.asarray(last["ncorrect"][-1:], np.float32)}
+    for i, p in enumerate(model.parameters()):
+        arrays[f"param{i}"] = np.asarray(p.data(), np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES, "outputs exceed the 64 MB dump budget"
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def main():
@@ -1055,8 +1081,15 @@ def main():
     ap.add_argument("--dp-backend", default="auto", choices=["auto", "p2p", "rccl"],
                     help="N > 1 gradient exchange: p2p = one-shot peer-to-peer all-reduce fused with Adam, rccl = ncclAllReduce; auto = p2p "
                          "when its self-check passes, else rccl")
-    ap.add_argument("--workloads", default="all", help="N = 1: the other BASELINE configs reported beside the headline: all | none | comma list")
+    ap.add_argument("--workloads", default="all", help="N = 1, --full: the other BASELINE configs reported beside the headline: all | none | comma list")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too (roofline, sustained, batch sweeps, CPU baseline, data-parallel figures, "
+                         "workloads; --no-* and --workloads select among them); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, hit count and updated parameters to DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     under_profiler = "rocprofiler-sdk" in os.environ.get("LD_PRELOAD", "") or bool(os.environ.get("ROCP_TOOL_LIBRARIES"))
@@ -1103,13 +1136,16 @@ def main():
         while time.perf_counter() - t_settle < args.settle_seconds:
             settle_steps += run_steps(T, trainer, loader, 256) // batch
             T.Device.sync()
-    samples, dt = timed_run(T, dist, trainer, loader, args.steps)
+    last = {} if args.dump_outputs else None
+    samples, dt = timed_run(T, dist, trainer, loader, args.steps, last)
+    if args.dump_outputs and rank == 0:      # before anything below steps this trainer again
+        dump_outputs(T, model, last, args.dump_outputs)
 
-    # N > 1: the single-GPU figure of the SAME per-GPU batch (no communicator), measured by rank 0 in the same run with the
+    # N > 1 (--full): the single-GPU figure of the SAME per-GPU batch (no communicator), measured by rank 0 in the same run with the
     # same W / K -- the denominator of SURVEY 8e's weak-scaling efficiency -- and the data-parallel figure at the N = 1
     # headline's 64 rows per GPU (comparable with a separate N = 1 run of this script)
     dp_extra = None
-    if world > 1 and not args.batch:
+    if world > 1 and not args.batch and args.full:
         dp_extra = {}
 
         dp_extra["replicas_bit_identical"] = replicas_identical(dist, model)
@@ -1192,7 +1228,7 @@ def main():
                                         note="latency-bound: 0.4 MB per rank; max over ranks of 200 back-to-back exchanges")
 
     sustained = None
-    if world == 1 and args.settle_seconds == 0 and not args.no_roofline and not under_profiler:   # (the trace is of the W + K run only)
+    if args.full and world == 1 and args.settle_seconds == 0 and not args.no_roofline and not under_profiler:   # (the trace is of the W + K run only)
         # the same K steps again after 0.25 s of continuous stepping: under sustained load the part settles at lower clocks
         # than it holds through the first ~50 ms of a run; both states are reported, `value` is the contract's W + K run
         T.Device.sync()
@@ -1209,11 +1245,11 @@ def main():
     if rank == 0:
         flops, nbytes = algorithmic_step(key, batch)
         roof = None
-        if key == "mlp_baseline" and under_profiler:
+        if args.full and key == "mlp_baseline" and under_profiler:
             # rocprofv3 (ROCm 7.2) segfaults in hipGraphLaunch once a process replays more than one
             # instantiated graph back to back; the Trainer's replays above are what the trace is for.
             roof = dict(skipped="per-kernel timers are not run under rocprofv3; see profiles/ for the trace of this command")
-        elif key == "mlp_baseline" and not args.no_roofline and batch <= 512 and world == 1:
+        elif args.full and key == "mlp_baseline" and not args.no_roofline and batch <= 512 and world == 1:
             # per-launch durations of the step's two kernels, measured live (HIP events on the ctx
             # stream, graph chains with / without each launch).  `roofline` is the kernel that carries
             # the step's HBM traffic (83% of its algorithmic bytes); the full list is in `kernels`.
@@ -1232,23 +1268,23 @@ def main():
             roof = dict(dp_extra["exchange"])           # N > 1: the kernel the job adds to the N = 1 step is the gradient exchange
         sweep = sweep_example = None
         # (not under rocprofv3: the trace of this command is for the headline workload's kernels only)
-        if key == "mlp_baseline" and world == 1 and not args.batch and not args.no_sweep and not under_profiler:
+        if args.full and key == "mlp_baseline" and world == 1 and not args.batch and not args.no_sweep and not under_profiler:
             sweep = batch_sweep(T, build_model, key, lr, ds)
             # the reference's OWN example model (examples/train_mnist.rs:40-48: two hidden layers) over the same batches: from 480 rows on its
             # step is th_mlp2_xent_deep (three launches)
             sweep_example = batch_sweep(T, build_model, "mlp_example", lr, ds, batches=(256, 1024, 4096, 16384, 60000))
         cpu = None
-        with_cpu = not args.no_cpu_baseline and world == 1          # the CPU leg is timed on rank 0 at N = 1 only
+        with_cpu = args.full and not args.no_cpu_baseline and world == 1          # the CPU leg is timed on rank 0 at N = 1 only
         if with_cpu:
             try:
                 cpu = cpu_baseline(key, batch, sample_shape, lr)
             except Exception as e:  # the baseline is reported, never required
                 cpu = dict(value=None, unit="samples/s", cores=1, kind="port", sample=f"failed: {e}")
-        if world > 1:   # the CPU leg is timed at N = 1 only (rank 0's host cores are shared by the N ranks here)
+        if args.full and world > 1:   # the CPU leg is timed at N = 1 only (rank 0's host cores are shared by the N ranks here)
             cpu = dict(value=None, unit="samples/s", cores=None, kind="port", sample="not timed at N > 1",
                        see="cpu_baseline of `python bench.py --gpus 1` (same box, same workload family)")
         dp_ceiling = None
-        if world == 1 and key == "mlp_baseline" and not args.batch and not under_profiler and args.workloads != "none":
+        if args.full and world == 1 and key == "mlp_baseline" and not args.batch and not under_profiler and args.workloads != "none":
             try:
                 dp_ceiling = dp_on_device(T, key, lr, ds)
             except Exception as e:   # reported, never required
@@ -1260,7 +1296,7 @@ def main():
             # same kernels with the same arguments, one host launch each -- so the trace holds their per-kernel durations, while their step
             # times in THIS run are host-launch-bound and are not the measurement
             os.environ["TAPER_NO_GRAPH"] = "1"
-        if world == 1 and not args.batch and args.workloads != "none" and args.workload == "mlp_784-128-10_b64":
+        if args.full and world == 1 and not args.batch and args.workloads != "none" and args.workload == "mlp_784-128-10_b64":
             only = None if args.workloads == "all" else set(args.workloads.split(","))
             workloads = extra_workloads(T, ds, with_cpu, only)
         out = {
@@ -1282,7 +1318,7 @@ def main():
             **({"data_parallel": dp_ceiling} if dp_ceiling is not None else {}),
             **({"workloads": workloads} if workloads is not None else {}),
         }
-        print(json.dumps(compact_line(out, write_details(out))), flush=True)
+        print(json.dumps(compact_line(out, write_details(out) if args.full else None)), flush=True)
     if dist is not None:
         dist.close()
 

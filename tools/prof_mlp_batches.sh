@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/mlp_batches
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for B in ${BATCHES:-1024 4096 16384}; do
-    ARGS="--gpus 1 --batch $B --steps ${STEPS:-400} --warmup 40 --workloads none --no-sweep --no-cpu-baseline ${EXTRA:-}"
+    ARGS="--gpus 1 --full --batch $B --steps ${STEPS:-400} --warmup 40 --workloads none --no-sweep --no-cpu-baseline ${EXTRA:-}"
     timeout -s KILL 200 python $ROOT/bench.py $ARGS > "$OUT/b$B.json" 2> "$OUT/b$B.err"
     timeout -s KILL 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$B" -- python $ROOT/bench.py $ARGS > /dev/null 2> "$OUT/trace_$B.err"
     find "$OUT/trace_$B" -name "*kernel_stats.csv" -exec cp {} "$OUT/b${B}_kernel_stats.csv" \;
