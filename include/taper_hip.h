@@ -367,6 +367,32 @@ int th_f16_to_f32(th_ctx *ctx, const uint16_t *d_x, float *d_y, size_t n);
 int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params);
 int th_dequantize_int8(th_ctx *ctx, const int8_t *d_q, float *d_y, size_t n, float scale, int zero_point, float min_val);
 
+/* ---- quantized inference: QuantizedLinear / QuantizedConv2d forward of src/nn.rs:88-120, 336-429 (csrc/qlinear.hip) ---- */
+/* Every weight takes exactly the value the codecs above give it -- int8: (float)(q + 128) * scale + min_val, two roundings, with
+ * {min_val, scale} read from the DEVICE pair th_quantize_int8 wrote (no host synchronisation between quantize and forward); f16: the
+ * reference's half decode -- and the products accumulate in f32 (no int8 / f16 matrix instructions: the reference computes in f32).
+ * Y[B,N] = X[B,K] . deq(W[N,K])^T + deq(b[N]) (b nullable), ReLU in the epilogue when relu != 0.  Up to th_qlinear_stream_max_batch()
+ * rows a weight-streaming kernel reads the codes straight from memory (K split over workgroups when N alone cannot fill the device, the
+ * slices combined in a fixed order: bit-identical from run to run); above it the weights are dequantized into a pooled workspace for the
+ * f32 product of th_linear_fwd and the workspace is returned before the call does. */
+int th_linear_q8_fwd(th_ctx *ctx, const float *d_x, int batch, int in_features, const int8_t *d_qw, int out_features, const float *d_wparams,
+                     const int8_t *d_qb, const float *d_bparams, int relu, float *d_y);
+int th_linear_h16_fwd(th_ctx *ctx, const float *d_x, int batch, int in_features, const uint16_t *d_hw, int out_features, const uint16_t *d_hb,
+                      int relu, float *d_y);
+int th_qlinear_stream_max_batch(void);   /* the largest batch the weight-streaming kernel takes (8) */
+/* One launch that dequantizes a list of tensors (a model's conv weights and biases) into f32, each to its own destination (typically
+ * slices of one pooled workspace).  qtype TH_QTYPE_INT8 reads {min_val, scale} from d_params; TH_QTYPE_F16 ignores it. */
+#define TH_QTYPE_INT8 0
+#define TH_QTYPE_F16 1
+typedef struct th_qtensor {
+    const void *d_codes;
+    const float *d_params;
+    float *d_out;
+    int64_t n;
+    int qtype;
+} th_qtensor;
+int th_dequantize_multi(th_ctx *ctx, const th_qtensor *h_items, int n_items);
+
 /* ---- broadcast / reduce / layout: src/tensor.rs ---------------------- */
 int th_transpose2d(th_ctx *ctx, const float *d_in, float *d_out, int rows, int cols);      /* tensor.rs:544-566 */
 /* dst[r*dst_ld + c] = src[r*src_ld + c] for r < rows, c < cols: the strided block copies behind slice_channels /

@@ -28,6 +28,7 @@ typedef struct tp_loader tp_loader;
 typedef struct tp_trainer tp_trainer;
 typedef struct tp_sched tp_sched;
 typedef struct tp_comm tp_comm;
+typedef struct tp_qmodule tp_qmodule;
 
 const char *tp_last_error(void);
 
@@ -125,6 +126,23 @@ int tp_module_free(tp_module *m);
 int tp_module_forward(const tp_module *m, const tp_tensor *x, tp_tensor **out);
 int tp_module_num_parameters(const tp_module *m, int *out);
 int tp_module_parameter(const tp_module *m, int i, tp_tensor **out);   /* shares storage with the model */
+
+/* ---- post-training quantization (src/nn.rs:14-23, the quantized twins of nn.rs:62-504) ----
+ * qtype: 0 Int8, 1 Float16; 2 Int4, 3 BFloat16 and 4 NF4 are placeholders in the reference (zeros) and are refused.  enabled == 0
+ * gives Float16 whatever qtype says (tensor.rs:2085-2088).  Linear, Conv2d / Conv2dReLU, Sequential, the pools, Flatten, ReLU and
+ * Sigmoid have twins; any other module (Dropout) fails with "Quantization not implemented for this module type" (nn.rs:15) before
+ * anything is allocated.  The codes are made on the device; the source model is not touched and can keep training. */
+int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **out);
+int tp_qmodule_free(tp_qmodule *q);
+/* QuantizedModule::forward: records no tape node; the output does not require a gradient */
+int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out);
+/* code bytes of every tensor, plus 8 bytes of {min_val, scale} per int8 tensor */
+int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out);
+/* the packed tensors in the order of the source's parameters(): length, then codes (n int8 or n uint16; h_codes nullable),
+ * {min_val, scale} (int8; {0, 0} for Float16; nullable) and the qtype (nullable) */
+int tp_qmodule_num_tensors(const tp_qmodule *q, int *out);
+int tp_qmodule_tensor_len(const tp_qmodule *q, int i, size_t *out);
+int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params, int *qtype);
 
 /* ---- optim (src/optim.rs) ---- */
 int tp_adam_new(tp_tensor *const *params, int n, float lr, float beta1, float beta2, float eps, float weight_decay,

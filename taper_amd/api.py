@@ -289,6 +289,60 @@ class Module:
             out.append(Tensor(_h=h.value))
         return out
 
+    def quantize(self, qtype="int8", enabled=True):
+        """nn.rs:14-23 Module::quantize -> QuantizedModule (post-training, on the device; this model is not touched).
+        qtype: "int8" | "float16" ("int4", "bfloat16", "nf4" are placeholders in the reference and are refused);
+        enabled=False gives float16 (tensor.rs:2085-2088)."""
+        code = QuantizedModule.QTYPES.get(qtype)
+        if code is None:
+            raise TaperError(f"quantize: unknown qtype {qtype!r}")
+        h = _p()
+        tp_check(host.tp_module_quantize(self._h, code, 1 if enabled else 0, C.byref(h)), "Module::quantize")
+        return QuantizedModule(h.value)
+
+
+class QuantizedModule:
+    """nn.rs:20-23: forward from the packed codes (no tape node, the output needs no gradient)"""
+    QTYPES = {"int8": 0, "float16": 1, "int4": 2, "bfloat16": 3, "nf4": 4}
+
+    def __init__(self, h):
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            host.tp_qmodule_free(h)
+
+    def forward(self, x: Tensor) -> Tensor:
+        h = _p()
+        tp_check(host.tp_qmodule_forward(self._h, x._h, C.byref(h)), "QuantizedModule::forward")
+        return Tensor(_h=h.value)
+
+    __call__ = forward
+
+    def storage_bytes(self) -> int:
+        n = C.c_size_t()
+        tp_check(host.tp_qmodule_storage_bytes(self._h, C.byref(n)), "QuantizedModule::storage_bytes")
+        return n.value
+
+    def tensors(self):
+        """[(qtype, codes, (min_val, scale))] in parameter order: codes int8 with its pair for "int8", uint16 half bits and
+        (0, 0) for "float16"."""
+        n = C.c_int()
+        tp_check(host.tp_qmodule_num_tensors(self._h, C.byref(n)), "QuantizedModule::tensors")
+        out = []
+        for i in range(n.value):
+            ln = C.c_size_t()
+            tp_check(host.tp_qmodule_tensor_len(self._h, i, C.byref(ln)), "QuantizedModule::tensors")
+            qt = C.c_int()
+            tp_check(host.tp_qmodule_tensor(self._h, i, None, None, C.byref(qt)), "QuantizedModule::tensors")
+            codes = np.zeros(ln.value, np.int8 if qt.value == 0 else np.uint16)
+            params = np.zeros(2, np.float32)
+            tp_check(host.tp_qmodule_tensor(self._h, i, codes.ctypes.data if ln.value else None, params.ctypes.data, None),
+                     "QuantizedModule::tensors")
+            out.append(("int8" if qt.value == 0 else "float16", codes, (params[0], params[1])))
+        return out
+
 
 def _mk(fn, name, *args):
     h = _p()

@@ -15,6 +15,7 @@ struct tp_loader { std::unique_ptr<DataLoader> l; };
 struct tp_trainer { std::unique_ptr<Trainer> t; };
 struct tp_comm { std::shared_ptr<Communicator> c; };
 struct tp_sched { std::shared_ptr<LRScheduler> s; };
+struct tp_qmodule { std::unique_ptr<QuantizedModule> q; std::vector<const QTensor *> tensors; };
 
 static thread_local std::string g_err;
 
@@ -221,6 +222,51 @@ int tp_sequential_new(tp_module *const *layers, int n, int fuse, tp_module **out
 }
 int tp_module_free(tp_module *m) { TP_BEGIN delete m; TP_END }
 int tp_module_forward(const tp_module *m, const tp_tensor *x, tp_tensor **out) { TP_BEGIN *out = wrap(m->m->forward(x->t)); TP_END }
+/* nn.rs:14-23 */
+int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **out) {
+    TP_BEGIN
+    TAPER_ASSERT(m && out, "tp_module_quantize: null argument");
+    auto h = std::make_unique<tp_qmodule>();
+    h->q = quantize(*m->m, (QType)qtype, enabled != 0);
+    h->q->tensors(&h->tensors);
+    *out = h.release();
+    TP_END
+}
+int tp_qmodule_free(tp_qmodule *q) { TP_BEGIN delete q; TP_END }
+int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out) {
+    TP_BEGIN
+    Tensor in = x->t;
+    in.set_requires_grad(false);   // inference: nothing below records a tape node
+    *out = wrap(q->q->forward(in));
+    TP_END
+}
+int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out) {
+    TP_BEGIN
+    size_t s = 0;
+    for (const QTensor *t : q->tensors) s += t->storage_bytes();
+    *out = s;
+    TP_END
+}
+int tp_qmodule_num_tensors(const tp_qmodule *q, int *out) { TP_BEGIN *out = (int)q->tensors.size(); TP_END }
+int tp_qmodule_tensor_len(const tp_qmodule *q, int i, size_t *out) {
+    TP_BEGIN
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor_len: index out of range");
+    *out = q->tensors[i]->n;
+    TP_END
+}
+int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params, int *qtype) {
+    TP_BEGIN
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor: index out of range");
+    const QTensor &t = *q->tensors[i];
+    th_ctx *ctx = Device::ctx();
+    if (h_codes && t.n) taper::th_check(th_memcpy_d2h(ctx, h_codes, t.codes->d, t.qtype == TH_QTYPE_INT8 ? t.n : 2 * t.n), "th_memcpy_d2h");
+    if (h_params) {
+        h_params[0] = h_params[1] = 0.f;
+        if (t.params) taper::th_check(th_memcpy_d2h(ctx, h_params, t.params->d, 2 * sizeof(float)), "th_memcpy_d2h");
+    }
+    if (qtype) *qtype = t.qtype;
+    TP_END
+}
 int tp_module_num_parameters(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->parameters().size(); TP_END }
 int tp_module_parameter(const tp_module *m, int i, tp_tensor **out) {
     TP_BEGIN

@@ -708,7 +708,9 @@ Conv2d::Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pai
     if (with_bias) bias = Tensor(std::vector<float>(out_ch, 0.f), {out_ch}).requires_grad();
 }
 
-Tensor Conv2d::forward(const Tensor &x) const {
+Tensor Conv2d::forward(const Tensor &x) const { return forward_with(x, weight, bias); }
+
+Tensor Conv2d::forward_with(const Tensor &x, const Tensor &weight, const Tensor &bias) const {
     if (groups == 1) return x.conv2d(weight, bias, stride, padding, dilation, fuse_relu);   // nn.rs:280-288
     // nn.rs:289-332: slices are fresh tensors without tape nodes, so nothing upstream of a grouped
     // convolution (and none of its own parameters) ever receives a gradient -- reproduced as is

@@ -1,0 +1,214 @@
+// quantized.cpp -- post-training quantization of a trained model (src/nn.rs:14-23 `Module::quantize`, the quantized twins of
+// nn.rs:62-504, tensor.rs:2084-2108 `Tensor::quantize`).  Every code is made on the device by the storage codecs (th_quantize_int8 /
+// th_f32_to_f16) from the live parameters; the source model is only read.  A twin keeps its codes and nothing else: no f32 copy of a
+// weight outlives a forward call (the reference caches one in QuantizedLinear -- storage only, the values are the same).
+#include "nn_internal.h"
+
+namespace taper {
+
+namespace {
+
+size_t code_bytes(int qtype, size_t n) { return qtype == TH_QTYPE_INT8 ? n : 2 * n; }
+
+QTensor quantize_tensor(const Tensor &t, int qtype) {   // tensor.rs:2084-2108 for the two codecs that do real work
+    QTensor q;
+    q.qtype = qtype;
+    q.n = t.len();
+    q.shape = t.shape();
+    q.codes = Buffer::alloc((code_bytes(qtype, q.n) + 3) / 4);
+    th_ctx *ctx = Device::ctx();
+    if (qtype == TH_QTYPE_INT8) {
+        q.params = Buffer::alloc(2);
+        TH(th_quantize_int8(ctx, t.dptr(), reinterpret_cast<int8_t *>(q.codes->d), q.n, q.params->d));
+    } else {
+        TH(th_f32_to_f16(ctx, t.dptr(), reinterpret_cast<uint16_t *>(q.codes->d), q.n));
+    }
+    return q;
+}
+
+// the reference's parameter-free layers: their twins run the float layer itself (values pass through unchanged)
+class QPass : public QuantizedModule {
+   public:
+    explicit QPass(std::shared_ptr<Module> m) : m_(std::move(m)) {}
+    Tensor forward(const Tensor &x) const override { return m_->forward(x); }
+    bool is_relu() const { return dynamic_cast<const ReLU *>(m_.get()) != nullptr; }
+
+   private:
+    std::shared_ptr<Module> m_;
+};
+
+class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
+   public:
+    QLinear(const Linear &l, int qtype) : w_(quantize_tensor(l.weight, qtype)), k_(l.weight.shape()[1]), n_(l.weight.shape()[0]) {
+        if (l.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(l.bias, qtype));
+    }
+    Tensor forward(const Tensor &x) const override { return forward_relu(x, false); }
+    // x . deq(W)^T + deq(b), and the ReLU behind it in the same launch when the Sequential twin pairs them
+    Tensor forward_relu(const Tensor &x, bool relu) const {
+        TAPER_ASSERT(x.shape().size() == 2 && x.shape()[1] == k_, "QuantizedLinear: input must be [batch, in_features]");
+        const size_t batch = x.shape()[0];
+        Tensor y = Tensor::empty({batch, n_});
+        th_ctx *ctx = Device::ctx();
+        if (w_.qtype == TH_QTYPE_INT8)
+            TH(th_linear_q8_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, w_.params->d,
+                                b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu ? 1 : 0, y.dptr()));
+        else
+            TH(th_linear_h16_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const uint16_t *>(w_.codes->d), (int)n_,
+                                 b_ ? reinterpret_cast<const uint16_t *>(b_->codes->d) : nullptr, relu ? 1 : 0, y.dptr()));
+        return y;
+    }
+    void tensors(std::vector<const QTensor *> *out) const override {
+        out->push_back(&w_);
+        if (b_) out->push_back(b_.get());
+    }
+
+   private:
+    QTensor w_;
+    std::unique_ptr<QTensor> b_;
+    size_t k_, n_;
+};
+
+class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
+   public:
+    QConv(const Conv2d &c, int qtype) : geom_(std::make_shared<Conv2d>(c)), w_(quantize_tensor(c.weight, qtype)) {
+        if (c.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(c.bias, qtype));
+        geom_->weight = Tensor();   // the twin keeps the geometry only, not the source's f32 storage
+        geom_->bias = Tensor();
+    }
+    Tensor forward(const Tensor &x) const override {   // alone: dequantize its own two tensors
+        std::vector<const QConv *> one{this};
+        std::vector<std::pair<float *, float *>> at;
+        auto ws = dequantize(one, &at);
+        return forward_with(x, at[0].first, at[0].second);
+    }
+    // nn.rs:336-429 on weights another call dequantized (d_w, d_b: slices of that call's workspace)
+    Tensor forward_with(const Tensor &x, float *d_w, float *d_b) const {
+        return geom_->forward_with(x, Tensor::from_device(d_w, w_.shape), d_b ? Tensor::from_device(d_b, b_->shape) : Tensor());
+    }
+    void tensors(std::vector<const QTensor *> *out) const override {
+        out->push_back(&w_);
+        if (b_) out->push_back(b_.get());
+    }
+    // ONE launch (th_dequantize_multi) for the weights and biases of `convs` into one pooled workspace; at[i] = {weight, bias} of convs[i]
+    static std::shared_ptr<Buffer> dequantize(const std::vector<const QConv *> &convs, std::vector<std::pair<float *, float *>> *at) {
+        auto up = [](size_t n) { return (n + 15) / 16 * 16; };   // 64-byte aligned slices
+        size_t total = 0;
+        for (const QConv *c : convs) total += up(c->w_.n) + (c->b_ ? up(c->b_->n) : 0);
+        auto ws = Buffer::alloc(total);
+        std::vector<th_qtensor> items;
+        size_t off = 0;
+        for (const QConv *c : convs) {
+            float *dw = ws->d + off, *db = nullptr;
+            items.push_back(c->w_.item(dw));
+            off += up(c->w_.n);
+            if (c->b_) {
+                db = ws->d + off;
+                items.push_back(c->b_->item(db));
+                off += up(c->b_->n);
+            }
+            at->push_back({dw, db});
+        }
+        TH(th_dequantize_multi(Device::ctx(), items.data(), (int)items.size()));
+        return ws;
+    }
+
+   private:
+    std::shared_ptr<Conv2d> geom_;
+    QTensor w_;
+    std::unique_ptr<QTensor> b_;
+};
+
+class QSequential : public QuantizedModule {   // nn.rs:153-177
+   public:
+    std::vector<std::unique_ptr<QuantizedModule>> layers;
+    Tensor forward(const Tensor &input) const override {
+        // every conv stage's weights in one dequantize launch, into one workspace that lives for this call
+        std::vector<const QConv *> convs;
+        for (const auto &l : layers)
+            if (auto *c = dynamic_cast<const QConv *>(l.get())) convs.push_back(c);
+        std::vector<std::pair<float *, float *>> at;
+        std::shared_ptr<Buffer> ws;
+        if (!convs.empty()) ws = QConv::dequantize(convs, &at);
+        Tensor x = input;
+        size_t ci = 0;
+        for (size_t i = 0; i < layers.size(); ++i) {
+            const QuantizedModule *l = layers[i].get();
+            if (auto *lin = dynamic_cast<const QLinear *>(l)) {
+                auto *next = i + 1 < layers.size() ? dynamic_cast<const QPass *>(layers[i + 1].get()) : nullptr;
+                if (next && next->is_relu()) {   // Linear + ReLU: one launch, the ReLU in its epilogue
+                    x = lin->forward_relu(x, true);
+                    ++i;
+                } else {
+                    x = lin->forward(x);
+                }
+            } else if (auto *cv = dynamic_cast<const QConv *>(l)) {
+                x = cv->forward_with(x, at[ci].first, at[ci].second);
+                ++ci;
+            } else {
+                x = l->forward(x);
+            }
+        }
+        return x;
+    }
+    void tensors(std::vector<const QTensor *> *out) const override {
+        for (const auto &l : layers) l->tensors(out);
+    }
+};
+
+// nn.rs:15: every module without a quantize() of its own (Dropout among them) panics
+void check_quantizable(const Module &m) {
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        for (const auto &l : s->layers) check_quantizable(*l);
+        return;
+    }
+    if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const ReLU *>(&m) ||
+        dynamic_cast<const Sigmoid *>(&m) || dynamic_cast<const MaxPool2d *>(&m) || dynamic_cast<const AvgPool2d *>(&m) ||
+        dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m))
+        return;
+    throw Error("Quantization not implemented for this module type");
+}
+
+template <class M>
+std::shared_ptr<Module> copy_of(const Module &m) {
+    auto *p = dynamic_cast<const M *>(&m);
+    return p ? std::make_shared<M>(*p) : nullptr;
+}
+
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype) {
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        auto q = std::make_unique<QSequential>();
+        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype));
+        return q;
+    }
+    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype);
+    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype);
+    std::shared_ptr<Module> p;
+    if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
+        !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))
+        throw Error("Quantization not implemented for this module type");
+    return std::make_unique<QPass>(p);
+}
+
+}  // namespace
+
+th_qtensor QTensor::item(float *d_out) const { return th_qtensor{codes->d, params ? params->d : nullptr, d_out, (int64_t)n, qtype}; }
+
+std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled) {
+    check_quantizable(m);   // before anything is allocated
+    int qt = TH_QTYPE_F16;  // tensor.rs:2085-2088: disabled quantization gives Float16
+    if (enabled) {
+        switch (qtype) {
+            case QType::Int8: qt = TH_QTYPE_INT8; break;
+            case QType::Float16: qt = TH_QTYPE_F16; break;
+            case QType::Int4:
+            case QType::BFloat16:
+            case QType::NF4:   // tensor.rs:2154-2188: placeholders whose codes are all zero
+                throw Error("Quantization type " + std::string(qtype == QType::Int4 ? "Int4" : qtype == QType::BFloat16 ? "BFloat16" : "NF4") +
+                            " is not supported: the reference's codec for it is a placeholder that returns zeros");
+            default: throw Error("unknown quantization type");
+        }
+    }
+    return quantize_checked(m, qt);
+}
+
+}  // namespace taper

@@ -345,6 +345,8 @@ class Conv2d : public Module {  // nn.rs:180-354
     Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride, std::pair<int, int> padding,
            bool with_bias, uint64_t seed, size_t groups = 1);
     Tensor forward(const Tensor &x) const override;
+    // nn.rs:280-332 with the given weight / bias (the quantized twin passes its dequantized tensors)
+    Tensor forward_with(const Tensor &x, const Tensor &w, const Tensor &b) const;
     std::vector<Tensor> parameters() const override;
     const char *name() const override { return fuse_relu ? "Conv2dReLU" : "Conv2d"; }
 };
@@ -425,6 +427,29 @@ class Sequential : public Module {  // nn.rs:130-162
     std::vector<Tensor> parameters() const override;
     const char *name() const override { return "Sequential"; }
 };
+
+// ---- post-training quantization (src/nn.rs:14-23 Module::quantize / QuantizedModule, quantized twins nn.rs:62-504) ----
+// quantize() of Linear, Conv2d / Conv2dReLU, Sequential and the parameter-free layers (pools, Flatten, ReLU, Sigmoid); any other module
+// throws the reference's panic message (nn.rs:15).  The codes are made on the device from the live parameters (th_quantize_int8 /
+// th_f32_to_f16) and the model is not touched.  forward records no tape node; its output never requires a gradient.
+enum class QType { Int8 = 0, Float16 = 1, Int4 = 2, BFloat16 = 3, NF4 = 4 };
+
+struct QTensor {   // a QuantizedTensor (tensor.rs:2084-2108) on the device: codes, and {min_val, scale} for int8
+    int qtype = TH_QTYPE_INT8;
+    size_t n = 0;
+    Shape shape;
+    std::shared_ptr<Buffer> codes, params;
+    size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? n + 2 * sizeof(float) : 2 * n; }
+    th_qtensor item(float *d_out) const;
+};
+
+class QuantizedModule {
+   public:
+    virtual ~QuantizedModule() = default;
+    virtual Tensor forward(const Tensor &input) const = 0;
+    virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
+};
+std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled);
 
 // ---- optim (src/optim.rs) ------------------------------------------------------
 // Parameters, their grads and the moments live in flat device arenas so that

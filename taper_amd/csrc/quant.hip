@@ -3,44 +3,9 @@
 // hand-rolled IEEE half conversion.  Integer / bit work: restated literally (including the half-up rounding whose mantissa
 // carry is OR-ed, not added, into the exponent field) and held to bit-exact parity.  HBM-bound, one pass each.
 #include "common.h"
+#include "quant_dev.h"
 
 namespace th {
-
-// tensor.rs:2191-2238
-__device__ __forceinline__ uint16_t f32_to_f16_bits(float value) {
-    const uint32_t bits = __float_as_uint(value);
-    const uint32_t sign = (bits >> 31) & 0x1, exponent = (bits >> 23) & 0xFF, mantissa = bits & 0x7FFFFF;
-    if (exponent == 0xFF) return (uint16_t)((sign << 15) | (0x1Fu << 10) | (mantissa != 0 ? 0x200u : 0u));   // inf / NaN
-    if (exponent == 0 && mantissa == 0) return (uint16_t)(sign << 15);                                          // +-0
-    const int f16_exponent = (int)exponent - 127 + 15;
-    if (f16_exponent >= 0x1F) return (uint16_t)((sign << 15) | (0x1Fu << 10));                                  // overflow -> inf
-    if (f16_exponent <= 0) {
-        if (f16_exponent < -10) return (uint16_t)(sign << 15);                                                  // underflow -> 0
-        const int shift = 1 - f16_exponent;
-        const uint32_t m = (mantissa | 0x800000u) >> (shift + 13);                                             // truncating
-        return (uint16_t)((sign << 15) | m);
-    }
-    const uint32_t m = (mantissa + 0x1000u) >> 13;                                                              // round half up; a carry (0x400) is OR-ed below
-    return (uint16_t)((sign << 15) | ((uint32_t)f16_exponent << 10) | m);
-}
-
-// tensor.rs:2241-2287
-__device__ __forceinline__ float f16_bits_to_f32(uint16_t value) {
-    const uint32_t bits = value, sign = (bits >> 15) & 0x1, exponent = (bits >> 10) & 0x1F, mantissa = bits & 0x3FF;
-    if (exponent == 0x1F) return __uint_as_float((sign << 31) | (0xFFu << 23) | (mantissa != 0 ? mantissa << 13 : 0u));
-    if (exponent == 0) {
-        if (mantissa == 0) return __uint_as_float(sign << 31);
-        int exp = -14;
-        uint32_t mant = mantissa;
-        while ((mant & 0x400) == 0) {
-            mant <<= 1;
-            exp -= 1;
-        }
-        mant &= 0x3FF;
-        return __uint_as_float((sign << 31) | (((uint32_t)(exp + 127) & 0xFF) << 23) | (mant << 13));
-    }
-    return __uint_as_float((sign << 31) | (((exponent + 127 - 15) & 0xFF) << 23) | (mantissa << 13));
-}
 
 __global__ __launch_bounds__(256) void f32_to_f16_kernel(const float *__restrict__ x, uint16_t *__restrict__ y, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = f32_to_f16_bits(x[i]);

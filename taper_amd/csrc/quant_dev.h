@@ -1,0 +1,47 @@
+// quant_dev.h -- the reference's IEEE half codec as device functions (src/tensor.rs:2191-2287), shared by the storage codecs
+// (quant.hip) and the quantized forward (qlinear.hip), plus the int8 dequantisation of one code (tensor.rs:353-360).
+#pragma once
+#include "common.h"
+
+namespace th {
+
+// tensor.rs:2191-2238
+__device__ __forceinline__ uint16_t f32_to_f16_bits(float value) {
+    const uint32_t bits = __float_as_uint(value);
+    const uint32_t sign = (bits >> 31) & 0x1, exponent = (bits >> 23) & 0xFF, mantissa = bits & 0x7FFFFF;
+    if (exponent == 0xFF) return (uint16_t)((sign << 15) | (0x1Fu << 10) | (mantissa != 0 ? 0x200u : 0u));   // inf / NaN
+    if (exponent == 0 && mantissa == 0) return (uint16_t)(sign << 15);                                          // +-0
+    const int f16_exponent = (int)exponent - 127 + 15;
+    if (f16_exponent >= 0x1F) return (uint16_t)((sign << 15) | (0x1Fu << 10));                                  // overflow -> inf
+    if (f16_exponent <= 0) {
+        if (f16_exponent < -10) return (uint16_t)(sign << 15);                                                  // underflow -> 0
+        const int shift = 1 - f16_exponent;
+        const uint32_t m = (mantissa | 0x800000u) >> (shift + 13);                                             // truncating
+        return (uint16_t)((sign << 15) | m);
+    }
+    const uint32_t m = (mantissa + 0x1000u) >> 13;                                                              // round half up; a carry (0x400) is OR-ed below
+    return (uint16_t)((sign << 15) | ((uint32_t)f16_exponent << 10) | m);
+}
+
+// tensor.rs:2241-2287
+__device__ __forceinline__ float f16_bits_to_f32(uint16_t value) {
+    const uint32_t bits = value, sign = (bits >> 15) & 0x1, exponent = (bits >> 10) & 0x1F, mantissa = bits & 0x3FF;
+    if (exponent == 0x1F) return __uint_as_float((sign << 31) | (0xFFu << 23) | (mantissa != 0 ? mantissa << 13 : 0u));
+    if (exponent == 0) {
+        if (mantissa == 0) return __uint_as_float(sign << 31);
+        int exp = -14;
+        uint32_t mant = mantissa;
+        while ((mant & 0x400) == 0) {
+            mant <<= 1;
+            exp -= 1;
+        }
+        mant &= 0x3FF;
+        return __uint_as_float((sign << 31) | (((uint32_t)(exp + 127) & 0xFF) << 23) | (mant << 13));
+    }
+    return __uint_as_float((sign << 31) | (((exponent + 127 - 15) & 0xFF) << 23) | (mantissa << 13));
+}
+
+// (q - zero_point) * scale + min_val with zero_point = -128: two roundings, never contracted (tensor.rs:357)
+__device__ __forceinline__ float dequant_int8(int q, float scale, float min_val) { return __fadd_rn(__fmul_rn((float)(q + 128), scale), min_val); }
+
+}  // namespace th

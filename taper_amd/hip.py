@@ -61,6 +61,10 @@ def conv_stages(stages):
     return arr, len(stages)
 
 
+class QTensor(C.Structure):   # th_qtensor (th_dequantize_multi)
+    _fields_ = [("d_codes", C.c_void_p), ("d_params", C.c_void_p), ("d_out", C.c_void_p), ("n", C.c_int64), ("qtype", C.c_int)]
+
+
 class DevBuf:
     """A device allocation from the ctx pool (freed on garbage collection)."""
 
