@@ -10,6 +10,21 @@
 #include "nn_internal.h"
 
 namespace taper {
+// the device scalar a fused loss launch writes accuracy() * B into, when the caller asks for one
+static float *n_correct_slot(Tensor *n_correct_out) {
+    if (!n_correct_out) return nullptr;
+    *n_correct_out = Tensor::empty({1});
+    return n_correct_out->dptr();
+}
+
+// where a fused launch writes a parameter's gradient (written, never accumulated: the slot holds none yet); nullptr for an absent bias
+static float *grad_slot(const Tensor &p) {
+    if (!p.defined()) return nullptr;
+    if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
+    p.grad_->known_zero = false;
+    return p.grad_->buf->d;
+}
+
 // ---------------------------------------------------------------- loss
 Tensor log_softmax(const Tensor &x, int dim) {  // loss.rs:101-126
     const int nd = (int)x.shape().size();
@@ -42,11 +57,7 @@ Tensor cross_entropy_loss(const Tensor &logits, const Tensor &targets, Tensor *n
     Tensor loss = Tensor::empty({1});
     // the gradient for an upstream grad of exactly 1 comes out of the forward kernel
     std::shared_ptr<Buffer> dunit = need_grad ? Buffer::alloc(logits.len()) : nullptr;
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
+    float *nc = n_correct_slot(n_correct_out);
     TH(th_softmax_xent_fwd(ctx, logits.dptr(), targets.dptr(), b, c, logp.dptr(), loss.dptr(), nullptr, nc,
                            dunit ? dunit->d : nullptr, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
                            log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr));
@@ -85,11 +96,7 @@ Tensor linear_cross_entropy(const Tensor &h, const Tensor &w, const Tensor &bias
     const int b = (int)h.shape()[0], k = (int)h.shape()[1], c = (int)w.shape()[0];
     th_ctx *ctx = Device::ctx();
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
+    float *nc = n_correct_slot(n_correct_out);
     const bool h_grad = h.get_requires_grad();
     const bool w_grad = w.get_requires_grad() && !w.has_grad();
     const bool b_grad = bias.defined() && bias.get_requires_grad() && !bias.has_grad();
@@ -157,18 +164,8 @@ Tensor linear_cross_entropy_wide(const Tensor &h, const Tensor &w, const Tensor 
     TAPER_ASSERT(targets.shape()[0] == h.shape()[0], "Batch sizes must match");
     const int b = (int)h.shape()[0], k = (int)h.shape()[1], c = (int)w.shape()[0];
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.defined()) return nullptr;
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
-    float *dw = slot(w), *db = slot(bias);
+    float *nc = n_correct_slot(n_correct_out);
+    float *dw = grad_slot(w), *db = grad_slot(bias);
     // the input is the flattened output of a bias-only Conv2dReLU + pool (Trainer step): it asked for column sums of dX * [x > 0], not for dX
     const bool colsum_mode = h.get_requires_grad() && h.grad_->wants_colsum && PoolBiasScope::active();
     std::shared_ptr<Buffer> dh = (h.get_requires_grad() && !colsum_mode) ? Buffer::alloc(h.len()) : nullptr;
@@ -258,21 +255,11 @@ Tensor conv_chain_head_cross_entropy(const Tensor &x, const std::vector<ConvStag
     Tensor map = x.conv_chain_head(stages, head);
     // launch 2: the sums over the batch, Adam in the epilogues (nothing there reads a parameter)
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.defined()) return nullptr;
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
-    float *dw = slot(w), *db = slot(bias), *gcb = cb_grad ? slot(cbias) : nullptr;
+    float *nc = n_correct_slot(n_correct_out);
+    float *dw = grad_slot(w), *db = grad_slot(bias), *gcb = cb_grad ? grad_slot(cbias) : nullptr;
     th_adam_fuse wf{}, bf{}, cf{};
     const bool fw = fa && fa->fuse_for(w, &wf), fb = fa && bias.defined() && fa->fuse_for(bias, &bf), fc = fa && cb_grad && fa->fuse_for(cbias, &cf);
-    const Communicator *xc = TailExchangeScope::active();
+    const Communicator *xc = log ? log->exchange : nullptr;
     if (xc && xc->n_ranks > 1) {
         // data parallel: the launch exchanges every finished sum with the peers; its epilogues apply the mean
         TAPER_ASSERT(fa && xc->wide_exchange_ok(n, k, classes, c_last), "conv_chain_head_cross_entropy: the in-launch exchange does not cover this step");
@@ -325,18 +312,8 @@ Tensor mlp_tail_cross_entropy(const Tensor &x, const Tensor &w1, const Tensor &b
                         fa ? fa->d_tick() : nullptr));
     // launch 2: everything else
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.defined()) return nullptr;
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
-    float *dw1 = slot(w1), *db1 = slot(b1), *dw2 = slot(w2), *db2 = slot(b2);
+    float *nc = n_correct_slot(n_correct_out);
+    float *dw1 = grad_slot(w1), *db1 = grad_slot(b1), *dw2 = grad_slot(w2), *db2 = grad_slot(b2);
     // a hidden layer that is not the first also hands dX down: the launch then reads W1, whose update is deferred like W2's
     const bool need_dx = x.get_requires_grad();
     std::shared_ptr<Buffer> dx = need_dx ? Buffer::alloc(x.len()) : nullptr;
@@ -346,7 +323,7 @@ Tensor mlp_tail_cross_entropy(const Tensor &x, const Tensor &w1, const Tensor &b
         if (!need_dx && fa->fuse_for(w1, &wf)) pw = &wf;
         if (b1.defined() && fa->fuse_for(b1, &bf)) pb = &bf;
     }
-    const Communicator *xc = TailExchangeScope::active();
+    const Communicator *xc = log ? log->exchange : nullptr;
     if (xc && xc->n_ranks > 1) {
         // data parallel: the launch exchanges every finished slice with the peers; its epilogues apply the mean
         TAPER_ASSERT(fa && !need_dx && xc->tail_exchange_ok(b, in_f, hid, c), "mlp_tail_cross_entropy: the in-launch exchange does not cover this step");
@@ -412,10 +389,6 @@ bool mlp2_supported(const th_row_source &src, size_t batch, const std::vector<Te
     return mlp2_shapes_ok(batch, w, src.n_rows);
 }
 
-bool mlp2_supported(const th_row_source &src, size_t batch, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2) {
-    return mlp2_supported(src, batch, std::vector<Tensor>{w1, w2}, std::vector<Tensor>{b1, b2});
-}
-
 Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vector<Tensor> &w, const std::vector<Tensor> &b,
                           Tensor *n_correct_out, const StepLogSink *log) {
     // nn.rs:54-60, activation.rs:10-12, loss.rs:136-195 and the backward closures of the Linear layers and the ReLU nodes
@@ -425,17 +398,7 @@ Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vec
     Adam *fa = FusedAdamScope::active();
     if (fa && fa->has_deferred()) fa->flush_deferred();   // updates an earlier (other) step form left behind: with their own counter
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.defined()) return nullptr;
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
+    float *nc = n_correct_slot(n_correct_out);
     // the finish launch holds every complete gradient and no launch of the step reads a parameter after it: every update rides there
     const size_t nl = w.size();
     th_adam_fuse fw[3], fb[3];
@@ -443,8 +406,8 @@ Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vec
     for (size_t l = 0; l < nl; ++l) {
         L[l].d_w = w[l].dptr();
         L[l].d_b = b[l].defined() ? b[l].dptr() : nullptr;
-        L[l].d_dw = slot(w[l]);
-        L[l].d_db = slot(b[l]);
+        L[l].d_dw = grad_slot(w[l]);
+        L[l].d_db = grad_slot(b[l]);
         L[l].w_fuse = (fa && fa->fuse_for(w[l], &fw[l])) ? &fw[l] : nullptr;
         L[l].b_fuse = (fa && b[l].defined() && fa->fuse_for(b[l], &fb[l])) ? &fb[l] : nullptr;
         L[l].out_features = (int)w[l].shape()[0];
@@ -471,11 +434,6 @@ Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vec
         for (const Tensor &p : ps) p.grad_->has = true;
     });
     return loss;
-}
-
-Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,
-                          Tensor *n_correct_out, const StepLogSink *log) {
-    return mlp2_cross_entropy(src, batch, std::vector<Tensor>{w1, w2}, std::vector<Tensor>{b1, b2}, n_correct_out, log);
 }
 
 // Linear + ReLU, Linear + ReLU, Linear, softmax cross-entropy -- the classifier of examples/train_mnist_cnn.rs:53-61 and the whole model of
@@ -505,20 +463,11 @@ Tensor mlp3_cross_entropy(const Tensor &x, const Tensor (&w)[3], const Tensor (&
     Adam *fa = FusedAdamScope::active();
     if (fa && fa->has_deferred()) fa->flush_deferred();   // updates an earlier (other) step form left behind: with their own counter
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
+    float *nc = n_correct_slot(n_correct_out);
     th_mlp3_layer layers[3];
     th_adam_fuse wf[3], bf[3];
     for (int l = 0; l < 3; ++l) {
-        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), slot(w[l]), slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
+        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), grad_slot(w[l]), grad_slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
         if (fa) {
             if (fa->fuse_for(w[l], &wf[l])) layers[l].w_fuse = &wf[l];
             if (fa->fuse_for(b[l], &bf[l])) layers[l].b_fuse = &bf[l];
@@ -594,20 +543,11 @@ Tensor conv_chain_mlp3_cross_entropy(const Tensor &x, const std::vector<ConvStag
     if (fa && fa->has_deferred()) fa->flush_deferred();   // updates an earlier (other) step form left behind: with their own counter
     const size_t n = x.shape()[0], c_last = stages.back().weight.shape()[0];
     Tensor loss = Tensor::empty({1});
-    float *nc = nullptr;
-    if (n_correct_out) {
-        *n_correct_out = Tensor::empty({1});
-        nc = n_correct_out->dptr();
-    }
-    auto slot = [](const Tensor &p) -> float * {
-        if (!p.grad_->buf) p.grad_->buf = Buffer::alloc(p.len());
-        p.grad_->known_zero = false;
-        return p.grad_->buf->d;
-    };
+    float *nc = n_correct_slot(n_correct_out);
     th_mlp3_layer layers[3];
     th_adam_fuse wf[3], bf[3];
     for (int l = 0; l < 3; ++l) {
-        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), slot(w[l]), slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
+        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), grad_slot(w[l]), grad_slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
         if (fa) {
             if (fa->fuse_for(w[l], &wf[l])) layers[l].w_fuse = &wf[l];
             if (fa->fuse_for(b[l], &bf[l])) layers[l].b_fuse = &bf[l];
@@ -625,7 +565,7 @@ Tensor conv_chain_mlp3_cross_entropy(const Tensor &x, const std::vector<ConvStag
         if (st.post == TH_CHAIN_MAXPOOL2) hw /= 4;
     if (cb_grad) {
         gap.d_cnt = cnt->d;
-        gap.d_gb = slot(cbias);
+        gap.d_gb = grad_slot(cbias);
         gap.hw = (int)hw;
         if (fa && fa->fuse_for(cbias, &gf)) gap.b_fuse = &gf;
     }
@@ -752,7 +692,6 @@ bool mlp3_fuse() {
 static bool g_conv_chain = [] { const char *e = std::getenv("TAPER_CONV_CHAIN"); return !(e && e[0] == '0'); }();
 void set_conv_chain(bool on) { g_conv_chain = on; }
 bool conv_chain_enabled() { return g_conv_chain; }
-static bool chain_fuse() { return g_conv_chain; }
 // TAPER_CHAIN_HEAD=0: the classifier behind a chain keeps its own launches (th_linear_xent_wide + the bias finish)
 static bool g_conv_chain_head = [] { const char *e = std::getenv("TAPER_CHAIN_HEAD"); return !(e && e[0] == '0'); }();
 void set_conv_chain_head(bool on) { g_conv_chain_head = on; }
@@ -795,7 +734,7 @@ Tensor Sequential::forward_prefix(const Tensor &input, size_t n_layers) const {
                 continue;
             }
         }
-        if (fuse && chain_fuse() && i + 1 < n_layers && PoolBiasScope::active() && x.shape().size() == 4) {
+        if (fuse && conv_chain_enabled() && i + 1 < n_layers && PoolBiasScope::active() && x.shape().size() == 4) {
             // Trainer steps: the whole run of Conv2dReLU(3x3, stride 1, pad 1) [+ MaxPool2d(2) | + global average pool] rows in front of the
             // classifier as ONE launch, when an instance is compiled for it (th_conv_chain_supported): the maps never leave the CU
             std::vector<ConvStage> stages;

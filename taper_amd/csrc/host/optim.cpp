@@ -192,13 +192,6 @@ FusedAdamScope::~FusedAdamScope() {
 Adam *FusedAdamScope::active() { return t_fused_adam; }
 
 namespace {
-thread_local const Communicator *t_tail_exchange = nullptr;
-}
-TailExchangeScope::TailExchangeScope(const Communicator *comm) : prev_(t_tail_exchange) { t_tail_exchange = comm; }
-TailExchangeScope::~TailExchangeScope() { t_tail_exchange = prev_; }
-const Communicator *TailExchangeScope::active() { return t_tail_exchange; }
-
-namespace {
 thread_local bool t_pool_bias = false;
 thread_local bool t_no_grad = false;
 }

@@ -248,6 +248,9 @@ struct StepLogSink {
     int64_t *d_state = nullptr;
     int64_t advance = 0;
     int32_t *d_adam_tick = nullptr;  // Adam's t += 1 folded into the loss kernel (fused-update steps)
+    // data parallel (Trainer-internal): the gradient launch of mlp_tail_cross_entropy / conv_chain_head_cross_entropy exchanges its sums
+    // with this communicator's peers itself (th_mlp_tail_dp / th_wide_head_grads_dp) -- what its fused epilogues apply is the mean
+    const class Communicator *exchange = nullptr;
 };
 // Classifier head = last Linear + cross-entropy as ONE launch (th_linear_xent_head), with the
 // backward products for loss.backward() from the root computed in the same launch.  Trainer-internal:
@@ -283,16 +286,13 @@ Tensor mlp3_cross_entropy(const Tensor &x, const Tensor (&w)[3], const Tensor (&
 bool mlp_tail_supported(const Tensor &x, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2);
 Tensor mlp_tail_cross_entropy(const Tensor &x, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,
                               const Tensor &targets, Tensor *n_correct_out, const StepLogSink *log);
-// Linear + ReLU, Linear, cross-entropy at LARGE batch: three launches (th_mlp2_xent), the batch's rows read where they lie -- a dense block or
-// rows of the resident dataset through the loader's index vector (no gathered copy).  Trainer-internal, like the forms above.
-bool mlp2_supported(const th_row_source &src, size_t batch, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2);
-// ... and for 2 or 3 Linear layers (one or two hidden layers: th_mlp2_xent / th_mlp2_xent_deep), first to last
+// Linear + ReLU (+ Linear + ReLU), Linear, cross-entropy at LARGE batch: three launches (th_mlp2_xent / th_mlp2_xent_deep), the batch's rows
+// read where they lie -- a dense block or rows of the resident dataset through the loader's index vector (no gathered copy).  `w`, `b`: 2 or
+// 3 Linear layers, first to last.  Trainer-internal, like the forms above.
 bool mlp2_params_ok(const std::vector<Tensor> &w, const std::vector<Tensor> &b);
 bool mlp2_supported(const th_row_source &src, size_t batch, const std::vector<Tensor> &w, const std::vector<Tensor> &b);
 Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vector<Tensor> &w, const std::vector<Tensor> &b,
                           Tensor *n_correct_out = nullptr, const StepLogSink *log = nullptr);
-Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2,
-                          Tensor *n_correct_out, const StepLogSink *log);
 // n_correct_out (optional): device scalar receiving accuracy()*B from the fused kernel
 Tensor cross_entropy_loss(const Tensor &logits, const Tensor &targets, Tensor *n_correct_out = nullptr,
                           const StepLogSink *log = nullptr);  // loss.rs:136-195
@@ -658,18 +658,6 @@ class FusedAdamScope {
     Adam *prev_;
 };
 
-// A data-parallel step whose gradient launch exchanges its slices itself (Trainer-internal): while active, mlp_tail_cross_entropy
-// launches th_mlp_tail_dp on this communicator -- what its fused epilogues apply is then the mean over the ranks.
-class TailExchangeScope {
-   public:
-    explicit TailExchangeScope(const class Communicator *comm);
-    ~TailExchangeScope();
-    static const class Communicator *active();
-
-   private:
-    const class Communicator *prev_;
-};
-
 // ---- data (src/data/mnist.rs) -----------------------------------------------------
 class MNISTDataset {
    public:
@@ -781,6 +769,21 @@ struct Metrics {  // train.rs:9-71
 // format of the checkpoint file (train.rs:283-285)
 std::string format_f32_display(float v);
 
+// The launch sequence of one step of the captured path, chosen by Trainer::plan_step before anything is launched; the step
+// (Trainer::enqueue_compute) and the key of the captured graphs both read it.
+enum class StepForm { Mlp2Rows, ChainMlp3, Mlp3, ChainHead, MlpTail, LinearHead, LinearWide, Layered };
+struct StepPlan {
+    StepForm form = StepForm::Layered;
+    size_t prefix = 0;                 // layers Sequential::forward_prefix runs in front of the fused part (Layered: the rest run one by one)
+    Linear *linear[3] = {};            // the fused part's Linear layers, first to last
+    std::vector<ConvStage> stages;     // ChainMlp3, ChainHead: the conv rows of the chain launch
+    bool fused_adam = false;           // what FusedAdamScope is opened with
+    bool pool_bias = false;            // what PoolBiasScope is opened with
+    bool conv_chain = false;           // conv_chain_enabled(): the prefix may take the one-launch conv chain
+    bool exchange = false;             // data parallel: the gradients are exchanged inside the gradient launch (StepLogSink::exchange)
+    void key(std::vector<uintptr_t> *out) const;   // appends what a captured step bakes in of it (the layers follow from the model)
+};
+
 class Trainer {  // train.rs:74-172
    public:
     std::shared_ptr<Module> model;
@@ -820,10 +823,8 @@ class Trainer {  // train.rs:74-172
     // gathers `steps` batches with one launch, then enqueues the compute of each step
     void enqueue_steps(const float *d_images, const float *d_labels, const int32_t *d_indices, int64_t n_indices,
                        size_t batch, size_t steps);
-    void enqueue_compute(float *d_xb, float *d_yb, size_t batch, const th_row_source *rows = nullptr);
-    bool mlp2_step(size_t batch, int64_t n_rows) const;   // this model at this batch takes th_mlp2_xent (rows read in place)
-    bool tail_exchange_step(size_t batch) const;          // data parallel: this step reduces its gradients inside its own launch (th_mlp_tail_dp)
-    bool chain_exchange_step(const Tensor &xin) const;    // ... the simple CNN's step does (th_wide_head_grads_dp)
+    void enqueue_compute(const StepPlan &plan, float *d_xb, float *d_yb, size_t batch, const th_row_source *rows = nullptr);
+    StepPlan plan_step(size_t batch, int64_t n_rows) const;   // n_rows: the rows the in-place form (Mlp2Rows) may read
     void drop_graphs();
     std::vector<std::pair<size_t, th_graph *>> graphs_;  // (steps per replay, graph), largest first
     std::vector<std::pair<size_t, th_graph *>> whole_graphs_;  // (steps, graph): state reset + that many full steps -- a whole call in one replay

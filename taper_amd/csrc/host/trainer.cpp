@@ -245,202 +245,184 @@ EpochResult Trainer::evaluate(DataLoader &loader) {  // train.rs:147-172
 // come from the device-resident dataset through the device cursor (ONE gather launch for a
 // whole chunk of steps), and the loss kernel itself appends {loss, n_correct} to the device
 // log and advances the step / cursor state.
-// The Linear layers of a model that is Linear + ReLU (+ Linear + ReLU) + Linear on the loader's 784-wide rows (BASELINE's 784-128-10,
-// examples/train_mnist.rs:40-48's 784-128-64-10); empty otherwise.
-static bool mlp2_layers(const Module *model, std::vector<Tensor> *w, std::vector<Tensor> *b) {
-    auto *seq = dynamic_cast<const Sequential *>(model);
-    if (!seq || !seq->fuse || (seq->layers.size() != 3 && seq->layers.size() != 5)) return false;
-    w->clear();
-    b->clear();
-    for (size_t i = 0; i < seq->layers.size(); ++i) {
-        if (i % 2 == 1) {
-            if (!dynamic_cast<ReLU *>(seq->layers[i].get())) return false;
-            continue;
-        }
-        auto *l = dynamic_cast<Linear *>(seq->layers[i].get());
-        if (!l) return false;
-        w->push_back(l->weight);
-        b->push_back(l->bias);
-    }
-    return (*w)[0].shape().size() == 2 && (*w)[0].shape()[1] == 784;   // (the loader's rows: data/mnist.rs:16)
+
+static const char *const step_form_names[] = {"mlp2_rows", "chain_mlp3", "mlp3", "chain_head", "mlp_tail", "linear_head", "linear_wide", "layered"};
+static_assert(sizeof step_form_names / sizeof *step_form_names == (size_t)StepForm::Layered + 1, "one name per StepForm");
+
+void StepPlan::key(std::vector<uintptr_t> *out) const {
+    out->push_back((uintptr_t)form);
+    out->push_back((uintptr_t)prefix);
+    out->push_back((uintptr_t)fused_adam | (uintptr_t)pool_bias << 1 | (uintptr_t)conv_chain << 2 | (uintptr_t)exchange << 3);
 }
 
-// this model at this batch takes th_mlp2_xent / th_mlp2_xent_deep, its rows read in place -- decided on EVERYTHING the step will ask for
-// (shapes, and the parameters' state: every one trains, no gradient already present, aligned storage), so that a model the large-batch
-// step cannot take (a frozen layer, gradients left by a manual backward) falls back to the gathered forms instead of failing inside the
-// step (r04 checked the shapes only)
-bool Trainer::mlp2_step(size_t batch, int64_t n_rows) const {
-    if (fuse_head < 2 || !sample_shape.empty() || batch < mlp2_min_batch()) return false;
-    std::vector<Tensor> w, b;
-    if (!(mlp2_layers(model.get(), &w, &b) && mlp2_params_ok(w, b) && mlp2_shapes_ok(batch, w, n_rows))) return false;
-    // Two hidden layers: below ~1 800 rows the two-launch classifier (th_mlp3_xent behind a gather) is the faster step where it applies --
-    // 26.7 / 30.3 / 32.8 / 39.2 us at 512 / 768 / 1 024 / 1 536 rows against 34.4 / 35.8 / 37.7 / 42.0 for th_mlp2_xent_deep, whose 16-row
-    // blocks each leave a whole [h2][h1] share of dW2 behind; 47.5 against 43.7 at 2 048 (tools/mlp_min_batch_probe.py, r05)
-    static const size_t deep_min = [] { const char *e = std::getenv("TAPER_MLP2_DEEP_MIN_BATCH"); return e ? (size_t)std::max(32, atoi(e)) : (size_t)1792; }();
-    if (w.size() == 3 && batch < deep_min && mlp3_fuse() &&
-        th_mlp3_supported((int)batch, (int)w[0].shape()[1], (int)w[0].shape()[0], (int)w[1].shape()[0], (int)w[2].shape()[0]))
-        return false;
-    return true;
-}
-
-void Trainer::enqueue_compute(float *d_xb, float *d_yb, size_t batch, const th_row_source *rows) {
-    int64_t *state = reinterpret_cast<int64_t *>(state_->d);
-    // Adam updates ride in the epilogues of the kernels that produce the gradients -- unless the
-    // gradients still have to be all-reduced across ranks first by a launch of their own.  The Linear + ReLU + Linear step over a
-    // peer-to-peer communicator reduces them INSIDE its gradient launch (th_mlp_tail_dp) and keeps the fused epilogues.
-    const bool dp_tail = comm && !rows && (tail_exchange_step(batch) || chain_exchange_step(shape_input(Tensor::from_device(d_xb, {batch, 784}), sample_shape)));
-    FusedAdamScope scope((fuse_adam && (!comm || dp_tail)) ? optimizer.get() : nullptr);
-    TailExchangeScope xscope(dp_tail ? comm.get() : nullptr);
-    PoolBiasScope pool_scope(fuse_head && dynamic_cast<Sequential *>(model.get()) != nullptr);
-    Tape::reset();
-    StepLogSink sink{metrics_->d, (int64_t)metrics_cap_, state, (int64_t)batch,
-                     FusedAdamScope::active() ? optimizer->d_tick() : nullptr};
-    Tensor ncorrect, loss;
+// The form of a step of `batch` rows, chosen on EVERYTHING the step will ask for -- the model's structure, the parameters' state (every one
+// trains, no gradient already present, aligned storage), the switches and the communicator -- so that no form has to fall back to another
+// once launches are enqueued (a frozen layer or gradients left by a manual backward take a slower form, they do not fail inside the step).
+// The fused ops keep their own TAPER_ASSERTs on the same predicates as the guard.  A predicate that reads the fused part's input is given a
+// stand-in of its shape: the step's rows in front of the first layer, else the [batch, in] output of the prefix, which is fresh and
+// requires a gradient exactly when a parameter in front of it does.
+StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
+    StepPlan p;
     auto *seq = dynamic_cast<Sequential *>(model.get());
-    if (rows) {
-        // Linear + ReLU (+ Linear + ReLU) + Linear at large batch: three launches for the whole step, the rows read in place (mlp2_step said so,
-        // on the same predicate, at the start of this chunk of steps; every step ends with zero_grad)
-        std::vector<Tensor> w, b;
-        TAPER_ASSERT(mlp2_layers(model.get(), &w, &b) && mlp2_supported(*rows, batch, w, b),
-                     "Trainer: the large-batch MLP step met parameters it cannot take (gradients already present?)");
-        loss = mlp2_cross_entropy(*rows, batch, w, b, &ncorrect, &sink);
-        loss.backward();
-        if (!(comm && optimizer->step_reduced(*comm))) {
-            reduce_grads(*this);
-            optimizer->step();
-            optimizer->set_step_guard(nullptr);   // (the guard is the communicator's word: it must not outlive this call in the optimizer -- ADVICE r04)
-        }
-        optimizer->zero_grad();
-        return;
-    }
-    Tensor x = Tensor::from_device(d_xb, {batch, 784});
-    Tensor y = Tensor::from_device(d_yb, {batch});
-    Tensor xin = shape_input(x, sample_shape);
-    Linear *last = (fuse_head && seq && !seq->layers.empty()) ? dynamic_cast<Linear *>(seq->layers.back().get()) : nullptr;
-    bool used_head = false;
-    Adam *adam = dynamic_cast<Adam *>(optimizer.get());
     const size_t nl = seq ? seq->layers.size() : 0;
-    Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && dynamic_cast<ReLU *>(seq->layers[nl - 2].get()))
-                         ? dynamic_cast<Linear *>(seq->layers[nl - 3].get()) : nullptr;
+    p.pool_bias = fuse_head && seq;
+    p.conv_chain = conv_chain_enabled();
+    auto linear = [&](size_t i) { return dynamic_cast<Linear *>(seq->layers[i].get()); };
+    auto relu = [&](size_t i) { return dynamic_cast<ReLU *>(seq->layers[i].get()) != nullptr; };
+    auto flatten = [&](size_t i) { auto *f = dynamic_cast<Flatten *>(seq->layers[i].get()); return f && f->start_dim == 1; };
+    const Tensor xin = shape_input(Tensor::from_device(nullptr, {batch, 784}), sample_shape);
+    auto input_of = [&](size_t i, size_t width) {
+        if (i == 0) return xin;
+        bool needs_grad = false;
+        for (size_t j = 0; j < i; ++j)
+            for (const Tensor &q : seq->layers[j]->parameters()) needs_grad = needs_grad || q.get_requires_grad();
+        Tensor h = Tensor::from_device(nullptr, {batch, width});
+        h.set_requires_grad(needs_grad);
+        return h;
+    };
+    // data parallel: the steps whose gradient launch can exchange with the peers keep their fused Adam epilogues, which apply the mean
+    const bool dp = comm && comm->is_p2p() && comm->fuse_adam && fuse_adam;
+    auto take = [&](StepForm f, size_t prefix, std::initializer_list<Linear *> ls, bool exchange = false) {
+        p.form = f;
+        p.prefix = prefix;
+        std::copy(ls.begin(), ls.end(), p.linear);
+        p.exchange = exchange;
+        // Adam updates ride in the epilogues of the kernels that produce the gradients -- unless the gradients still have to be all-reduced
+        // across ranks first, by a launch of their own
+        p.fused_adam = fuse_adam && (!comm || exchange);
+        return p;
+    };
+    Linear *last = (fuse_head && nl) ? linear(nl - 1) : nullptr;
+    Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && relu(nl - 2)) ? linear(nl - 3) : nullptr;
+    Linear *hidden0 = (hidden && mlp3_fuse() && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;
+    // the conv rows in front of the classifier as one launch with the classifier's rows in its last epilogue
+    const bool chain_head = fuse_head >= 2 && seq && seq->fuse && conv_chain_enabled() && conv_chain_head_enabled() && xin.shape().size() == 4;
+
+    // Linear + ReLU (+ Linear + ReLU) + Linear on the loader's 784-wide rows (BASELINE's 784-128-10, examples/train_mnist.rs:40-48's
+    // 784-128-64-10) at large batch: three launches for the whole step, the rows read in place
+    if (hidden && sample_shape.empty() && batch >= mlp2_min_batch() && (nl == 3 || (nl == 5 && relu(1) && linear(0)))) {
+        std::vector<Tensor> w, b;
+        for (size_t i = 0; i < nl; i += 2) {
+            w.push_back(linear(i)->weight);
+            b.push_back(linear(i)->bias);
+        }
+        // Two hidden layers: below ~1 800 rows the two-launch classifier (th_mlp3_xent behind a gather) is the faster step where it applies --
+        // 26.7 / 30.3 / 32.8 / 39.2 us at 512 / 768 / 1 024 / 1 536 rows against 34.4 / 35.8 / 37.7 / 42.0 for th_mlp2_xent_deep, whose 16-row
+        // blocks each leave a whole [h2][h1] share of dW2 behind; 47.5 against 43.7 at 2 048 (tools/mlp_min_batch_probe.py, r05)
+        static const size_t deep_min = [] { const char *e = std::getenv("TAPER_MLP2_DEEP_MIN_BATCH"); return e ? (size_t)std::max(32, atoi(e)) : (size_t)1792; }();
+        const bool mlp3_faster = nl == 5 && batch < deep_min && mlp3_fuse() &&
+                                 th_mlp3_supported((int)batch, (int)w[0].shape()[1], (int)w[0].shape()[0], (int)w[1].shape()[0], (int)w[2].shape()[0]);
+        if (w[0].shape()[1] == 784 && mlp2_params_ok(w, b) && mlp2_shapes_ok(batch, w, n_rows) && !mlp3_faster)
+            return nl == 3 ? take(StepForm::Mlp2Rows, 0, {hidden, last}) : take(StepForm::Mlp2Rows, 0, {linear(0), hidden, last});
+    }
     // Linear + ReLU + Linear + ReLU + Linear + cross-entropy: two launches for the whole classifier (th_mlp3_xent)
-    Linear *hidden0 = (hidden && mlp3_fuse() && nl >= 5 && dynamic_cast<ReLU *>(seq->layers[nl - 4].get()))
-                          ? dynamic_cast<Linear *>(seq->layers[nl - 5].get()) : nullptr;
     if (hidden0) {
         const Tensor w3[3] = {hidden0->weight, hidden->weight, last->weight}, b3[3] = {hidden0->bias, hidden->bias, last->bias};
-        // (shapes first: the prefix is only run once the form of the step is known)
-        const size_t in_f = hidden0->weight.shape()[1];
         // the reference CNN whole (conv rows + pools, global average pool, Flatten, this classifier): its rows in the chain launch
-        if (fuse_head >= 2 && seq->fuse && conv_chain_enabled() && conv_chain_head_enabled() && PoolBiasScope::active() && xin.shape().size() == 4 &&
-            nl >= 8) {
-            auto *fl = dynamic_cast<Flatten *>(seq->layers[nl - 6].get());
-            std::vector<ConvStage> stages;
-            if (fl && fl->start_dim == 1 && seq->conv_stages_at(0, nl - 6, &stages) == nl - 6 && conv_chain_mlp3_supported(xin, stages, w3, b3)) {
-                loss = conv_chain_mlp3_cross_entropy(xin, stages, w3, b3, y, &ncorrect, &sink);
-                used_head = true;
-            }
-        }
-        if (!used_head && th_mlp3_supported((int)batch, (int)in_f, (int)w3[0].shape()[0], (int)w3[1].shape()[0], (int)w3[2].shape()[0])) {
-            Tensor xh = seq->forward_prefix(xin, nl - 5);
-            if (mlp3_supported(xh, w3, b3)) {
-                loss = mlp3_cross_entropy(xh, w3, b3, y, &ncorrect, &sink);
-                used_head = true;
-            } else {
-                // (cannot happen for parameters homed in this Trainer's optimizer; keep the step correct anyway)
-                if (adam) adam->flush_deferred();
-                Tensor h = xh;
-                for (size_t i = nl - 5; i < nl; ++i) h = seq->layers[i]->forward(h);
-                loss = cross_entropy_loss(h, y, &ncorrect, &sink);
-                used_head = true;
-            }
-        }
+        if (chain_head && nl >= 8 && flatten(nl - 6) && seq->conv_stages_at(0, nl - 6, &p.stages) == nl - 6 &&
+            conv_chain_mlp3_supported(xin, p.stages, w3, b3))
+            return take(StepForm::ChainMlp3, 0, {hidden0, hidden, last});
+        p.stages.clear();
+        const size_t in_f = hidden0->weight.shape()[1];
+        // (parameters th_mlp3_xent cannot take -- a frozen layer, a Linear without a bias: the classifier runs layer by layer, unfused)
+        if (th_mlp3_supported((int)batch, (int)in_f, (int)w3[0].shape()[0], (int)w3[1].shape()[0], (int)w3[2].shape()[0]))
+            return mlp3_supported(input_of(nl - 5, in_f), w3, b3) ? take(StepForm::Mlp3, nl - 5, {hidden0, hidden, last})
+                                                                  : take(StepForm::Layered, nl - 5, {});
     }
-    if (last && !hidden && !used_head && fuse_head >= 2 && seq->fuse && conv_chain_enabled() && conv_chain_head_enabled() && nl >= 3 &&
-        PoolBiasScope::active() && xin.shape().size() == 4) {
-        // conv rows + Flatten + Linear + cross-entropy (the simple CNN): two launches per step
-        auto *fl = dynamic_cast<Flatten *>(seq->layers[nl - 2].get());
-        std::vector<ConvStage> stages;
-        if (fl && fl->start_dim == 1 && seq->conv_stages_at(0, nl - 2, &stages) == nl - 2 &&
-            conv_chain_head_supported(xin, stages, last->weight, last->bias)) {
-            loss = conv_chain_head_cross_entropy(xin, stages, last->weight, last->bias, y, &ncorrect, &sink);
-            used_head = true;
-        }
+    // conv rows + Flatten + Linear + cross-entropy (the simple CNN): two launches per step
+    if (last && !hidden && chain_head && nl >= 3 && flatten(nl - 2) && seq->conv_stages_at(0, nl - 2, &p.stages) == nl - 2 &&
+        conv_chain_head_supported(xin, p.stages, last->weight, last->bias)) {
+        // (data parallel: the compiled simple chain, whose tick carries the step number, and the batch sums' launch can take the exchange)
+        const bool exchange = dp && xin.conv_chain_head_supported(p.stages, (int)last->weight.shape()[0]) == 2 &&
+                              comm->wide_exchange_ok((int)batch, (int)last->weight.shape()[1], (int)last->weight.shape()[0],
+                                                     (int)p.stages.back().weight.shape()[0]);
+        return take(StepForm::ChainHead, 0, {last}, exchange);
     }
-    if (last && !used_head) {
-        Tensor h;
-        if (hidden) {   // Linear + ReLU + Linear + cross-entropy: two launches per step
-            Tensor xh = seq->forward_prefix(xin, nl - 3);
-            if (mlp_tail_supported(xh, hidden->weight, hidden->bias, last->weight, last->bias)) {
-                if (adam && FusedAdamScope::active()) adam->set_carry_deferred(true);   // flushed by enqueue_steps
-                loss = mlp_tail_cross_entropy(xh, hidden->weight, hidden->bias, last->weight, last->bias, y, &ncorrect, &sink);
-                used_head = true;
-            } else {
-                if (adam) adam->flush_deferred();
-                h = hidden->forward_fused_relu(xh);
-            }
-        } else {
+    p.stages.clear();
+    if (!last) return take(StepForm::Layered, nl, {});
+    // Linear + ReLU + Linear + cross-entropy: two launches per step
+    if (hidden && mlp_tail_supported(input_of(nl - 3, hidden->weight.shape()[1]), hidden->weight, hidden->bias, last->weight, last->bias)) {
+        // (data parallel: straight on the loader's rows with both biases, and the communicator can exchange the slices inside the launch)
+        const bool exchange = dp && nl == 3 && sample_shape.empty() && hidden->bias.defined() && last->bias.defined() &&
+                              comm->tail_exchange_ok((int)batch, 784, (int)hidden->weight.shape()[0], (int)last->weight.shape()[0]);
+        return take(StepForm::MlpTail, nl - 3, {hidden, last}, exchange);
+    }
+    const Tensor h = input_of(nl - 1, last->weight.shape()[1]);
+    if (linear_cross_entropy_supported(h, last->weight) && !last->weight.has_grad() && !(last->bias.defined() && last->bias.has_grad()))
+        return take(StepForm::LinearHead, nl - 1, {last});
+    if (fuse_head >= 2 && linear_cross_entropy_wide_supported(h, last->weight, last->bias)) return take(StepForm::LinearWide, nl - 1, {last});
+    return take(StepForm::Layered, nl, {});
+}
+
+void Trainer::enqueue_compute(const StepPlan &plan, float *d_xb, float *d_yb, size_t batch, const th_row_source *rows) {
+    int64_t *state = reinterpret_cast<int64_t *>(state_->d);
+    FusedAdamScope scope(plan.fused_adam ? optimizer.get() : nullptr);
+    PoolBiasScope pool_scope(plan.pool_bias);
+    Tape::reset();
+    StepLogSink sink{metrics_->d, (int64_t)metrics_cap_, state, (int64_t)batch, plan.fused_adam ? optimizer->d_tick() : nullptr,
+                     plan.exchange ? comm.get() : nullptr};
+    Adam *adam = optimizer.get();
+    auto *seq = dynamic_cast<Sequential *>(model.get());
+    Linear *const *L = plan.linear;
+    Tensor ncorrect, loss, xin, y;
+    if (!rows) {
+        xin = shape_input(Tensor::from_device(d_xb, {batch, 784}), sample_shape);
+        y = Tensor::from_device(d_yb, {batch});
+    }
+    switch (plan.form) {
+        case StepForm::Mlp2Rows: {   // (every step ends with zero_grad: the parameters' state plan_step saw holds for each)
+            std::vector<Tensor> w, b;
+            for (Linear *l : plan.linear)
+                if (l) {
+                    w.push_back(l->weight);
+                    b.push_back(l->bias);
+                }
+            loss = mlp2_cross_entropy(*rows, batch, w, b, &ncorrect, &sink);
+            break;
+        }
+        case StepForm::ChainMlp3:
+        case StepForm::Mlp3: {
+            const Tensor w3[3] = {L[0]->weight, L[1]->weight, L[2]->weight}, b3[3] = {L[0]->bias, L[1]->bias, L[2]->bias};
+            loss = plan.form == StepForm::ChainMlp3 ? conv_chain_mlp3_cross_entropy(xin, plan.stages, w3, b3, y, &ncorrect, &sink)
+                                                    : mlp3_cross_entropy(seq->forward_prefix(xin, plan.prefix), w3, b3, y, &ncorrect, &sink);
+            break;
+        }
+        case StepForm::ChainHead:
+            loss = conv_chain_head_cross_entropy(xin, plan.stages, L[0]->weight, L[0]->bias, y, &ncorrect, &sink);
+            break;
+        case StepForm::MlpTail: {
+            Tensor xh = seq->forward_prefix(xin, plan.prefix);
+            if (plan.fused_adam) adam->set_carry_deferred(true);   // flushed by enqueue_steps
+            loss = mlp_tail_cross_entropy(xh, L[0]->weight, L[0]->bias, L[1]->weight, L[1]->bias, y, &ncorrect, &sink);
+            break;
+        }
+        case StepForm::LinearHead:
+        case StepForm::LinearWide: {
             // updates a previous tail step left for its successor must run with ITS counter: before this step's tick
-            if (adam) adam->flush_deferred();
-            h = seq->forward_prefix(xin, nl - 1);
+            adam->flush_deferred();
+            Tensor h = seq->forward_prefix(xin, plan.prefix);
+            loss = plan.form == StepForm::LinearHead ? linear_cross_entropy(h, L[0]->weight, L[0]->bias, y, &ncorrect, &sink)
+                                                     : linear_cross_entropy_wide(h, L[0]->weight, L[0]->bias, y, &ncorrect, &sink);
+            break;
         }
-        if (!used_head) {
-            if (linear_cross_entropy_supported(h, last->weight) && !last->weight.has_grad() &&
-                !(last->bias.defined() && last->bias.has_grad()))
-                loss = linear_cross_entropy(h, last->weight, last->bias, y, &ncorrect, &sink);
-            else if (fuse_head >= 2 && linear_cross_entropy_wide_supported(h, last->weight, last->bias))
-                loss = linear_cross_entropy_wide(h, last->weight, last->bias, y, &ncorrect, &sink);
-            else
-                loss = cross_entropy_loss(last->forward(h), y, &ncorrect, &sink);
-            used_head = true;
+        case StepForm::Layered: {
+            adam->flush_deferred();
+            Tensor h = seq ? seq->forward_prefix(xin, plan.prefix) : model->forward(xin);
+            for (size_t i = plan.prefix; seq && i < seq->layers.size(); ++i) h = seq->layers[i]->forward(h);
+            loss = cross_entropy_loss(h, y, &ncorrect, &sink);
+            break;
         }
-    }
-    if (!used_head) {
-        if (adam) adam->flush_deferred();
-        loss = cross_entropy_loss(model->forward(xin), y, &ncorrect, &sink);
     }
     loss.backward();
-    if (dp_tail) {
+    if (plan.exchange) {
         optimizer->step();   // (nothing is left: every update ran in an epilogue, on the mean gradient, or waits for the next step's first launch)
     } else if (!(comm && optimizer->step_reduced(*comm))) {   // peer-to-peer communicator: all-reduce + Adam in one launch
         reduce_grads(*this);
         optimizer->step();
-        optimizer->set_step_guard(nullptr);
+        optimizer->set_step_guard(nullptr);   // (the guard is the communicator's word: it must not outlive this call in the optimizer -- ADVICE r04)
     }
     optimizer->zero_grad();
-    if (adam) adam->set_carry_deferred(false);
-}
-
-// this step is the simple CNN's (conv rows ending in a pooled map, Flatten, Linear, cross-entropy: two launches), the optimizer is Adam with
-// fused updates on, and the communicator can exchange the batch sums inside their launch: the single-GPU step with the mean gradient in the
-// second launch's epilogues.  The same conditions the step's own choice of form checks (enqueue_compute), decided before the scopes open.
-bool Trainer::chain_exchange_step(const Tensor &xin) const {
-    if (!comm || !comm->is_p2p() || !comm->fuse_adam || !fuse_adam || fuse_head < 2 || xin.shape().size() != 4) return false;
-    auto *seq = dynamic_cast<Sequential *>(model.get());
-    if (!seq || !seq->fuse || !conv_chain_enabled() || !conv_chain_head_enabled() || !dynamic_cast<Adam *>(optimizer.get())) return false;
-    const size_t nl = seq->layers.size();
-    if (nl < 3) return false;
-    auto *last = dynamic_cast<Linear *>(seq->layers.back().get());
-    auto *fl = dynamic_cast<Flatten *>(seq->layers[nl - 2].get());
-    if (!last || !fl || fl->start_dim != 1) return false;
-    std::vector<ConvStage> stages;
-    if (seq->conv_stages_at(0, nl - 2, &stages) != nl - 2 || !conv_chain_head_supported(xin, stages, last->weight, last->bias)) return false;
-    if (xin.conv_chain_head_supported(stages, (int)last->weight.shape()[0]) != 2) return false;      // the compiled simple chain: its tick carries the step number
-    return comm->wide_exchange_ok((int)xin.shape()[0], (int)last->weight.shape()[1], (int)last->weight.shape()[0], (int)stages.back().weight.shape()[0]);
-}
-
-// this step is Linear + ReLU + Linear + cross-entropy straight on the loader's rows, every parameter trains and has no gradient yet, the
-// optimizer is Adam with fused updates on, and the communicator can exchange the slices inside the launch: the two-launch step of one GPU,
-// with the mean gradient in its epilogues
-bool Trainer::tail_exchange_step(size_t batch) const {
-    if (!comm || !comm->is_p2p() || !comm->fuse_adam || !fuse_adam || fuse_head < 2 || !sample_shape.empty()) return false;
-    auto *seq = dynamic_cast<Sequential *>(model.get());
-    if (!seq || !seq->fuse || seq->layers.size() != 3 || !dynamic_cast<Adam *>(optimizer.get())) return false;
-    auto *l1 = dynamic_cast<Linear *>(seq->layers[0].get());
-    auto *l2 = dynamic_cast<Linear *>(seq->layers[2].get());
-    if (!l1 || !l2 || !dynamic_cast<ReLU *>(seq->layers[1].get()) || l1->weight.shape()[1] != 784) return false;
-    for (const Tensor *p : {&l1->weight, &l1->bias, &l2->weight, &l2->bias})
-        if (p->defined() && (!p->get_requires_grad() || p->has_grad())) return false;
-    if (!l1->bias.defined() || !l2->bias.defined()) return false;
-    return comm->tail_exchange_ok((int)batch, 784, (int)l1->weight.shape()[0], (int)l2->weight.shape()[0]);
+    adam->set_carry_deferred(false);
 }
 
 void Trainer::enqueue_steps(const float *d_images, const float *d_labels, const int32_t *d_indices, int64_t n_indices,
@@ -453,22 +435,23 @@ void Trainer::enqueue_steps(const float *d_images, const float *d_labels, const 
         Guard(const uint32_t *w, uint32_t *step) { TH(th_ctx_set_update_guard(Device::ctx(), w, step)); }
         ~Guard() { th_ctx_set_update_guard(Device::ctx(), nullptr, nullptr); }
     } guard(comm && comm->is_p2p() ? comm->error_word() : nullptr, comm && comm->is_p2p() ? comm->step_word() : nullptr);
-    if (mlp2_step(batch, d_indices ? n_indices : (int64_t)batch)) {
+    const StepPlan plan = plan_step(batch, d_indices ? n_indices : (int64_t)batch);
+    if (plan.form == StepForm::Mlp2Rows) {
         // the step reads its rows where they lie: through the index vector at the device cursor (every step's log advances it), or the
         // dataset itself for the one-step epoch in index order -- no gather launch, no staging buffer
         const th_row_source rows{d_images, d_labels, d_indices, d_indices ? state + 1 : nullptr, d_indices ? n_indices : 0,
                                  d_indices ? n_indices : (int64_t)batch};
-        for (size_t s = 0; s < steps; ++s) enqueue_compute(nullptr, nullptr, batch, &rows);
+        for (size_t s = 0; s < steps; ++s) enqueue_compute(plan, nullptr, nullptr, batch, &rows);
     } else if (d_indices == nullptr) {
         // one step over the whole dataset in index order: the "gathered" batch IS the dataset (no copy)
-        enqueue_compute(const_cast<float *>(d_images), const_cast<float *>(d_labels), batch);
+        enqueue_compute(plan, const_cast<float *>(d_images), const_cast<float *>(d_labels), batch);
     } else {
         TH(th_gather_batch(Device::ctx(), d_images, d_labels, d_indices, n_indices, state + 1, (int)(batch * steps), 784, xb_->d,
                            yb_->d));
-        for (size_t s = 0; s < steps; ++s) enqueue_compute(xb_->d + s * batch * 784, yb_->d + s * batch, batch);
+        for (size_t s = 0; s < steps; ++s) enqueue_compute(plan, xb_->d + s * batch * 784, yb_->d + s * batch, batch);
     }
     // a tail step leaves the head's W / b updates for its successor's first launch; the last one's run here
-    if (auto *adam = dynamic_cast<Adam *>(optimizer.get())) adam->flush_deferred();
+    optimizer->flush_deferred();
 }
 
 void Trainer::drop_graphs() {
@@ -490,16 +473,17 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
     size_t nb = loader.num_batches();
     if (max_steps && max_steps < nb) nb = max_steps;
     const size_t n_full = std::min(nb, n / bs);
-    // steps per replay: graph_chunk, capped so that the gathered batches of one chunk stay within 256 MB (steps that read their rows in
-    // place -- mlp2_step -- gather nothing)
-    const bool full_in_place = mlp2_step(bs, (int64_t)n);
+    // the forms of the full and the last, partial batch; steps per replay: graph_chunk, capped so that the gathered batches of one chunk stay
+    // within 256 MB (steps that read their rows in place gather nothing)
+    const size_t rem_rows = nb > n_full ? n - n_full * bs : 0;
+    const StepPlan plan = plan_step(bs, (int64_t)n), rem_plan = rem_rows ? plan_step(rem_rows, (int64_t)n) : StepPlan{};
+    const bool full_in_place = plan.form == StepForm::Mlp2Rows;
     const size_t chunk = full_in_place ? std::max<size_t>(graph_chunk, 1) : std::max<size_t>(std::min<size_t>(graph_chunk, ((size_t)1 << 26) / (bs * 784)), 1);
     const float *d_img = ds.images.dptr(), *d_lab = ds.labels.dptr();
     // full batch, index order (mnist.rs:355-363 without shuffle): the gather would be an identity copy of 188 MB
     const int32_t *d_idx = (!loader.shuffled() && bs >= n && nb == 1) ? nullptr : loader.d_indices();
     // staging rows for the gathered forms: a chunk of full batches, and / or the last partial batch when it is too small for the in-place form
-    const size_t rem_rows = nb > n_full ? n - n_full * bs : 0;
-    const size_t stage_rows = std::max(full_in_place ? (size_t)0 : chunk * bs, (rem_rows && !mlp2_step(rem_rows, (int64_t)n)) ? rem_rows : (size_t)0);
+    const size_t stage_rows = std::max(full_in_place ? (size_t)0 : chunk * bs, (rem_rows && rem_plan.form != StepForm::Mlp2Rows) ? rem_rows : (size_t)0);
     if (d_idx && stage_rows && (!xb_ || xb_->n < stage_rows * 784)) {   // (the zero-copy forms read the dataset in place: no staging buffers)
         drop_graphs();
         xb_ = Buffer::alloc(stage_rows * 784);
@@ -515,14 +499,16 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         // host reads it after ONE stream synchronisation -- a staged device-to-host copy costs a short run (the contract's 20 steps) ~20 us
         metrics_ = Buffer::alloc_host(2 * metrics_cap_);
     }
-    // Everything a captured step bakes in as a kernel argument or as a choice of launch sequence: the dataset and index
-    // buffers (two loaders over one dataset share the images but own their index vectors), the epoch length the gather
-    // wraps at, the label buffer, the fusion switches, the input reshape, the communicator, the optimizer's arenas.
-    // (nullptr indices = the zero-copy full-batch form, a different graph.)  Any mismatch re-records.
-    std::vector<uintptr_t> key{(uintptr_t)d_img, (uintptr_t)d_lab, (uintptr_t)d_idx, (uintptr_t)n, (uintptr_t)bs, (uintptr_t)fuse_head,
-                               (uintptr_t)fuse_adam, (uintptr_t)comm.get(), (uintptr_t)model.get(), (uintptr_t)optimizer.get(),
-                               (uintptr_t)optimizer->flat().p_arena->d, (uintptr_t)optimizer->flat().g_arena->d, (uintptr_t)(xb_ ? xb_->d : nullptr),
-                               (uintptr_t)metrics_->d};
+    // Everything a captured step bakes in: the full batch's plan (the choice of launch sequence, and every switch it read -- a communicator's
+    // inkernel / fuse_adam included), then the kernel arguments and what the layered path reads: the dataset and index buffers (two loaders
+    // over one dataset share the images but own their index vectors), the epoch length the gather wraps at, the label buffer, the input
+    // reshape, the communicator, the optimizer's arenas.  (nullptr indices = the zero-copy full-batch form, a different graph.)  Any
+    // mismatch re-records.  (The last, partial batch is never captured -- enqueue_steps plans it afresh every call -- and a call cut short
+    // by max_steps has none: keying on its plan would re-record the graphs whenever such calls alternate with whole epochs.)
+    std::vector<uintptr_t> key{(uintptr_t)d_img, (uintptr_t)d_lab, (uintptr_t)d_idx, (uintptr_t)n, (uintptr_t)bs, (uintptr_t)comm.get(),
+                               (uintptr_t)model.get(), (uintptr_t)optimizer.get(), (uintptr_t)optimizer->flat().p_arena->d,
+                               (uintptr_t)optimizer->flat().g_arena->d, (uintptr_t)(xb_ ? xb_->d : nullptr), (uintptr_t)metrics_->d};
+    plan.key(&key);
     for (size_t d : sample_shape) key.push_back((uintptr_t)d);
     // beta1 / beta2 / eps / weight decay are kernel arguments BY VALUE (only lr and t live in device memory)
     for (float h : {optimizer->beta1(), optimizer->beta2(), optimizer->eps(), optimizer->weight_decay()}) {
@@ -531,11 +517,7 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         key.push_back(bits);
     }
     key.push_back((uintptr_t)full_backward());
-    key.push_back((uintptr_t)conv_chain_enabled());
-    key.push_back((uintptr_t)conv_chain_head_enabled());
-    // what the choice of launch sequence reads of the parameters themselves (Trainer::mlp2_step, tail_exchange_step: every parameter trains and
-    // has no gradient yet): freezing a layer behind a capture must re-record, not replay the other sequence's graphs
-    key.push_back((uintptr_t)full_in_place);
+    // which parameters train, as the layered path's tape bakes it in (freezing a layer behind a capture re-records -- ADVICE r05)
     {
         uintptr_t h = 1469598103934665603ull;
         for (const Tensor &p : optimizer->flat().params) h = (h ^ (uintptr_t)(p.get_requires_grad() ? 2 : 1)) * 1099511628211ull;
@@ -694,7 +676,8 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
     const double us_enqueued = us_since(t_enter);
     Device::sync();
     check_comm();
-    if (trace) fprintf(stderr, "taper trace: train_epoch_graph %zu steps: state reset enqueued at %.1f - %.1f us, all enqueued after %.1f us, stream idle after %.1f us\n", nb, us_prep, us_fill, us_enqueued, us_since(t_enter));
+    if (trace) fprintf(stderr, "taper trace: train_epoch_graph %zu steps (%s%s%s): state reset enqueued at %.1f - %.1f us, all enqueued after %.1f us, stream idle after %.1f us\n", nb,
+                       step_form_names[(int)plan.form], rem_rows ? ", last batch " : "", rem_rows ? step_form_names[(int)rem_plan.form] : "", us_prep, us_fill, us_enqueued, us_since(t_enter));
     const float *mt = metrics_->d;   // host-visible (th_host_malloc); every step's entry has landed once the stream is idle
     EpochResult r;
     r.num_batches = nb;

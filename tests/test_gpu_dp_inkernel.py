@@ -127,3 +127,44 @@ def test_loopback_simple_cnn_step_is_the_single_gpu_step_bit_for_bit(batch):
     assert got[2] == ref[2] == 2 * steps
     np.testing.assert_array_equal(got[3], ref[3])
     np.testing.assert_array_equal(got[4], ref[4])
+
+
+
+def _two_epochs_switching_off(T, switch, fresh_trainer):
+    """MLP 784-128-10 at batch 64 over a one-rank peer-to-peer communicator (the loopback one has no all-reduce launch to fall back on):
+    one captured epoch in the in-launch form -- with one rank, the single-GPU launches and their fused Adam epilogues, no all-reduce --
+    then `switch`(False) and a second epoch, through the same Trainer or through a new one on the same model, optimizer and communicator"""
+    batch, steps = 64, 5
+    model = _mlp(T)
+    opt = T.Adam(model.parameters(), 1e-3, None, None, 1e-4)
+    comm = T.Communicator.p2p(1, 0)
+    comm.connect(comm.export_arena(opt))
+    tr = T.Trainer(model, opt, comm=comm)
+    x, y = _data(batch * steps)
+    loader = T.DataLoader(T.MNISTDataset.from_host(x, y), batch, False)
+    first = tr.run_epoch(loader, T.Trainer.GRAPH)["losses"]
+    stats = comm.stats()
+    getattr(comm, switch)(False)
+    if fresh_trainer:
+        tr = T.Trainer(model, opt, comm=comm)
+    second = tr.run_epoch(loader, T.Trainer.GRAPH)["losses"]
+    assert not comm.timed_out()
+    return first, second, [p.data() for p in model.parameters()], stats, comm
+
+
+@pytest.mark.parametrize("switch", ["set_inkernel", "set_fuse_adam"])
+def test_switching_the_exchange_off_re_records_the_captured_step(switch):
+    """the captured graphs are keyed on the step's plan, which reads the communicator's switches -- turning the in-launch
+    exchange off after a capture takes the all-reduce form from the next epoch on instead of replaying the recorded launches"""
+    import taper_amd as T
+    got = _two_epochs_switching_off(T, switch, False)
+    ref = _two_epochs_switching_off(T, switch, True)
+    first, second, params, stats, comm = got
+    assert stats["fused"] + stats["inplace"] == 0, stats          # the first epoch: the in-launch form, no all-reduce launch
+    after = comm.stats()
+    assert after["fused"] + after["inplace"] > 0, after             # the second: the all-reduce form, recorded anew
+    assert comm.inkernel_launches() == 0
+    np.testing.assert_array_equal(first, ref[0])
+    np.testing.assert_array_equal(second, ref[1])
+    for a, b in zip(params, ref[2]):
+        np.testing.assert_array_equal(a, b)
