@@ -393,6 +393,25 @@ typedef struct th_qtensor {
 } th_qtensor;
 int th_dequantize_multi(th_ctx *ctx, const th_qtensor *h_items, int n_items);
 
+/* ---- quantization-aware training: fake quantization (src/quantization/fake_quantize.rs, csrc/fake_quant.hip) ---- */
+/* A weight list through the storage codecs and back: TH_QTYPE_INT8 is th_quantize_int8 + th_dequantize_int8 (finite min / max ->
+ * d_params = {min_val, scale}, written on the device; nullable), TH_QTYPE_F16 the half codec both ways -- bit for bit.  d_y must not
+ * overlap d_x.  d_items is a DEVICE array of n_items descriptors (uploaded by the caller; nothing is read back on the host): two launches
+ * for the whole list, no host synchronisation, capturable. */
+typedef struct th_fq_item {
+    const float *d_x;
+    float *d_y;
+    float *d_params;
+    int64_t n;
+    int qtype;
+} th_fq_item;
+int th_fake_quant_multi(th_ctx *ctx, const th_fq_item *d_items, int n_items);
+/* One activation tensor (fake_quantize.rs:71-118, 155-162 with zero_point 0): TH_QTYPE_INT8 is symmetric per tensor with the scale of
+ * this tensor -- finite min / max (all zero -> (0, 1); all equal to m -> (0.9 m, 1.1 m)), scale = max(|min|, |max|) / 127,
+ * y = clamp(round(x / scale) as i32, -128, 127) * scale -- written to d_scale (nullable; 0 for TH_QTYPE_F16, the half round trip).
+ * Two launches (int8) or one (f16), capturable. */
+int th_fake_quant_act(th_ctx *ctx, const float *d_x, float *d_y, int64_t n, int qtype, float *d_scale);
+
 /* ---- broadcast / reduce / layout: src/tensor.rs ---------------------- */
 int th_transpose2d(th_ctx *ctx, const float *d_in, float *d_out, int rows, int cols);      /* tensor.rs:544-566 */
 /* dst[r*dst_ld + c] = src[r*src_ld + c] for r < rows, c < cols: the strided block copies behind slice_channels /

@@ -144,6 +144,30 @@ int tp_qmodule_num_tensors(const tp_qmodule *q, int *out);
 int tp_qmodule_tensor_len(const tp_qmodule *q, int i, size_t *out);
 int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params, int *qtype);
 
+/* ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager}.rs) ----
+ * config: qtype 0 Int8 / 1 Float16 (2..4 refused like tp_module_quantize), activations (fake-quantize each layer's output, before any
+ * ReLU), symmetric (must be 1) and per_channel (must be 0) -- a refused config fails before the device is touched.  module_id: the
+ * qat_manager key (nullable: "linear_<in>" / "conv2d_<in>_<out>" as qat_layers.rs names them).  Initial weights are those of
+ * tp_linear_new / tp_conv2d_new with the same seed; parameters() are the inner layer's; tp_module_quantize packs the inner layer.
+ * While active a layer runs on the codec's round trip of its weight AND bias (what tp_module_quantize packs) and, with activations, of
+ * its output; gradients pass straight through to the f32 masters. */
+int tp_qat_linear_new(int in_features, int out_features, int with_bias, int qtype, int activations, int symmetric, int per_channel,
+                      const char *module_id, uint64_t seed, tp_module **out);
+/* groups 1 only; fuse_relu: a QAT Conv2dReLU (the ReLU follows the activation fake-quant) */
+int tp_qat_conv2d_new(int in_ch, int out_ch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, int with_bias, int fuse_relu,
+                      int qtype, int activations, int symmetric, int per_channel, const char *module_id, uint64_t seed, tp_module **out);
+/* the process-wide state (qat_manager.rs global::): QAT enabled (default 0), training mode (default 1); a QAT layer fake-quantizes
+ * while both are on and its own flag is (tp_qat_module_set_enabled also sets the manager's entry of its id) */
+int tp_qat_enable(int on);
+int tp_qat_set_training(int on);
+int tp_qat_is_training(int *out);
+int tp_qat_module_set_enabled(tp_module *m, int on);
+int tp_qat_status(int *global_enabled, int *training_mode, size_t *module_count, size_t *enabled_modules);
+/* observer readout: {weight min_val, weight scale, activation scale} of the layer's last fake-quantized forward (int8; zeros before) */
+int tp_qat_module_observed(const tp_module *m, float *out3);
+/* the round trip of the layer's weight (which 0) or bias (1) that its last active forward ran with (a copy; no gradient) */
+int tp_qat_module_fake_quantized(const tp_module *m, int which, tp_tensor **out);
+
 /* ---- optim (src/optim.rs) ---- */
 int tp_adam_new(tp_tensor *const *params, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                 tp_optim **out);

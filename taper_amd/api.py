@@ -435,6 +435,100 @@ class Sequential(Module):
         super().__init__(_mk(host.tp_sequential_new, "Sequential::new", arr, len(self.layers), 1 if fuse else 0))
 
 
+
+# -- src/quantization/{qat_config,qat_layers,qat_manager}.rs ---------------------------
+class QATConfig:
+    """qat_config.rs: the codec the QAT layers train against ("int8" | "float16") and whether their outputs are fake-quantized too.
+    int4 / bfloat16 / nf4, symmetric=False and per_channel=True are refused here, before anything reaches the device."""
+    QTYPES = QuantizedModule.QTYPES
+
+    def __init__(self, qtype="int8", activations=True, symmetric=True, per_channel=False):
+        if qtype not in self.QTYPES:
+            raise TaperError(f"QATConfig: unknown qtype {qtype!r}")
+        if qtype in ("int4", "bfloat16", "nf4"):
+            raise TaperError(f"QAT quantization type {qtype} is not supported: the reference's codec for it is a placeholder that returns zeros")
+        if not symmetric:
+            raise TaperError("QAT with symmetric = false is not supported: the reference's asymmetric zero point and clamp cut off the "
+                             "upper half of the range")
+        if per_channel:
+            raise TaperError("QAT with per_channel = true is not supported: the reference never implements per-channel scales")
+        self.qtype, self.activations, self.symmetric, self.per_channel = qtype, bool(activations), bool(symmetric), bool(per_channel)
+
+    def _args(self):
+        return self.QTYPES[self.qtype], int(self.activations), int(self.symmetric), int(self.per_channel)
+
+
+class _QATLayer(Module):
+    def enable_qat(self, enabled=True):
+        """qat_layers.rs:68-71: the layer's own flag and the QAT manager's entry of its id"""
+        tp_check(host.tp_qat_module_set_enabled(self._h, 1 if enabled else 0), "enable_qat")
+
+    def observed(self):
+        """the observer readout of the last fake-quantized forward: weight (min_val, scale) and the activation scale (int8)"""
+        out = (C.c_float * 3)()
+        tp_check(host.tp_qat_module_observed(self._h, out), "QAT observed")
+        return dict(weight_min=float(out[0]), weight_scale=float(out[1]), activation_scale=float(out[2]))
+
+    def fake_quantized(self, which="weight") -> Tensor:
+        """the round trip of the weight ("weight") or the bias ("bias") the last active forward ran with (a copy)"""
+        h = _p()
+        tp_check(host.tp_qat_module_fake_quantized(self._h, 0 if which == "weight" else 1, C.byref(h)), "QAT fake_quantized")
+        return Tensor(_h=h.value)
+
+    @property
+    def weight(self): return self.parameters()[0]
+
+    @property
+    def bias(self):
+        p = self.parameters()
+        return p[1] if len(p) > 1 else None
+
+
+class QATLinear(_QATLayer):
+    """qat_layers.rs:10-134: a Linear (same initial weights for the same seed) trained against its quantized weights"""
+
+    def __init__(self, in_features, out_features, with_bias=True, config=None, module_id=None, seed=1):
+        c = config or QATConfig()
+        super().__init__(_mk(host.tp_qat_linear_new, "QATLinear::new", int(in_features), int(out_features), 1 if with_bias else 0,
+                             *c._args(), module_id.encode() if module_id else None, int(seed)))
+
+
+class QATConv2d(_QATLayer):
+    """qat_layers.rs:136-265 (groups 1); relu=True stands in for Conv2dReLU, its ReLU behind the activation fake-quant"""
+
+    def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, bias=True, relu=False, config=None, module_id=None, seed=1):
+        c = config or QATConfig()
+        s, p = stride or (1, 1), padding or (0, 0)
+        super().__init__(_mk(host.tp_qat_conv2d_new, "QATConv2d::new", int(in_ch), int(out_ch), kernel_size[0], kernel_size[1], s[0], s[1],
+                             p[0], p[1], 1 if bias else 0, 1 if relu else 0, *c._args(), module_id.encode() if module_id else None, int(seed)))
+
+
+class qat:
+    """qat_manager.rs `global::`: the process-wide QAT switches"""
+
+    @staticmethod
+    def enable(): tp_check(host.tp_qat_enable(1), "qat.enable")
+
+    @staticmethod
+    def disable(): tp_check(host.tp_qat_enable(0), "qat.disable")
+
+    @staticmethod
+    def set_training_mode(training: bool): tp_check(host.tp_qat_set_training(1 if training else 0), "qat.set_training_mode")
+
+    @staticmethod
+    def is_training() -> bool:
+        out = C.c_int()
+        tp_check(host.tp_qat_is_training(C.byref(out)), "qat.is_training")
+        return bool(out.value)
+
+    @staticmethod
+    def status():
+        g, t, n, e = C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+        tp_check(host.tp_qat_status(C.byref(g), C.byref(t), C.byref(n), C.byref(e)), "qat.status")
+        return dict(global_enabled=bool(g.value), training_mode=bool(t.value), module_count=n.value, enabled_modules=e.value,
+                    is_active=bool(g.value) and bool(t.value))
+
+
 # -- src/optim.rs -----------------------------------------------------------------
 class _Optim:
     def __del__(self):

@@ -267,6 +267,53 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
     if (qtype) *qtype = t.qtype;
     TP_END
 }
+static QATConfig qat_config(int qtype, int activations, int symmetric, int per_channel) {
+    QATConfig c;
+    c.qtype = (QType)qtype;
+    c.activations = activations != 0;
+    c.symmetric = symmetric != 0;
+    c.per_channel = per_channel != 0;
+    c.check();
+    return c;
+}
+static QATModule *as_qat(const tp_module *m) {
+    auto *q = m ? dynamic_cast<QATModule *>(m->m.get()) : nullptr;
+    TAPER_ASSERT(q, "not a QAT layer");
+    return q;
+}
+int tp_qat_linear_new(int in_f, int out_f, int bias, int qtype, int activations, int symmetric, int per_channel, const char *module_id,
+                      uint64_t seed, tp_module **out) {
+    TP_BEGIN
+    const QATConfig c = qat_config(qtype, activations, symmetric, per_channel);
+    const std::string id = module_id ? module_id : "linear_" + std::to_string(in_f);   // qat_layers.rs:35
+    *out = new tp_module{std::make_shared<QATLinear>((size_t)in_f, (size_t)out_f, bias != 0, c, id, seed)};
+    TP_END
+}
+int tp_qat_conv2d_new(int ic, int oc, int kh, int kw, int sh, int sw, int ph, int pw, int bias, int relu, int qtype, int activations,
+                      int symmetric, int per_channel, const char *module_id, uint64_t seed, tp_module **out) {
+    TP_BEGIN
+    const QATConfig c = qat_config(qtype, activations, symmetric, per_channel);
+    const std::string id = module_id ? module_id : "conv2d_" + std::to_string(ic) + "_" + std::to_string(oc);   // qat_layers.rs:166-167
+    *out = new tp_module{std::make_shared<QATConv2d>((size_t)ic, (size_t)oc, std::make_pair(kh, kw), std::make_pair(sh, sw),
+                                                     std::make_pair(ph, pw), bias != 0, relu != 0, c, id, seed)};
+    TP_END
+}
+int tp_qat_enable(int on) { TP_BEGIN qat::enable(on != 0); TP_END }
+int tp_qat_set_training(int on) { TP_BEGIN qat::set_training_mode(on != 0); TP_END }
+int tp_qat_is_training(int *out) { TP_BEGIN *out = qat::is_training() ? 1 : 0; TP_END }
+int tp_qat_module_set_enabled(tp_module *m, int on) { TP_BEGIN as_qat(m)->enable_qat(on != 0); TP_END }
+int tp_qat_status(int *global_enabled, int *training_mode, size_t *module_count, size_t *enabled_modules) {
+    TP_BEGIN
+    const qat::Status st = qat::status();
+    if (global_enabled) *global_enabled = st.global_enabled ? 1 : 0;
+    if (training_mode) *training_mode = st.training_mode ? 1 : 0;
+    if (module_count) *module_count = st.module_count;
+    if (enabled_modules) *enabled_modules = st.enabled_modules;
+    TP_END
+}
+int tp_qat_module_observed(const tp_module *m, float *out3) { TP_BEGIN as_qat(m)->observed(out3); TP_END }
+int tp_qat_module_fake_quantized(const tp_module *m, int which, tp_tensor **out) { TP_BEGIN *out = wrap(as_qat(m)->fake_quantized(which)); TP_END }
+
 int tp_module_num_parameters(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->parameters().size(); TP_END }
 int tp_module_parameter(const tp_module *m, int i, tp_tensor **out) {
     TP_BEGIN

@@ -161,7 +161,7 @@ void check_quantizable(const Module &m) {
         for (const auto &l : s->layers) check_quantizable(*l);
         return;
     }
-    if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const ReLU *>(&m) ||
+    if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const QATModule *>(&m) || dynamic_cast<const ReLU *>(&m) ||
         dynamic_cast<const Sigmoid *>(&m) || dynamic_cast<const MaxPool2d *>(&m) || dynamic_cast<const AvgPool2d *>(&m) ||
         dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m))
         return;
@@ -182,6 +182,9 @@ std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype) {
     }
     if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype);
     if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype);
+    // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
+    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype);
+    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
         !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))

@@ -451,6 +451,102 @@ class QuantizedModule {
 };
 std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled);
 
+// ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
+// A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the
+// int8 / f16 round trip of its weight and bias (th_fake_quant_multi: bit-identical to what quantize() packs and dequantizes -- the bias
+// too, which the reference leaves in f32 although quantize() packs it) and, with `activations`, fake-quantizes its output before any
+// ReLU (th_fake_quant_act).  The backward is the straight-through estimator: the fake-quantized weight
+// and bias share the masters' grad slots, so their gradients land there (an optimizer arena view included) and Adam updates the master.
+// Active = QAT enabled globally, training mode on and the module's own flag on (qat_layers.rs:93-97); otherwise forward is the plain
+// inner layer.  QAT layers derive from neither Linear nor Conv2d: the Trainer's fused step forms never see them (a QAT model trains in
+// the Layered form).
+struct QATConfig {            // qat_config.rs:10-25 (what the training path reads)
+    QType qtype = QType::Int8;
+    bool activations = true;  // fake-quantize each layer's output too (the reference always does)
+    bool symmetric = true;
+    bool per_channel = false;
+    void check() const;       // int4 / bfloat16 / nf4, asymmetric and per-channel are refused
+};
+
+namespace qat {   // the process-wide state of qat_manager.rs `global::`
+void enable(bool on = true);                            // enable_qat (default off)
+inline void disable() { enable(false); }                // disable_qat
+bool enabled();
+void set_training_mode(bool on);                        // default on
+bool is_training();
+void set_module(const std::string &id, bool on);        // set_module_qat
+bool module_enabled(const std::string &id);             // enabled() && (the module's entry, default true)
+struct Status { bool global_enabled, training_mode; size_t module_count, enabled_modules; };
+Status status();                                        // get_status
+}  // namespace qat
+
+class QATModule : public Module {
+   public:
+    QATConfig config;
+    std::string module_id;
+    bool qat_enabled = true;                            // the layer's own flag (qat_layers.rs:68-76)
+    QATModule(const QATConfig &c, std::string id);
+    void enable_qat(bool on);                           // the flag and the global entry of its id
+    bool active() const { return qat_enabled && qat::module_enabled(module_id) && qat::is_training(); }
+    virtual const Tensor &master_weight() const = 0;
+    virtual const Tensor &master_bias() const = 0;        // undefined without a bias
+    // the fake-quantized weight and bias of this forward: views of persistent buffers that share the masters' grad slots.  Made by this
+    // call unless a QATWeightPass made them for the coming forward
+    void fake_quant_params(Tensor *w, Tensor *b) const;
+    Tensor fake_quant_activation(const Tensor &y) const;   // one tape node; backward passes the gradient through (adopted when it can)
+    void items(std::vector<th_fq_item> *out) const;        // the weight's (and bias's) descriptors
+    Tensor fake_quantized(int which) const;                // a copy of the last round trip of the weight (0) or the bias (1)
+    void observed(float out[3]) const;                     // {weight min_val, weight scale, activation scale} of the last forward (synchronises)
+    mutable bool prepared = false;
+
+   protected:
+    void alloc_buffers();
+    int codec() const { return config.qtype == QType::Int8 ? TH_QTYPE_INT8 : TH_QTYPE_F16; }
+    std::shared_ptr<Buffer> wq_, bq_, obs_;               // obs_: {w min_val, w scale, act scale, b min_val, b scale}
+    mutable std::shared_ptr<class QATWeightPass> own_pass_;
+};
+
+class QATLinear : public QATModule {   // qat_layers.rs:10-134
+   public:
+    Linear inner;
+    QATLinear(size_t in_features, size_t out_features, bool with_bias, const QATConfig &c, std::string id, uint64_t seed);
+    Tensor forward(const Tensor &x) const override;
+    std::vector<Tensor> parameters() const override { return inner.parameters(); }
+    const Tensor &master_weight() const override { return inner.weight; }
+    const Tensor &master_bias() const override { return inner.bias; }
+    const char *name() const override { return "QATLinear"; }
+};
+
+class QATConv2d : public QATModule {   // qat_layers.rs:136-265; relu = a QAT Conv2dReLU (the ReLU behind the activation fake-quant)
+   public:
+    Conv2d inner;
+    QATConv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride, std::pair<int, int> padding, bool with_bias,
+              bool relu, const QATConfig &c, std::string id, uint64_t seed);
+    Tensor forward(const Tensor &x) const override;
+    std::vector<Tensor> parameters() const override { return inner.parameters(); }
+    const Tensor &master_weight() const override { return inner.weight; }
+    const Tensor &master_bias() const override { return inner.bias; }
+    const char *name() const override { return inner.fuse_relu ? "QATConv2dReLU" : "QATConv2d"; }
+};
+
+// The QAT layers of a model (a Sequential's, or the module itself; only the active ones with active_only), in order
+void qat_modules(const Module &m, std::vector<const QATModule *> *out, bool active_only);
+// Fake-quantizes the weights and biases of every active QAT layer of `m` with ONE th_fake_quant_multi call and marks them for their next forward.
+// The descriptor list lives on the device in a buffer of its own, replaced (and the old one freed) when the list changes -- never while a
+// graph is being captured.  generation() counts the replacements: a captured launch reads the buffer of the generation it was recorded in.
+class QATWeightPass {
+   public:
+    size_t run(const Module &m);                                   // -> layers covered
+    size_t run(const std::vector<const QATModule *> &mods);
+    bool sync(const std::vector<const QATModule *> &mods);         // upload the list if it changed (-> true); no launch
+    uint64_t generation() const { return generation_; }
+
+   private:
+    std::vector<th_fq_item> items_;
+    std::shared_ptr<Buffer> d_items_;
+    uint64_t generation_ = 0;
+};
+
 // ---- optim (src/optim.rs) ------------------------------------------------------
 // Parameters, their grads and the moments live in flat device arenas so that
 // (a) Adam is ONE kernel launch and (b) data-parallel training all-reduces ONE
@@ -832,6 +928,8 @@ class Trainer {  // train.rs:74-172
     std::vector<size_t> whole_capture_failed_;                 // call lengths whose whole-call capture failed once: not tried again
     std::vector<uintptr_t> graph_key_;   // what the captured steps bake in (train_epoch_graph); a mismatch drops the graphs
     std::shared_ptr<Buffer> xb_, yb_, state_, metrics_, step_loss_, step_ncorrect_;
+    QATWeightPass qat_pass_;             // QAT models: every active layer's weights fake-quantized by one launch pair per step
+    bool has_qat() const;                // (throws for a model that holds one QAT layer twice)
     size_t metrics_cap_ = 0;
 };
 

@@ -143,6 +143,10 @@ static void reduce_grads(Trainer &t) {
 
 void Trainer::train_step(const Tensor &images, const Tensor &labels, float *loss_out, float *acc_out) {
     Tape::reset();                                              // train_mnist.rs:91
+    if (has_qat()) {
+        TAPER_ASSERT(!comm, "QAT: data-parallel training of a QAT model is not supported");
+        qat_pass_.run(*model);                                  // every active QAT layer's weights: one launch pair
+    }
     Tensor logits = model->forward(shape_input(images, sample_shape));  // :101
     Tensor loss = cross_entropy_loss(logits, labels);           // :107
     const float acc = accuracy(logits, labels);                 // :110
@@ -292,6 +296,11 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
         p.fused_adam = fuse_adam && (!comm || exchange);
         return p;
     };
+    // a QAT model trains layer by layer: its layers fake-quantize their weights and outputs, which no fused form does
+    if (has_qat()) {
+        TAPER_ASSERT(!comm, "QAT: data-parallel training of a QAT model is not supported");
+        return take(StepForm::Layered, nl, {});
+    }
     Linear *last = (fuse_head && nl) ? linear(nl - 1) : nullptr;
     Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && relu(nl - 2)) ? linear(nl - 3) : nullptr;
     Linear *hidden0 = (hidden && mlp3_fuse() && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;
@@ -407,6 +416,7 @@ void Trainer::enqueue_compute(const StepPlan &plan, float *d_xb, float *d_yb, si
         }
         case StepForm::Layered: {
             adam->flush_deferred();
+            qat_pass_.run(*model);   // (after the flush: this step's fake-quantized weights are made from the updated masters)
             Tensor h = seq ? seq->forward_prefix(xin, plan.prefix) : model->forward(xin);
             for (size_t i = plan.prefix; seq && i < seq->layers.size(); ++i) h = seq->layers[i]->forward(h);
             loss = cross_entropy_loss(h, y, &ncorrect, &sink);
@@ -452,6 +462,17 @@ void Trainer::enqueue_steps(const float *d_images, const float *d_labels, const 
     }
     // a tail step leaves the head's W / b updates for its successor's first launch; the last one's run here
     optimizer->flush_deferred();
+}
+
+bool Trainer::has_qat() const {
+    std::vector<const QATModule *> mods;
+    qat_modules(*model, &mods, false);
+    // the same layer twice: its backward launches would both accumulate into one master gradient, and a fused Adam update deferred by the
+    // first could ride in the second (Adam::take_deferred recognises a shared weight by the pointer the launch reads: here the round trip)
+    for (size_t i = 0; i < mods.size(); ++i)
+        for (size_t j = i + 1; j < mods.size(); ++j)
+            TAPER_ASSERT(mods[i] != mods[j], "QAT: the model holds the same QAT layer twice; the Trainer does not train a shared QAT layer");
+    return !mods.empty();
 }
 
 void Trainer::drop_graphs() {
@@ -522,6 +543,21 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         uintptr_t h = 1469598103934665603ull;
         for (const Tensor &p : optimizer->flat().params) h = (h ^ (uintptr_t)(p.get_requires_grad() ? 2 : 1)) * 1099511628211ull;
         key.push_back(h);
+    }
+    // QAT: whether each layer fake-quantizes (the global switch, training mode, every layer's own flag) and its codec and activation switch,
+    // and the descriptor buffer the steps read: uploaded here, before any step of this call, and keyed by its generation -- a buffer
+    // replaced since (an eager train_step after a layer switched) has gone back to the pool, and the graphs that read it must not replay
+    {
+        std::vector<const QATModule *> mods, active;
+        qat_modules(*model, &mods, false);
+        qat_modules(*model, &active, true);
+        if (!mods.empty()) {
+            qat_pass_.sync(active);
+            key.push_back((uintptr_t)qat::enabled() | (uintptr_t)qat::is_training() << 1);
+            key.push_back((uintptr_t)qat_pass_.generation());
+        }
+        for (const QATModule *q : mods)
+            key.push_back((uintptr_t)q->active() | (uintptr_t)q->config.activations << 1 | (uintptr_t)q->config.qtype << 2);
     }
     if (!graphs_.empty() && graph_key_ != key) drop_graphs();
 

@@ -49,28 +49,14 @@ __global__ __launch_bounds__(256) void int8_params_kernel(const float *__restric
         mn = fminf(mn, part[2 * i]);
         mx = fmaxf(mx, part[2 * i + 1]);
     }
-    if (mn == mx) {
-        mn -= 0.1f;
-        mx += 0.1f;
-    }
-    params[0] = mn;
-    params[1] = (mx - mn) / 255.0f;   // qrange = qmax - qmin = 255
-}
-
-__device__ __forceinline__ int rust_f32_as_i32(float v) {   // `as i32`: saturating, NaN -> 0
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return 2147483647;
-    if (v <= -2147483648.0f) return (int)0x80000000;
-    return (int)v;
+    int8_params(mn, mx, &params[0], &params[1]);
 }
 
 __global__ __launch_bounds__(256) void quantize_int8_kernel(const float *__restrict__ x, int8_t *__restrict__ q, size_t n,
                                                             const float *__restrict__ params) {
     const float mn = params[0], scale = params[1];
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const int v = rust_f32_as_i32(roundf((x[i] - mn) / scale));                  // f32::round: half away from zero
-        const long w = (long)v + (-128);                                              // i32 add (cannot overflow after the clamp range check below)
-        q[i] = (int8_t)(w < -128 ? -128 : (w > 127 ? 127 : w));
+        q[i] = (int8_t)quant_int8(x[i], mn, scale);
     }
 }
 

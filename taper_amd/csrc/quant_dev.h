@@ -41,6 +41,30 @@ __device__ __forceinline__ float f16_bits_to_f32(uint16_t value) {
     return __uint_as_float((sign << 31) | (((exponent + 127 - 15) & 0xFF) << 23) | (mantissa << 13));
 }
 
+// tensor.rs:2127-2134: {min_val, scale} from the finite min / max (widened by 0.1 each way when they are equal); qrange = 255
+__device__ __forceinline__ void int8_params(float mn, float mx, float *min_val, float *scale) {
+    if (mn == mx) {
+        mn -= 0.1f;
+        mx += 0.1f;
+    }
+    *min_val = mn;
+    *scale = (mx - mn) / 255.0f;
+}
+
+__device__ __forceinline__ int rust_f32_as_i32(float v) {   // `as i32`: saturating, NaN -> 0
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return 2147483647;
+    if (v <= -2147483648.0f) return (int)0x80000000;
+    return (int)v;
+}
+
+// tensor.rs:2136-2143: q = round((x - min) / scale) as i32 + qmin, clamped to [-128, 127] (f32::round: half away from zero)
+__device__ __forceinline__ int quant_int8(float x, float min_val, float scale) {
+    const int v = rust_f32_as_i32(roundf((x - min_val) / scale));
+    const long w = (long)v + (-128);
+    return (int)(w < -128 ? -128 : (w > 127 ? 127 : w));
+}
+
 // (q - zero_point) * scale + min_val with zero_point = -128: two roundings, never contracted (tensor.rs:357)
 __device__ __forceinline__ float dequant_int8(int q, float scale, float min_val) { return __fadd_rn(__fmul_rn((float)(q + 128), scale), min_val); }
 

@@ -65,6 +65,10 @@ class QTensor(C.Structure):   # th_qtensor (th_dequantize_multi)
     _fields_ = [("d_codes", C.c_void_p), ("d_params", C.c_void_p), ("d_out", C.c_void_p), ("n", C.c_int64), ("qtype", C.c_int)]
 
 
+class FqItem(C.Structure):   # th_fq_item (th_fake_quant_multi: an array of these in device memory)
+    _fields_ = [("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_params", C.c_void_p), ("n", C.c_int64), ("qtype", C.c_int)]
+
+
 class DevBuf:
     """A device allocation from the ctx pool (freed on garbage collection)."""
 
