@@ -19,7 +19,7 @@ int th_debug_mlp2_only(int which);
  * walk the hand-off's forms); 0 = the default choice */
 int th_debug_mlp2_ksplit(int ksplit);
 /* 1 = conv chains over more than 256 images run as min(n, 256) workgroups that WALK the images (r05: bit-identical, measured 3 - 5 % slower
- * than one workgroup per image, off by default); 0 = never; -1 = default */
+ * than one workgroup per image, off by default); 0 / -1 = default */
 int th_debug_set_chain_loop(int on);
 /* 1: th_conv_chain_mlp3_xent enqueues its first launch (the chain with the classifier's rows) alone -- per-launch timing; 0: both */
 int th_debug_chain_mlp3_only(int which);
@@ -27,7 +27,7 @@ int th_debug_chain_mlp3_only(int which);
 int th_debug_set_chain_generic(int on);
 /* launch configuration of the most recent matrix-core 3x3 convolution this thread enqueued (the parity
  * tests assert which kernel instance a shape takes): out6 = {16-channel tiles per workgroup (1/2/4), 1 if the
- * operands are staged by LDS-DMA (2-5: the image-resident kernel; 6: a conv chain, out6[0] = its instance id), waves per workgroup / 4, grid.x, grid.y, 1 if the epilogue is the fused 2x2 pool}. */
+ * operands are staged by LDS-DMA (2 / 4: the image-resident kernel, generic / compiled patch geometry; 6: a conv chain, out6[0] = its instance id), waves per workgroup / 4, grid.x, grid.y, 1 if the epilogue is the fused 2x2 pool}. */
 int th_debug_last_conv_config(th_ctx *ctx, int *out6);
 /* which matrix-core kernel takes a 3x3 launch.  -1 (default): the image-resident kernel (whole images per
  * workgroup, every output tile in registers; out6[1] == 2 in th_debug_last_conv_config, out6[2] = pixel tiles per wave,

@@ -1594,7 +1594,7 @@ const CompiledChain kCompiled[] = {
     {1, 1, 28, 5, {32, 32, 64, 64, 128}, {TH_CHAIN_NONE, TH_CHAIN_MAXPOOL2, TH_CHAIN_NONE, TH_CHAIN_MAXPOOL2, TH_CHAIN_GLOBAL_AVG}},   // examples/train_mnist_cnn.rs:35-62
     {2, 1, 28, 2, {32, 64, 0, 0, 0}, {TH_CHAIN_MAXPOOL2, TH_CHAIN_MAXPOOL2, 0, 0, 0}},                                                  // BASELINE configs[2]
 };
-thread_local int t_chain_generic = [] { const char *e = getenv("TAPER_CHAIN_GENERIC"); return (e && e[0] == '1') ? 1 : 0; }();   // 1: never a compiled instance
+thread_local int t_chain_generic = 0;   // th_debug_set_chain_generic: 1 = never a compiled instance
 
 int compiled_chain(int c_in, int h, int w, const th_conv_stage *st, int n) {
     if (t_chain_generic) return 0;
@@ -1765,7 +1765,7 @@ int th_debug_chain_mlp3_only(int which) {
     t_chain_mlp3_only = which == 1 ? 1 : 0;
     return 0;
 }
-int th_debug_set_chain_loop(int on) {   // test hook: 1 = batches above 256 images take the walking instances on this thread; 0 = never; -1 = default (off)
+int th_debug_set_chain_loop(int on) {   // test hook: 1 = batches above 256 images take the walking instances on this thread; 0 / -1 = default (off)
     t_chain_loop = on < 0 ? -1 : (on ? 1 : 0);
     return 0;
 }
@@ -1793,10 +1793,16 @@ static int rt_launch(th_ctx *ctx, RtChainArgs &a, int lds_floats, const float *d
 // 4 096 images (reference front 405 against 393 us per 1 024-image step, simple 118.9 against 113.2): the hardware hands a CU its next
 // workgroup within ~1 us, and what the walk saves on top of that (the image and first-weight round trips, ~2 us per image) the loop's code
 // gives back -- with the per-image addresses hoisted out of the image loop the k loops spilled (+15 us per image; made opaque per image:
-// the figures above).  OFF by default; TAPER_CHAIN_LOOP=1 / th_debug_set_chain_loop(1) turn it on.
-static bool chain_loop(int n) {
-    static const bool env_on = getenv("TAPER_CHAIN_LOOP") && getenv("TAPER_CHAIN_LOOP")[0] == '1';
-    return (t_chain_loop >= 0 ? t_chain_loop != 0 : env_on) && n > kNumCU;
+// the figures above).  OFF by default; th_debug_set_chain_loop(1) turns it on for the parity tests.  (The instances stay compiled: without
+// them the compiler emits different code for the other chain kernels of this file.)
+static bool chain_loop(int n) { return t_chain_loop > 0 && n > kNumCU; }
+
+// More than one image per CU: the simple chain's 128-register instance, two workgroups to a CU.  From 257 images on, not 512: the
+// one-to-a-CU instance runs a second round for the 257th image (264 images: 48.7 against 43.3 us).  TAPER_CHAIN_LEAN = 0 | 1 forces it
+// off / on (A/B probe: tools/chain_lean_ab.py).
+static bool chain_lean(int n) {
+    static const int env = [] { const char *e = getenv("TAPER_CHAIN_LEAN"); return e ? atoi(e) : -1; }();
+    return env >= 0 ? env != 0 : n > kNumCU;
 }
 
 int th_conv_chain_fwd(th_ctx *ctx, const float *d_x, const th_conv_stage *stages, int n_stages, float *d_y, float *d_cnt, int n, int c_in,
@@ -1825,11 +1831,10 @@ int th_conv_chain_fwd(th_ctx *ctx, const float *d_x, const th_conv_stage *stages
             }
         } else {
             const int lds = CS_LDS * (int)sizeof(float);
-            static const int lean_env = [] { const char *e = getenv("TAPER_CHAIN_LEAN"); return e ? atoi(e) : -1; }();
             if (chain_loop(n)) {
                 TH_SET_MAX_LDS(ctx, (conv_chain_simple_kernel<false, 1, true>), lds);
                 hipLaunchKernelGGL((conv_chain_simple_kernel<false, 1, true>), dim3(kNumCU), dim3(CH_NT), lds, ctx->stream, a);
-            } else if (lean_env >= 0 ? lean_env != 0 : n > kNumCU) {      // more than one image per CU: two workgroups to a CU (as th_conv_chain_head_fwd)
+            } else if (chain_lean(n)) {
                 TH_SET_MAX_LDS(ctx, (conv_chain_simple_kernel<false, 1, false, true>), lds);
                 hipLaunchKernelGGL((conv_chain_simple_kernel<false, 1, false, true>), dim3(n), dim3(CH_NT), lds, ctx->stream, a);
             } else {
@@ -1936,11 +1941,7 @@ int th_conv_chain_head_fwd(th_ctx *ctx, const float *d_x, const th_conv_stage *s
         TH_SET_MAX_LDS(ctx, (conv_chain_simple_kernel<true, NC_, LOOP_>), lds);     \
         hipLaunchKernelGGL((conv_chain_simple_kernel<true, NC_, LOOP_>), dim3(GRID_), dim3(CH_NT), lds, ctx->stream, a);                          \
     } while (0)
-        // more than one image per CU: the 128-register instance, two workgroups to a CU (TAPER_CHAIN_LEAN = 0 | 1 forces it off / on: A/B probe).
-        // From 257 images on, not 512: the one-to-a-CU instance runs a second round for the 257th image (264 images: 48.7 against 43.3 us)
-        static const int lean_env = [] { const char *e = getenv("TAPER_CHAIN_LEAN"); return e ? atoi(e) : -1; }();
-        const bool lean = lean_env >= 0 ? lean_env != 0 : n > kNumCU;
-        if (head->classes <= 10 && lean) {
+        if (head->classes <= 10 && chain_lean(n)) {
             TH_SET_MAX_LDS(ctx, (conv_chain_simple_kernel<true, 10, false, true>), lds);
             hipLaunchKernelGGL((conv_chain_simple_kernel<true, 10, false, true>), dim3(n), dim3(CH_NT), lds, ctx->stream, a);
         } else if (head->classes <= 10) {

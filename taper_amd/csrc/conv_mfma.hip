@@ -427,9 +427,9 @@ __global__ void conv_img_tables_kernel(int *goff, int *pix, int n_goff, int n_pi
 // the MFMAs alone take 832, in phase or in anti-phase; a v_add costs ~4.8 cycles of the SIMD, a ds_read_b32 ~9.  The k loop is therefore
 // priced per k-step and wave as 32 P Q + 9 (P + Q) + 4.8 P cycles (P pixel tiles x Q channel tiles: P + Q operand reads, P address adds),
 // and what pays is operand REUSE: a wave that owns Q = 2 channel tiles feeds two MFMAs from every pixel operand.
-//   NW = 8: 8 waves, every wave ONE channel tile (CT = 2: waves 0-3 / 4-7 take tile 0 / 1 on pixel groups 0-3; CT = 1: 8 pixel groups)
-//   NW = 4: 4 waves, every wave ALL CT channel tiles on its pixel group (tile = wave + 4 i)
-// The launch planner prices both and picks per layer.
+// 8 waves, every wave ONE channel tile (CT = 2: waves 0-3 / 4-7 take tile 0 / 1 on pixel groups 0-3; CT = 1: 8 pixel groups).  A four-wave
+// form (every wave ALL CT channel tiles on its pixel group) measured 10-17 % SLOWER on all four batch-256 layers (28x28: 59.2 vs 50.4 us):
+// one wave per SIMD; retired after r06.
 // WP > 0: the patch geometry (pitch WP = w_out + 2, channel stride CIS = images x (h_out + 2) x WP) is a compile-time constant and
 // the 72 k of a pass are walked as (channel group of 4, tap): k-step s covers tap s % 9 of channels 4 (s / 9) + lane group.  A lane's
 // operand address is then (its window corner + its channel offset) + a per-step constant that fits the ds_read offset field -- the P
@@ -437,13 +437,13 @@ __global__ void conv_img_tables_kernel(int *goff, int *pix, int n_goff, int n_pi
 // permutation.  Sums
 // are formed in another order than in the generic instances (WP = 0, k = channel-major like the reference's im2col column): equal within
 // fp32 rounding, not bit for bit.
-template <int CT, int TPW, bool POOL, int NW, int WP = 0, int CIS = 0>
-__global__ __launch_bounds__(64 * NW, 1) void conv3x3_img_kernel(ConvImgArgs a) {
+template <int CT, int TPW, bool POOL, int WP = 0, int CIS = 0>
+__global__ __launch_bounds__(512, 1) void conv3x3_img_kernel(ConvImgArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int CO_B = 16 * CT, KS = 18, NT = 64 * NW, WQ = KS * 4 * CO_B / 4, WPT = (WQ + NT - 1) / NT;
-    constexpr int CTW = NW == 4 ? CT : 1;                    // channel tiles per wave
-    constexpr int PG = NW == 4 ? 4 : (CT == 2 ? 4 : 8);      // pixel groups of waves
+    constexpr int CO_B = 16 * CT, KS = 18, NT = 512, WQ = KS * 4 * CO_B / 4, WPT = (WQ + NT - 1) / NT;
+    constexpr int CTW = 1;                                   // channel tiles per wave
+    constexpr int PG = CT == 2 ? 4 : 8;                      // pixel groups of waves
     constexpr int PPT = IM_PPT * 512 / NT;                   // patch elements per thread per pass
     // units of one image group sit on one XCD (blocks go round-robin over the 8 XCDs): its channel blocks share the input in that L2
     const int xcd = blockIdx.x & 7, q8 = blockIdx.x >> 3;
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_img_kernel(ConvImgArgs a) 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), l16 = lane & 15, g4 = lane >> 4;
     // pixel group, first channel tile of this wave.  Waves w and w + 4 share a SIMD: with two channel tiles the two waves of a pixel group
     // (the only group that owns a pixel tile more than the others when the tiles do not divide evenly) sit on DIFFERENT SIMDs
-    const int pg = NW == 8 && CT == 2 ? wave >> 1 : wave % PG, cj = NW == 4 ? 0 : (CT == 2 ? wave & 1 : wave / PG);
+    const int pg = CT == 2 ? wave >> 1 : wave % PG, cj = CT == 2 ? wave & 1 : wave / PG;
     const int wp = a.w_out + 2, rp = a.h_out + 2;
     const int img_stride = rp * wp, ci_stride = a.img_t * img_stride, patch_n = MF_CI * ci_stride;
     const int img0 = grp * a.img_t, co0 = cob * CO_B;
@@ -727,48 +727,41 @@ __global__ __launch_bounds__(64 * NW, 1) void conv3x3_img_kernel(ConvImgArgs a) 
 #endif
 }
 
-// (IMG, CT, TPW, NW) of the image-resident kernel for a launch, or false: the 128-pixel kernel keeps it.  A candidate costs
+// (IMG, CT, TPW) of the image-resident kernel for a launch, or false: the 128-pixel kernel keeps it.  A candidate costs
 // rounds of units over the 256 CUs x waves per SIMD x (32 P Q + 9 (P + Q) + 4.8 P) cycles per k-step (see the kernel's header);
 // the instance table fixes P to 4 / 7 / 13.
-struct ConvImgPlan { int img_t, ct, tpw, nw, n_groups, n_co; size_t lds; int tile_store; };
+struct ConvImgPlan { int img_t, ct, tpw, n_groups, n_co; size_t lds; int tile_store; };
 static bool conv_img_plan(int n, int c_in, int h, int w_in, int c_out, int pad, bool pool, ConvImgPlan *out, bool gap = false) {
     const int h_out = h + 2 * pad - 2, w_out = w_in + 2 * pad - 2;
     if (c_in % MF_CI != 0 || h_out < 1 || w_out < 1) return false;
     if (pool && !gap && ((h_out | w_out) & 1)) return false;
-    static const int nw_env = getenv("TAPER_CONV_IMG_NW") ? atoi(getenv("TAPER_CONV_IMG_NW")) : 0;   // tuning probe: force 4 / 8 waves
     double best = -1;
-    for (int nw = 4; nw <= 8; nw += 4) {
-        // measured: the 4-wave form (every pixel operand feeds two MFMAs, but one wave per SIMD) is 10-17 % SLOWER on all four batch-256
-        // layers (28x28: 59.2 vs 50.4 us): it only runs when asked for
-        if (nw != (nw_env ? nw_env : 8)) continue;
-        for (int ct = 1; ct <= 2; ++ct) {
-            if (ct == 2 && c_out <= 16) continue;
-            const int pg = nw == 4 ? 4 : (ct == 2 ? 4 : 8), q = nw == 4 ? ct : 1;
-            for (int img = 1; img <= 16; ++img) {
-                const long px = (long)img * h_out * w_out;
-                const int npt = (int)((px + 15) / 16), tpw_need = (npt + pg - 1) / pg;
-                const int tpw = tpw_need <= 4 ? 4 : (tpw_need <= 7 ? 7 : (tpw_need <= 13 ? 13 : 0));
-                if (!tpw) break;
-                const long patch_n = (long)MF_CI * img * (h_out + 2) * (w_out + 2);
-                if (patch_n > (long)IM_PPT * 512) break;
-                size_t lds = (size_t)2 * ((((size_t)patch_n + 4) & ~(size_t)3) + (size_t)72 * 16 * ct) * sizeof(float);
-                if (pool) lds = std::max(lds, (size_t)16 * ct * ((size_t)px | 1) * sizeof(float));
-                // plain outputs of >= 2 MB with 16-byte aligned planes: through an LDS tile, whole planes as float4
-                static const int tile_env = getenv("TAPER_CONV_TILE_STORE") ? atoi(getenv("TAPER_CONV_TILE_STORE")) : 1;   // tuning probe
-                const size_t tile_lds = (size_t)16 * ct * ((((size_t)px + 3) & ~(size_t)3) + 4) * sizeof(float);
-                const int tile_store = tile_env && !pool && (h_out * w_out) % 4 == 0 && (long)n * c_out * h_out * w_out >= (1L << 19) &&
-                                       std::max(lds, tile_lds) <= (150u << 10);
-                if (tile_store) lds = std::max(lds, tile_lds);
-                if (lds > (150u << 10)) continue;
-                if ((long)img * c_in * h * w_in >= (1L << 28) || (long)9 * c_in * c_out >= (1L << 28)) continue;
-                const int n_groups = ceil_div(n, img), n_co = ceil_div(c_out, 16 * ct);
-                const long units = (long)n_groups * n_co, rounds = (units + kNumCU - 1) / kNumCU;
-                double cost = (double)rounds * (nw / 4) * (32.0 * tpw * q + 9.0 * (tpw + q) + 4.8 * tpw);
-                if (units < kNumCU) cost *= 1.0 + 0.5 * (double)(kNumCU - units) / kNumCU;   // idle CUs: prefer the split that fills the chip
-                if (best < 0 || cost < best) {
-                    best = cost;
-                    *out = ConvImgPlan{img, ct, tpw, nw, n_groups, n_co, lds, tile_store};
-                }
+    for (int ct = 1; ct <= 2; ++ct) {
+        if (ct == 2 && c_out <= 16) continue;
+        const int pg = ct == 2 ? 4 : 8;   // pixel groups of waves (Q = 1 channel tile per wave, two waves per SIMD)
+        for (int img = 1; img <= 16; ++img) {
+            const long px = (long)img * h_out * w_out;
+            const int npt = (int)((px + 15) / 16), tpw_need = (npt + pg - 1) / pg;
+            const int tpw = tpw_need <= 4 ? 4 : (tpw_need <= 7 ? 7 : (tpw_need <= 13 ? 13 : 0));
+            if (!tpw) break;
+            const long patch_n = (long)MF_CI * img * (h_out + 2) * (w_out + 2);
+            if (patch_n > (long)IM_PPT * 512) break;
+            size_t lds = (size_t)2 * ((((size_t)patch_n + 4) & ~(size_t)3) + (size_t)72 * 16 * ct) * sizeof(float);
+            if (pool) lds = std::max(lds, (size_t)16 * ct * ((size_t)px | 1) * sizeof(float));
+            // plain outputs of >= 2 MB with 16-byte aligned planes: through an LDS tile, whole planes as float4
+            const size_t tile_lds = (size_t)16 * ct * ((((size_t)px + 3) & ~(size_t)3) + 4) * sizeof(float);
+            const int tile_store = !pool && (h_out * w_out) % 4 == 0 && (long)n * c_out * h_out * w_out >= (1L << 19) &&
+                                   std::max(lds, tile_lds) <= (150u << 10);
+            if (tile_store) lds = std::max(lds, tile_lds);
+            if (lds > (150u << 10)) continue;
+            if ((long)img * c_in * h * w_in >= (1L << 28) || (long)9 * c_in * c_out >= (1L << 28)) continue;
+            const int n_groups = ceil_div(n, img), n_co = ceil_div(c_out, 16 * ct);
+            const long units = (long)n_groups * n_co, rounds = (units + kNumCU - 1) / kNumCU;
+            double cost = (double)rounds * 2 * (32.0 * tpw + 9.0 * (tpw + 1) + 4.8 * tpw);
+            if (units < kNumCU) cost *= 1.0 + 0.5 * (double)(kNumCU - units) / kNumCU;   // idle CUs: prefer the split that fills the chip
+            if (best < 0 || cost < best) {
+                best = cost;
+                *out = ConvImgPlan{img, ct, tpw, n_groups, n_co, lds, tile_store};
             }
         }
     }
@@ -813,10 +806,8 @@ bool conv3x3_mfma_pool_supported(int c_in, int h, int w, int pad) {   // whole 2
 }
 
 // -1: the image-resident kernel takes launches with >= one unit per two CUs; 0: never; 1: whenever a plan exists
-// (TAPER_CONV_IMG at load, th_debug_set_conv_img at run time: the parity tests force both kernels onto the same shapes)
-int g_conv_img_mode = getenv("TAPER_CONV_IMG") ? atoi(getenv("TAPER_CONV_IMG")) : -1;
-// TAPER_CONV_LAYER_CHAIN=0: the four compiled layer geometries keep the image-resident kernel (measurement probe)
-static const bool g_conv_layer_chain = !(getenv("TAPER_CONV_LAYER_CHAIN") && getenv("TAPER_CONV_LAYER_CHAIN")[0] == '0');
+// (th_debug_set_conv_img: the parity tests force both kernels onto the same shapes)
+int g_conv_img_mode = -1;
 int conv_layer_chain_launch(th_ctx *ctx, const float *x, const float *w, const float *bias, float *y, float *cnt, int n, int c_in, int hw, int c_out,
                             int post, bool linear);   // conv_chain.hip
 
@@ -835,7 +826,7 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
     // place, ReLU on, pad 1, default kernel choice only (th_debug_set_conv_img forces the kernels below)
     // (+ the plain sum -- no bias, no ReLU: an input gradient -- for the shapes conv_layer_chain_launch lists)
     const bool lin = !relu && !bias && !pool && !gap;
-    if (g_conv_img_mode == -1 && g_conv_layer_chain && !accum && (relu || lin) && pad == 1 && h == w_in && w_ld == c_out && w_cols == c_out) {
+    if (g_conv_img_mode == -1 && !accum && (relu || lin) && pad == 1 && h == w_in && w_ld == c_out && w_cols == c_out) {
         const int rc = conv_layer_chain_launch(ctx, x, w, bias, y, gap ? gap_cnt : nullptr, n, c_in, h, c_out, gap ? 2 : (pool ? 1 : 0), lin);
         if (rc < 0) { th::set_error("conv_layer_chain_kernel: launch failed"); return 1; }
         if (rc == 1) {
@@ -845,7 +836,7 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
         }
     }
     {
-        // launches with at least a unit per two CUs take the image-resident kernel (TAPER_CONV_IMG = 0 / 1: never / whenever it fits)
+        // launches with at least a unit per two CUs take the image-resident kernel (th_debug_set_conv_img 0 / 1: never / whenever it fits)
         const int img_env = g_conv_img_mode;
         ConvImgPlan pl{};
         if ((img_env != 0 || gap) && !accum && c_in >= MF_CI && conv_img_plan(n, c_in, h, w_in, c_out, pad, pool, &pl, gap) &&
@@ -857,7 +848,7 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
             g.img_t = pl.img_t; g.n_groups = pl.n_groups; g.n_co = pl.n_co; g.relu = relu;
             g.gap = gap ? 1 : 0; g.gap_cnt = gap_cnt; g.tile_store = pl.tile_store;
             {   // staging plans of this geometry: built on device the first time, kept with the ctx
-                const int pgs = pl.nw == 4 ? 4 : (pl.ct == 2 ? 4 : 8), n_goff = 512 * IM_PPT, n_pix = pgs * pl.tpw * 16;
+                const int pgs = pl.ct == 2 ? 4 : 8, n_goff = 512 * IM_PPT, n_pix = pgs * pl.tpw * 16;
                 const std::array<int, 8> key{h, w_in, pad, c_in, pl.img_t, pgs, pl.tpw, 0};
                 auto it = ctx->conv_plans.find(key);
                 if (it == ctx->conv_plans.end()) {
@@ -872,38 +863,29 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
                 g.pix_tab = g.goff_tab + n_goff;
             }
             const dim3 grid(8 * ceil_div(pl.n_groups, 8) * pl.n_co);
-#define TH_IMG2(CTV, TPWV, PL, NWV)                                                                                         \
-            { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, PL, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
-              hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, PL, NWV>), grid, dim3(64 * NWV), pl.lds, ctx->stream, g); }
-#define TH_IMG(CTV, TPWV)                                                                                                   \
-            if (pool) { if (pl.nw == 4) TH_IMG2(CTV, TPWV, true, 4) else TH_IMG2(CTV, TPWV, true, 8) }                     \
-            else { if (pl.nw == 4) TH_IMG2(CTV, TPWV, false, 4) else TH_IMG2(CTV, TPWV, false, 8) }
+#define TH_IMG2(CTV, TPWV, PL, WPV, CISV)                                                                                   \
+            { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
+              hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>), grid, dim3(512), pl.lds, ctx->stream, g); }
             // instances with the patch geometry compiled in (the batch-256 layers of the two CNNs); everything else takes the generic ones
-#define TH_IMG_GEO(CTV, TPWV, WPV, CISV)                                                                                    \
-            { if (pool) { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, true, 8, WPV, CISV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
-                          hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, true, 8, WPV, CISV>), grid, dim3(512), pl.lds, ctx->stream, g); }                                 \
-              else { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, false, 8, WPV, CISV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);    \
-                     hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, false, 8, WPV, CISV>), grid, dim3(512), pl.lds, ctx->stream, g); } }
+#define TH_IMG_GEO(CTV, TPWV, WPV, CISV) { if (pool) TH_IMG2(CTV, TPWV, true, WPV, CISV) else TH_IMG2(CTV, TPWV, false, WPV, CISV) }
+#define TH_IMG(CTV, TPWV) TH_IMG_GEO(CTV, TPWV, 0, 0)
             const int wp_ = g.w_out + 2, cis_ = pl.img_t * (g.h_out + 2) * wp_;
-            static const int geo_env = getenv("TAPER_CONV_IMG_GEO") ? atoi(getenv("TAPER_CONV_IMG_GEO")) : 1;   // tuning probe: 0 = generic instances only
-            bool special = false;
-            if (geo_env && pl.nw == 8) {
-                special = true;
-                if (pl.ct == 2 && pl.tpw == 13 && wp_ == 30 && cis_ == 900) TH_IMG_GEO(2, 13, 30, 900)          // 28x28, one image
-                else if (pl.ct == 1 && pl.tpw == 7 && wp_ == 16 && cis_ == 1024) TH_IMG_GEO(1, 7, 16, 1024)      // 14x14, four images
-                else if (pl.ct == 1 && pl.tpw == 4 && wp_ == 9 && cis_ == 648) TH_IMG_GEO(1, 4, 9, 648)          // 7x7, eight images
-                else special = false;
-            }
-            if (special) {
-            } else if (pl.ct == 2) {
-                if (pl.tpw == 4) { TH_IMG(2, 4) } else if (pl.tpw == 7) { TH_IMG(2, 7) } else { TH_IMG(2, 13) }
-            } else {
-                if (pl.tpw == 4) { TH_IMG(1, 4) } else if (pl.tpw == 7) { TH_IMG(1, 7) } else { TH_IMG(1, 13) }
+            bool special = true;
+            if (pl.ct == 2 && pl.tpw == 13 && wp_ == 30 && cis_ == 900) TH_IMG_GEO(2, 13, 30, 900)          // 28x28, one image
+            else if (pl.ct == 1 && pl.tpw == 7 && wp_ == 16 && cis_ == 1024) TH_IMG_GEO(1, 7, 16, 1024)      // 14x14, four images
+            else if (pl.ct == 1 && pl.tpw == 4 && wp_ == 9 && cis_ == 648) TH_IMG_GEO(1, 4, 9, 648)          // 7x7, eight images
+            else {
+                special = false;
+                if (pl.ct == 2) {
+                    if (pl.tpw == 4) TH_IMG(2, 4) else if (pl.tpw == 7) TH_IMG(2, 7) else TH_IMG(2, 13)
+                } else {
+                    if (pl.tpw == 4) TH_IMG(1, 4) else if (pl.tpw == 7) TH_IMG(1, 7) else TH_IMG(1, 13)
+                }
             }
 #undef TH_IMG_GEO
 #undef TH_IMG2
 #undef TH_IMG
-            t_last_conv_cfg[0] = pl.ct; t_last_conv_cfg[1] = 2 + (pl.nw == 4 ? 1 : 0) + (special ? 2 : 0); t_last_conv_cfg[2] = pl.tpw;   // 2 / 3: the image-resident kernel with 8 / 4 waves
+            t_last_conv_cfg[0] = pl.ct; t_last_conv_cfg[1] = special ? 4 : 2; t_last_conv_cfg[2] = pl.tpw;   // 2 / 4: the image-resident kernel, generic / compiled geometry
             t_last_conv_cfg[3] = (int)grid.x; t_last_conv_cfg[4] = pl.img_t; t_last_conv_cfg[5] = pool ? 1 : 0;
             TH_LAUNCH_CHECK();
             return 0;
@@ -928,19 +910,14 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
     // workgroup's staging / barriers -- halve the channel block instead (measured 45.2 -> 40.5 us; it costs 7-9 us
     // on the 14x14 layers, which have 430 workgroups)
     if (ct == 4 && (long)ceil_div(n, a.img_t) * a.bands * ceil_div(c_out, 64) < 384) ct = 2;
-    static const int ct_env = getenv("TAPER_CONV_CT") ? atoi(getenv("TAPER_CONV_CT")) : 0;   // tuning probe
-    if (ct_env && ct > ct_env) ct = ct_env;
     a.co_b = ct * 16;
     const size_t patch_n = (size_t)cit * a.img_t * (a.rows_t + 2) * (a.w_out + 2);
     size_t lds = (((patch_n + 4) & ~(size_t)3) + (size_t)((cit * 9 + 3) / 4 * 4) * a.co_b) * sizeof(float);
     // whole 8-channel blocks, plain (non-accumulating) output: operands go global -> LDS directly, two LDS stages
-    static const int dma_env = getenv("TAPER_CONV_DMA") ? atoi(getenv("TAPER_CONV_DMA")) : 1;   // tuning probe: 0 = register-staged passes
-    const bool dma = dma_env && cit == MF_CI && c_in % MF_CI == 0 && !accum && ct >= 2 &&
+    const bool dma = cit == MF_CI && c_in % MF_CI == 0 && !accum && ct >= 2 &&
                      (long)a.img_t * c_in * h * w_in < (1L << 28) && (long)9 * c_in * w_ld < (1L << 28);
     if (dma) lds *= 2;
     if (pool) lds = std::max(lds, (size_t)a.co_b * ((size_t)(a.img_t * a.rows_t * a.w_out) | 1) * sizeof(float));   // the epilogue tile
-    static const int lds_min_kb = getenv("TAPER_CONV_LDS_KB") ? atoi(getenv("TAPER_CONV_LDS_KB")) : 0;   // tuning probe: caps workgroups per CU
-    if (lds_min_kb) lds = std::max(lds, (size_t)lds_min_kb * 1024);
     dim3 grid(ceil_div(n, a.img_t) * a.bands, ceil_div(c_out, a.co_b));
 #define TH_MF(CTV, ACC, PL, WHV)                                                                                                   \
     if (cit == 1) hipLaunchKernelGGL((conv3x3_mfma_kernel<CTV, ACC, 1, PL, WHV>), grid, dim3(256 * WHV), lds, ctx->stream, a);     \
@@ -954,9 +931,8 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
     }
     // launches with < 3 workgroups per CU: 8 waves per workgroup (see WH; 14x14 layers 38.3 / 62.5 -> 34.4 / 56.5 us, 7x7: 40.0 -> 36.8 us;
     // the 28x28 layer has 1792 workgroups and gains nothing)
-    static const int wh_env = getenv("TAPER_CONV_WH") ? atoi(getenv("TAPER_CONV_WH")) : 0;   // tuning probe: 1 forces 4 waves
     // (with LDS-DMA staging there is no per-pass staging work left for extra waves to hide: 4 waves measure 2-6 % faster on those layers)
-    const bool wh2 = ct >= 2 && wh_env != 1 && (wh_env == 2 || (!dma && (long)grid.x * grid.y < 768));
+    const bool wh2 = ct >= 2 && !dma && (long)grid.x * grid.y < 768;
     t_last_conv_cfg[0] = ct; t_last_conv_cfg[1] = (dma && !accum && ct >= 2 && cit != 1) ? 1 : 0; t_last_conv_cfg[2] = wh2 ? 2 : 1;
     t_last_conv_cfg[3] = (int)grid.x; t_last_conv_cfg[4] = (int)grid.y; t_last_conv_cfg[5] = pool ? 1 : 0;
     if (pool) TH_MF_CT(false, true) else if (accum) TH_MF_CT(true, false) else TH_MF_CT(false, false)
@@ -1366,8 +1342,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_img_kernel(WgradImgArgs a) 
 
 // 1: launched (slabs in *part_out, *n_slabs of them); 0: not one of the compiled shapes / batch too small
 static int conv_wgrad_img_launch(th_ctx *ctx, const float *x, const float *gy, int n, int c_in, int hw, int c_out, float **part_out, int *n_slabs) {
-    static const bool off = getenv("TAPER_WGRAD_IMG") && getenv("TAPER_WGRAD_IMG")[0] == '0';   // measurement / parity knob
-    if (off || n < kNumCU / 2) return 0;
+    if (n < kNumCU / 2) return 0;
     const size_t xb = (size_t)n * c_in * hw * hw * 4, gb = (size_t)n * c_out * hw * hw * 4;
     if (xb >= (1u << 31) || gb >= (1u << 31)) return 0;
     WgradImgArgs a{x, gy, nullptr, n, 1, (unsigned)xb, (unsigned)gb};
@@ -1448,9 +1423,9 @@ int conv3x3_wgrad_mfma_launch(th_ctx *ctx, const float *x, const float *gy, floa
     const int co_b = ct * 16;
     const int slabs = ceil_div(c_in, WG_CI), co_blocks = ceil_div(c_out, co_b);
     a.co_ld = co_blocks * co_b;
-    // workgroups per CU in total (LDS: <= 58 KB each): two -- TAPER_WGRAD_WGS = 1 .. 4 (measurement knob)
-    static const int wgs = [] { const char *e = getenv("TAPER_WGRAD_WGS"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 4 ? v : 2; }();
-    int G = ceil_div(wgs * kNumCU, slabs * co_blocks);
+    // workgroups per CU in total (LDS: <= 58 KB each): two
+    constexpr int kWgradWgsPerCU = 2;
+    int G = ceil_div(kWgradWgsPerCU * kNumCU, slabs * co_blocks);
     if (G > a.n_pb) G = a.n_pb;
     if (G > 512) G = 512;
     a.G = G;

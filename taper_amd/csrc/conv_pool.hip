@@ -1304,8 +1304,7 @@ int th_conv3x3_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, floa
     {
         // one input channel, planes that fit the LDS (conv1): one image per workgroup, partial slabs per image
         const size_t lds = ((size_t)(((h + 2) * (w + 2) + 3) & ~3) + (size_t)C1W_CO * (h_out * w_out + 1) + (size_t)C1W_NS * C1W_CO * 9) * sizeof(float);
-        static const bool off = getenv("TAPER_CONV1_WGRAD") && getenv("TAPER_CONV1_WGRAD")[0] == '0';   // measurement / parity knob
-        if (!off && c_in == 1 && n >= 32 && h_out > 0 && w_out > 0 && lds <= (160u << 10)) {
+        if (c_in == 1 && n >= 32 && h_out > 0 && w_out > 0 && lds <= (160u << 10)) {
             void *part = nullptr;
             if (th_malloc(ctx, (size_t)n * 9 * c_out * sizeof(float), &part)) return 1;
             TH_SET_MAX_LDS(ctx, conv1_wgrad_kernel, 160 << 10);
@@ -1469,8 +1468,7 @@ int th_maxpool2d_bwd(th_ctx *ctx, const float *d_gout, const int64_t *d_argmax, 
     const int h_out = (h + 2 * pad_h - k_h) / s_h + 1, w_out = (w + 2 * pad_w - k_w) / s_w + 1;
     const long total = (long)n * c * h * w;
     if (total == 0) return 0;
-    static const bool fast_off = getenv("TAPER_POOL_BWD_GENERAL") && getenv("TAPER_POOL_BWD_GENERAL")[0] == '1';   // measurement / parity knob
-    if (!fast_off && maxpool2_fast(n, c, h, w, k_h, k_w, s_h, s_w, pad_h, pad_w) && (((uintptr_t)d_gin) & 7) == 0) {
+    if (maxpool2_fast(n, c, h, w, k_h, k_w, s_h, s_w, pad_h, pad_w) && (((uintptr_t)d_gin) & 7) == 0) {
         const int planes = n * c;
         hipLaunchKernelGGL(maxpool2_bwd_kernel<false>, dim3(std::min(ceil_div(planes, 4), 8 * kNumCU)), dim3(256), 0, ctx->stream, d_gout, d_argmax,
                            (const float *)nullptr, (const float *)nullptr, d_gin, (float *)nullptr, planes, h, w, zero_first);

@@ -949,8 +949,6 @@ int adam_slice(th_ctx *ctx, const AdamDev &a, const float *d_g, int64_t n);  // 
 static inline int tile128_kz(int m, int n, int k) {
     const long tiles = (long)ceil_div(m, BM) * ceil_div(n, BN);
     if (tiles >= 384 || k < 512) return 1;
-    static const int kz_env = [] { const char *e = getenv("TAPER_GEMM_KZ"); return e ? atoi(e) : 0; }();   // measurement probe
-    if (kz_env > 0) return kz_env;
     // 2 workgroups per CU (__launch_bounds__(256, 2)) = 512 places: as many slices as fit in ONE round of them (r05 rounded up: 14 tiles x 37
     // slices = 518 workgroups, six of which ran a second round on their own)
     int kz = (int)(512 / tiles);
@@ -971,9 +969,8 @@ static inline int tile64_kz(int m, int n, int k) {
 
 template <int TS, bool A_KC, bool B_KC>
 static inline bool rag_dma(int m, int n, int k, bool vec, long lda, long ldb) {
-    static const bool on = [] { const char *e = getenv("TAPER_GEMM_RAG"); return !e || atoi(e) != 0; }();   // 0: the clamped register loads (A/B probe)
     // (`vec`: 16-byte aligned rows and whole quads in or out of range along each operand's contiguous axis)
-    return on && TS == 128 && vec && ((A_KC || B_KC) ? k % 4 == 0 : k % BK == 0) && lda < (1L << 22) && ldb < (1L << 22);
+    return TS == 128 && vec && ((A_KC || B_KC) ? k % 4 == 0 : k % BK == 0) && lda < (1L << 22) && ldb < (1L << 22);
 }
 
 template <int TS, bool A_KC, bool B_KC>
@@ -1002,23 +999,21 @@ static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, in
     // 16.7 M parameters of a 4096 x 4096 layer cost a pass of 75 us over p / m / v / g as a launch of their own)
     Epilogue kep = ep;
     kep.adam.p = nullptr;
-    static const bool adam_ep_on = [] { const char *e = getenv("TAPER_GEMM_ADAM_EP"); return !e || atoi(e) != 0; }();   // 0: a slice launch behind the product (measurement)
+    // tile order: groups of kRasterRows tile rows (sgemm_tile)
+    constexpr int kRasterRows = 8;
     if constexpr (TS == 128 && !A_KC && !B_KC) {
-        if (ep.adam.p && kz == 1 && exact && adam_ep_on && !ep.mask && !ep.colpart) {
+        if (ep.adam.p && kz == 1 && exact && !ep.mask && !ep.colpart) {
             auto kern = sgemm_tile<TS, A_KC, B_KC, false, false, true>;
             TH_SET_MAX_LDS(ctx, kern, lds);
-            static const int raster_a = [] { const char *e = getenv("TAPER_GEMM_RASTER"); return e ? atoi(e) : 8; }();
             hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, 1), dim3(256), lds, ctx->stream, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, tiles_m, tiles_n, ep,
-                               kslice, (float *)nullptr, 1, raster_a);
+                               kslice, (float *)nullptr, 1, kRasterRows);
             TH_LAUNCH_CHECK();
             return 0;
         }
     }
-    // tile order: groups of 8 tile rows (TAPER_GEMM_RASTER = n: groups of n; 0: r02's whole columns)
-    static const int raster0 = [] { const char *e = getenv("TAPER_GEMM_RASTER"); return e ? atoi(e) : 8; }();
-    // K slices of at least this many chunks are handed to the XCDs slice by slice (sgemm_tile; TAPER_GEMM_SLICE_XCD_CHUNKS, 0 = always, large = never)
-    static const int slice_xcd_chunks = [] { const char *e = getenv("TAPER_GEMM_SLICE_XCD_CHUNKS"); return e ? atoi(e) : 14; }();
-    const int raster = raster0 + ((raster0 >= 0 && kz > 1 && kslice >= slice_xcd_chunks * BK) ? 0x100 : 0);
+    // K slices of at least this many 32-k chunks are handed to the XCDs slice by slice (sgemm_tile)
+    constexpr int kSliceXcdChunks = 14;
+    const int raster = kRasterRows + ((kz > 1 && kslice >= kSliceXcdChunks * BK) ? 0x100 : 0);
     if (ep.mask || ep.colpart) {     // the dX product with the backward of the layer in front in its epilogue (th_linear_bwd_adam_ex2: unsplit by its predicate)
         if (kz != 1) { th::set_error("sgemm_tile: the masked epilogue needs an unsplit product"); return 2; }
         if (exact) {
@@ -1078,10 +1073,21 @@ static inline bool gemm_is_big(int m, int n, int k) {
 // 64x64 tiles: outputs with too few 128-tiles for the big kernel but far too much work for 16x16 tiles straight from L2
 // (the MLP's tall-skinny products at batch 512..8192: [B,128] = X . W1^T and [128,784] = dZ^T . X)
 static inline bool gemm_is_mid(int m, int n, int k) {
-    static const long min_macs = getenv("TAPER_GEMM_MID_MACS") ? atol(getenv("TAPER_GEMM_MID_MACS")) : 300000000L;
+    constexpr long kMidMinMacs = 300000000L;
     if (m < 64 || n < 64 || k < 64) return false;
     const long tiles64 = (long)ceil_div(m, 64) * ceil_div(n, 64);
-    return (long)m * n * k >= min_macs && tiles64 * tile64_kz(m, n, k) >= 32;
+    return (long)m * n * k >= kMidMinMacs && tiles64 * tile64_kz(m, n, k) >= 32;
+}
+
+// which kernel takes a product: 128-tiles, 64-tiles or 16x16 tiles.  A "big" product whose 128-tiles (x K slices) cannot give every CU a
+// workgroup runs on 64-tiles instead.
+enum class TileClass { Small, Tile64, Tile128 };
+static inline TileClass gemm_tile_class(int m, int n, int k) {
+    constexpr long kBigMinWorkgroups = 460;
+    const bool big = gemm_is_big(m, n, k);
+    const long wg128 = (long)ceil_div(m, BM) * ceil_div(n, BN) * tile128_kz(m, n, k);
+    if (gemm_is_mid(m, n, k) && (!big || wg128 < kBigMinWorkgroups)) return TileClass::Tile64;
+    return big ? TileClass::Tile128 : TileClass::Small;
 }
 
 // op(A)[i,k] = A[i*a_rs + k*a_cs], op(B)[k,j] = B[k*b_rs + j*b_cs]
@@ -1091,38 +1097,14 @@ int gemm_dispatch(th_ctx *ctx, int trans_a, int trans_b, int m, int n, int k, co
     const long a_rs = trans_a ? 1 : k, a_cs = trans_a ? m : 1;  // gemm.rs:88-92
     const long b_rs = trans_b ? 1 : n, b_cs = trans_b ? k : 1;  // gemm.rs:93-97
     const bool a_kc = !trans_a, b_kc = trans_b != 0;
-    const bool big = gemm_is_big(m, n, k);
-    // Layouts.  r01 ran deep NN / TN / TT products as NT on transposed COPIES (a transpose launch per m/n-contiguous operand); r02 transposed
-    // such operands on their way into LDS; r03 stages every operand in the layout it has in memory (sgemm_tile: two LDS images, one MFMA loop).
-    // TAPER_GEMM_PRETRANSPOSE=1 still runs the r01 form for comparison.
-    static const int pretranspose = getenv("TAPER_GEMM_PRETRANSPOSE") ? atoi(getenv("TAPER_GEMM_PRETRANSPOSE")) : 0;   // measurement probe
-    if (pretranspose && big && k >= 1024 && m >= 1024 && n >= 1024 && (!a_kc || !b_kc)) {
-        void *at = nullptr, *bt = nullptr;
-        const float *A2 = A, *B2 = B;
-        if (!a_kc) {  // A stored [k][m] -> [m][k]
-            if (th_malloc(ctx, (size_t)m * k * sizeof(float), &at)) return 1;
-            if (int rc = th_transpose2d(ctx, A, (float *)at, k, m)) return rc;
-            A2 = (const float *)at;
-        }
-        if (!b_kc) {  // B stored [k][n] -> [n][k]
-            if (th_malloc(ctx, (size_t)n * k * sizeof(float), &bt)) return 1;
-            if (int rc = th_transpose2d(ctx, B, (float *)bt, k, n)) return rc;
-            B2 = (const float *)bt;
-        }
-        if (int rc = launch_tile128<true, true>(ctx, A2, B2, C, m, n, k, k, 1, 1, k, ep)) return rc;
-        if (at && th_free(ctx, at)) return 1;
-        if (bt && th_free(ctx, bt)) return 1;
-        return 0;
-    }
-    // a "big" product whose 128-tiles (x K slices) cannot give every CU a workgroup runs on 64-tiles instead
-    static const long big_min_wg = getenv("TAPER_GEMM_BIG_WG") ? atol(getenv("TAPER_GEMM_BIG_WG")) : 460;
-    const long wg128 = (long)ceil_div(m, BM) * ceil_div(n, BN) * tile128_kz(m, n, k);
-    const bool mid = gemm_is_mid(m, n, k) && (!big || wg128 < big_min_wg);
+    // Layouts: every operand is staged in the layout it has in memory (sgemm_tile: two LDS images, one MFMA loop; r03).  r01 ran deep
+    // NN / TN / TT products as NT on transposed copies, r02 transposed such operands on their way into LDS.
+    const TileClass tc = gemm_tile_class(m, n, k);
 #define TH_GEMM_CASE(AK, BKC)                                                                         \
     if (a_kc == AK && b_kc == BKC)                                                                          \
-        return mid ? launch_tile<64, AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep)            \
-             : big ? launch_tile128<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep)             \
-                   : launch_small<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
+        return tc == TileClass::Tile64  ? launch_tile<64, AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep) \
+             : tc == TileClass::Tile128 ? launch_tile128<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep)  \
+                                        : launch_small<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
     TH_GEMM_CASE(true, true)
     TH_GEMM_CASE(true, false)
     TH_GEMM_CASE(false, true)
@@ -1183,8 +1165,6 @@ int linear_fwd_partials(th_ctx *ctx, const float *x, const float *w, int m, int 
     int kz = (int)std::min<long>((256 + tiles - 1) / tiles, k / 512);
     if (kz < 1) kz = 1;
     if (kz > 8) kz = 8;   // wide_head.hip reads all slices of a logit at once (WH_KZ_MAX)
-    static const int kz_env = getenv("TAPER_WIDE_KZ") ? atoi(getenv("TAPER_WIDE_KZ")) : 0;   // tuning probe: cap on the K slices
-    if (kz_env > 0 && kz > kz_env) kz = kz_env;
     const int kslice = (ceil_div(k, kz) + 15) / 16 * 16;
     kz = ceil_div(k, kslice);
     p.kslice = kslice;
@@ -1245,8 +1225,7 @@ int th_linear_fwd_ex(th_ctx *ctx, const float *d_x, const float *d_w, const floa
         p.b_vec = aligned16(d_w) && (k % 4 == 0);
         const AdamSlices x = make_adam_slices(extra, n_extra, ctx);
         const dim3 grid(ceil_div(n, 16), ceil_div(m, 16) + 1, 1);
-        static const int xcd_map = [] { const char *e = std::getenv("TAPER_K1_XCD_MAP"); return e ? atoi(e) : 1; }();
-        p.xcd_blocks = xcd_map && grid.x == 8 && grid.y == 5;
+        p.xcd_blocks = grid.x == 8 && grid.y == 5;
         if (tiles < 256 && k >= 256) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
         else hipLaunchKernelGGL((sgemm_small16_tick<true, true, 4>), grid, dim3(256), 0, ctx->stream, p, x, d_tick);
         TH_LAUNCH_CHECK();
@@ -1309,11 +1288,7 @@ __global__ __launch_bounds__(256) void linear_dx_thin_kernel(const float *__rest
 static int dx_epilogue_rows(int batch, int in_f, int out_f) {
     if (batch <= 0 || in_f <= 0 || out_f <= 0) return 0;
     if (out_f <= 16 && in_f % 4 == 0 && (long)batch * in_f >= (1L << 20)) return ceil_div(batch, THIN_ROWS);          // the thin kernel
-    const bool big = gemm_is_big(batch, in_f, out_f);
-    const long wg128 = (long)ceil_div(batch, BM) * ceil_div(in_f, BN) * tile128_kz(batch, in_f, out_f);
-    static const long big_min_wg = getenv("TAPER_GEMM_BIG_WG") ? atol(getenv("TAPER_GEMM_BIG_WG")) : 460;
-    const bool mid = gemm_is_mid(batch, in_f, out_f) && (!big || wg128 < big_min_wg);
-    if (big && !mid && tile128_kz(batch, in_f, out_f) == 1) return ceil_div(batch, BM);                                // sgemm_tile<128>, unsplit
+    if (gemm_tile_class(batch, in_f, out_f) == TileClass::Tile128 && tile128_kz(batch, in_f, out_f) == 1) return ceil_div(batch, BM);   // sgemm_tile<128>, unsplit
     return 0;
 }
 

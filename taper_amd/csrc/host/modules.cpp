@@ -170,45 +170,23 @@ Tensor linear_cross_entropy_wide(const Tensor &h, const Tensor &w, const Tensor 
     const bool colsum_mode = h.get_requires_grad() && h.grad_->wants_colsum && PoolBiasScope::active();
     std::shared_ptr<Buffer> dh = (h.get_requires_grad() && !colsum_mode) ? Buffer::alloc(h.len()) : nullptr;
     std::shared_ptr<Buffer> cs = colsum_mode ? Buffer::alloc((size_t)k) : nullptr;
-    // With the Adam fusion on, the whole tail of the step fits these two launches: no dX is stored, so every workgroup owns its columns of W
-    // (Adam in its epilogue), the lead owns b, and the last workgroup to arrive finishes the conv bias from the column sums and ticks t.
-    Adam *fa = FusedAdamScope::active();
-    const std::shared_ptr<GradSlot> cbs = colsum_mode ? h.grad_->colsum_bias : nullptr;
-    // (measured on the simple CNN at batch 256: the head grows from 11.9 to 22.5 us -- Adam's p / m / v round trip behind the dW reduction in
-    // every workgroup, an agent-scope fence per workgroup, the last arriver's serial finish -- against the 5.0 us finishing launch it replaces:
-    // step 57.2 -> 64.1 us.  Off unless TAPER_WIDE_FUSED=1.)
-    static const bool wide_fused = std::getenv("TAPER_WIDE_FUSED") && std::getenv("TAPER_WIDE_FUSED")[0] == '1';
-    const bool full = wide_fused && colsum_mode && fa && log && log->d_adam_tick && cbs && cbs->buf && cbs->buf_is_arena && !cbs->has &&
-                      (long)h.grad_->colsum_c * h.grad_->colsum_hw == k;
-    bool fused_done = false;
-    if (full) {
-        th_wide_fuse f{};
-        const bool ok = fa->fuse_for(w, &f.w) && (!bias.defined() || fa->fuse_for(bias, &f.b)) && fa->fuse_for_slot(cbs, &f.conv_b);
-        TAPER_ASSERT(ok, "linear_cross_entropy_wide: a parameter of the fused tail is not held by the active optimizer");
-        f.d_conv_gb = cbs->buf->d;
-        f.conv_c = h.grad_->colsum_c;
-        f.conv_hw = h.grad_->colsum_hw;
-        TH(th_linear_xent_wide_fused(Device::ctx(), h.dptr(), w.dptr(), bias.defined() ? bias.dptr() : nullptr, targets.dptr(), b, k, c, loss.dptr(),
-                                     nc, dw, db, log->d_metrics, log->capacity, log->d_state, log->advance, log->d_adam_tick, cs->d, &f));
-        cbs->has = true;
-        cbs->known_zero = false;
-        fused_done = true;
-    } else {
-        TH(th_linear_xent_wide_ex(Device::ctx(), h.dptr(), w.dptr(), bias.defined() ? bias.dptr() : nullptr, targets.dptr(), b, k, c, loss.dptr(),
-                                  nc, dh ? dh->d : nullptr, dw, db, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                                  log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr, cs ? cs->d : nullptr));
-        if (fa) {   // complete gradients; every workgroup of the launch read W
-            fa->defer_for(w);
-            if (bias.defined()) fa->defer_for(bias);
-        }
+    // (th_linear_xent_wide_fused can also finish the conv bias and run Adam on W, b and that bias in the same launch.  Measured on the simple
+    // CNN at batch 256 (r05 / r06, with a knob since retired; HISTORY.md): the head grew from 11.9 to 22.5 us -- Adam's p / m / v round trip
+    // behind the dW reduction in every workgroup, an agent-scope fence per workgroup, the last arriver's serial finish -- against the 5.0 us
+    // finishing launch it replaces: step 57.2 -> 64.1 us.  The Trainer does not use it.)
+    TH(th_linear_xent_wide_ex(Device::ctx(), h.dptr(), w.dptr(), bias.defined() ? bias.dptr() : nullptr, targets.dptr(), b, k, c, loss.dptr(),
+                              nc, dh ? dh->d : nullptr, dw, db, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
+                              log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr, cs ? cs->d : nullptr));
+    if (Adam *fa = FusedAdamScope::active()) {   // complete gradients; every workgroup of the launch read W
+        fa->defer_for(w);
+        if (bias.defined()) fa->defer_for(bias);
     }
     loss.set_requires_grad(true);
     Tensor hh = h, ww = w, bb = bias, out = loss;
-    Tape::push(loss, true, [hh, ww, bb, out, dh, cs, fused_done]() {
+    Tape::push(loss, true, [hh, ww, bb, out, dh, cs]() {
         if (!out.has_grad()) return;
         TAPER_ASSERT(out.grad_->shared_const, "linear_cross_entropy_wide: only loss.backward() from the root is supported");
-        if (fused_done) hh.grad_->colsum_done = true;
-        else if (cs) hh.grad_->colsum = cs;
+        if (cs) hh.grad_->colsum = cs;
         if (dh) {
             TAPER_ASSERT(!hh.has_grad() && !hh.grad_->buf_is_arena, "linear_cross_entropy_wide: input already has a gradient");
             hh.grad_->buf = dh;
@@ -355,13 +333,6 @@ Tensor mlp_tail_cross_entropy(const Tensor &x, const Tensor &w1, const Tensor &b
             if (p->defined()) p->grad_->has = true;
     });
     return loss;
-}
-
-// TAPER_MLP2_MIN_BATCH: from this batch on a Linear + ReLU + Linear classifier steps through th_mlp2_xent (default 480: the crossover
-// measured with bench.py --batch B, both settings -- launch-per-layer forms 24.9 us at 448 rows, 30.8 at 512; th_mlp2_xent 25.5 / 28.3)
-size_t mlp2_min_batch() {
-    static const size_t v = [] { const char *e = std::getenv("TAPER_MLP2_MIN_BATCH"); return e ? (size_t)std::max(32, atoi(e)) : (size_t)480; }();
-    return v;
 }
 
 // What th_mlp2_xent / th_mlp2_xent_deep need of the parameters themselves, whatever the rows: gradients are written, never accumulated
@@ -517,8 +488,8 @@ Tensor mlp3_cross_entropy(const Tensor &x, const Tensor (&w)[3], const Tensor (&
 
 bool conv_chain_mlp3_supported(const Tensor &x, const std::vector<ConvStage> &stages, const Tensor (&w)[3], const Tensor (&b)[3]) {
     if (stages.empty() || stages.back().post != TH_CHAIN_GLOBAL_AVG || x.shape().size() != 4) return false;
-    static const size_t max_batch = [] { const char *e = std::getenv("TAPER_CHAIN_MLP3_MAX_BATCH"); return e ? (size_t)std::max(0, atoi(e)) : (size_t)384; }();
-    if (x.shape()[0] > max_batch) return false;   // (one image per workgroup: at 1 024 images the classifier's own row launch is the faster form, 393 against 403 us)
+    constexpr size_t kMaxBatch = 384;   // (one image per workgroup: at 1 024 images the classifier's own row launch is the faster form, 393 against 403 us)
+    if (x.shape()[0] > kMaxBatch) return false;
     size_t in_f = stages.back().weight.shape()[0];
     for (int l = 0; l < 3; ++l) {
         if (w[l].shape().size() != 2 || w[l].shape()[1] != in_f) return false;
@@ -680,12 +651,6 @@ Tensor AvgPool2d::forward(const Tensor &x) const {  // nn.rs:593-608
 Tensor AdaptiveAvgPool2d::forward(const Tensor &x) const {  // nn.rs:670-686
     const int kh = (int)x.shape()[2] / output_size.first, kw = (int)x.shape()[3] / output_size.second;
     return x.avg_pool2d({kh, kw}, {kh, kw}, {0, 0});
-}
-
-// TAPER_MLP3=0: three-layer classifiers keep the launch-per-layer forms (measurement probe; default: th_mlp3_xent, two launches)
-bool mlp3_fuse() {
-    static const bool on = [] { const char *e = std::getenv("TAPER_MLP3"); return !(e && e[0] == '0'); }();
-    return on;
 }
 
 // TAPER_CONV_CHAIN=0: Trainer steps launch the convolutional front layer by layer (measurement probe; default: one launch where compiled)

@@ -6,7 +6,8 @@
 
 namespace taper {
 // modules.cpp, used by the Trainer's choice of step form (trainer.cpp)
-size_t mlp2_min_batch();                                                        // TAPER_MLP2_MIN_BATCH: from this batch on th_mlp2_xent
+// From this batch on a Linear + ReLU + Linear classifier steps through th_mlp2_xent: the crossover measured with bench.py --batch B (r05, with
+// a knob since retired; HISTORY.md) -- launch-per-layer forms 24.9 us at 448 rows, 30.8 at 512; th_mlp2_xent 25.5 / 28.3
+constexpr size_t kMlp2MinBatch = 480;
 bool mlp2_shapes_ok(size_t batch, const std::vector<Tensor> &w, int64_t n_rows);
-bool mlp3_fuse();                                                               // TAPER_MLP3: the three-layer classifier as two launches
 }  // namespace taper

@@ -91,9 +91,6 @@ struct GradSlot {
     // needs of the gradient are the per-column sums of dX * [x > 0], which the wide classifier head leaves here instead of writing dX
     bool wants_colsum = false;
     std::shared_ptr<Buffer> colsum;   // [numel / batch]
-    std::shared_ptr<GradSlot> colsum_bias;   // that conv's bias (grad slot) and geometry: the head can finish it in its own launch (th_linear_xent_wide_fused)
-    int colsum_c = 0, colsum_hw = 0;
-    bool colsum_done = false;                // ... and did
     // Trainer-internal peephole (PoolBiasScope): the tensor is the (flattened) [n, c] output of a bias-only Conv2dReLU + GLOBAL AVERAGE pool:
     // {counts of outputs > 0 per plane, that conv's bias slot, plane size} -- a classifier launch that forms the tensor's gradient anyway
     // (th_mlp3_xent) can finish the conv's bias there and say so
@@ -269,7 +266,7 @@ Tensor linear_cross_entropy_wide(const Tensor &h, const Tensor &weight, const Te
 bool conv_chain_head_supported(const Tensor &x, const std::vector<ConvStage> &stages, const Tensor &weight, const Tensor &bias);
 // examples/train_mnist_cnn.rs:35-100 whole -- conv rows, global average pool, Flatten, Linear + ReLU, Linear + ReLU, Linear, cross-entropy -- as
 // TWO launches: the chain with the classifier's rows in its last epilogue, then every parameter gradient with Adam in the epilogues
-// (th_conv_chain_mlp3_xent).  One image per workgroup: worth it while the batch is about one image per CU (TAPER_CHAIN_MLP3_MAX_BATCH, default 384).
+// (th_conv_chain_mlp3_xent).  One image per workgroup: worth it while the batch is about one image per CU (up to 384 images: conv_chain_mlp3_supported).
 bool conv_chain_mlp3_supported(const Tensor &x, const std::vector<ConvStage> &stages, const Tensor (&w)[3], const Tensor (&b)[3]);
 Tensor conv_chain_mlp3_cross_entropy(const Tensor &x, const std::vector<ConvStage> &stages, const Tensor (&w)[3], const Tensor (&b)[3],
                                      const Tensor &targets, Tensor *n_correct_out = nullptr, const StepLogSink *log = nullptr);

@@ -625,12 +625,7 @@ Tensor Tensor::reshape(const Shape &s) const {  // tensor.rs:803-840
     if (requires_grad_) {
         out.requires_grad_ = true;
         // a view of [n, ...] as [n, rest] keeps the columns of a sample together: the column-sum wish (GradSlot) travels with it
-        if (PoolBiasScope::active() && grad_->wants_colsum && !s.empty() && !shape_.empty() && s[0] == shape_[0]) {
-            out.grad_->wants_colsum = true;
-            out.grad_->colsum_bias = grad_->colsum_bias;
-            out.grad_->colsum_c = grad_->colsum_c;
-            out.grad_->colsum_hw = grad_->colsum_hw;
-        }
+        if (PoolBiasScope::active() && grad_->wants_colsum && !s.empty() && !shape_.empty() && s[0] == shape_[0]) out.grad_->wants_colsum = true;
         if (PoolBiasScope::active() && grad_->gapfin_cnt && !s.empty() && !shape_.empty() && s[0] == shape_[0]) {
             out.grad_->gapfin_cnt = grad_->gapfin_cnt;
             out.grad_->gapfin_bias = grad_->gapfin_bias;
@@ -641,10 +636,6 @@ Tensor Tensor::reshape(const Shape &s) const {  // tensor.rs:803-840
             if (r.grad_->gapfin_done) {   // the classifier finished the conv bias in its own launch (the gradient itself travels on as usual)
                 r.grad_->gapfin_done = false;
                 in.grad_->gapfin_done = true;
-            }
-            if (r.grad_->colsum_done) {   // the classifier head finished the conv bias in its own launch
-                in.grad_->colsum_done = true;
-                return;
             }
             if (r.grad_->colsum) {   // the classifier head left column sums instead of a gradient: hand them on
                 in.grad_->colsum = std::move(r.grad_->colsum);
@@ -968,17 +959,8 @@ static void push_pooled_conv_bias_node(Tensor &out, const Tensor &bias, int n, i
         out.requires_grad_ = true;
         // inside a Trainer step (one consumer per tensor) the sums of dX * [x > 0] per column are all this node needs of its gradient
         out.grad_->wants_colsum = PoolBiasScope::active() && !bias.has_grad();
-        if (out.grad_->wants_colsum) {
-            out.grad_->colsum_bias = bias.grad_;
-            out.grad_->colsum_c = c_out;
-            out.grad_->colsum_hw = hp * wp;
-        }
         Tensor b = bias, r = out;
         Tape::push(out, true, [b, r, n, c_out, hp, wp]() {
-            if (r.grad_->colsum_done) {   // gradient and Adam update of the bias already happened in the head's launch
-                r.grad_->colsum_done = false;
-                return;
-            }
             if (r.grad_->colsum) {
                 th_ctx *ctx = Device::ctx();
                 bool none;

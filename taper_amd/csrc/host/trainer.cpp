@@ -303,13 +303,13 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
     }
     Linear *last = (fuse_head && nl) ? linear(nl - 1) : nullptr;
     Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && relu(nl - 2)) ? linear(nl - 3) : nullptr;
-    Linear *hidden0 = (hidden && mlp3_fuse() && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;
+    Linear *hidden0 = (hidden && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;   // a three-layer classifier: th_mlp3_xent, two launches
     // the conv rows in front of the classifier as one launch with the classifier's rows in its last epilogue
     const bool chain_head = fuse_head >= 2 && seq && seq->fuse && conv_chain_enabled() && conv_chain_head_enabled() && xin.shape().size() == 4;
 
     // Linear + ReLU (+ Linear + ReLU) + Linear on the loader's 784-wide rows (BASELINE's 784-128-10, examples/train_mnist.rs:40-48's
     // 784-128-64-10) at large batch: three launches for the whole step, the rows read in place
-    if (hidden && sample_shape.empty() && batch >= mlp2_min_batch() && (nl == 3 || (nl == 5 && relu(1) && linear(0)))) {
+    if (hidden && sample_shape.empty() && batch >= kMlp2MinBatch && (nl == 3 || (nl == 5 && relu(1) && linear(0)))) {
         std::vector<Tensor> w, b;
         for (size_t i = 0; i < nl; i += 2) {
             w.push_back(linear(i)->weight);
@@ -317,9 +317,10 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
         }
         // Two hidden layers: below ~1 800 rows the two-launch classifier (th_mlp3_xent behind a gather) is the faster step where it applies --
         // 26.7 / 30.3 / 32.8 / 39.2 us at 512 / 768 / 1 024 / 1 536 rows against 34.4 / 35.8 / 37.7 / 42.0 for th_mlp2_xent_deep, whose 16-row
-        // blocks each leave a whole [h2][h1] share of dW2 behind; 47.5 against 43.7 at 2 048 (tools/mlp_min_batch_probe.py, r05)
-        static const size_t deep_min = [] { const char *e = std::getenv("TAPER_MLP2_DEEP_MIN_BATCH"); return e ? (size_t)std::max(32, atoi(e)) : (size_t)1792; }();
-        const bool mlp3_faster = nl == 5 && batch < deep_min && mlp3_fuse() &&
+        // blocks each leave a whole [h2][h1] share of dW2 behind; 47.5 against 43.7 at 2 048 (r05, with a probe and a knob since retired;
+        // HISTORY.md)
+        constexpr size_t kDeepMinBatch = 1792;
+        const bool mlp3_faster = nl == 5 && batch < kDeepMinBatch &&
                                  th_mlp3_supported((int)batch, (int)w[0].shape()[1], (int)w[0].shape()[0], (int)w[1].shape()[0], (int)w[2].shape()[0]);
         if (w[0].shape()[1] == 784 && mlp2_params_ok(w, b) && mlp2_shapes_ok(batch, w, n_rows) && !mlp3_faster)
             return nl == 3 ? take(StepForm::Mlp2Rows, 0, {hidden, last}) : take(StepForm::Mlp2Rows, 0, {linear(0), hidden, last});
@@ -594,9 +595,9 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
     // a binary ladder of sizes (chunk, chunk/2, chunk/4, ..., 1): whatever an epoch (or a short run: 20 steps = 16 + 4)
     // leaves over after its whole chunks replays as at most log2(chunk) graphs instead of dozens of single-step
     // launches (~10 us of host time each).  A size is recorded by the first call long enough to use it.
-    static const size_t ladder_div = std::getenv("TAPER_GRAPH_LADDER") ? (size_t)std::max(2, atoi(std::getenv("TAPER_GRAPH_LADDER"))) : 2;   // probe: 4 = r01's ladder
+    // (r01's ladder divided by 4)
     std::vector<size_t> want;
-    for (size_t steps = chunk;; steps /= ladder_div) {
+    for (size_t steps = chunk;; steps /= 2) {
         if (steps < 1) steps = 1;
         if (!((steps > 1 && n_full < steps + 1) || have(steps)) && std::find(want.begin(), want.end(), steps) == want.end())
             want.push_back(steps);
@@ -636,7 +637,7 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         const size_t tail = n_full - done > 0 ? (n_full - done) % chunk : 0;
         size_t exact = 0;
         for (auto &g : graphs_) exact += (g.first & (g.first - 1)) != 0 ? 1 : 0;
-        if (tail > 2 && (tail & (tail - 1)) != 0 && ladder_div == 2 && !have(tail) && have(1) && exact < 4 && !graph_capture_failed_ &&
+        if (tail > 2 && (tail & (tail - 1)) != 0 && !have(tail) && have(1) && exact < 4 && !graph_capture_failed_ &&
             graph_key_ == key) {
             TH(th_graph_begin(ctx));
             th_graph *g = nullptr;

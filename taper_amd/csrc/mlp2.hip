@@ -8,7 +8,7 @@
 //             (loss.rs:101-195, 271-290), dH = dlogits W2 and the ReLU mask (ops.rs:254-265, 358-369).  Writes the masked dZ1 -- the
 //             only activation-sized tensor that leaves the CU -- and the workgroup's partial sums of everything that adds over rows but
 //             is small: dW2, db1, db2, NLL, hits.  H itself never reaches memory.  Its first thread opens the optimizer step (t += 1).
-//   launch 2  mlp2_dw1_kernel       dW1 = dZ1^T X (ops.rs:266-294): 128 x 128 tiles of the [hidden][in] output, the batch split into K
+//   launch 2  mlp2_dw1_kernel8      dW1 = dZ1^T X (ops.rs:266-294): 128 x 112 tiles of the [hidden][in] output, the batch split into K
 //             slices over the workgroups; both operands by LDS-DMA as they lie in memory (X rows through the index vector again);
 //             every slice writes its raw accumulators.
 //   launch 3  mlp2_finish_kernel    adds the K slices of dW1 and the row-block partials of launch 1 in fixed order (deterministic),
@@ -112,10 +112,10 @@ struct Mlp2RowsArgs {
 // The k chunks travel through a ring of NS stages: chunk it + NS - 1 is requested while chunk it is contracted, so a request has NS - 1
 // iterations (~0.5-1 us each) to cross the fabric -- with two stages the loop ran at the memory latency, not at the MFMA rate (r04: 52.7 us
 // for 3.3 GFLOP at batch 16 384).
-// NW = 4 (default) or 8 waves.  With eight, two waves share a SIMD: the waves are two groups of four column quarters -- on 64-row tiles the
-// groups are the two 32-row halves (one accumulator tile per wave); on 32-row tiles both groups hold the same 32 x 32 tile and split every
-// chunk's four k rounds between them, two accumulators that are added, group 0 + group 1, when H goes to LDS.  Built to test whether one
-// wave per SIMD was what held the k loop back; it was not (see the launcher), the form stays as a measurement knob.
+// NW = 4 waves (the launcher builds no other).  With eight, two waves share a SIMD: the waves are two groups of four column quarters -- on
+// 64-row tiles the groups are the two 32-row halves (one accumulator tile per wave); on 32-row tiles both groups hold the same 32 x 32 tile and
+// split every chunk's four k rounds between them, two accumulators that are added, group 0 + group 1, when H goes to LDS.  Built to test
+// whether one wave per SIMD was what held the k loop back; it was not (see the launcher).
 // DEEP: TWO hidden layers (examples/train_mnist.rs:40-48: 784-128-64-10).  The second hidden layer is a hid -> h2 contraction on the H tile
 // that is in LDS anyway, and everything behind it is still row-parallel: A2 = relu(A1 W2^T + b2) on v_mfma_f32_16x16x4_f32 (a wave owns a
 // 16-column tile of h2, W2's operand registers requested when the k loop ends), the classifier and its backward on A2 exactly as the shallow
@@ -703,144 +703,10 @@ __global__ __launch_bounds__(64 * NW, (!DEEP && NW == 4 && (RT == 32 || (RT == 6
 }
 
 // ---------------------------------------------------------------------------------------------------------------- launch 2
-struct Mlp2DwArgs {
-    RowSource src;
-    const float *dz1;     // [rows_pad][hid]
-    unsigned dz_bytes;
-    int rows_pad, batch, in_f, hid;
-    float *partial;       // [kz][hid][in_f]
-    int tiles_n, kz, kslice;   // kslice a multiple of 32
-};
-
-// dW1[m = hidden][n = in] over rows [z kslice, (z + 1) kslice): A(m, k) = dZ1[k][m], B(k, n) = X[row k][n] -- both m / n-contiguous, staged as
-// they lie in memory ([32 k][128] images, gemm.hip's m/n-contiguous form: ds_read_b32, lanes on consecutive m / n).  The last n tile reads
-// beyond a row's end (into the next row; beyond the buffer: zeros): those columns are never stored.
-template <int NS, int WGS, bool INDEXED>
-__global__ __launch_bounds__(256, WGS) void mlp2_dw1_kernel(Mlp2DwArgs a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int TS = 128, T_T = TS * M2_BK, STG = 2 * T_T, L = 8;
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), li = lane & 31, lk = lane >> 5;
-    // block b runs on XCD b % 8: every XCD takes a contiguous run of (K slice, n tile) pairs, n innermost -- the tiles of a slice share its dZ1 rows
-    const int nwg = a.tiles_n * a.kz, bid = blockIdx.x;
-    const int xcd = bid % kNumXCD, q = nwg / kNumXCD, rmd = nwg % kNumXCD;
-    const int w = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + bid / kNumXCD;
-    const int z = w / a.tiles_n, tn = w % a.tiles_n;
-    const int n0 = tn * TS, in_f = a.in_f, hid = a.hid;
-    const int kbeg = z * a.kslice, kend = min(a.rows_pad, kbeg + a.kslice), nt = (kend - kbeg) / M2_BK;
-    // The dataset rows of this K slice, resolved once into LDS (behind the ring): row r of the batch is idx[(cursor + r) % n].  The cursor was
-    // advanced by the PREVIOUS step's finish launch; positions are cursor % n + r < 2 n (batch <= n, host-checked).  In the loop a lane then
-    // picks its rows' entries with ds_read -- a scalar or vector load there would sit in the same in-order / unordered counters as the ring's
-    // LDS-DMA and the operand reads, and waiting for it would drain them.
-    int *rows_l = reinterpret_cast<int *>(smem + NS * STG);
-    {
-        const int n_idx = INDEXED ? (int)a.src.n_idx : 1;
-        const int cur = (INDEXED && a.src.cursor) ? (int)(sload(a.src.cursor) % a.src.n_idx) : 0;
-        for (int i = t; i < nt * M2_BK; i += 256) {
-            const int row = min(kbeg + i, a.batch - 1);
-            const int p = cur + row;
-            rows_l[i] = INDEXED ? a.src.idx[p >= n_idx ? p - n_idx : p] : row;
-        }
-    }
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-
-    // staging: instruction j of wave w fills 16-byte units 64 (4 j + w) .. + 63 of the image = k rows 2 (4 j + w) and + 1, 32 quads each.
-    // The two rows' dataset indices are wave-uniform: scalar loads, a chunk ahead of the fetch that needs them.
-    int a_voff[4];
-    const int quad = lane & 31, upper = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a_voff[j] = (int)((unsigned)(2 * (4 * j + wave) + upper) * (unsigned)hid * 4u + (unsigned)(quad << 4));
-    const i32x4 rs_a = make_rsrc(a.dz1, a.dz_bytes), rs_x = make_rsrc(a.src.x, a.src.x_bytes);
-    const unsigned lds0 = lds_addr(smem);
-    const unsigned xq = (unsigned)(n0 + quad * 4) * 4u;
-    auto fetch = [&](int it, int stage) {
-        const int k0 = kbeg + it * M2_BK;
-        const unsigned st = lds0 + (unsigned)(stage * STG) * 4u;
-        int srow[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) srow[j] = rows_l[it * M2_BK + 2 * (4 * j + wave) + upper];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            lds_dma16(rs_a, st + 1024u * (unsigned)(4 * j + wave), a_voff[j], (int)((unsigned)k0 * (unsigned)hid * 4u));
-            lds_dma16(rs_x, st + (unsigned)T_T * 4u + 1024u * (unsigned)(4 * j + wave), (int)((unsigned)srow[j] * (unsigned)in_f * 4u + xq), 0);
-        }
-    };
-
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    int ao[2], bo[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        ao[i] = 4 * lk * TS + wm + 32 * i + li;
-        bo[i] = 4 * lk * TS + wn + 32 * i + li;
-    }
-    M2_STAMP(6, blockIdx.x == 0);
-    __syncthreads();                              // rows_l is complete
-#pragma unroll
-    for (int s = 0; s < NS - 1; ++s)
-        if (s < nt) fetch(s, s);
-    int stage = 0;
-    for (int it = 0; it < nt; ++it) {
-        if (it + NS - 1 <= nt) wait_vmcnt<(NS - 2) * L>();
-        else wait_vmcnt<0>();
-        lds_barrier();
-        const int nxt = it + NS - 1;
-        if (nxt < nt) fetch(nxt, stage == 0 ? NS - 1 : stage - 1);
-        const float *as = smem + stage * STG, *bs = as + T_T;
-        float4 af[2][2], bf[2][2];
-#define M2_FRAG(S, O, RR) make_float4((S)[(O) + (8 * (RR)) * TS], (S)[(O) + (8 * (RR) + 1) * TS], (S)[(O) + (8 * (RR) + 2) * TS], (S)[(O) + (8 * (RR) + 3) * TS])
-#define M2_REQ(SET, RR)                                  \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {      \
-        af[SET][i] = M2_FRAG(as, ao[i], RR);             \
-        bf[SET][i] = M2_FRAG(bs, bo[i], RR);             \
-    }
-#define M2_MFMA(CS, E)                                   \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i)        \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[CS][i].E, bf[CS][j].E, acc[i][j], 0, 0, 0);
-        M2_REQ(0, 0)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int cs = r & 1;
-            if (r + 1 < 4) { M2_REQ(cs ^ 1, r + 1) }
-            __builtin_amdgcn_sched_barrier(0);
-            M2_MFMA(cs, x)
-            M2_MFMA(cs, y)
-            M2_MFMA(cs, z)
-            M2_MFMA(cs, w)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#undef M2_MFMA
-#undef M2_REQ
-#undef M2_FRAG
-        stage = stage + 1 == NS ? 0 : stage + 1;
-    }
-    M2_STAMP(7, blockIdx.x == 0);
-    float *out = a.partial + (long)z * hid * in_f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wn + 32 * j + li;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * lk;
-                if (row < hid && col < in_f) out[(long)row * in_f + col] = acc[i][j][e];
-            }
-        }
-    M2_STAMP(8, blockIdx.x == 0);
-    M2_STAMP(9, blockIdx.x == gridDim.x - 1);
-#endif
-}
-
-// ---- launch 2, second form (default): ONE workgroup of eight waves per CU on a 128 x 112 tile -----------------------------------------
-// 784 = 7 x 112: no padded columns (the 128-wide tiles above compute 896).  The K slices hand out whole 32-row chunks, the first
-// n_chunks % kz slices one more than the rest, and 7 kz <= 256: every CU holds exactly one workgroup, all of (nearly) equal length -- the
-// 2 x 448 layout above leaves a quarter of the CUs with one workgroup and the rest with two.  Half as many slices: half the partial sums
+// ONE workgroup of eight waves per CU on a 128 x 112 tile.
+// 784 = 7 x 112: no padded columns (128-wide tiles compute 896).  The K slices hand out whole 32-row chunks, the first
+// n_chunks % kz slices one more than the rest, and 7 kz <= 256: every CU holds exactly one workgroup, all of (nearly) equal length -- r04's
+// four-wave form on 128 x 128 tiles (2 x 448 workgroups) left a quarter of the CUs with one workgroup and the rest with two.  Half as many slices: half the partial sums
 // written here and read by launch 3.  Eight waves keep two waves on every SIMD (one wave alone stalls its matrix pipe at every operand wait),
 // and one workgroup per CU leaves LDS for a four-stage ring (4 x 30 KB).
 //   wave w: rows m = 16 w .. 16 w + 15 of the tile, all 112 columns: seven v_mfma_f32_16x16x4_f32 accumulators.
@@ -1114,8 +980,6 @@ thread_local int t_mlp2_only = 0;      // th_debug_mlp2_only: 0 = the step; 1 / 
 thread_local int t_mlp2_ksplit = 0;    // th_debug_mlp2_ksplit: 1 .. 8 = that k split on the 16-row tiles whatever the cap says (tests/test_gpu_repro.py); 0 = default
 
 static int m2_rows_per_block(int batch) {
-    static const int forced = [] { const char *e = getenv("TAPER_MLP2_RT"); return e ? atoi(e) : 0; }();
-    if (forced == 16 || forced == 32 || forced == 64) return forced;
     // 64-row tiles once they fill the chip (>= 192 workgroups); 32-row tiles down to 128 workgroups; 16-row tiles below (256 workgroups at 4 096
     // rows: with 32-row tiles half the CUs sat idle while the others ran a 23 us k loop)
     return batch >= 12288 ? 64 : (batch > 4096 ? 32 : 16);
@@ -1144,48 +1008,29 @@ static int mlp2_run(th_ctx *ctx, const th_row_source *src, int batch, int in_fea
     // {nll, hits}; with two hidden layers then dW2 [h2][hidden], db1 [hidden] at o_deep
     const int o_nll = classes * kl + kl + 16, o_deep = (o_nll + 2 + 3) & ~3;
     const int part_len = deep ? o_deep + h2 * hidden + hidden : o_nll + 2, stride = (part_len + 3) & ~3;
-    // launch 2's form: 8 (default) = one eight-wave workgroup per CU on 128 x 112 tiles; TAPER_MLP2_DW = 22 | 31 | 32 | 41 = the four-wave
-    // 128 x 128 form with that many ring stages x workgroups per CU (measurement knob)
-    static const int variant = [] { const char *e = getenv("TAPER_MLP2_DW"); return e ? atoi(e) : 8; }();
-    const bool dw8 = variant == 8;
-    const int tiles_n = ceil_div(in_features, dw8 ? 112 : 128);
-    static const int kz_forced = [] { const char *e = getenv("TAPER_MLP2_KZ"); return e ? atoi(e) : 0; }();
-    int kz, kslice = 0;
-    if (dw8) {
-        // as many slices as fit one workgroup per CU, at least one 32-row chunk each
-        kz = kz_forced > 0 ? kz_forced : kNumCU / tiles_n;
-        // at least two 32-row chunks per slice unless the knob says otherwise: one-chunk slices (batch 1 024: 32 of them) write twice the
-        // partial sums for launch 3 to read and gain nothing -- measured 33.3 -> 31.2 us per step at 1 024 rows, 36.0 -> 35.4 at 2 048
-        kz = std::max(1, std::min(kz, kz_forced > 0 ? rows_pad / M2_BK : std::max(1, rows_pad / (2 * M2_BK))));
-    } else {
-        // two workgroups per CU (two 64 KB double buffers), slices of at least 256 rows
-        const int dw_wgs = variant % 10 == 1 ? 1 : 2;
-        kz = kz_forced > 0 ? kz_forced : ceil_div(dw_wgs * kNumCU, tiles_n);
-        const int kz_max = rows_pad / 256 > 0 ? rows_pad / 256 : 1;
-        if (kz > kz_max) kz = kz_max;
-        kslice = ceil_div(ceil_div(rows_pad, kz), M2_BK) * M2_BK;
-        kz = ceil_div(rows_pad, kslice);
-    }
+    // launch 2: one eight-wave workgroup per CU on 128 x 112 tiles, as many K slices as fit one workgroup per CU, and at least two 32-row
+    // chunks per slice: one-chunk slices (batch 1 024: 32 of them) write twice the partial sums for launch 3 to read and gain nothing --
+    // measured 33.3 -> 31.2 us per step at 1 024 rows, 36.0 -> 35.4 at 2 048
+    const int tiles_n = ceil_div(in_features, 112);
+    const int kz = std::max(1, std::min(kNumCU / tiles_n, std::max(1, rows_pad / (2 * M2_BK))));
     // launch 1 on the 16-row tiles with few row blocks: as many workgroups per block as fill the CUs (up to 8) share its k chunks
     // (mlp2_rows_kernel): 4 at batch 1 024, 2 at 2 048, none from 4 096 on.  Measured through the C ABI: 31.1 -> 27.3 us per step at 1 024
-    // rows (launch 1: 15.6 -> 11.5 us), 35.5 -> 33.1 at 2 048.  TAPER_MLP2_KSPLIT=1 turns it off (measurement knob).
-    static const int ksplit_env = [] { const char *e = getenv("TAPER_MLP2_KSPLIT"); return e ? atoi(e) : 0; }();
-    const int ksplit_forced = t_mlp2_ksplit ? t_mlp2_ksplit : ksplit_env;
+    // rows (launch 1: 15.6 -> 11.5 us), 35.5 -> 33.1 at 2 048.
+    const int ksplit_forced = t_mlp2_ksplit;
     int ksplit = RT != 16 ? 1 : std::max(1, std::min(8, kNumCU / n_blk));
     if (RT == 16 && ksplit_forced >= 1 && ksplit_forced <= 8 && n_blk <= 512) ksplit = ksplit_forced;   // (the kernel sums up to 8 splits)
-    // th_mlp2_set_max_ksplit / TAPER_MLP2_KSPLIT_MAX cap the split (default 8 = the kernel's limit; 1 = off).  (The hand-off's stores are one
+    // th_mlp2_set_max_ksplit caps the split (default 8 = the kernel's limit; 1 = off).  (The hand-off's stores are one
     // asm statement with their wait -- mlp2_rows_kernel: as two statements the compiler reused the first store's data registers while it
     // was still reading them, and with other processes on the GPU 5 - 8 of 30 captured runs had a wrong step: tools/dp512_flake_probe.py,
     // tools/mlp2_repro_stress.py)
-    static const int cap_env = [] { const char *e = getenv("TAPER_MLP2_KSPLIT_MAX"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 8 ? v : 0; }();
-    if (!(RT == 16 && ksplit_forced >= 1 && ksplit_forced <= 8)) ksplit = std::max(1, std::min(ksplit, cap_env ? cap_env : ctx->m2_max_ksplit));   // (TAPER_MLP2_KSPLIT forces a split past the cap: the parity tests)
+    if (!(RT == 16 && ksplit_forced >= 1 && ksplit_forced <= 8)) ksplit = std::max(1, std::min(ksplit, ctx->m2_max_ksplit));   // (th_debug_mlp2_ksplit forces a split past the cap: the parity tests)
     const size_t n_dz = (size_t)rows_pad * hidden, n_part = (size_t)n_blk * stride, n_partial = (size_t)kz * hidden * in_features;
     const size_t n_kpart = ksplit > 1 ? (size_t)n_blk * ksplit * 2048 : 0;
     void *ws = nullptr;
     if (th_malloc(ctx, (n_dz + n_part + n_partial + n_kpart + (size_t)rows_pad) * sizeof(float), &ws)) return 1;
     float *dz1 = (float *)ws, *part = dz1 + n_dz, *partial = part + n_part, *kpart = partial + n_partial;
     // (t_mlp2_only: a timing hook that runs one launch alone -- launch 2 then resolves its rows itself)
-    int32_t *rows_res = (dw8 && src->d_indices && t_mlp2_only == 0) ? reinterpret_cast<int32_t *>(kpart + n_kpart) : nullptr;
+    int32_t *rows_res = (src->d_indices && t_mlp2_only == 0) ? reinterpret_cast<int32_t *>(kpart + n_kpart) : nullptr;
 
     RowSource rs{src->d_rows, src->d_labels, src->d_indices, src->d_indices ? src->d_cursor : nullptr, src->n_indices,
                  (unsigned)((size_t)src->n_rows * in_features * 4)};
@@ -1206,30 +1051,24 @@ static int mlp2_run(th_ctx *ctx, const th_row_source *src, int batch, int in_fea
         TH_SET_MAX_LDS(ctx, (mlp2_rows_kernel<RT_, NS_, NW_, DEEP_>), lds);                                                        \
         hipLaunchKernelGGL((mlp2_rows_kernel<RT_, NS_, NW_, DEEP_>), dim3(n_blk * (RT_ == 16 ? ksplit : 1)), dim3(64 * NW_), lds, ctx->stream, r); \
     } while (0)
-#define M2_ROWS_LAUNCH(RT_, NS_, NW_) do { if (deep) M2_ROWS_LAUNCH_(RT_, NS_, 4, true); else M2_ROWS_LAUNCH_(RT_, NS_, NW_, false); } while (0)
-    // waves per workgroup of launch 1: four.  TAPER_MLP2_NW=8 (two waves per SIMD on the same ring; on 32-row tiles the two wave groups split
-    // every chunk's k rounds) measured the same to 2 %: 39.7 / 23.7 / 22.7 us against 39.2-40.5 / 23.5 / 22.5 us at 16 384 / 4 096 / 1 024 rows --
-    // the k loop already runs at the rate the matrix pipes sustain at the clocks the part holds under this load
-    static const int nw = [] { const char *e = getenv("TAPER_MLP2_NW"); return e && atoi(e) == 8 ? 8 : 4; }();
+#define M2_ROWS_LAUNCH(RT_, NS_) do { if (deep) M2_ROWS_LAUNCH_(RT_, NS_, 4, true); else M2_ROWS_LAUNCH_(RT_, NS_, 4, false); } while (0)
+    // waves per workgroup of launch 1: four.  Eight (two waves per SIMD on the same ring; on 32-row tiles the two wave groups split every
+    // chunk's k rounds) measured the same to 2 %: 39.7 / 23.7 / 22.7 us against 39.2-40.5 / 23.5 / 22.5 us at 16 384 / 4 096 / 1 024 rows --
+    // the k loop already runs at the rate the matrix pipes sustain at the clocks the part holds under this load.
     // 64-row tiles: a THREE-stage ring (72 KB) so that two workgroups share a CU once there are more workgroups than CUs -- one's first-chunk
     // latency and classifier epilogue (8.4 us of a workgroup's 38) run under the other's k loop: launch 1 at 32 768 rows 73.6 -> 60.8 us (0.69 of
-    // the matrix peak), at 60 000 rows 142.7 -> 116.4 us; unchanged up to 16 384 rows (<= 256 workgroups).  TAPER_MLP2_NS64=4: r04's first form.
-    static const int ns64 = [] { const char *e = getenv("TAPER_MLP2_NS64"); return e ? atoi(e) : 3; }();
+    // the matrix peak), at 60 000 rows 142.7 -> 116.4 us; unchanged up to 16 384 rows (<= 256 workgroups).  r04's first form had four stages.
     const int only = t_mlp2_only;
     if (only == 0 || only == 1) {
-        if (RT == 16) M2_ROWS_LAUNCH(16, 8, 4);          // (an eight-stage ring: a chunk is 0.25 us of MFMA work, a request ~2 us away)
-        else if (RT == 64 && nw == 8) M2_ROWS_LAUNCH(64, 4, 8);
-        else if (RT == 64 && ns64 == 3) M2_ROWS_LAUNCH(64, 3, 4);
-        else if (RT == 64) M2_ROWS_LAUNCH(64, 4, 4);
-        else if (nw == 8) M2_ROWS_LAUNCH(32, 4, 8);
-        else M2_ROWS_LAUNCH(32, 4, 4);
+        if (RT == 16) M2_ROWS_LAUNCH(16, 8);          // (an eight-stage ring: a chunk is 0.25 us of MFMA work, a request ~2 us away)
+        else if (RT == 64) M2_ROWS_LAUNCH(64, 3);
+        else M2_ROWS_LAUNCH(32, 4);
     }
 #undef M2_ROWS_LAUNCH
 #undef M2_ROWS_LAUNCH_
     TH_LAUNCH_CHECK();
 
-    if (only != 0 && only != 2) {
-    } else if (dw8) {
+    if (only == 0 || only == 2) {
         Mlp2Dw8Args d{};
         d.src = rs;
         d.dz1 = dz1; d.dz_bytes = (unsigned)(n_dz * 4);
@@ -1243,26 +1082,6 @@ static int mlp2_run(th_ctx *ctx, const th_row_source *src, int batch, int in_fea
         TH_SET_MAX_LDS(ctx, (mlp2_dw1_kernel8<NS8, false>), 160 << 10);
         if (rs.idx) hipLaunchKernelGGL((mlp2_dw1_kernel8<NS8, true>), dim3(tiles_n * kz), dim3(512), lds, ctx->stream, d);
         else hipLaunchKernelGGL((mlp2_dw1_kernel8<NS8, false>), dim3(tiles_n * kz), dim3(512), lds, ctx->stream, d);
-    } else {
-        Mlp2DwArgs d{};
-        d.src = rs;
-        d.dz1 = dz1; d.dz_bytes = (unsigned)(n_dz * 4);
-        d.rows_pad = rows_pad; d.batch = batch; d.in_f = in_features; d.hid = hidden;
-        d.partial = partial; d.tiles_n = tiles_n; d.kz = kz; d.kslice = kslice;
-        const int ns = variant / 10 >= 2 && variant / 10 <= 4 ? variant / 10 : 2;
-        const size_t lds = (size_t)ns * 2 * 128 * M2_BK * sizeof(float) + (size_t)kslice * sizeof(int);
-#define M2_DW_LAUNCH(NS_, WGS_)                                                                                                       \
-    do {                                                                                                                              \
-        TH_SET_MAX_LDS(ctx, (mlp2_dw1_kernel<NS_, WGS_, true>), 160 << 10);                                                          \
-        TH_SET_MAX_LDS(ctx, (mlp2_dw1_kernel<NS_, WGS_, false>), 160 << 10);                                                         \
-        if (rs.idx) hipLaunchKernelGGL((mlp2_dw1_kernel<NS_, WGS_, true>), dim3(tiles_n * kz), dim3(256), lds, ctx->stream, d);       \
-        else hipLaunchKernelGGL((mlp2_dw1_kernel<NS_, WGS_, false>), dim3(tiles_n * kz), dim3(256), lds, ctx->stream, d);             \
-    } while (0)
-        if (variant == 31) M2_DW_LAUNCH(3, 1);
-        else if (variant == 32) M2_DW_LAUNCH(3, 2);
-        else if (variant == 41) M2_DW_LAUNCH(4, 1);
-        else M2_DW_LAUNCH(2, 2);
-#undef M2_DW_LAUNCH
     }
     TH_LAUNCH_CHECK();
 

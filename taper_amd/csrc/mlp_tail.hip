@@ -855,12 +855,7 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
     TH_REQUIRE((((uintptr_t)d_h | (uintptr_t)d_w2) & 15) == 0, "th_mlp_tail: d_h and d_w2 must be 16-byte aligned");
     TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_mlp_tail: metrics need d_state and a capacity");
     TH_REQUIRE(!(b1_fuse && b1_fuse->d_p) || d_db1, "th_mlp_tail: fused b1 update needs d_db1");
-    static const int tn_env = [] {   // measurement probe: TAPER_TAIL_TN = 1 | 2 | 4 input tiles per dW1 workgroup
-        const char *e = getenv("TAPER_TAIL_TN");
-        const int v = e ? atoi(e) : 2;
-        return (v == 1 || v == 4) ? v : 2;
-    }();
-    const int tn = comm ? 2 : tn_env;
+    constexpr int TN = 2;   // input tiles per dW1 workgroup
     TailArgs a{};
     a.x = d_x; a.h = d_h; a.w2 = d_w2; a.b2 = d_b2; a.targets = d_targets;
     a.batch = batch; a.in_f = in_features; a.hid = hidden; a.c = classes;
@@ -869,21 +864,18 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
     a.w1_adam = make_adam_dev(w1_fuse);
     a.b1_adam = make_adam_dev(b1_fuse);
     a.tiles_m = ceil_div(hidden, 16);
-    a.groups = ceil_div(in_features, 16 * tn);
+    a.groups = ceil_div(in_features, 16 * TN);
     a.n_dw = (a.tiles_m * a.groups + 7) & ~7;
     a.n_head = (a.tiles_m + 7) & ~7;
     a.w1 = d_w1;
     a.dx = d_dx;
     a.xgroups = ceil_div(in_features, 32);
     // waves per workgroup of the whole-tile kernel: one 16-row block per wave and pass -- 4 up to 64 rows, 8 above (16 waves need
-    // <= 128 VGPRs: spills, and measured no better); TAPER_TAIL_NW = 4 | 8 forces a count (measurement probe)
-    static const int nw_env = getenv("TAPER_TAIL_NW") ? atoi(getenv("TAPER_TAIL_NW")) : 0;
-    const int nw_eff = (!comm && (nw_env == 4 || nw_env == 8)) ? nw_env : (batch <= 64 ? 4 : 8);
-    const int nw = nw_eff;
-    const int grid = a.n_dw + a.n_head + (d_dx ? a.xgroups * ceil_div(batch, 16 * nw_eff) : 0);
+    // <= 128 VGPRs: spills, and measured no better)
+    const int nw = batch <= 64 ? 4 : 8;
+    const int grid = a.n_dw + a.n_head + (d_dx ? a.xgroups * ceil_div(batch, 16 * nw) : 0);
     // whole tiles everywhere (the MNIST MLP: 784-128-10, batches of 64 / 32): the short-instruction-stream kernel
-    const bool exact = tail_whole_tiles(batch, in_features, hidden) &&
-                       (d_dx || !(getenv("TAPER_TAIL_GENERAL") && getenv("TAPER_TAIL_GENERAL")[0] == '1'));
+    const bool exact = tail_whole_tiles(batch, in_features, hidden);
     if (comm) {
         const DpDev *dp = comm_dp_dev(comm);
         TH_REQUIRE(dp && th_mlp_tail_dp_supported(comm, ctx, batch, in_features, hidden, classes),
@@ -897,7 +889,7 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
         comm_dp_count_launch(comm);
         return 0;
     }
-#define TH_TAIL_LAUNCH(KS, TN)                                                                                        \
+#define TH_TAIL_LAUNCH(KS)                                                                                            \
     do {                                                                                                              \
         if (exact && d_dx && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
         else if (exact && d_dx) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 4>), dim3(grid), dim3(256), 0, ctx->stream, a);     \
@@ -905,17 +897,10 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
         else if (exact) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 4>), dim3(grid), dim3(256), 0, ctx->stream, a);     \
         else hipLaunchKernelGGL((mlp_tail_kernel<KS, TN>), dim3(grid), dim3(256), 0, ctx->stream, a);                 \
     } while (0)
-#define TH_TAIL_KS(TN)                          \
-    do {                                        \
-        if (exact && hidden == 32) TH_TAIL_LAUNCH(2, TN); \
-        else if (hidden <= 64) TH_TAIL_LAUNCH(4, TN);  \
-        else if (hidden <= 128) TH_TAIL_LAUNCH(8, TN); \
-        else TH_TAIL_LAUNCH(16, TN);                   \
-    } while (0)
-    if (tn == 1) TH_TAIL_KS(1);
-    else if (tn == 4) TH_TAIL_KS(4);
-    else TH_TAIL_KS(2);
-#undef TH_TAIL_KS
+    if (exact && hidden == 32) TH_TAIL_LAUNCH(2);
+    else if (hidden <= 64) TH_TAIL_LAUNCH(4);
+    else if (hidden <= 128) TH_TAIL_LAUNCH(8);
+    else TH_TAIL_LAUNCH(16);
 #undef TH_TAIL_LAUNCH
     TH_LAUNCH_CHECK();
     return 0;

@@ -581,7 +581,7 @@ def test_maxpool_windows_without_a_maximum(ctx, O, n, c, h, w, k, s, pad):
 @pytest.mark.parametrize("n,c,h,w", [(4, 32, 28, 28), (3, 64, 14, 14), (2, 3, 8, 8), (1, 1, 2, 2), (2, 5, 30, 18), (1, 2, 40, 40)])
 @pytest.mark.parametrize("zero_first", [1, 0])
 def test_maxpool2_bwd_fast_path_equals_the_general_kernel(ctx, n, c, h, w, zero_first):
-    """th_maxpool2d_bwd on 2x2 / stride 2 / unpadded pools takes a wave-per-plane kernel; TAPER_POOL_BWD_GENERAL is not set here, so the
+    """th_maxpool2d_bwd on 2x2 / stride 2 / unpadded pools takes a wave-per-plane kernel; the
     comparison is against the scatter itself: gin[argmax[o]] (+)= gout[o] in ascending o (tensor.rs:1496-1519), with windows that kept
     the default index (all NaN) landing on their plane's pixel (0,0) -- bit-exact, both with zero_first (Q5) and accumulating."""
     rng = np.random.default_rng(n * 100 + c * 10 + h)

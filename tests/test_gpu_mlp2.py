@@ -245,22 +245,19 @@ def test_trainer_large_batch_graph_equals_eager_launches():
     T.Tape.reset()
 
 
-def test_mlp2_measurement_forms_in_a_subprocess():
-    """the knobs kept for measurements (launch 2 as four-wave 128 x 128 tiles, launch 1 as eight waves on 64-row tiles at every batch) give
-    the same results: the dense-row and index-vector cases again under TAPER_MLP2_DW=22 TAPER_MLP2_RT=64 TAPER_MLP2_NW=8, the 32-row
-    eight-wave form (k rounds split over two wave groups) under TAPER_MLP2_RT=32, and the 16-row tiles at every batch with a row block's
-    k chunks on one workgroup (TAPER_MLP2_KSPLIT=1) and on three (the default splits by the CU count) -- the choice is read once per process"""
-    import os
-    import subprocess
-    import sys
-    if os.environ.get("TAPER_MLP2_DW"):
-        pytest.skip("already inside the knob run")
-    env = dict(os.environ, TAPER_MLP2_DW="22", TAPER_MLP2_RT="64", TAPER_MLP2_NW="8")
-    for extra in ({}, {"TAPER_MLP2_RT": "32", "TAPER_MLP2_DW": "8"}, {"TAPER_MLP2_RT": "16", "TAPER_MLP2_DW": "8", "TAPER_MLP2_NW": "4", "TAPER_MLP2_KSPLIT": "1"},
-                  {"TAPER_MLP2_RT": "16", "TAPER_MLP2_DW": "8", "TAPER_MLP2_NW": "4", "TAPER_MLP2_KSPLIT": "3"}):
-        r = subprocess.run([sys.executable, "-m", "pytest", __file__, "-q", "-m", "gpu", "-k", "dense_rows or index_vector", "-p", "no:cacheprovider"],
-                           env=dict(env, **extra), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+@pytest.mark.parametrize("form,ksplit", [("dense", 1), ("dense", 3), ("index", 1), ("index", 3)])
+def test_mlp2_forced_ksplit(ctx, O, form, ksplit):
+    """the 16-row tiles with a row block's k chunks on one workgroup and on three (th_debug_mlp2_ksplit; at 1 024 / 2 048 rows the launcher
+    itself splits by 4 / 2), dense rows and rows through the index vector, against the oracle"""
+    from taper_amd._lib import hip as lib
+    lib.th_debug_mlp2_ksplit(ksplit)
+    try:
+        if form == "dense":
+            test_mlp2_dense_rows(ctx, O, 1024, 784, 128, 10)
+        else:
+            test_mlp2_rows_through_the_index_vector(ctx, O, 5000, 2048, 4000)
+    finally:
+        lib.th_debug_mlp2_ksplit(0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ two hidden layers

@@ -1,5 +1,4 @@
-"""Times th_mlp2_xent (three launches) through the C ABI with HIP events: python tools/mlp2_time.py [batch ...]
-Env: TAPER_MLP2_RT (32 | 64), TAPER_MLP2_KZ (K slices of launch 2)."""
+"""Times th_mlp2_xent (three launches) through the C ABI with HIP events: python tools/mlp2_time.py [batch ...]"""
 import ctypes as C
 import os
 import sys
