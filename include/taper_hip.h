@@ -412,6 +412,28 @@ int th_fake_quant_multi(th_ctx *ctx, const th_fq_item *d_items, int n_items);
  * Two launches (int8) or one (f16), capturable. */
 int th_fake_quant_act(th_ctx *ctx, const float *d_x, float *d_y, int64_t n, int qtype, float *d_scale);
 
+/* ---- quantization observers (src/quantization/observers.rs, csrc/observers.hip) ---- */
+/* The statistics stay on the device; every call below only enqueues work on the stream (no synchronisation, nothing read back).
+ * MinMaxObserver::observe (observers.rs:50-72): the first observation copies d_x into both vectors; a later one folds the first
+ * n = min(m, len) elements in with f32::min / f32::max (a NaN loses to a number). */
+int th_obs_minmax_first(th_ctx *ctx, const float *d_x, float *d_min, float *d_max, int64_t n);
+int th_obs_minmax_update(th_ctx *ctx, const float *d_x, float *d_min, float *d_max, int64_t n);
+/* global_min / global_max (observers.rs:85-98): d_out2 = {fold of d_min[0, n) from +inf with f32::min, fold of d_max[0, n) from -inf with
+ * f32::max}; infinities take part, NaNs lose; n == 0 gives {+inf, -inf}.  d_min and d_max may be the same array. */
+int th_obs_fold(th_ctx *ctx, const float *d_min, const float *d_max, int64_t n, float *d_out2);
+/* HistogramObserver's first observation (observers.rs:168-179): {min_val, max_val} = th_obs_fold of d_x, bin_width = (max_val - min_val)
+ * / num_bins as f32, d_edges[i] = min_val + i as f32 * bin_width for i in 0..=num_bins; each operation rounded once.  num_bins >= 1. */
+int th_obs_hist_edges(th_ctx *ctx, const float *d_x, int64_t n, int num_bins, float *d_edges);
+/* The counting pass (observers.rs:182-201): d_bins[find_bin(v)] += 1 for every element, find_bin the reference's scan -- the first edge with
+ * v <= edge, minus one, saturating; past the last edge and every NaN: the last bin.  d_bins: num_bins 64-bit counters (zeroed by the
+ * caller before the first observation).  Integer atomics only: the result does not depend on the order of arrival.  Up to
+ * th_obs_hist_lds_max_bins() bins the edges and 32-bit counters of a workgroup live in LDS (n < 2^40); above it, and for edges that are
+ * not finite and non-decreasing (where the literal scan runs), the counters are the global ones. */
+int th_obs_hist_count(th_ctx *ctx, const float *d_x, int64_t n, const float *d_edges, int num_bins, uint64_t *d_bins);
+int th_obs_hist_lds_max_bins(void);   /* 8192 */
+/* HistogramObserver::get_stats (observers.rs:226-245): d_out3 = {sum of the bins, sum of i * bins[i] (wrapping), the largest bin} */
+int th_obs_hist_stats(th_ctx *ctx, const uint64_t *d_bins, int num_bins, uint64_t *d_out3);
+
 /* ---- broadcast / reduce / layout: src/tensor.rs ---------------------- */
 int th_transpose2d(th_ctx *ctx, const float *d_in, float *d_out, int rows, int cols);      /* tensor.rs:544-566 */
 /* dst[r*dst_ld + c] = src[r*src_ld + c] for r < rows, c < cols: the strided block copies behind slice_channels /

@@ -168,6 +168,53 @@ int tp_qat_module_observed(const tp_module *m, float *out3);
 /* the round trip of the layer's weight (which 0) or bias (1) that its last active forward ran with (a copy; no gradient) */
 int tp_qat_module_fake_quantized(const tp_module *m, int which, tp_tensor **out);
 
+/* ---- quantization observers (src/quantization/observers.rs) ----
+ * Statistics of the tensors an observer is shown, kept on the device: tp_observer_observe only enqueues work (no synchronisation, nothing
+ * read back), the read-outs wait.  kind TP_OBSERVER_MINMAX: the running min / max PER ELEMENT of the flat data (the first observation
+ * fixes the length; later ones update the first min(m, len) elements); TP_OBSERVER_HISTOGRAM: num_bins >= 1 64-bit counts between
+ * num_bins + 1 edges that the first observation fixes (0 bins fail before the device is touched; num_bins is ignored for MINMAX).  A
+ * disabled observer ignores observations and does not count them; reset returns every device buffer and the next observation is a
+ * first one again.  A read-out of the other kind's group fails. */
+#define TP_OBSERVER_MINMAX 0
+#define TP_OBSERVER_HISTOGRAM 1
+typedef struct tp_observer tp_observer;
+typedef struct tp_observer_manager tp_observer_manager;
+int tp_observer_new(int kind, size_t num_bins, tp_observer **out);
+int tp_observer_free(tp_observer *o);
+int tp_observer_set_enabled(tp_observer *o, int on);
+int tp_observer_is_enabled(const tp_observer *o, int *out);
+int tp_observer_observe(tp_observer *o, const tp_tensor *t);
+int tp_observer_num_observations(const tp_observer *o, size_t *out);
+int tp_observer_reset(tp_observer *o);
+/* MinMax read-outs: the vectors' length (0 before the first observation), the vectors (each nullable), and get_stats -- global_min /
+ * global_max are the NaN-ignoring folds from +inf / -inf, made on the device; range = global_max - global_min (-inf when empty) */
+int tp_observer_minmax_len(const tp_observer *o, size_t *out);
+int tp_observer_minmax_values(const tp_observer *o, float *h_min, float *h_max);
+int tp_observer_minmax_stats(const tp_observer *o, size_t *num_observations, float *global_min, float *global_max, float *range);
+/* Histogram read-outs: num_bins counts, the edges (tp_observer_hist_num_edges: num_bins + 1, or 0 while there are none), and get_stats:
+ * mean_bin = (sum of i * count) as f32 / total_count as f32, 0 when empty */
+int tp_observer_hist_num_bins(const tp_observer *o, size_t *out);
+int tp_observer_hist_bins(const tp_observer *o, uint64_t *h_bins);
+int tp_observer_hist_num_edges(const tp_observer *o, size_t *out);
+int tp_observer_hist_edges(const tp_observer *o, float *h_edges);
+int tp_observer_hist_stats(const tp_observer *o, size_t *num_observations, uint64_t *total_count, float *mean_bin, uint64_t *max_bin_count);
+/* ObserverManager (observers.rs:268-345): observers by name, one map per kind; adding an existing name replaces the observer with a
+ * fresh one; observing an unknown name does nothing, asking its stats sets *found = 0 -- neither is an error.  tp_observer_manager_names:
+ * the minmax names then the histogram names, each sorted, '\n'-separated and NUL-terminated into buf (truncated to cap; nullable),
+ * *n_names their number and *needed the bytes the whole list takes with its NUL. */
+int tp_observer_manager_new(tp_observer_manager **out);
+int tp_observer_manager_free(tp_observer_manager *m);
+int tp_observer_manager_add_minmax(tp_observer_manager *m, const char *name);
+int tp_observer_manager_add_histogram(tp_observer_manager *m, const char *name, size_t num_bins);
+int tp_observer_manager_observe_minmax(tp_observer_manager *m, const char *name, const tp_tensor *t);
+int tp_observer_manager_observe_histogram(tp_observer_manager *m, const char *name, const tp_tensor *t);
+int tp_observer_manager_minmax_stats(const tp_observer_manager *m, const char *name, int *found, size_t *num_observations, float *global_min,
+                                     float *global_max, float *range);
+int tp_observer_manager_histogram_stats(const tp_observer_manager *m, const char *name, int *found, size_t *num_observations,
+                                        uint64_t *total_count, float *mean_bin, uint64_t *max_bin_count);
+int tp_observer_manager_reset_all(tp_observer_manager *m);
+int tp_observer_manager_names(const tp_observer_manager *m, char *buf, size_t cap, size_t *n_names, size_t *needed);
+
 /* ---- optim (src/optim.rs) ---- */
 int tp_adam_new(tp_tensor *const *params, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                 tp_optim **out);

@@ -529,6 +529,173 @@ class qat:
                     is_active=bool(g.value) and bool(t.value))
 
 
+# -- src/quantization/observers.rs -------------------------------------------------
+class _Observer:
+    """An observer's statistics live on the device: observe() only enqueues work on the stream; the read-outs wait."""
+    _KIND = None
+
+    def __init__(self, num_bins=0):
+        h = _p()
+        tp_check(host.tp_observer_new(self._KIND, int(num_bins), C.byref(h)), f"{type(self).__name__}::new")
+        self._h = h.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            host.tp_observer_free(self._h)
+            self._h = None
+
+    def set_enabled(self, enabled: bool): tp_check(host.tp_observer_set_enabled(self._h, 1 if enabled else 0), "Observer::set_enabled")
+
+    def is_enabled(self) -> bool:
+        out = C.c_int()
+        tp_check(host.tp_observer_is_enabled(self._h, C.byref(out)), "Observer::is_enabled")
+        return bool(out.value)
+
+    def observe(self, tensor: Tensor): tp_check(host.tp_observer_observe(self._h, tensor._h), "Observer::observe")
+
+    def num_observations(self) -> int:
+        out = C.c_size_t()
+        tp_check(host.tp_observer_num_observations(self._h, C.byref(out)), "Observer::num_observations")
+        return out.value
+
+    def reset(self): tp_check(host.tp_observer_reset(self._h), "Observer::reset")
+
+
+def _minmax_stats(call, what):
+    n, lo, hi, rng = C.c_size_t(), C.c_float(), C.c_float(), C.c_float()
+    if not call(C.byref(n), C.byref(lo), C.byref(hi), C.byref(rng), what):
+        return None
+    f = np.float32
+    return dict(num_observations=n.value, global_min=f(lo.value), global_max=f(hi.value), range=f(rng.value))
+
+
+def _histogram_stats(call, what):
+    n, total, mean, most = C.c_size_t(), C.c_uint64(), C.c_float(), C.c_uint64()
+    if not call(C.byref(n), C.byref(total), C.byref(mean), C.byref(most), what):
+        return None
+    return dict(num_observations=n.value, total_count=total.value, mean_bin=np.float32(mean.value), max_bin_count=most.value)
+
+
+class MinMaxObserver(_Observer):
+    """observers.rs:11-121: the running min / max PER ELEMENT of the flat data.  The first observation fixes the vectors' length; a later
+    one of m elements updates the first min(m, len).  min / max are f32::min / f32::max (a NaN loses to a number)."""
+    _KIND = 0
+
+    def __init__(self):
+        super().__init__(0)
+
+    def _values(self, which):
+        n = C.c_size_t()
+        tp_check(host.tp_observer_minmax_len(self._h, C.byref(n)), "MinMaxObserver::len")
+        out = np.empty(n.value, np.float32)
+        ptr = out.ctypes.data if n.value else None
+        tp_check(host.tp_observer_minmax_values(self._h, ptr if which == 0 else None, ptr if which == 1 else None), "MinMaxObserver::values")
+        return out
+
+    def min_values(self) -> np.ndarray: return self._values(0)
+    def max_values(self) -> np.ndarray: return self._values(1)
+    def global_min(self): return self.get_stats()["global_min"]
+    def global_max(self): return self.get_stats()["global_max"]
+
+    def get_stats(self):
+        """ObserverStats: num_observations, global_min, global_max, range (the folds run on the device; +inf / -inf / -inf when empty)"""
+        def call(n, lo, hi, rng, what):
+            tp_check(host.tp_observer_minmax_stats(self._h, n, lo, hi, rng), what)
+            return True
+        return _minmax_stats(call, "MinMaxObserver::get_stats")
+
+    stats = get_stats
+
+
+class HistogramObserver(_Observer):
+    """observers.rs:125-246: num_bins 64-bit counts between num_bins + 1 edges that the first observation fixes; bin k is
+    (edge[k], edge[k + 1]], bin 0 also takes everything below, the last bin everything above and every NaN."""
+    _KIND = 1
+
+    def __init__(self, num_bins):
+        if int(num_bins) < 1:
+            raise TaperError("HistogramObserver: num_bins must be at least 1 (the reference's find_bin underflows with 0 bins)")
+        super().__init__(num_bins)
+        self.num_bins = int(num_bins)
+
+    def bins(self) -> np.ndarray:
+        out = np.empty(self.num_bins, np.uint64)
+        tp_check(host.tp_observer_hist_bins(self._h, out.ctypes.data), "HistogramObserver::bins")
+        return out
+
+    def bin_edges(self) -> np.ndarray:
+        n = C.c_size_t()
+        tp_check(host.tp_observer_hist_num_edges(self._h, C.byref(n)), "HistogramObserver::bin_edges")
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            tp_check(host.tp_observer_hist_edges(self._h, out.ctypes.data), "HistogramObserver::bin_edges")
+        return out
+
+    edges = bin_edges
+
+    def get_stats(self):
+        """HistogramStats: num_observations, total_count, mean_bin, max_bin_count"""
+        def call(n, total, mean, most, what):
+            tp_check(host.tp_observer_hist_stats(self._h, n, total, mean, most), what)
+            return True
+        return _histogram_stats(call, "HistogramObserver::get_stats")
+
+    stats = get_stats
+
+
+class ObserverManager:
+    """observers.rs:268-345: observers by name, one map per kind (a name may be in both).  Adding an existing name replaces its observer
+    with a fresh one; observing an unknown name does nothing and its stats are None."""
+
+    def __init__(self):
+        h = _p()
+        tp_check(host.tp_observer_manager_new(C.byref(h)), "ObserverManager::new")
+        self._h = h.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            host.tp_observer_manager_free(self._h)
+            self._h = None
+
+    def add_minmax_observer(self, name: str):
+        tp_check(host.tp_observer_manager_add_minmax(self._h, name.encode()), "ObserverManager::add_minmax_observer")
+
+    def add_histogram_observer(self, name: str, num_bins: int):
+        if int(num_bins) < 1:
+            raise TaperError("HistogramObserver: num_bins must be at least 1 (the reference's find_bin underflows with 0 bins)")
+        tp_check(host.tp_observer_manager_add_histogram(self._h, name.encode(), int(num_bins)), "ObserverManager::add_histogram_observer")
+
+    def observe_minmax(self, name: str, tensor: Tensor):
+        tp_check(host.tp_observer_manager_observe_minmax(self._h, name.encode(), tensor._h), "ObserverManager::observe_minmax")
+
+    def observe_histogram(self, name: str, tensor: Tensor):
+        tp_check(host.tp_observer_manager_observe_histogram(self._h, name.encode(), tensor._h), "ObserverManager::observe_histogram")
+
+    def get_minmax_stats(self, name: str):
+        def call(n, lo, hi, rng, what):
+            found = C.c_int()
+            tp_check(host.tp_observer_manager_minmax_stats(self._h, name.encode(), C.byref(found), n, lo, hi, rng), what)
+            return bool(found.value)
+        return _minmax_stats(call, "ObserverManager::get_minmax_stats")
+
+    def get_histogram_stats(self, name: str):
+        def call(n, total, mean, most, what):
+            found = C.c_int()
+            tp_check(host.tp_observer_manager_histogram_stats(self._h, name.encode(), C.byref(found), n, total, mean, most), what)
+            return bool(found.value)
+        return _histogram_stats(call, "ObserverManager::get_histogram_stats")
+
+    def reset_all(self): tp_check(host.tp_observer_manager_reset_all(self._h), "ObserverManager::reset_all")
+
+    def get_observer_names(self):
+        """the minmax names, then the histogram names, each sorted"""
+        count, needed = C.c_size_t(), C.c_size_t()
+        tp_check(host.tp_observer_manager_names(self._h, None, 0, C.byref(count), C.byref(needed)), "ObserverManager::get_observer_names")
+        buf = C.create_string_buffer(needed.value)
+        tp_check(host.tp_observer_manager_names(self._h, buf, needed.value, None, None), "ObserverManager::get_observer_names")
+        return buf.value.decode().split("\n") if count.value else []
+
+
 # -- src/optim.rs -----------------------------------------------------------------
 class _Optim:
     def __del__(self):

@@ -16,6 +16,8 @@ struct tp_trainer { std::unique_ptr<Trainer> t; };
 struct tp_comm { std::shared_ptr<Communicator> c; };
 struct tp_sched { std::shared_ptr<LRScheduler> s; };
 struct tp_qmodule { std::unique_ptr<QuantizedModule> q; std::vector<const QTensor *> tensors; };
+struct tp_observer { std::unique_ptr<MinMaxObserver> minmax; std::unique_ptr<HistogramObserver> hist; };   // one of the two, by kind
+struct tp_observer_manager { ObserverManager m; };
 
 static thread_local std::string g_err;
 
@@ -313,6 +315,141 @@ int tp_qat_status(int *global_enabled, int *training_mode, size_t *module_count,
 }
 int tp_qat_module_observed(const tp_module *m, float *out3) { TP_BEGIN as_qat(m)->observed(out3); TP_END }
 int tp_qat_module_fake_quantized(const tp_module *m, int which, tp_tensor **out) { TP_BEGIN *out = wrap(as_qat(m)->fake_quantized(which)); TP_END }
+
+// ---- observers ----
+static MinMaxObserver &as_minmax(const tp_observer *o) {
+    TAPER_ASSERT(o && o->minmax, "not a MinMax observer");
+    return *o->minmax;
+}
+static HistogramObserver &as_hist(const tp_observer *o) {
+    TAPER_ASSERT(o && o->hist, "not a Histogram observer");
+    return *o->hist;
+}
+static void put_stats(const ObserverStats &s, size_t *n, float *gmin, float *gmax, float *range) {
+    if (n) *n = s.num_observations;
+    if (gmin) *gmin = s.global_min;
+    if (gmax) *gmax = s.global_max;
+    if (range) *range = s.range;
+}
+static void put_hist_stats(const HistogramStats &s, size_t *n, uint64_t *total, float *mean_bin, uint64_t *max_count) {
+    if (n) *n = s.num_observations;
+    if (total) *total = s.total_count;
+    if (mean_bin) *mean_bin = s.mean_bin;
+    if (max_count) *max_count = s.max_bin_count;
+}
+int tp_observer_new(int kind, size_t num_bins, tp_observer **out) {
+    TP_BEGIN
+    TAPER_ASSERT(kind == TP_OBSERVER_MINMAX || kind == TP_OBSERVER_HISTOGRAM, "tp_observer_new: kind is neither TP_OBSERVER_MINMAX nor TP_OBSERVER_HISTOGRAM");
+    auto o = std::make_unique<tp_observer>();
+    if (kind == TP_OBSERVER_MINMAX) o->minmax = std::make_unique<MinMaxObserver>();
+    else o->hist = std::make_unique<HistogramObserver>(num_bins);
+    *out = o.release();
+    TP_END
+}
+int tp_observer_free(tp_observer *o) { TP_BEGIN delete o; TP_END }
+int tp_observer_set_enabled(tp_observer *o, int on) {
+    TP_BEGIN
+    if (o->minmax) o->minmax->set_enabled(on != 0);
+    else o->hist->set_enabled(on != 0);
+    TP_END
+}
+int tp_observer_is_enabled(const tp_observer *o, int *out) { TP_BEGIN *out = (o->minmax ? o->minmax->is_enabled() : o->hist->is_enabled()) ? 1 : 0; TP_END }
+int tp_observer_observe(tp_observer *o, const tp_tensor *t) {
+    TP_BEGIN
+    if (o->minmax) o->minmax->observe(t->t);
+    else o->hist->observe(t->t);
+    TP_END
+}
+int tp_observer_num_observations(const tp_observer *o, size_t *out) {
+    TP_BEGIN *out = o->minmax ? o->minmax->num_observations() : o->hist->num_observations(); TP_END
+}
+int tp_observer_reset(tp_observer *o) {
+    TP_BEGIN
+    if (o->minmax) o->minmax->reset();
+    else o->hist->reset();
+    TP_END
+}
+int tp_observer_minmax_len(const tp_observer *o, size_t *out) { TP_BEGIN *out = as_minmax(o).len(); TP_END }
+int tp_observer_minmax_values(const tp_observer *o, float *h_min, float *h_max) {
+    TP_BEGIN
+    const MinMaxObserver &m = as_minmax(o);
+    if (h_min) {
+        auto v = m.min_values();
+        std::memcpy(h_min, v.data(), v.size() * sizeof(float));
+    }
+    if (h_max) {
+        auto v = m.max_values();
+        std::memcpy(h_max, v.data(), v.size() * sizeof(float));
+    }
+    TP_END
+}
+int tp_observer_minmax_stats(const tp_observer *o, size_t *num_observations, float *global_min, float *global_max, float *range) {
+    TP_BEGIN put_stats(as_minmax(o).get_stats(), num_observations, global_min, global_max, range); TP_END
+}
+int tp_observer_hist_num_bins(const tp_observer *o, size_t *out) { TP_BEGIN *out = as_hist(o).num_bins(); TP_END }
+int tp_observer_hist_bins(const tp_observer *o, uint64_t *h_bins) {
+    TP_BEGIN
+    auto v = as_hist(o).bins();
+    std::memcpy(h_bins, v.data(), v.size() * sizeof(uint64_t));
+    TP_END
+}
+int tp_observer_hist_num_edges(const tp_observer *o, size_t *out) {
+    TP_BEGIN
+    const HistogramObserver &h = as_hist(o);
+    *out = h.has_edges() ? h.num_bins() + 1 : 0;
+    TP_END
+}
+int tp_observer_hist_edges(const tp_observer *o, float *h_edges) {
+    TP_BEGIN
+    auto v = as_hist(o).bin_edges();
+    std::memcpy(h_edges, v.data(), v.size() * sizeof(float));
+    TP_END
+}
+int tp_observer_hist_stats(const tp_observer *o, size_t *num_observations, uint64_t *total_count, float *mean_bin, uint64_t *max_bin_count) {
+    TP_BEGIN put_hist_stats(as_hist(o).get_stats(), num_observations, total_count, mean_bin, max_bin_count); TP_END
+}
+
+int tp_observer_manager_new(tp_observer_manager **out) { TP_BEGIN *out = new tp_observer_manager; TP_END }
+int tp_observer_manager_free(tp_observer_manager *m) { TP_BEGIN delete m; TP_END }
+int tp_observer_manager_add_minmax(tp_observer_manager *m, const char *name) { TP_BEGIN m->m.add_minmax_observer(name); TP_END }
+int tp_observer_manager_add_histogram(tp_observer_manager *m, const char *name, size_t num_bins) {
+    TP_BEGIN m->m.add_histogram_observer(name, num_bins); TP_END
+}
+int tp_observer_manager_observe_minmax(tp_observer_manager *m, const char *name, const tp_tensor *t) { TP_BEGIN m->m.observe_minmax(name, t->t); TP_END }
+int tp_observer_manager_observe_histogram(tp_observer_manager *m, const char *name, const tp_tensor *t) {
+    TP_BEGIN m->m.observe_histogram(name, t->t); TP_END
+}
+int tp_observer_manager_minmax_stats(const tp_observer_manager *m, const char *name, int *found, size_t *num_observations, float *global_min,
+                                     float *global_max, float *range) {
+    TP_BEGIN
+    ObserverStats s{};
+    *found = m->m.get_minmax_stats(name, &s) ? 1 : 0;
+    if (*found) put_stats(s, num_observations, global_min, global_max, range);
+    TP_END
+}
+int tp_observer_manager_histogram_stats(const tp_observer_manager *m, const char *name, int *found, size_t *num_observations,
+                                        uint64_t *total_count, float *mean_bin, uint64_t *max_bin_count) {
+    TP_BEGIN
+    HistogramStats s{};
+    *found = m->m.get_histogram_stats(name, &s) ? 1 : 0;
+    if (*found) put_hist_stats(s, num_observations, total_count, mean_bin, max_bin_count);
+    TP_END
+}
+int tp_observer_manager_reset_all(tp_observer_manager *m) { TP_BEGIN m->m.reset_all(); TP_END }
+int tp_observer_manager_names(const tp_observer_manager *m, char *buf, size_t cap, size_t *n_names, size_t *needed) {
+    TP_BEGIN
+    const std::vector<std::string> names = m->m.get_observer_names();
+    std::string all;
+    for (size_t i = 0; i < names.size(); ++i) all += (i ? "\n" : "") + names[i];
+    if (n_names) *n_names = names.size();
+    if (needed) *needed = all.size() + 1;
+    if (buf && cap) {
+        const size_t k = std::min(all.size(), cap - 1);
+        std::memcpy(buf, all.data(), k);
+        buf[k] = '\0';
+    }
+    TP_END
+}
 
 int tp_module_num_parameters(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->parameters().size(); TP_END }
 int tp_module_parameter(const tp_module *m, int i, tp_tensor **out) {

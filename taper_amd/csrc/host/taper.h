@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <random>
 #include <stdexcept>
@@ -542,6 +543,78 @@ class QATWeightPass {
     std::vector<th_fq_item> items_;
     std::shared_ptr<Buffer> d_items_;
     uint64_t generation_ = 0;
+};
+
+// ---- quantization observers (src/quantization/observers.rs; csrc/observers.hip) ----
+// The statistics live in pooled device buffers.  observe() only enqueues kernels on the context's stream -- whether it is the first
+// observation is known on the host -- and the read-outs are the only calls that synchronise.  reset() and destruction return every
+// buffer to the pool.  Semantics are the reference's, quirks included ("Observers").
+struct ObserverStats {     // observers.rs:249-255
+    size_t num_observations;
+    float global_min, global_max, range;
+};
+struct HistogramStats {    // observers.rs:258-264
+    size_t num_observations;
+    uint64_t total_count;
+    float mean_bin;
+    uint64_t max_bin_count;
+};
+
+class MinMaxObserver {     // observers.rs:11-121: min / max PER ELEMENT of the flat data, their length fixed by the first observation
+   public:
+    void set_enabled(bool on) { enabled_ = on; }
+    bool is_enabled() const { return enabled_; }
+    void observe(const Tensor &t);              // disabled: nothing, not counted; later observations update the first min(m, len) elements
+    size_t len() const { return min_ ? min_->n : 0; }
+    std::vector<float> min_values() const;      // (synchronises)
+    std::vector<float> max_values() const;
+    float global_min() const { return get_stats().global_min; }   // +inf before any observation
+    float global_max() const { return get_stats().global_max; }   // -inf
+    size_t num_observations() const { return count_; }
+    void reset();
+    ObserverStats get_stats() const;            // the folds run on the device: two floats come back
+
+   private:
+    std::shared_ptr<Buffer> min_, max_;
+    size_t count_ = 0;
+    bool enabled_ = true;
+};
+
+class HistogramObserver {  // observers.rs:125-246: edges fixed by the first observation, 64-bit counts
+   public:
+    explicit HistogramObserver(size_t num_bins);   // 0 bins (and more than 2^30) throw before the device is touched
+    void set_enabled(bool on) { enabled_ = on; }
+    bool is_enabled() const { return enabled_; }
+    void observe(const Tensor &t);
+    size_t num_bins() const { return num_bins_; }
+    bool has_edges() const { return (bool)edges_; }
+    std::vector<uint64_t> bins() const;        // num_bins counts (zeros before any observation; synchronises after one)
+    std::vector<float> bin_edges() const;       // num_bins + 1 edges, empty before the first observation and after reset()
+    size_t num_observations() const { return count_; }
+    void reset();
+    HistogramStats get_stats() const;
+
+   private:
+    size_t num_bins_;
+    std::shared_ptr<Buffer> bins_, edges_;      // bins_: num_bins 64-bit counters
+    size_t count_ = 0;
+    bool enabled_ = true;
+};
+
+class ObserverManager {    // observers.rs:268-345: two maps by name; a name may be in both
+   public:
+    void add_minmax_observer(const std::string &name);                       // an existing name gets a fresh observer
+    void add_histogram_observer(const std::string &name, size_t num_bins);
+    void observe_minmax(const std::string &name, const Tensor &t);           // unknown name: nothing
+    void observe_histogram(const std::string &name, const Tensor &t);
+    bool get_minmax_stats(const std::string &name, ObserverStats *out) const;        // false: not found
+    bool get_histogram_stats(const std::string &name, HistogramStats *out) const;
+    void reset_all();
+    std::vector<std::string> get_observer_names() const;   // the minmax names, then the histogram names, each sorted
+
+   private:
+    std::map<std::string, std::unique_ptr<MinMaxObserver>> minmax_;
+    std::map<std::string, std::unique_ptr<HistogramObserver>> histogram_;
 };
 
 // ---- optim (src/optim.rs) ------------------------------------------------------
