@@ -19,10 +19,11 @@
 // from run to run.  More bins than that, or edges that are not finite (an infinity or only NaNs in the first observation: the literal scan
 // is the definition there): a second form with a search per element over the edges in global memory and atomics on the global bins.
 #include "common.h"
+#include "stream_dev.h"
 
 namespace th {
 
-constexpr int kObsThreads = 256;
+constexpr int kObsThreads = kStreamThreads;
 constexpr int kObsParts = 512;                     // workgroups of a fold's first pass (2 per CU)
 constexpr int64_t kObsPartMin = 4 * 256 * 8;       // elements per fold workgroup at least
 constexpr int kObsMapGrid = 2048;                  // workgroups of the element-wise passes at most (8 per CU)
@@ -33,157 +34,27 @@ constexpr int kHistGrid = 256;                     // one workgroup per CU
 constexpr int64_t kHistWgMin = 4 * 1024 * 4;       // elements per counting workgroup at least: a small tensor pays few table loads and merges
 constexpr int kHistGlobalGrid = 1024;
 
-__host__ __device__ __forceinline__ int obs_spread(int64_t n, int64_t per, int most) {
-    const int64_t k = (n + per - 1) / per;
-    return (int)(k < 1 ? 1 : (k < most ? k : most));
-}
-
 // ---- MinMaxObserver::observe ----
 __global__ __launch_bounds__(kObsThreads) void obs_minmax_first_kernel(const float *__restrict__ x, float *__restrict__ mn, float *__restrict__ mx, int64_t n) {
-    const int64_t t0 = (int64_t)blockIdx.x * kObsThreads + threadIdx.x, stride = (int64_t)gridDim.x * kObsThreads;
-    int64_t head = 0;
-    if ((((uintptr_t)x | (uintptr_t)mn | (uintptr_t)mx) & 15) == 0) {
-        const float4 *x4 = (const float4 *)x;
-        float4 *mn4 = (float4 *)mn, *mx4 = (float4 *)mx;
-        const int64_t n4 = n >> 2;
-        int64_t j = t0;
-        for (; j + stride < n4; j += 2 * stride) {
-            const float4 a = x4[j], b = x4[j + stride];
-            mn4[j] = a;
-            mx4[j] = a;
-            mn4[j + stride] = b;
-            mx4[j + stride] = b;
-        }
-        for (; j < n4; j += stride) {
-            const float4 a = x4[j];
-            mn4[j] = a;
-            mx4[j] = a;
-        }
-        head = n4 << 2;
-    }
-    for (int64_t i = head + t0; i < n; i += stride) {
-        const float v = x[i];
-        mn[i] = v;
-        mx[i] = v;
-    }
+    span_walk<2>(aligned16(x, mn, mx), n, grid_t0(), grid_stride(), [=](int64_t j, const auto &a) {
+        put(mn, j, a);
+        put(mx, j, a);
+    }, x);
 }
 
-// f32::min / f32::max: a NaN operand loses to a number (fminf / fmaxf)
-__device__ __forceinline__ float4 min4(float4 a, float4 b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), fminf(a.w, b.w)); }
-__device__ __forceinline__ float4 max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-
+// f32::min / f32::max: a NaN operand loses to a number (fminf / fmaxf); six loads in flight per lane
 __global__ __launch_bounds__(kObsThreads) void obs_minmax_update_kernel(const float *__restrict__ x, float *__restrict__ mn, float *__restrict__ mx, int64_t n) {
-    const int64_t t0 = (int64_t)blockIdx.x * kObsThreads + threadIdx.x, stride = (int64_t)gridDim.x * kObsThreads;
-    int64_t head = 0;
-    if ((((uintptr_t)x | (uintptr_t)mn | (uintptr_t)mx) & 15) == 0) {
-        const float4 *x4 = (const float4 *)x;
-        float4 *mn4 = (float4 *)mn, *mx4 = (float4 *)mx;
-        const int64_t n4 = n >> 2;
-        int64_t j = t0;
-        for (; j + stride < n4; j += 2 * stride) {   // six loads in flight per lane
-            const float4 a = x4[j], b = x4[j + stride];
-            const float4 la = mn4[j], lb = mn4[j + stride], ha = mx4[j], hb = mx4[j + stride];
-            mn4[j] = min4(la, a);
-            mx4[j] = max4(ha, a);
-            mn4[j + stride] = min4(lb, b);
-            mx4[j + stride] = max4(hb, b);
-        }
-        for (; j < n4; j += stride) {
-            const float4 a = x4[j];
-            mn4[j] = min4(mn4[j], a);
-            mx4[j] = max4(mx4[j], a);
-        }
-        head = n4 << 2;
-    }
-    for (int64_t i = head + t0; i < n; i += stride) {
-        const float v = x[i];
-        mn[i] = fminf(mn[i], v);
-        mx[i] = fmaxf(mx[i], v);
-    }
+    span_walk<2>(aligned16(x, mn, mx), n, grid_t0(), grid_stride(), [=](int64_t j, const auto &a, const auto &lo, const auto &hi) {
+        put(mn, j, vmap([](float l, float v) { return fminf(l, v); }, lo, a));
+        put(mx, j, vmap([](float h, float v) { return fmaxf(h, v); }, hi, a));
+    }, x, mn, mx);
 }
 
-// ---- the NaN-ignoring folds ----
-// min over a[0, n) from +inf and max over b[0, n) from -inf of this lane's share (a == b for a histogram's first observation: one read)
-template <bool kSame>
-__device__ __forceinline__ void obs_fold_span(const float *__restrict__ a, const float *__restrict__ b, int64_t n, int64_t t0, int64_t stride,
-                                              float *mn_out, float *mx_out) {
-    float mn = INFINITY, mx = -INFINITY;
-    auto take = [&](float4 p, float4 q) {
-        mn = fminf(fminf(mn, p.x), fminf(fminf(p.y, p.z), p.w));   // (min / max are exact: any grouping gives the fold's value)
-        mx = fmaxf(fmaxf(mx, q.x), fmaxf(fmaxf(q.y, q.z), q.w));
-    };
-    int64_t head = 0;
-    if ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) {
-        const float4 *a4 = (const float4 *)a, *b4 = (const float4 *)b;
-        const int64_t n4 = n >> 2;
-        int64_t j = t0;
-        for (; j + 3 * stride < n4; j += 4 * stride) {   // four (eight) loads in flight per lane
-            const float4 p0 = a4[j], p1 = a4[j + stride], p2 = a4[j + 2 * stride], p3 = a4[j + 3 * stride];
-            if (kSame) {
-                take(p0, p0); take(p1, p1); take(p2, p2); take(p3, p3);
-            } else {
-                const float4 q0 = b4[j], q1 = b4[j + stride], q2 = b4[j + 2 * stride], q3 = b4[j + 3 * stride];
-                take(p0, q0); take(p1, q1); take(p2, q2); take(p3, q3);
-            }
-        }
-        for (; j < n4; j += stride) {
-            const float4 p = a4[j];
-            take(p, kSame ? p : b4[j]);
-        }
-        head = n4 << 2;
-    }
-    for (int64_t i = head + t0; i < n; i += stride) {
-        mn = fminf(mn, a[i]);
-        mx = fmaxf(mx, kSame ? a[i] : b[i]);
-    }
-    *mn_out = mn;
-    *mx_out = mx;
-}
-
-// every lane of a 256-lane workgroup leaves with the workgroup's min / max (s: 8 floats of LDS)
-__device__ __forceinline__ void obs_block_minmax(float *mn, float *mx, float *s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        *mn = fminf(*mn, __shfl_xor(*mn, off, 64));
-        *mx = fmaxf(*mx, __shfl_xor(*mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s[threadIdx.x >> 6] = *mn;
-        s[4 + (threadIdx.x >> 6)] = *mx;
-    }
-    __syncthreads();
-    *mn = fminf(fminf(s[0], s[1]), fminf(s[2], s[3]));
-    *mx = fmaxf(fmaxf(s[4], s[5]), fmaxf(s[6], s[7]));
-    __syncthreads();
-}
-
-template <bool kSame>
-__global__ __launch_bounds__(kObsThreads) void obs_fold_parts_kernel(const float *__restrict__ a, const float *__restrict__ b, int64_t n, float *__restrict__ part) {
-    __shared__ float s[8];
-    float mn, mx;
-    obs_fold_span<kSame>(a, b, n, (int64_t)blockIdx.x * kObsThreads + threadIdx.x, (int64_t)gridDim.x * kObsThreads, &mn, &mx);
-    obs_block_minmax(&mn, &mx, s);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = mn;
-        part[2 * blockIdx.x + 1] = mx;
-    }
-}
-
-__device__ __forceinline__ void obs_fold_parts(const float *__restrict__ part, int nb, float *mn, float *mx, float *s) {
-    float a = INFINITY, b = -INFINITY;
-    for (int k = threadIdx.x; k < nb; k += kObsThreads) {
-        a = fminf(a, part[2 * k]);
-        b = fmaxf(b, part[2 * k + 1]);
-    }
-    obs_block_minmax(&a, &b, s);
-    *mn = a;
-    *mx = b;
-}
-
+// ---- the NaN-ignoring folds (stream_dev.h's MinMaxNanIgnoring: min over a[0, n), max over b[0, n); a == b for a histogram's first observation) ----
 __global__ __launch_bounds__(kObsThreads) void obs_fold_final_kernel(const float *__restrict__ part, int n_parts, float *__restrict__ out2) {
     __shared__ float s[8];
     float mn, mx;
-    obs_fold_parts(part, n_parts, &mn, &mx, s);
+    fold_parts(part, n_parts, &mn, &mx, s);
     if (threadIdx.x == 0) {
         out2[0] = mn;
         out2[1] = mx;
@@ -194,7 +65,7 @@ __global__ __launch_bounds__(kObsThreads) void obs_fold_final_kernel(const float
 __global__ __launch_bounds__(kObsThreads) void obs_edges_kernel(const float *__restrict__ part, int n_parts, int num_bins, float *__restrict__ edges) {
     __shared__ float s[8];
     float mn, mx;
-    obs_fold_parts(part, n_parts, &mn, &mx, s);
+    fold_parts(part, n_parts, &mn, &mx, s);
     const float width = __fdiv_rn(__fsub_rn(mx, mn), (float)num_bins);
     for (int i = threadIdx.x; i <= num_bins; i += kObsThreads) edges[i] = __fadd_rn(mn, __fmul_rn((float)i, width));
 }
@@ -326,7 +197,8 @@ __global__ __launch_bounds__(kHistThreads) void obs_hist_lds_kernel(const float 
         const float4 *x4 = (const float4 *)x;
         const int64_t n4 = n >> 2;
         // whole waves only (jw is the wave's first index: the trip count is wave-uniform, so hot / hot_n stay uniform and every ballot
-        // sees 64 lanes); four 16-byte loads in flight per lane
+        // sees 64 lanes) -- which is why this walk is written out here and is not stream_dev.h's span_walk, whose lanes stop one by one;
+        // four 16-byte loads in flight per lane
         int64_t jw = t0 - (threadIdx.x & 63);
         for (; jw + 3 * stride + 63 < n4; jw += 4 * stride) {
             const int64_t j = jw + (threadIdx.x & 63);
@@ -417,15 +289,15 @@ __global__ __launch_bounds__(kObsThreads) void obs_hist_stats_kernel(const unsig
     }
 }
 
-static int obs_map_grid(int64_t n) { return obs_spread(n, 4 * kObsThreads, kObsMapGrid); }
+static int obs_map_grid(int64_t n) { return stream_grid(n, 4 * kObsThreads, kObsMapGrid); }
 
 // the first pass of a fold into a pooled block of partials (freed by the caller after the second pass is enqueued)
-static int obs_fold_parts_launch(th_ctx *ctx, const float *d_a, const float *d_b, int64_t n, void **part, int *n_parts) {
-    *n_parts = n > 0 ? obs_spread(n, kObsPartMin, kObsParts) : 0;
+static int obs_minmax_parts_launch(th_ctx *ctx, const float *d_a, const float *d_b, int64_t n, void **part, int *n_parts) {
+    *n_parts = n > 0 ? stream_grid(n, kObsPartMin, kObsParts) : 0;
     if (th_malloc(ctx, (size_t)std::max(*n_parts, 1) * 2 * sizeof(float), part)) return 1;
     if (*n_parts == 0) return 0;
-    if (d_a == d_b) hipLaunchKernelGGL(obs_fold_parts_kernel<true>, dim3(*n_parts), dim3(kObsThreads), 0, ctx->stream, d_a, d_b, n, (float *)*part);
-    else hipLaunchKernelGGL(obs_fold_parts_kernel<false>, dim3(*n_parts), dim3(kObsThreads), 0, ctx->stream, d_a, d_b, n, (float *)*part);
+    if (d_a == d_b) hipLaunchKernelGGL((minmax_parts_kernel<MinMaxNanIgnoring, true>), dim3(*n_parts), dim3(kObsThreads), 0, ctx->stream, d_a, d_b, n, (float *)*part);
+    else hipLaunchKernelGGL((minmax_parts_kernel<MinMaxNanIgnoring, false>), dim3(*n_parts), dim3(kObsThreads), 0, ctx->stream, d_a, d_b, n, (float *)*part);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -456,7 +328,7 @@ int th_obs_fold(th_ctx *ctx, const float *d_min, const float *d_max, int64_t n, 
     TH_REQUIRE(ctx && d_out2 && n >= 0 && (n == 0 || (d_min && d_max)), "th_obs_fold: null argument or negative length");
     void *part = nullptr;
     int n_parts = 0;
-    if (obs_fold_parts_launch(ctx, d_min, d_max, n, &part, &n_parts)) return 1;
+    if (obs_minmax_parts_launch(ctx, d_min, d_max, n, &part, &n_parts)) return 1;
     hipLaunchKernelGGL(obs_fold_final_kernel, dim3(1), dim3(kObsThreads), 0, ctx->stream, (const float *)part, n_parts, d_out2);
     TH_LAUNCH_CHECK();
     return th_free(ctx, part);
@@ -467,7 +339,7 @@ int th_obs_hist_edges(th_ctx *ctx, const float *d_x, int64_t n, int num_bins, fl
     TH_REQUIRE(num_bins >= 1, "th_obs_hist_edges: num_bins must be at least 1 (got %d)", num_bins);
     void *part = nullptr;
     int n_parts = 0;
-    if (obs_fold_parts_launch(ctx, d_x, d_x, n, &part, &n_parts)) return 1;
+    if (obs_minmax_parts_launch(ctx, d_x, d_x, n, &part, &n_parts)) return 1;
     hipLaunchKernelGGL(obs_edges_kernel, dim3(1), dim3(kObsThreads), 0, ctx->stream, (const float *)part, n_parts, num_bins, d_edges);
     TH_LAUNCH_CHECK();
     return th_free(ctx, part);
@@ -484,10 +356,10 @@ int th_obs_hist_count(th_ctx *ctx, const float *d_x, int64_t n, const float *d_e
     if (num_bins <= kObsLdsMaxBins) {
         const size_t lds = (size_t)(2 * num_bins + 1) * sizeof(float);
         TH_SET_MAX_LDS(ctx, obs_hist_lds_kernel, lds);
-        hipLaunchKernelGGL(obs_hist_lds_kernel, dim3(obs_spread(n, kHistWgMin, kHistGrid)), dim3(kHistThreads), lds, ctx->stream, d_x, n, d_edges,
+        hipLaunchKernelGGL(obs_hist_lds_kernel, dim3(stream_grid(n, kHistWgMin, kHistGrid)), dim3(kHistThreads), lds, ctx->stream, d_x, n, d_edges,
                            num_bins, (unsigned long long *)d_bins);
     } else {
-        hipLaunchKernelGGL(obs_hist_global_kernel, dim3(obs_spread(n, kObsThreads, kHistGlobalGrid)), dim3(kObsThreads), 0, ctx->stream, d_x, n,
+        hipLaunchKernelGGL(obs_hist_global_kernel, dim3(stream_grid(n, kObsThreads, kHistGlobalGrid)), dim3(kObsThreads), 0, ctx->stream, d_x, n,
                            d_edges, num_bins, (unsigned long long *)d_bins);
     }
     TH_LAUNCH_CHECK();

@@ -4,6 +4,7 @@
 // carry is OR-ed, not added, into the exponent field) and held to bit-exact parity.  HBM-bound, one pass each.
 #include "common.h"
 #include "quant_dev.h"
+#include "stream_dev.h"
 
 namespace th {
 
@@ -14,49 +15,22 @@ __global__ __launch_bounds__(256) void f16_to_f32_kernel(const uint16_t *__restr
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = f16_bits_to_f32(x[i]);
 }
 
-// finite min / max (tensor.rs:2117-2125): per-block partials, then one block folds them; min / max are order-independent
-__global__ __launch_bounds__(256) void minmax_finite_kernel(const float *__restrict__ x, size_t n, float *__restrict__ part) {
-    __shared__ float smin[4], smax[4];
-    float mn = INFINITY, mx = -INFINITY;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = x[i];
-        if (isfinite(v)) {
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, off, 64));
-        mx = fmaxf(mx, __shfl_down(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smin[threadIdx.x >> 6] = mn;
-        smax[threadIdx.x >> 6] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
-        part[2 * blockIdx.x + 1] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-    }
-}
-
+// int8 affine over the finite min / max (stream_dev.h's MinMaxFinite partials, folded by every workgroup here as fq_act_int8_kernel does):
 // params = {min_val, scale} (tensor.rs:2127-2134), then q = round((x - min) / scale) as i32 + qmin, clamped (2136-2143)
-__global__ __launch_bounds__(256) void int8_params_kernel(const float *__restrict__ part, int n_part, float *__restrict__ params) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int i = 0; i < n_part; ++i) {
-        mn = fminf(mn, part[2 * i]);
-        mx = fmaxf(mx, part[2 * i + 1]);
-    }
-    int8_params(mn, mx, &params[0], &params[1]);
-}
+constexpr int kQuantParts = 1024;   // workgroups of the min / max pass at most, 256 elements each at least
 
 __global__ __launch_bounds__(256) void quantize_int8_kernel(const float *__restrict__ x, int8_t *__restrict__ q, size_t n,
-                                                            const float *__restrict__ params) {
-    const float mn = params[0], scale = params[1];
+                                                            const float *__restrict__ part, int nb, float *__restrict__ params) {
+    __shared__ float s[8];
+    float mn, mx, min_val, scale;
+    fold_parts(part, nb, &mn, &mx, s);   // (no partials for n == 0: +inf / -inf, as the empty fold always left them)
+    int8_params(mn, mx, &min_val, &scale);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        params[0] = min_val;
+        params[1] = scale;
+    }
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        q[i] = (int8_t)quant_int8(x[i], mn, scale);
+        q[i] = (int8_t)quant_int8(x[i], min_val, scale);
     }
 }
 
@@ -90,17 +64,15 @@ int th_f16_to_f32(th_ctx *ctx, const uint16_t *d_x, float *d_y, size_t n) {
 
 int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params) {
     TH_REQUIRE(ctx && d_params && (n == 0 || (d_x && d_q)), "th_quantize_int8: null argument");
-    const int blocks = n == 0 ? 1 : (int)std::min<size_t>(1024, (n + 255) / 256);
+    const int nb = n == 0 ? 0 : stream_grid((int64_t)n, 256, kQuantParts);
     void *part = nullptr;
-    if (th_malloc(ctx, (size_t)blocks * 2 * sizeof(float), &part)) return 1;
-    hipLaunchKernelGGL(minmax_finite_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d_x, n, (float *)part);
-    TH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(int8_params_kernel, dim3(1), dim3(64), 0, ctx->stream, (const float *)part, blocks, d_params);
-    TH_LAUNCH_CHECK();
-    if (n) {
-        hipLaunchKernelGGL(quantize_int8_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, ctx->stream, d_x, d_q, n, (const float *)d_params);
+    if (th_malloc(ctx, (size_t)std::max(nb, 1) * 2 * sizeof(float), &part)) return 1;
+    if (nb) {
+        hipLaunchKernelGGL((minmax_parts_kernel<MinMaxFinite, true>), dim3(nb), dim3(256), 0, ctx->stream, d_x, d_x, (int64_t)n, (float *)part);
         TH_LAUNCH_CHECK();
     }
+    hipLaunchKernelGGL(quantize_int8_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, ctx->stream, d_x, d_q, n, (const float *)part, nb, d_params);
+    TH_LAUNCH_CHECK();
     return th_free(ctx, part);
 }
 

@@ -41,6 +41,8 @@ __device__ __forceinline__ float f16_bits_to_f32(uint16_t value) {
     return __uint_as_float((sign << 31) | (((exponent + 127 - 15) & 0xFF) << 23) | (mantissa << 13));
 }
 
+__device__ __forceinline__ float f16_round_trip(float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); }
+
 // tensor.rs:2127-2134: {min_val, scale} from the finite min / max (widened by 0.1 each way when they are equal); qrange = 255
 __device__ __forceinline__ void int8_params(float mn, float mx, float *min_val, float *scale) {
     if (mn == mx) {

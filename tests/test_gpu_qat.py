@@ -147,6 +147,55 @@ def test_activation_kernel_edge_inputs(ctx):
         assert _bits(ctx.download(ds, (1,))).tolist() == _bits([scale]).tolist(), name
 
 
+def _off4_cases():
+    rng = np.random.default_rng(11)
+    cases = {f"n{n}": (rng.standard_normal(n) * 0.7).astype(f32) for n in (0, 1, 3, 4099, 256 * 1024 + 3)}
+    cases.update(_edge_inputs(rng))
+    return cases
+
+
+@pytest.mark.parametrize("name", list(_off4_cases()))
+def test_quant_kernels_on_unaligned_pointers(ctx, name):
+    """th_quantize_int8, th_fake_quant_act (both codecs) and th_fake_quant_multi with every data pointer 4 bytes off a 16-byte boundary:
+    the scalar walk of the shared span helper, bit for bit against the oracle's codecs (the item descriptors keep their 8-byte alignment)"""
+    from taper_amd import hip as H
+    a = _off4_cases()[name]
+    n = a.size
+
+    def down(ptr, dtype=f32):   # (length 0: the parameters only)
+        return ctx.download(ptr, (n,), dtype) if n else np.empty(0, dtype)
+
+    dx = ctx.upload(np.concatenate([np.zeros(1, f32), a]))   # (kept alive: x is dx.offset(4))
+    x = dx.offset(4)
+    assert x % 16 == 4
+
+    q_ref, scale, _, mn = OX.quantize_int8(a)
+    keep = [ctx.empty(n // 4 + 2), ctx.empty(3)]
+    dq, dp = keep[0].offset(4), keep[1].offset(4)
+    ctx.call("th_quantize_int8", x, dq, n, dp)
+    assert _bits(ctx.download(dp, (2,))).tolist() == _bits([mn, scale]).tolist()
+    np.testing.assert_array_equal(down(dq, np.int8), q_ref)
+
+    for qtype, code in (("int8", 0), ("float16", 1)):
+        keep = [ctx.empty(n + 2), ctx.empty(3)]
+        dy, ds = keep[0].offset(4), keep[1].offset(4)
+        ctx.call("th_fake_quant_act", x, dy, n, code, ds)
+        ref, scale_ref = fq_act_int8(a) if qtype == "int8" else (fq_f16(a), f32(0))
+        np.testing.assert_array_equal(_bits(down(dy)), _bits(ref), err_msg=qtype)
+        assert _bits(ctx.download(ds, (1,))).tolist() == _bits([scale_ref]).tolist(), qtype
+
+    keep = [ctx.empty(n + 2), ctx.empty(n + 2), ctx.empty(3), ctx.empty(3)]
+    y8, y16, p8, p16 = (b.offset(4) for b in keep)
+    for pp in (p8, p16):
+        ctx.call("th_fill_f32", pp, float("nan"), 2)
+    items = (H.FqItem * 2)(H.FqItem(x, y8, p8, n, 0), H.FqItem(x, y16, p16, n, 1))
+    ctx.call("th_fake_quant_multi", ctx.upload(np.frombuffer(bytes(items), np.uint8)), 2)
+    ref8, (mn8, scale8) = fq_int8(a)
+    np.testing.assert_array_equal(_bits(down(y8)), _bits(ref8))
+    assert _bits(ctx.download(p8, (2,))).tolist() == _bits([mn8, scale8]).tolist()
+    np.testing.assert_array_equal(_bits(down(y16)), _bits(fq_f16(a)))
+
+
 # ---------------------------------------------------------------- models
 @pytest.fixture
 def qat_on():

@@ -2,9 +2,9 @@
 the f32 step.
 
 Kernel rows: th_fake_quant_multi (int8) on one 4096^2 weight, on 784x128 + 128x10, and on all weights of the reference CNN; th_fake_quant_act
-(int8) on [64, 128] and [256, 32, 28, 28].  Each: us per call and the share of the 8 TB/s HBM bound, counting a min / max read, a read and
-a write of every element (12 bytes per element), cold (a 512 MiB buffer written elsewhere before every timed call) and replayed (back to
-back).  Step rows: us per step of train_epoch_graph (20-step calls, median of --calls) for MLP 784-128-10 at B = 64 and the simple CNN at
+(int8) on [64, 128] and [256, 32, 28, 28]; th_quantize_int8 on one 4096^2 weight.  Each: us per call and the share of the 8 TB/s HBM bound,
+counting a min / max read, a read and a write of every element (12 bytes per element; 9 for th_quantize_int8, whose write is one byte),
+cold (a 512 MiB buffer written elsewhere before every timed call) and replayed (back to back).  Step rows: us per step of train_epoch_graph (20-step calls, median of --calls) for MLP 784-128-10 at B = 64 and the simple CNN at
 B = 256, f32 (the fused forms) against QAT int8 with and without activation fake-quant (the layered form).
 
     python tools/bench_qat.py [--reps 50] [--calls 20] [--out profiles/qat.json]
@@ -111,8 +111,8 @@ def main():
     flush = ctx.empty(128 << 20)
     rows = []
 
-    def report(kind, case, n, cold, warm):
-        nbytes = 12 * n
+    def report(kind, case, n, cold, warm, per=12):
+        nbytes = per * n
         r = dict(kind=kind, case=case, elements=n, bytes=nbytes, cold_us=round(cold, 2), replay_us=round(warm, 2),
                  cold_bw_share=round(nbytes / (cold * 1e-6) / HBM, 3), replay_bw_share=round(nbytes / (warm * 1e-6) / HBM, 3))
         rows.append(r)
@@ -128,6 +128,11 @@ def main():
         x, y, s = ctx.upload(rng.standard_normal(n).astype(np.float32)), ctx.empty(n), ctx.empty(1)
         cold, warm = timed(ctx, lambda: ctx.call("th_fake_quant_act", x, y, n, 0, s), a.reps, flush)
         report("th_fake_quant_act int8", str(list(shape)), n, cold, warm)
+
+    n = 4096 * 4096   # post-training quantization of one weight: a min / max read, a read and a one-byte code of every element (9 bytes)
+    x, q, p = ctx.upload((rng.standard_normal(n) * 0.05).astype(np.float32)), ctx.empty(n // 4), ctx.empty(2)
+    cold, warm = timed(ctx, lambda: ctx.call("th_quantize_int8", x, q, n, p), a.reps, flush)
+    report("th_quantize_int8", "4096x4096", n, cold, warm, per=9)
 
     steps = []
     T.qat.enable()
@@ -152,7 +157,7 @@ def main():
 def table(rows, steps, reps, calls):
     lines = [f"# Quantization-aware training on MI355X (`tools/bench_qat.py`, {reps} reps; cold = median after writing 512 MiB elsewhere, "
              "replay = back to back)", "",
-             "Kernel bytes count a min / max read, a read and a write of every element (12 B each); share = bytes / time / 8 TB/s.",
+             "Kernel bytes count a min / max read, a read and a write of every element (12 B each; 9 B for th_quantize_int8); share = bytes / time / 8 TB/s.",
              "The 4096² call reaches 0.5 replayed, not cold: by a kernel trace (rocprofv3) its min / max pass takes ~27 µs cold (it reads behind",
              "the 512 MiB of dirty lines the flush left: 2.5 TB/s) and ~12 µs warm (5.6 TB/s); the applying pass ~23.7 µs either way (5.4 TB/s;",
              "by instruction count about half of it is the codec's arithmetic, its correctly rounded division first).  In a training step the weights are warm: Adam has just written them.", "",
