@@ -34,6 +34,12 @@ int th_debug_last_conv_config(th_ctx *ctx, int *out6);
  * out6[4] = images per unit) when the launch has at least one unit per two CUs, the 128-pixel kernel otherwise; 0: never;
  * 1: whenever the shape fits it. */
 int th_debug_set_conv_img(th_ctx *ctx, int mode);
+/* what th_linear_q8_fwd (qtype TH_QTYPE_INT8) / th_linear_h16_fwd (TH_QTYPE_F16) would do with this shape and these pointers
+ * (x / w: bytes off a 16-byte boundary) -- pure host code, no context, the function the launch itself consumes: out8 = {1 if the weight-
+ * streaming kernel takes it (0: the dequantize workspace and th_linear_fwd; the rest is 0 then), 1 if its vector-load instance, batch tile
+ * (1 / 2 / 4 / 8), k positions per slice, slices (grid.y; > 1: a combine launch follows), grid.x, slices asked for, k steps of a wave over
+ * a whole row}. */
+int th_debug_qlinear_plan(int qtype, int batch, int in_features, int out_features, int x_misalign_bytes, int w_misalign_bytes, int *out8);
 
 /* post-mortem of the in-launch exchange (csrc/dp_dev.h) on stderr: the communicator's state words and, per parity and source block of the
  * receive region, the slots that hold words.  Trainer::check_comm calls it under TAPER_DP_POSTMORTEM=1 when a time-out is reported. */

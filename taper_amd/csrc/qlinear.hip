@@ -201,14 +201,35 @@ static void launch_stream(th_ctx *ctx, bool vec, dim3 grid, const float *x, int 
     else hipLaunchKernelGGL((qgemv_kernel<QT, BT, false>), grid, dim3(256), 0, ctx->stream, x, B, K, w, N, wp, bc, bp, relu, y, part, kslice);
 }
 
+// Every host decision of a quantized Linear forward (qlinear_fwd launches from it; th_debug_qlinear_plan reports it): the workspace
+// path above kStreamMaxBatch rows, else the streaming kernel's instance (vec, bt) and its grid blocks_n x S with kslice k positions a slice.
+// E: codes per 16-byte load; x_bits / w_bits: the pointers (only their low 4 bits matter).
+struct QPlan {
+    int stream, vec, bt, kslice, S, blocks_n, want, steps;
+};
+
+static QPlan qlinear_plan(int E, int B, int K, int N, uintptr_t x_bits, uintptr_t w_bits) {
+    QPlan p{};
+    if (B > kStreamMaxBatch) return p;
+    p.stream = 1;
+    p.vec = K % E == 0 && (x_bits & 15) == 0 && (w_bits & 15) == 0;
+    p.blocks_n = ceil_div(N, 4 * kRowsPerWave);
+    p.steps = ceil_div(K, 64 * E);                                              // k steps of a wave over the whole row
+    p.want = std::max(1, std::min(p.steps, ceil_div(4 * kNumCU, p.blocks_n)));   // ~4 workgroups per CU in all
+    p.kslice = ceil_div(p.steps, p.want) * 64 * E;
+    p.S = ceil_div(K, p.kslice);
+    p.bt = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : 8;
+    return p;
+}
+
 template <int QT>
 static int qlinear_fwd(th_ctx *ctx, const char *name, const float *x, int B, int K, const void *w, int N, const float *wp, const void *bc,
                        const float *bp, int relu, float *y) {
     TH_REQUIRE(ctx && x && w && y && (QT != TH_QTYPE_INT8 || wp) && (!bc || QT != TH_QTYPE_INT8 || bp), "%s: null argument", name);
     TH_REQUIRE(B >= 0 && K > 0 && N > 0, "%s: bad shape B=%d K=%d N=%d", name, B, K, N);
     if (B == 0) return 0;
-    constexpr int E = QCodes<QT>::kPerLoad;
-    if (B > kStreamMaxBatch) {
+    const QPlan p = qlinear_plan(QCodes<QT>::kPerLoad, B, K, N, (uintptr_t)x, (uintptr_t)w);
+    if (!p.stream) {
         // dequantize W (and b) into one pooled workspace, the f32 product, the workspace back to the pool
         const size_t wn = (size_t)K * N, boff = (wn + 63) / 64 * 64;
         void *ws = nullptr;
@@ -220,17 +241,12 @@ static int qlinear_fwd(th_ctx *ctx, const char *name, const float *x, int B, int
         const int rf = th_free(ctx, ws);
         return rc ? rc : rf;
     }
-    const bool vec = K % E == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0;
-    const int blocks_n = ceil_div(N, 4 * kRowsPerWave);
-    const int steps = ceil_div(K, 64 * E);                                    // k steps of a wave over the whole row
-    const int want = std::max(1, std::min(steps, ceil_div(4 * kNumCU, blocks_n)));   // ~4 workgroups per CU in all
-    const int kslice = ceil_div(steps, want) * 64 * E;
-    const int S = ceil_div(K, kslice);
+    const bool vec = p.vec != 0;
+    const int kslice = p.kslice, S = p.S;
     float *part = nullptr;
     if (S > 1 && th_malloc(ctx, (size_t)S * B * N * sizeof(float), (void **)&part)) return 1;
-    const dim3 grid(blocks_n, S);
-    const int bt = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : 8;
-    switch (bt) {
+    const dim3 grid(p.blocks_n, S);
+    switch (p.bt) {
         case 1: launch_stream<QT, 1>(ctx, vec, grid, x, B, K, w, N, wp, bc, bp, relu, y, part, kslice); break;
         case 2: launch_stream<QT, 2>(ctx, vec, grid, x, B, K, w, N, wp, bc, bp, relu, y, part, kslice); break;
         case 4: launch_stream<QT, 4>(ctx, vec, grid, x, B, K, w, N, wp, bc, bp, relu, y, part, kslice); break;
@@ -266,6 +282,17 @@ int th_linear_h16_fwd(th_ctx *ctx, const float *d_x, int batch, int in_features,
 }
 
 int th_qlinear_stream_max_batch(void) { return kStreamMaxBatch; }
+
+int th_debug_qlinear_plan(int qtype, int batch, int in_features, int out_features, int x_misalign_bytes, int w_misalign_bytes, int *out8) {
+    TH_REQUIRE(out8 && (qtype == TH_QTYPE_INT8 || qtype == TH_QTYPE_F16), "th_debug_qlinear_plan: null argument or bad qtype %d", qtype);
+    TH_REQUIRE(batch >= 1 && in_features > 0 && out_features > 0 && x_misalign_bytes >= 0 && w_misalign_bytes >= 0,
+               "th_debug_qlinear_plan: bad shape B=%d K=%d N=%d", batch, in_features, out_features);
+    const QPlan p = qlinear_plan(qtype == TH_QTYPE_INT8 ? QCodes<TH_QTYPE_INT8>::kPerLoad : QCodes<TH_QTYPE_F16>::kPerLoad, batch, in_features,
+                                 out_features, (uintptr_t)x_misalign_bytes, (uintptr_t)w_misalign_bytes);
+    const int out[8] = {p.stream, p.vec, p.bt, p.kslice, p.S, p.blocks_n, p.want, p.steps};
+    std::copy(out, out + 8, out8);
+    return 0;
+}
 
 int th_dequantize_multi(th_ctx *ctx, const th_qtensor *h_items, int n_items) {
     TH_REQUIRE(ctx && n_items >= 0 && (n_items == 0 || h_items), "th_dequantize_multi: null argument");

@@ -96,13 +96,62 @@ def _grouped(rng):   # Conv2d(4, 8, 3x3, groups 2, pad 1) + ReLU, Flatten, Linea
             dict(kind="relu"), dict(kind="flatten", start_dim=1), backends._lin(rng, 8 * 8 * 8, 10)]
 
 
+def _no_bias(layer):
+    layer["b"] = None
+    return layer
+
+
+def _mlp_nobias(rng):   # Linear layers built without a bias: the kernels' null bias pointers, one tensor a layer
+    return [_no_bias(backends._lin(rng, 784, 100)), dict(kind="relu"), _no_bias(backends._lin(rng, 100, 10))]
+
+
+def _cnn_nobias(rng):
+    return [_no_bias(backends._conv(rng, 1, 8)), dict(kind="maxpool", kernel=(2, 2), stride=(2, 2)), _no_bias(backends._conv(rng, 8, 8, relu=False)),
+            dict(kind="relu"), dict(kind="flatten", start_dim=1), _no_bias(backends._lin(rng, 8 * 4 * 4, 10))]
+
+
+def _cnn_sigmoid_avg(rng):   # the pass-through twins no other model holds: Sigmoid, AvgPool2d, AdaptiveAvgPool2d
+    return [backends._conv(rng, 1, 8, relu=False), dict(kind="sigmoid"), dict(kind="avgpool", kernel=(2, 2), stride=(2, 2)),
+            backends._conv(rng, 8, 16), dict(kind="adaptive_avgpool", out=(1, 1)), dict(kind="flatten", start_dim=1), backends._lin(rng, 16, 10)]
+
+
+def _nested(rng):   # a Sequential holding a Sequential that holds convs: the inner twin dequantizes its own convs, the outer one its own
+    return [backends._conv(rng, 1, 4),
+            dict(kind="sequential", layers=[backends._conv(rng, 4, 8), dict(kind="maxpool", kernel=(2, 2), stride=(2, 2)),
+                                            dict(kind="sequential", layers=[backends._conv(rng, 8, 8, relu=False), dict(kind="relu")])]),
+            dict(kind="flatten", start_dim=1), dict(kind="sequential", layers=[backends._lin(rng, 8 * 4 * 4, 32), dict(kind="relu")]),
+            backends._lin(rng, 32, 10)]
+
+
+def _conv17(rng):   # 17 convs = 34 conv tensors in one QSequential: two chunks of th_dequantize_multi (32 tensors a launch)
+    return [backends._conv(rng, 2, 2) for _ in range(17)] + [dict(kind="flatten", start_dim=1), backends._lin(rng, 2 * 4 * 4, 10)]
+
+
 MODELS = {"mlp_baseline": (backends.mlp_baseline, (784,)), "mlp_example": (backends.mlp_example, (784,)),
           "mlp_100_52": (backends.mlp_100_52, (784,)), "cnn_simple": (backends.cnn_simple, (1, 28, 28)),
-          "cnn_reference": (backends.cnn_reference, (1, 28, 28)), "grouped": (_grouped, (4, 8, 8))}
+          "cnn_reference": (backends.cnn_reference, (1, 28, 28)), "grouped": (_grouped, (4, 8, 8)),
+          "mlp_nobias": (_mlp_nobias, (784,)), "cnn_nobias": (_cnn_nobias, (1, 8, 8)), "cnn_sigmoid_avg": (_cnn_sigmoid_avg, (1, 12, 12)),
+          "nested": (_nested, (1, 8, 8)), "conv17": (_conv17, (2, 4, 4))}
+MLPS = ("mlp_baseline", "mlp_example", "mlp_100_52")
+
+
+def _flat(spec):
+    """the layers of a spec in forward order, nested Sequentials opened (the same dicts: editing one edits the spec)"""
+    out = []
+    for s in spec:
+        out += _flat(s["layers"]) if s["kind"] == "sequential" else [s]
+    return out
+
+
+def _max_batch():
+    from taper_amd._lib import hip as H
+    return int(H.th_qlinear_stream_max_batch())
 
 
 def _hip_model(spec):
     import taper_amd as T
+    if any(s["kind"] == "sequential" for s in spec):
+        return T.Sequential([_hip_model(s["layers"]) if s["kind"] == "sequential" else backends.HipBackend().sequential([s]).layers[0] for s in spec])
     if any(s.get("groups", 1) > 1 for s in spec):
         layers = []
         for s in spec:
@@ -127,8 +176,9 @@ def _hip_model(spec):
 
 def _reference_forward(spec, deq, x, shape):
     """the oracle's Sequential forward on the dequantized weights (the grouped convolution, which the oracle does not build, goes
-    through the float HIP model holding the same weights)"""
-    spec = [dict(s) for s in spec]
+    through the float HIP model holding the same weights; a nested Sequential computes what its layers in a row compute, so the oracle
+    runs them flat)"""
+    spec = [dict(s) for s in _flat(spec)]
     it = iter(deq)
     for s in spec:
         if "w" in s:
@@ -148,13 +198,16 @@ def test_quantized_model_matches_oracle_on_dequantized_weights(name, mode):
     import taper_amd as T
     build, shape = MODELS[name]
     rng = np.random.default_rng(11)
-    spec = backends.nonzero_biases(build(rng), rng)
+    spec = build(rng)
+    backends.nonzero_biases(_flat(spec), rng)
     model = _hip_model(spec)
     q = model.quantize("int8" if mode == "int8" else "float16") if mode != "disabled" else model.quantize("int4", enabled=False)
     ts = q.tensors()
     assert all(k == ("int8" if mode == "int8" else "float16") for k, _, _ in ts)
+    assert len(ts) == sum(("w" in s) + (s.get("b") is not None) for s in _flat(spec))
     deq = [_deq(k, c, p) for k, c, p in ts]
-    for B in (1, 64, 256):
+    M = _max_batch()
+    for B in (1, 64, 256) + ((M, M + 1, 2) if name in MLPS else ()):   # (the MLPs also on both sides of the switch between the Linear paths)
         x = rng.uniform(0, 1, (B, int(np.prod(shape)))).astype(np.float32)
         T.Tape.reset()
         xt = T.Tensor(x, (B, *shape)).requires_grad()
@@ -163,6 +216,31 @@ def test_quantized_model_matches_oracle_on_dequantized_weights(name, mode):
         got = y.data()
         ref = np.asarray(_reference_forward(spec, deq, x, shape)).reshape(got.shape)
         assert _err(got, ref) <= RTOL, (B, _err(got, ref))
+
+
+@pytest.mark.parametrize("mode", ["int8", "float16"])
+@pytest.mark.parametrize("name", MLPS)
+def test_quantized_mlp_across_the_switch_between_the_linear_paths(name, mode):
+    """The same model on the same rows on both sides of th_qlinear_stream_max_batch(): the first max rows of a max + 1 batch (the
+    dequantize workspace and th_linear_fwd) agree with the max batch (the streaming kernel) within RTOL, and the rows of the max batch
+    are bit-identical to the rows sent one by one (each (weight row, batch row) accumulator of the streaming kernel is its own chain
+    whose order depends on K and N only, layer after layer)."""
+    import taper_amd as T
+    build, shape = MODELS[name]
+    rng = np.random.default_rng(13)
+    model = _hip_model(backends.nonzero_biases(build(rng), rng))
+    q = model.quantize(mode)
+    M = _max_batch()
+    x = rng.uniform(0, 1, (M + 1, 784)).astype(np.float32)
+
+    def run(rows):
+        return q(T.Tensor(rows, (rows.shape[0], *shape))).data()
+
+    at_max, over = run(x[:M]), run(x)
+    assert at_max.shape == (M, 10) and over.shape == (M + 1, 10) and np.isfinite(over).all()
+    assert _err(over[:M], at_max) <= RTOL, _err(over[:M], at_max)
+    for b in range(M):
+        np.testing.assert_array_equal(run(x[b:b + 1])[0].view(np.uint32), at_max[b].view(np.uint32), err_msg=f"row {b} alone")
 
 
 @pytest.mark.parametrize("name", ["mlp_baseline", "cnn_reference"])
