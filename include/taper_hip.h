@@ -434,6 +434,29 @@ int th_obs_hist_lds_max_bins(void);   /* 8192 */
 /* HistogramObserver::get_stats (observers.rs:226-245): d_out3 = {sum of the bins, sum of i * bins[i] (wrapping), the largest bin} */
 int th_obs_hist_stats(th_ctx *ctx, const uint64_t *d_bins, int num_bins, uint64_t *d_out3);
 
+/* ---- batch normalisation (csrc/batchnorm.hip) ----
+ * BatchNorm2d over an NCHW map [n, c, hw]: upstream only announces the layer (nn.rs:829-857); the semantics are torch.nn.BatchNorm2d's.
+ * training != 0: per channel over its M = n * hw elements mean, the biased var and invstd = 1 / sqrt(var + eps);
+ * y = (x - mean) * (invstd * gamma) + beta, then max(y, 0) with relu; d_save_mean / d_save_invstd [c] are left for the backward and, in
+ * stream order on the device, running_mean = (1 - momentum) * running_mean + momentum * mean and running_var the same with the UNBIASED
+ * var * M / (M - 1).  training == 0: mean = running_mean, invstd = 1 / sqrt(running_var + eps), both also written to d_save_*; nothing
+ * else is modified.  The variance is taken of values shifted by a per-channel constant near the mean; no float atomics: results are
+ * bit-identical from run to run.  Launches: two for the training forward (one when th_batchnorm2d_split is 1), one for eval; capturable.
+ * Refused before anything is enqueued: n, c, hw <= 0 (and n * hw >= 2^31), a null pointer, eps not finite or <= 0, momentum outside
+ * [0, 1], and training with M == 1 ("Expected more than 1 value per channel when training"). */
+int th_batchnorm2d_fwd(th_ctx *ctx, const float *d_x, const float *d_gamma, const float *d_beta, float *d_y, float *d_running_mean,
+                       float *d_running_var, float *d_save_mean, float *d_save_invstd, int n, int c, int hw, float eps, float momentum,
+                       int training, int relu);
+/* With xh = (x - mean) * invstd and gy masked by y > 0 when d_y_or_null is given (the fused ReLU): gbeta = sum gy, ggamma = sum gy * xh,
+ * gx = gamma * invstd * (gy - gbeta / M - xh * ggamma / M); batch_stats == 0 (the forward ran on the running pair): gx = gamma * invstd
+ * * gy.  d_gx_or_null null skips the map.  accumulate_mask: bit 0 gx, bit 1 ggamma, bit 2 gbeta -- set: += into a slot that holds a
+ * gradient; clear: overwrite (no zero fill needed).  Two launches (one when th_batchnorm2d_split is 1). */
+int th_batchnorm2d_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const float *d_y_or_null, const float *d_gamma,
+                       const float *d_save_mean, const float *d_save_invstd, float *d_gx_or_null, float *d_ggamma, float *d_gbeta, int n, int c,
+                       int hw, int batch_stats, int accumulate_mask);
+/* the workgroups a channel's n * hw elements are shared among (1: every call above is a single launch); 0 for a shape that is refused */
+int th_batchnorm2d_split(int n, int c, int hw);
+
 /* ---- broadcast / reduce / layout: src/tensor.rs ---------------------- */
 int th_transpose2d(th_ctx *ctx, const float *d_in, float *d_out, int rows, int cols);      /* tensor.rs:544-566 */
 /* dst[r*dst_ld + c] = src[r*src_ld + c] for r < rows, c < cols: the strided block copies behind slice_channels /

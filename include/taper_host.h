@@ -126,6 +126,24 @@ int tp_module_free(tp_module *m);
 int tp_module_forward(const tp_module *m, const tp_tensor *x, tp_tensor **out);
 int tp_module_num_parameters(const tp_module *m, int *out);
 int tp_module_parameter(const tp_module *m, int i, tp_tensor **out);   /* shares storage with the model */
+/* ---- BatchNorm2d / BasicBlock (nn.rs:829-857 announces both and writes neither: torch.nn.BatchNorm2d's semantics) ----
+ * input [N, num_features, H, W]; parameters {gamma (ones), beta (zeros)}, buffers {running_mean (zeros), running_var (ones)}.  In
+ * training mode (the layer's own flag, default on) the forward normalises with the batch's mean and biased variance and updates the
+ * running pair on the device (momentum; unbiased variance); in eval mode it normalises with the running pair.  fuse_relu: max(y, 0) in
+ * the same pass.  num_features <= 0, eps not finite or <= 0 and momentum outside [0, 1] fail before the device is touched; a training
+ * forward of one value per channel fails with "Expected more than 1 value per channel when training". */
+int tp_batchnorm2d_new(int num_features, float eps, float momentum, int fuse_relu, tp_module **out);
+int tp_batchnorm2d_set_training(tp_module *m, int training);
+int tp_batchnorm2d_is_training(const tp_module *m, int *out);
+int tp_batchnorm2d_running_stats(const tp_module *m, float *h_mean, float *h_var);               /* each output nullable */
+int tp_batchnorm2d_set_running_stats(tp_module *m, const float *h_mean, const float *h_var);
+/* Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) with the ReLU fused; parameters(): the conv's, then gamma, beta */
+int tp_basic_block_new(int in_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
+/* saved-but-not-trained state (the running statistics), concatenated over a Sequential's / BasicBlock's children; shares storage */
+int tp_module_num_buffers(const tp_module *m, int *out);
+int tp_module_buffer(const tp_module *m, int i, tp_tensor **out);
+/* train() / eval() of every BatchNorm2d and every Dropout inside m */
+int tp_module_set_training(tp_module *m, int on);
 
 /* ---- post-training quantization (src/nn.rs:14-23, the quantized twins of nn.rs:62-504) ----
  * qtype: 0 Int8, 1 Float16; 2 Int4, 3 BFloat16 and 4 NF4 are placeholders in the reference (zeros) and are refused.  enabled == 0

@@ -289,6 +289,24 @@ class Module:
             out.append(Tensor(_h=h.value))
         return out
 
+    def buffers(self):
+        """state that is saved but not trained (BatchNorm2d's running statistics), children's concatenated; shares storage with the model"""
+        n = C.c_int()
+        tp_check(host.tp_module_num_buffers(self._h, C.byref(n)), "num_buffers")
+        out = []
+        for i in range(n.value):
+            h = _p()
+            tp_check(host.tp_module_buffer(self._h, i, C.byref(h)), "buffer")
+            out.append(Tensor(_h=h.value))
+        return out
+
+    def train(self):
+        """training mode for every BatchNorm2d and every Dropout inside this module"""
+        tp_check(host.tp_module_set_training(self._h, 1), "Module::train")
+
+    def eval(self):
+        tp_check(host.tp_module_set_training(self._h, 0), "Module::eval")
+
     def quantize(self, qtype="int8", enabled=True):
         """nn.rs:14-23 Module::quantize -> QuantizedModule (post-training, on the device; this model is not touched).
         qtype: "int8" | "float16" ("int4", "bfloat16", "nf4" are placeholders in the reference and are refused);
@@ -426,6 +444,54 @@ class Dropout(Module):
         h = _p()
         tp_check(host.tp_dropout_last_mask(self._h, C.byref(h)), "Dropout::last_mask")
         return Tensor(_h=h.value)
+
+
+class BatchNorm2d(Module):
+    """torch.nn.BatchNorm2d's semantics over [N, C, H, W] (upstream announces the layer in nn.rs:829-857 and never writes it): batch
+    statistics in training mode (default), the running pair in eval mode; fuse_relu applies max(y, 0) in the same pass."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, fuse_relu=False):
+        self.num_features = int(num_features)
+        super().__init__(_mk(host.tp_batchnorm2d_new, "BatchNorm2d::new", int(num_features), float(eps), float(momentum), 1 if fuse_relu else 0))
+
+    def train(self): tp_check(host.tp_batchnorm2d_set_training(self._h, 1), "BatchNorm2d::train")
+    def eval(self): tp_check(host.tp_batchnorm2d_set_training(self._h, 0), "BatchNorm2d::eval")
+
+    def is_training(self) -> bool:
+        out = C.c_int()
+        tp_check(host.tp_batchnorm2d_is_training(self._h, C.byref(out)), "BatchNorm2d::is_training")
+        return bool(out.value)
+
+    def _running(self, which):
+        a = np.zeros(self.num_features, np.float32)
+        tp_check(host.tp_batchnorm2d_running_stats(self._h, a.ctypes.data if which == 0 else None, a.ctypes.data if which == 1 else None),
+                 "BatchNorm2d::running_stats")
+        return a
+
+    @property
+    def running_mean(self) -> np.ndarray: return self._running(0)
+
+    @property
+    def running_var(self) -> np.ndarray: return self._running(1)
+
+    def set_running_stats(self, mean, var):
+        m, v = np.ascontiguousarray(mean, np.float32).ravel(), np.ascontiguousarray(var, np.float32).ravel()
+        if m.size != self.num_features or v.size != self.num_features:
+            raise TaperError("BatchNorm2d::set_running_stats: num_features values each expected")
+        tp_check(host.tp_batchnorm2d_set_running_stats(self._h, m.ctypes.data, v.ctypes.data), "BatchNorm2d::set_running_stats")
+
+    @property
+    def gamma(self): return self.parameters()[0]
+
+    @property
+    def beta(self): return self.parameters()[1]
+
+
+class BasicBlock(Module):
+    """nn.rs:829-857 as announced: Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) -> ReLU; parameters(): the conv's, then gamma, beta"""
+
+    def __init__(self, in_channels, out_channels, stride=1, seed=1):
+        super().__init__(_mk(host.tp_basic_block_new, "BasicBlock::new", int(in_channels), int(out_channels), int(stride), int(seed)))
 
 
 class Sequential(Module):

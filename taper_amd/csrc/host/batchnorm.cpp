@@ -1,0 +1,118 @@
+// batchnorm.cpp -- BatchNorm2d and BasicBlock (nn.rs:829-857 announces both; torch.nn.BatchNorm2d's semantics).  The arithmetic is on the
+// device (csrc/batchnorm.hip): the forward leaves the statistics it used for the backward and updates the running pair in stream order,
+// so a captured step replays it with no host work.
+#include <cmath>
+
+#include "nn_internal.h"
+
+namespace taper {
+
+// (the checks come first: a refused layer never reaches the device)
+static size_t checked_features(size_t num_features, float eps, float momentum) {
+    TAPER_ASSERT(num_features > 0 && num_features <= 0x7fffffffu, "BatchNorm2d: num_features must be positive");
+    TAPER_ASSERT(std::isfinite(eps) && eps > 0.0f, "BatchNorm2d: eps must be finite and positive");
+    TAPER_ASSERT(momentum >= 0.0f && momentum <= 1.0f, "BatchNorm2d: momentum must be in [0, 1]");
+    return num_features;
+}
+
+BatchNorm2d::BatchNorm2d(size_t nf, float eps_, float momentum_, bool relu)
+    : num_features(checked_features(nf, eps_, momentum_)), eps(eps_), momentum(momentum_), fuse_relu(relu) {
+    gamma = Tensor(std::vector<float>(nf, 1.0f), {nf}).requires_grad();
+    beta = Tensor(std::vector<float>(nf, 0.0f), {nf}).requires_grad();
+    running_mean = Tensor(std::vector<float>(nf, 0.0f), {nf});
+    running_var = Tensor(std::vector<float>(nf, 1.0f), {nf});
+}
+
+void BatchNorm2d::set_running_stats(const std::vector<float> &mean, const std::vector<float> &var) {
+    TAPER_ASSERT(mean.size() == num_features && var.size() == num_features, "BatchNorm2d::set_running_stats: num_features values each expected");
+    running_mean.set_data(mean);
+    running_var.set_data(var);
+}
+
+Tensor BatchNorm2d::forward(const Tensor &x) const {
+    TAPER_ASSERT(x.shape().size() == 4, "BatchNorm2d: expected a 4-D input [N, C, H, W]");
+    TAPER_ASSERT(x.shape()[1] == num_features, "BatchNorm2d: input has " + std::to_string(x.shape()[1]) + " channels, the layer " +
+                                                   std::to_string(num_features));
+    const size_t hw_ = x.shape()[2] * x.shape()[3];
+    TAPER_ASSERT(x.shape()[0] <= 0x7fffffffu && hw_ <= 0x7fffffffu, "BatchNorm2d: input too large");
+    const int n = (int)x.shape()[0], c = (int)num_features, hw = (int)hw_;
+    const bool batch_stats = training_;
+    Tensor out = Tensor::empty(x.shape());
+    auto saved = Buffer::alloc(2 * num_features);   // {mean, invstd} this forward normalised with
+    TH(th_batchnorm2d_fwd(Device::ctx(), x.dptr(), gamma.dptr(), beta.dptr(), out.dptr(), running_mean.dptr(), running_var.dptr(), saved->d,
+                          saved->d + num_features, n, c, hw, eps, momentum, batch_stats ? 1 : 0, fuse_relu ? 1 : 0));
+    if ((x.get_requires_grad() || gamma.get_requires_grad() || beta.get_requires_grad()) && !NoGradScope::active()) {
+        out.set_requires_grad(true);
+        Tensor in = x, r = out, g = gamma, b = beta;
+        const bool relu = fuse_relu;
+        Tape::push(out, true, [in, r, g, b, saved, n, c, hw, batch_stats, relu]() {
+            if (!r.has_grad()) return;
+            // gradients go straight into the slots: += where one is Some already, overwritten otherwise; a frozen gamma / beta gets scratch
+            int mask = 0;
+            bool none;
+            float *gx = nullptr, *gg = nullptr, *gb = nullptr;
+            std::shared_ptr<Buffer> scratch;
+            if (in.get_requires_grad()) {
+                gx = in.grad_for_write(&none);
+                if (!none) mask |= 1;
+            }
+            if (g.get_requires_grad()) {
+                gg = g.grad_for_write(&none);
+                if (!none) mask |= 2;
+            }
+            if (b.get_requires_grad()) {
+                gb = b.grad_for_write(&none);
+                if (!none) mask |= 4;
+            }
+            if (!gg || !gb) {
+                scratch = Buffer::alloc(2 * (size_t)c);
+                if (!gg) gg = scratch->d;
+                if (!gb) gb = scratch->d + c;
+            }
+            TH(th_batchnorm2d_bwd(Device::ctx(), r.grad_dptr(), in.dptr(), relu ? r.dptr() : nullptr, g.dptr(), saved->d, saved->d + c, gx, gg, gb,
+                                  n, c, hw, batch_stats ? 1 : 0, mask));
+        });
+    }
+    return out;
+}
+
+BasicBlock::BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed)
+    : conv(in_ch, out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, true, seed), bn(out_ch, 1e-5f, 0.1f, true) {}
+
+std::vector<Tensor> BasicBlock::parameters() const {
+    std::vector<Tensor> p = conv.parameters();
+    for (const Tensor &t : bn.parameters()) p.push_back(t);
+    return p;
+}
+
+std::vector<Tensor> Sequential::buffers() const {
+    std::vector<Tensor> b;
+    for (auto &l : layers)
+        for (auto &t : l->buffers()) b.push_back(t);
+    return b;
+}
+
+void batchnorm_modules(Module &m, std::vector<BatchNorm2d *> *out) {
+    if (auto *s = dynamic_cast<Sequential *>(&m)) {
+        for (const auto &l : s->layers) batchnorm_modules(*l, out);
+    } else if (auto *bb = dynamic_cast<BasicBlock *>(&m)) {
+        out->push_back(&bb->bn);
+    } else if (auto *bn = dynamic_cast<BatchNorm2d *>(&m)) {
+        out->push_back(bn);
+    }
+}
+
+void set_training(Module &m, bool on) {
+    if (auto *s = dynamic_cast<Sequential *>(&m)) {
+        for (const auto &l : s->layers) set_training(*l, on);
+    } else if (auto *bb = dynamic_cast<BasicBlock *>(&m)) {
+        bb->bn.set_training(on);
+    } else if (auto *bn = dynamic_cast<BatchNorm2d *>(&m)) {
+        bn->set_training(on);
+    } else if (auto *d = dynamic_cast<Dropout *>(&m)) {
+        if (on) d->train();
+        else d->eval();
+    }
+}
+
+}  // namespace taper

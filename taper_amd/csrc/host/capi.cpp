@@ -172,6 +172,58 @@ int tp_dropout_set_training(tp_module *m, int training) {
 }
 int tp_dropout_last_mask(const tp_module *m, tp_tensor **out) { TP_BEGIN *out = wrap(as_dropout(m)->last_mask()); TP_END }
 
+// ---- BatchNorm2d / BasicBlock ----
+static BatchNorm2d *as_batchnorm(const tp_module *m) {
+    auto *b = m ? dynamic_cast<BatchNorm2d *>(m->m.get()) : nullptr;
+    TAPER_ASSERT(b, "not a BatchNorm2d module");
+    return b;
+}
+int tp_batchnorm2d_new(int num_features, float eps, float momentum, int fuse_relu, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_batchnorm2d_new: null argument");
+    TAPER_ASSERT(num_features > 0, "BatchNorm2d: num_features must be positive");
+    *out = new tp_module{std::make_shared<BatchNorm2d>((size_t)num_features, eps, momentum, fuse_relu != 0)};
+    TP_END
+}
+int tp_batchnorm2d_set_training(tp_module *m, int training) { TP_BEGIN as_batchnorm(m)->set_training(training != 0); TP_END }
+int tp_batchnorm2d_is_training(const tp_module *m, int *out) { TP_BEGIN *out = as_batchnorm(m)->is_training() ? 1 : 0; TP_END }
+int tp_batchnorm2d_running_stats(const tp_module *m, float *h_mean, float *h_var) {
+    TP_BEGIN
+    const BatchNorm2d *b = as_batchnorm(m);
+    if (h_mean) {
+        auto v = b->running_mean.data();
+        std::memcpy(h_mean, v.data(), v.size() * sizeof(float));
+    }
+    if (h_var) {
+        auto v = b->running_var.data();
+        std::memcpy(h_var, v.data(), v.size() * sizeof(float));
+    }
+    TP_END
+}
+int tp_batchnorm2d_set_running_stats(tp_module *m, const float *h_mean, const float *h_var) {
+    TP_BEGIN
+    BatchNorm2d *b = as_batchnorm(m);
+    TAPER_ASSERT(h_mean && h_var, "tp_batchnorm2d_set_running_stats: null argument");
+    b->set_running_stats(std::vector<float>(h_mean, h_mean + b->num_features), std::vector<float>(h_var, h_var + b->num_features));
+    TP_END
+}
+int tp_basic_block_new(int in_ch, int out_ch, int stride, uint64_t seed, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_basic_block_new: null argument");
+    TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "BasicBlock: in_channels, out_channels and stride must be positive");
+    *out = new tp_module{std::make_shared<BasicBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed)};
+    TP_END
+}
+int tp_module_num_buffers(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->buffers().size(); TP_END }
+int tp_module_buffer(const tp_module *m, int i, tp_tensor **out) {
+    TP_BEGIN
+    auto b = m->m->buffers();
+    TAPER_ASSERT(i >= 0 && (size_t)i < b.size(), "buffer index out of range");
+    *out = wrap(b[i]);
+    TP_END
+}
+int tp_module_set_training(tp_module *m, int on) { TP_BEGIN TAPER_ASSERT(m, "tp_module_set_training: null argument"); set_training(*m->m, on != 0); TP_END }
+
 int tp_linear_new(int in_f, int out_f, int bias, uint64_t seed, tp_module **out) {
     TP_BEGIN *out = new tp_module{std::make_shared<Linear>((size_t)in_f, (size_t)out_f, bias != 0, seed)}; TP_END
 }
@@ -613,7 +665,18 @@ int tp_trainer_new(tp_module *m, tp_optim *o, tp_trainer **out) {
     TP_END
 }
 int tp_trainer_set_sample_shape(tp_trainer *t, const size_t *shape, int nd) { TP_BEGIN t->t->sample_shape = mkshape(shape, nd); TP_END }
-int tp_trainer_set_comm(tp_trainer *t, tp_comm *c) { TP_BEGIN t->t->comm = c ? c->c : nullptr; TP_END }
+int tp_trainer_set_comm(tp_trainer *t, tp_comm *c) {
+    TP_BEGIN
+    auto prev = t->t->comm;
+    t->t->comm = c ? c->c : nullptr;
+    try {
+        t->t->check_batchnorm_comm();   // (refused here already, and again by every step: the model's layers can change behind the Trainer)
+    } catch (...) {
+        t->t->comm = prev;
+        throw;
+    }
+    TP_END
+}
 int tp_trainer_set_options(tp_trainer *t, int graph_chunk, int fuse_head, int fuse_adam) {
     TP_BEGIN
     TAPER_ASSERT(graph_chunk >= 1, "graph_chunk must be >= 1");

@@ -306,6 +306,7 @@ class Module {
     virtual ~Module() = default;
     virtual Tensor forward(const Tensor &input) const = 0;  // nn.rs:11
     virtual std::vector<Tensor> parameters() const = 0;     // nn.rs:12
+    virtual std::vector<Tensor> buffers() const { return {}; }   // state that is saved but not trained (BatchNorm2d's running statistics)
     virtual const char *name() const = 0;
 };
 using Layer = Module;  // north_star calls the trait "nn::Layer"
@@ -412,6 +413,44 @@ class Dropout : public Module {  // nn.rs:773-827
     mutable Tensor last_mask_;
 };
 
+// torch.nn.BatchNorm2d's semantics (upstream announces the layer in nn.rs:829-857 and never writes it; csrc/batchnorm.hip).  Training
+// mode (the layer's own flag, default on) normalises with the batch's statistics and updates the running pair on the device, in stream
+// order; eval mode normalises with the running pair.  One tape node; nothing is recorded under NoGradScope.
+class BatchNorm2d : public Module {
+   public:
+    Tensor gamma, beta;                 // [num_features]: ones, zeros
+    Tensor running_mean, running_var;   // [num_features]: zeros, ones -- buffers, pooled device memory
+    size_t num_features;
+    float eps, momentum;
+    bool fuse_relu;
+    // num_features == 0, eps not finite or <= 0 and momentum outside [0, 1] throw before the device is touched
+    explicit BatchNorm2d(size_t num_features, float eps = 1e-5f, float momentum = 0.1f, bool fuse_relu = false);
+    void train() { training_ = true; }
+    void eval() { training_ = false; }
+    void set_training(bool on) { training_ = on; }
+    bool is_training() const { return training_; }
+    void set_running_stats(const std::vector<float> &mean, const std::vector<float> &var);
+    Tensor forward(const Tensor &x) const override;   // x: [N, num_features, H, W]
+    std::vector<Tensor> parameters() const override { return {gamma, beta}; }
+    std::vector<Tensor> buffers() const override { return {running_mean, running_var}; }
+    const char *name() const override { return fuse_relu ? "BatchNorm2dReLU" : "BatchNorm2d"; }
+
+   private:
+    bool training_ = true;
+};
+
+// nn.rs:829-857 as announced: Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) -> ReLU (fused into the normalisation's map)
+class BasicBlock : public Module {
+   public:
+    Conv2d conv;
+    BatchNorm2d bn;
+    BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed);
+    Tensor forward(const Tensor &x) const override { return bn.forward(conv.forward(x)); }
+    std::vector<Tensor> parameters() const override;   // the conv's, then gamma, beta (nn.rs:852-856)
+    std::vector<Tensor> buffers() const override { return bn.buffers(); }
+    const char *name() const override { return "BasicBlock"; }
+};
+
 class Sequential : public Module {  // nn.rs:130-162
    public:
     std::vector<std::shared_ptr<Module>> layers;
@@ -423,8 +462,14 @@ class Sequential : public Module {  // nn.rs:130-162
     // stage list); returns the index of the first layer behind the run
     size_t conv_stages_at(size_t i, size_t n_layers, std::vector<ConvStage> *stages) const;
     std::vector<Tensor> parameters() const override;
+    std::vector<Tensor> buffers() const override;
     const char *name() const override { return "Sequential"; }
 };
+
+// The BatchNorm2d layers of a model (a Sequential's and a BasicBlock's, or the module itself), in order
+void batchnorm_modules(Module &m, std::vector<BatchNorm2d *> *out);
+// train() / eval() of every BatchNorm2d and every Dropout inside `m`
+void set_training(Module &m, bool on);
 
 // ---- post-training quantization (src/nn.rs:14-23 Module::quantize / QuantizedModule, quantized twins nn.rs:62-504) ----
 // quantize() of Linear, Conv2d / Conv2dReLU, Sequential and the parameter-free layers (pools, Flatten, ReLU, Sigmoid); any other module
@@ -966,6 +1011,7 @@ class Trainer {  // train.rs:74-172
     // one step exactly as examples/train_mnist.rs:89-121 (reads loss + accuracy back every step)
     void train_step(const Tensor &images, const Tensor &labels, float *loss_out, float *acc_out);
     void check_comm() const;   // throws when the peer-to-peer communicator has timed out (after any stream synchronisation)
+    void check_batchnorm_comm() const;   // throws for a communicator together with a model that holds a BatchNorm2d (statistics are per rank)
     EpochResult train_epoch(DataLoader &loader);              // train.rs:98-144 (eager, synchronising)
     EpochResult evaluate(DataLoader &loader);                 // train.rs:147-172
     // same arithmetic, but the step's op list is captured once into a hipGraph

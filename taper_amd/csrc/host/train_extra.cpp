@@ -261,6 +261,12 @@ void Trainer::save_checkpoint(const std::string &path) const {  // train.rs:264-
     const std::vector<Tensor> params = model->parameters();
     f << params.size() << '\n';
     for (const Tensor &p : params) write_tensor_block(f, p.shape(), p.data());
+    // a model with buffers (BatchNorm2d's running statistics): "buffers <k>", then k blocks in the same format; none: today's bytes
+    const std::vector<Tensor> bufs = model->buffers();
+    if (!bufs.empty()) {
+        f << "buffers " << bufs.size() << '\n';
+        for (const Tensor &b : bufs) write_tensor_block(f, b.shape(), b.data());
+    }
     TAPER_ASSERT(f.good(), "save_checkpoint: write failed");
 }
 
@@ -271,6 +277,13 @@ void Trainer::load_checkpoint(const std::string &path) {
     size_t n = 0;
     TAPER_ASSERT((bool)(f >> n) && n == params.size(), "load_checkpoint: parameter count mismatch");
     for (size_t i = 0; i < n; ++i) params[i].set_data(read_tensor_block(f, params[i].shape(), "load_checkpoint: parameter " + std::to_string(i)));
+    std::vector<Tensor> bufs = model->buffers();
+    std::string tag;
+    size_t k = 0;
+    if (f >> tag) TAPER_ASSERT(tag == "buffers" && (bool)(f >> k), "load_checkpoint: expected a buffers line behind the parameters");
+    TAPER_ASSERT(k == bufs.size(), "load_checkpoint: buffer count mismatch (the file has " + std::to_string(k) + ", the model " +
+                                       std::to_string(bufs.size()) + ")");
+    for (size_t i = 0; i < k; ++i) bufs[i].set_data(read_tensor_block(f, bufs[i].shape(), "load_checkpoint: buffer " + std::to_string(i)));
 }
 
 void Trainer::save_optimizer_state(const std::string &path) const {

@@ -143,6 +143,7 @@ static void reduce_grads(Trainer &t) {
 
 void Trainer::train_step(const Tensor &images, const Tensor &labels, float *loss_out, float *acc_out) {
     Tape::reset();                                              // train_mnist.rs:91
+    check_batchnorm_comm();
     if (has_qat()) {
         TAPER_ASSERT(!comm, "QAT: data-parallel training of a QAT model is not supported");
         qat_pass_.run(*model);                                  // every active QAT layer's weights: one launch pair
@@ -208,6 +209,21 @@ EpochResult Trainer::evaluate(DataLoader &loader) {  // train.rs:147-172
     const size_t nb = loader.num_batches();
     r.num_batches = nb;
     if (nb == 0) return r;
+    // BatchNorm2d layers run on their running statistics for the duration; each gets its own flag back (Dropout is left as it is)
+    struct EvalMode {
+        std::vector<std::pair<BatchNorm2d *, bool>> was;
+        explicit EvalMode(Module &m) {
+            std::vector<BatchNorm2d *> bns;
+            batchnorm_modules(m, &bns);
+            for (BatchNorm2d *b : bns) {
+                was.emplace_back(b, b->is_training());
+                b->eval();
+            }
+        }
+        ~EvalMode() {
+            for (auto &w : was) w.first->set_training(w.second);
+        }
+    } eval_mode(*model);
     th_ctx *ctx = Device::ctx();
     auto log = Buffer::alloc(2 * nb), st = Buffer::alloc(4);
     TH(th_fill_f32(ctx, st->d, 0.f, 4));
@@ -296,6 +312,7 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
         p.fused_adam = fuse_adam && (!comm || exchange);
         return p;
     };
+    check_batchnorm_comm();
     // a QAT model trains layer by layer: its layers fake-quantize their weights and outputs, which no fused form does
     if (has_qat()) {
         TAPER_ASSERT(!comm, "QAT: data-parallel training of a QAT model is not supported");
@@ -465,6 +482,15 @@ void Trainer::enqueue_steps(const float *d_images, const float *d_labels, const 
     optimizer->flush_deferred();
 }
 
+void Trainer::check_batchnorm_comm() const {
+    if (!comm) return;
+    // per-rank batch statistics: the replicas' running pairs -- and, through the normalised activations, their gradients' meaning -- would
+    // drift apart; synchronised statistics are not implemented
+    std::vector<BatchNorm2d *> bns;
+    batchnorm_modules(*model, &bns);
+    TAPER_ASSERT(bns.empty(), "BatchNorm2d: data-parallel training of a model with batch normalisation is not supported (statistics are per rank)");
+}
+
 bool Trainer::has_qat() const {
     std::vector<const QATModule *> mods;
     qat_modules(*model, &mods, false);
@@ -559,6 +585,12 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         }
         for (const QATModule *q : mods)
             key.push_back((uintptr_t)q->active() | (uintptr_t)q->config.activations << 1 | (uintptr_t)q->config.qtype << 2);
+    }
+    // BatchNorm2d: each layer's mode (a captured step bakes in which statistics it normalises with and whether it updates the running pair)
+    {
+        std::vector<BatchNorm2d *> bns;
+        batchnorm_modules(*model, &bns);
+        for (const BatchNorm2d *b : bns) key.push_back((uintptr_t)0xb0 | (uintptr_t)b->is_training());
     }
     if (!graphs_.empty() && graph_key_ != key) drop_graphs();
 
