@@ -1,9 +1,11 @@
 """BatchNorm2d / BasicBlock on the GPU (csrc/batchnorm.hip, csrc/host/batchnorm.cpp) against the float64 restatement of
 tests/batchnorm_ref.py, which tests/test_batchnorm_abi.py pins against torch.  Comparisons go through margins.check with the project's
 parity bound, 1e-4 of the tensor's scale (a float32 restatement of the same formulas stays at or below 6e-6 on these shapes); bit
-equality where the issue asks for it (determinism, the constant channel, untouched buffers, graph against eager)."""
+equality where the issue asks for it (determinism, the constant channel, untouched buffers, graph against eager, and the recorded
+bits of tests/golden/batchnorm_bits.npz, which pin every kernel form's order of operations)."""
 import ctypes as C
 import tempfile
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -18,9 +20,10 @@ F = np.float32
 BOUND = 1e-4
 EPS, MOM = 1e-5, 0.1
 # the issue's shapes, then the forms they leave out: [n, c, 1, 1] with its rows shared among workgroups and a channel tile that is not
-# full (the column form), and a channel shared among workgroups whose planes are no multiple of four floats
+# full (the column form), a channel shared among workgroups whose planes are no multiple of four floats, and more channels than the
+# grid has workgroups (2048), so that a workgroup takes a second item: in single floats and in float4s
 SHAPES = [(2, 5, 3, 3), (4, 3, 1, 1), (1, 3, 5, 7), (3, 67, 5, 5), (8, 3, 16, 16), (64, 4, 7, 7), (64, 2, 56, 56), (2, 300, 2, 2),
-          (200, 70, 1, 1), (40, 2, 15, 15)]
+          (200, 70, 1, 1), (40, 2, 15, 15), (2, 2050, 1, 2), (2, 2050, 2, 2)]
 _ids = ["x".join(map(str, s)) for s in SHAPES]
 
 
@@ -51,12 +54,9 @@ def _in_use(ctx):
 _CASES = {}
 
 
-def _case(shape, offset=None):
-    """inputs of a shape, made once: x ~ N(m_c, s_c) with m_c in [-1, 1] (or = offset) and s_c in [0.5, 2] (1 with an offset),
-    gy ~ N(0.5, 1), gamma in [0.5, 1.5], beta ~ N(0, 1), a running pair; and the float64 references of every mode"""
-    key = (shape, offset)
-    if key in _CASES:
-        return _CASES[key]
+def _inputs(shape, offset=None):
+    """x ~ N(m_c, s_c) with m_c in [-1, 1] (or = offset) and s_c in [0.5, 2] (1 with an offset), gy ~ N(0.5, 1), gamma in [0.5, 1.5],
+    beta ~ N(0, 1), a running pair"""
     n, c, h, w = shape
     rng = np.random.default_rng(int(np.prod(shape)) * 8 + shape[1] + (0 if offset is None else 4096))
     m = rng.uniform(-1, 1, c) if offset is None else np.full(c, float(offset))
@@ -64,6 +64,16 @@ def _case(shape, offset=None):
     d = dict(x=(rng.standard_normal(shape) * s.reshape(1, c, 1, 1) + m.reshape(1, c, 1, 1)).astype(F),
              gy=(rng.standard_normal(shape) + 0.5).astype(F), gamma=rng.uniform(0.5, 1.5, c).astype(F), beta=rng.standard_normal(c).astype(F),
              rm=rng.uniform(-1, 1, c).astype(F), rv=rng.uniform(0.5, 2.0, c).astype(F))
+    return d
+
+
+def _case(shape, offset=None):
+    """the inputs of a shape, made once, and the float64 references of every mode"""
+    key = (shape, offset)
+    if key in _CASES:
+        return _CASES[key]
+    c = shape[1]
+    d = _inputs(shape, offset)
     d["xs"] = [d["x"]] + [(d["x"] * F(1 + 0.25 * k) + F(0.125 * k)).astype(F) for k in (1, 2)]     # three batches for three calls in a row
     for relu in (False, True):
         rm, rv = np.zeros(c), np.ones(c)
@@ -78,11 +88,30 @@ def _case(shape, offset=None):
     return d
 
 
-class _Dev:
-    """device buffers of one layer: parameters, the running pair (zeros, ones) and the saved statistics"""
+class _Shifted:
+    """`size` floats that begin `off` bytes into their allocation (off = 4: on no 16-byte boundary), holding `data` when given"""
 
-    def __init__(self, ctx, c, gamma, beta, rm=None, rv=None):
-        self.ctx, self.c = ctx, c
+    def __init__(self, ctx, size, off, data=None):
+        self.ctx, self.floats = ctx, size + off // 4
+        self.buf = ctx.empty(self.floats)
+        self.ptr = self.buf.offset(off)
+        if data is not None:
+            a = np.ascontiguousarray(data, F)
+            assert _lib().th_memcpy_h2d(ctx.h, self.ptr, a.ctypes.data, a.nbytes) == 0
+
+    def __int__(self):
+        return self.ptr
+
+    def fill(self, value):
+        self.ctx.call("th_fill_f32", self.buf, value, self.floats)
+
+
+class _Dev:
+    """device buffers of one layer: parameters, the running pair (zeros, ones) and the saved statistics; x, y, gy and gx begin `off`
+    bytes into their allocations"""
+
+    def __init__(self, ctx, c, gamma, beta, rm=None, rv=None, off=0):
+        self.ctx, self.c, self.off = ctx, c, off
         self.gamma, self.beta = ctx.upload(gamma), ctx.upload(beta)
         self.rm = ctx.upload(np.zeros(c, F) if rm is None else rm)
         self.rv = ctx.upload(np.ones(c, F) if rv is None else rv)
@@ -92,8 +121,8 @@ class _Dev:
 
     def fwd(self, x, training=True, relu=False, eps=EPS, mom=MOM):
         n, c, h, w = x.shape
-        self.x, self.y = self.ctx.upload(x), self.ctx.empty(x.size)
-        self.ctx.call("th_batchnorm2d_fwd", self.x, self.gamma, self.beta, self.y, self.rm, self.rv, self.sm, self.si, n, c, h * w, eps, mom,
+        self.x, self.y = _Shifted(self.ctx, x.size, self.off, x), _Shifted(self.ctx, x.size, self.off)
+        self.ctx.call("th_batchnorm2d_fwd", int(self.x), self.gamma, self.beta, int(self.y), self.rm, self.rv, self.sm, self.si, n, c, h * w, eps, mom,
                       1 if training else 0, 1 if relu else 0)
         return self.ctx.download(self.y, x.shape)
 
@@ -101,17 +130,19 @@ class _Dev:
         d = self.ctx.download
         return d(self.sm, (self.c,)), d(self.si, (self.c,)), d(self.rm, (self.c,)), d(self.rv, (self.c,))
 
-    def bwd(self, gy, relu, batch_stats=True, want_gx=True, acc=0, out=None):
-        """-> (gx or None, ggamma, gbeta) -- into `out` = (gx, ggamma, gbeta) device buffers when given"""
+    def bwd(self, gy, relu, batch_stats=True, want_gx=True, acc=0, out=None, gx_off=None):
+        """-> (gx or None, ggamma, gbeta) -- into `out` = (gx, ggamma, gbeta) device buffers when given; gx_off: gx alone begins that
+        many bytes into its allocation"""
         n, c, h, w = gy.shape
-        dgy = self.ctx.upload(gy)
+        dgy = _Shifted(self.ctx, gy.size, self.off, gy)
         if out is None:
-            out = (self.ctx.empty(gy.size), self.ctx.empty(c), self.ctx.empty(c))
-            for b, k in zip(out, (gy.size, c, c)):
-                self.ctx.call("th_fill_f32", b, float("nan"), k)
+            out = (_Shifted(self.ctx, gy.size, self.off if gx_off is None else gx_off), self.ctx.empty(c), self.ctx.empty(c))
+            out[0].fill(float("nan"))
+            for b in out[1:]:
+                self.ctx.call("th_fill_f32", b, float("nan"), c)
         gx, gg, gb = out
-        self.ctx.call("th_batchnorm2d_bwd", dgy, self.x, self.y if relu else None, self.gamma, self.sm, self.si, gx if want_gx else None, gg, gb,
-                      n, c, h * w, 1 if batch_stats else 0, acc)
+        self.ctx.call("th_batchnorm2d_bwd", int(dgy), int(self.x), int(self.y) if relu else None, self.gamma, self.sm, self.si,
+                      int(gx) if want_gx else None, gg, gb, n, c, h * w, 1 if batch_stats else 0, acc)
         self.last = out
         d = self.ctx.download
         return (d(gx, gy.shape) if want_gx else None), d(gg, (c,)), d(gb, (c,))
@@ -225,6 +256,108 @@ def test_two_runs_are_bit_identical(ctx, shape):
         runs.append((y,) + dev.stats() + dev.bwd(d["gy"], True))
     for a, b in zip(*runs):
         assert np.array_equal(_bits(a), _bits(b))
+
+
+# ---- 6b. the recorded bits of every kernel form ----
+def _hashed(size, mult, lo, width):
+    """element i = lo + width * ((i * mult) mod 2^32) / 2^32: integers until the one rounding to float32, the same whatever numpy does"""
+    k = (np.arange(size, dtype=np.uint64) * np.uint64(mult)) & np.uint64(0xFFFFFFFF)
+    return (lo + width * (k.astype(np.float64) / 4294967296.0)).astype(F)
+
+
+def _bit_inputs(shape):
+    """x in [-2, 2) plus the channel's offset (ch % 5 - 2) / 4, gy in [-1.5, 2.5), and per-channel vectors, all from integer formulas"""
+    n, c, h, w = shape
+    ch = np.arange(c)
+    size = n * c * h * w
+    x = _hashed(size, 2654435761, -2.0, 4.0).reshape(shape) + ((ch % 5 - 2) / 4.0).astype(F).reshape(1, c, 1, 1)
+    return dict(x=x.astype(F), gy=_hashed(size, 2246822519, -1.5, 4.0).reshape(shape), gamma=(0.5 + (ch * 7 % 11) / 11.0).astype(F),
+                beta=((ch * 5 % 7) / 7.0 - 0.5).astype(F), rm=((ch * 3 % 8) / 4.0 - 1.0).astype(F), rv=(0.5 + (ch * 5 % 12) / 8.0).astype(F))
+
+
+# shape -> th_batchnorm2d_split, one case per kernel form: plane scalar / float4 in one launch; plane scalar split; plane float4 split with
+# shares of 1024 float4s (every lane prefetches a trip) and of 960 (lanes 0-191 do, the others do not); column in one launch with a
+# partial tile; column split with a partial second tile
+BIT_CASES = {(2, 5, 3, 3): 1, (8, 3, 16, 16): 1, (40, 2, 15, 15): 3, (3, 2, 64, 64): 3, (5, 2, 48, 48): 3, (4, 3, 1, 1): 1, (200, 70, 1, 1): 6}
+
+
+def bits_record(ctx, shape):
+    """-> name -> uint32 array: the bit patterns of every per-channel output and the CRC-32 of every map of one training forward with
+    the ReLU, a masked backward with gx, an unmasked backward without gx, and an eval forward"""
+    d, c = _bit_inputs(shape), shape[1]
+    crc = lambda a: np.array([zlib.crc32(np.ascontiguousarray(a, F).tobytes())], np.uint32)
+    out = {}
+    dev = _Dev(ctx, c, d["gamma"], d["beta"])
+    out["train_y_crc"] = crc(dev.fwd(d["x"], True, True))
+    out["save_mean"], out["save_invstd"], out["running_mean"], out["running_var"] = map(_bits, dev.stats())
+    gx, gg, gb = dev.bwd(d["gy"], True)
+    out["masked_gx_crc"], out["masked_ggamma"], out["masked_gbeta"] = crc(gx), _bits(gg), _bits(gb)
+    _, gg, gb = dev.bwd(d["gy"], False, want_gx=False)
+    out["unmasked_ggamma"], out["unmasked_gbeta"] = _bits(gg), _bits(gb)
+    dev = _Dev(ctx, c, d["gamma"], d["beta"], d["rm"], d["rv"])
+    out["eval_y_crc"] = crc(dev.fwd(d["x"], False, False))
+    out["eval_save_invstd"] = _bits(dev.stats()[1])
+    return out
+
+
+@pytest.mark.parametrize("shape", list(BIT_CASES), ids=["x".join(map(str, s)) for s in BIT_CASES])
+def test_bits_match_the_recorded_parent(ctx, shape):
+    """Every kernel form gives the bits tests/golden/batchnorm_bits.npz holds, recorded on an MI355X before the plane and column kernels
+    became one set.  Nothing is compiled with fast-math and contraction is off, so the bits follow from the source's order of operations:
+    a mismatch means that order changed.  A pull request that changes the summation order on purpose regenerates the fixture with
+    tests/golden/make_golden_batchnorm_bits.py and says so."""
+    assert _lib().th_batchnorm2d_split(shape[0], shape[1], shape[2] * shape[3]) == BIT_CASES[shape]
+    tag = "x".join(map(str, shape))
+    want, k = np.load(GOLDEN / "batchnorm_bits.npz")[tag], 0        # (the arrays of bits_record one after the other, in its order)
+    for name, got in bits_record(ctx, shape).items():
+        w = want[k:k + got.size]
+        k += got.size
+        assert np.array_equal(got, w), f"{tag}: {name} is the first array that differs from the recorded bits ({got[:4]} against {w[:4]})"
+    assert k == want.size
+
+
+# ---- 6c. more items than workgroups in the column form ----
+def test_column_form_loops_over_its_items(ctx):
+    """[4, 131073, 1, 1]: 2049 channel tiles for 2048 workgroups, the last tile one channel wide; one forward and one backward"""
+    shape = (4, 131073, 1, 1)
+    d, c = _inputs(shape), shape[1]
+    for relu in (False, True):
+        ref = R.forward(d["x"], d["gamma"], d["beta"], np.zeros(c), np.ones(c), EPS, MOM, True, relu)
+        dev = _Dev(ctx, c, d["gamma"], d["beta"])
+        margins.check("y", dev.fwd(d["x"], True, relu), ref["y"], BOUND)
+        sm, si, rm, rv = dev.stats()
+        margins.check("save_mean", sm, ref["save_mean"], BOUND)
+        margins.check("var_from_save_invstd", 1.0 / si.astype(np.float64) ** 2 - EPS, ref["var"], BOUND)
+        margins.check("running_mean", rm, ref["running_mean"], BOUND)
+        margins.check("running_var", rv, ref["running_var"], BOUND)
+        rgx, rgg, rgb = R.backward(d["gy"], d["x"], d["gamma"], ref["save_mean"], ref["save_invstd"], ref["y"] if relu else None)
+        gx, gg, gb = dev.bwd(d["gy"], relu)
+        margins.check("gx", gx, rgx, BOUND)
+        margins.check("ggamma", gg, rgg, BOUND)
+        margins.check("gbeta", gb, rgb, BOUND)
+
+
+# ---- 6d. pointers off the 16-byte boundary: the scalar kernels on a shape whose planes are whole float4s ----
+@pytest.mark.parametrize("shape", [(3, 2, 64, 64), (8, 3, 16, 16)], ids=["3x2x64x64_split", "8x3x16x16_one_launch"])
+def test_unaligned_pointers_take_the_scalar_kernels(ctx, shape):
+    """x, y, gy and gx 4 bytes into their allocations, then gx alone: held to the reference (not to the aligned run's bits: single floats
+    and float4s group their sums differently)"""
+    d, c = _case(shape), shape[1]
+    ref = d["train", True]
+    rgx, rgg, rgb = R.backward(d["gy"], d["x"], d["gamma"], ref["save_mean"], ref["save_invstd"], ref["y"])
+    for off, gx_off in ((4, None), (0, 4)):
+        tag = "all_shifted" if off else "gx_shifted"
+        dev = _Dev(ctx, c, d["gamma"], d["beta"], off=off)
+        margins.check(f"y_{tag}", dev.fwd(d["x"], True, True), ref["y"], BOUND)
+        sm, si, rm, rv = dev.stats()
+        margins.check(f"save_mean_{tag}", sm, ref["save_mean"], BOUND)
+        margins.check(f"var_from_save_invstd_{tag}", 1.0 / si.astype(np.float64) ** 2 - EPS, ref["var"], BOUND)
+        margins.check(f"running_mean_{tag}", rm, ref["running_mean"], BOUND)
+        margins.check(f"running_var_{tag}", rv, ref["running_var"], BOUND)
+        gx, gg, gb = dev.bwd(d["gy"], True, gx_off=gx_off)
+        margins.check(f"gx_{tag}", gx, rgx, BOUND)
+        margins.check(f"ggamma_{tag}", gg, rgg, BOUND)
+        margins.check(f"gbeta_{tag}", gb, rgb, BOUND)
 
 
 # ---- 7. refusals ----
