@@ -393,6 +393,32 @@ typedef struct th_qtensor {
 } th_qtensor;
 int th_dequantize_multi(th_ctx *ctx, const th_qtensor *h_items, int n_items);
 
+/* ---- calibrated int8 inference: int8 activations x int8 weights on the integer matrix cores (csrc/qgemm_i8.hip) ----
+ * With weight codes qw[n][k] and {mw, sw} = th_quantize_int8's {min_val, scale} (a decoded weight is (qw + 128) * sw + mw), a
+ * device-resident activation scale sx and qx = clamp(round(x / sx) as i32, -128, 127) (th_fake_quant_act's int8 code: NaN -> 0, +-inf
+ * saturate):
+ *     acc = sum_k qx[b][k] * qw[n][k], rs = sum_k qx[b][k], t = acc + 128 * rs                      (int32, exact)
+ *     y   = sx * (sw * (float)t + mw * (float)rs)  [+ (float)(qb[n] + 128) * sb + mb]  [max(y, 0)]   (f32, each operation rounded once)
+ * A row's result depends on that row alone.  None of the calls synchronises or reads anything back: all can be captured.
+ *
+ * th_quantize_act_int8: f32 [rows, k] -> codes [rows, pitch] (pitch >= k, pitch % 16 == 0; bytes k .. pitch - 1 of every row are 0) and
+ * d_rowsum[rows] = the int32 sum of each row's codes (in-workgroup integer reduction: bit-identical from run to run).  One launch;
+ * 16-byte loads and stores when d_x and d_q are 16-byte aligned and k % 4 == 0. */
+int th_quantize_act_int8(th_ctx *ctx, const float *d_x, int rows, int k, const float *d_scale, int8_t *d_q, int pitch, int *d_rowsum);
+/* packed [rows, k] codes -> [rows, pitch] with zero padding (d_dst 16-byte aligned): once per weight, at quantize time */
+int th_pad_rows_int8(th_ctx *ctx, const int8_t *d_src, int rows, int k, int8_t *d_dst, int pitch);
+/* The product.  d_qx / d_qw 16-byte aligned, both pitches multiples of 16 and >= in_features, in_features <= 65 536 (|t| < 2^31):
+ * anything else is refused before a launch.  The bytes in_features .. pitch_x - 1 of every row of d_qx must be 0 (those of d_qw may
+ * hold anything).  d_qb / d_bparams nullable. */
+int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                       const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams,
+                       int relu, float *d_y);
+int th_qlinear_i8_kstep(void);   /* bytes of K the product stages at a time (64): the pitch a caller should round in_features up to */
+/* Calibration: d_range2 = {min, max} over the FINITE elements of every tensor shown so far (first != 0: of this tensor alone) and
+ * d_scale = the scale th_fake_quant_act gives that range: max(|min|, |max|) / 127, all zero -> (0, 1), all equal to m -> (0.9 m, 1.1 m).
+ * Two launches on th_quantize_int8's min / max partials. */
+int th_act_range_update(th_ctx *ctx, const float *d_x, int64_t n, int first, float *d_range2, float *d_scale);
+
 /* ---- quantization-aware training: fake quantization (src/quantization/fake_quantize.rs, csrc/fake_quant.hip) ---- */
 /* A weight list through the storage codecs and back: TH_QTYPE_INT8 is th_quantize_int8 + th_dequantize_int8 (finite min / max ->
  * d_params = {min_val, scale}, written on the device; nullable), TH_QTYPE_F16 the half codec both ways -- bit for bit.  d_y must not

@@ -40,6 +40,10 @@ int th_debug_set_conv_img(th_ctx *ctx, int mode);
  * (1 / 2 / 4 / 8), k positions per slice, slices (grid.y; > 1: a combine launch follows), grid.x, slices asked for, k steps of a wave over
  * a whole row}. */
 int th_debug_qlinear_plan(int qtype, int batch, int in_features, int out_features, int x_misalign_bytes, int w_misalign_bytes, int *out8);
+/* what th_linear_q8q8_fwd would do with this shape -- pure host code, the function the launch itself consumes: out4 = {1 if the few-rows
+ * form takes it (a workgroup per 32 x 32 tile, K split over its four waves; 0: the 128 x 128 form through LDS), tile rows, tile columns,
+ * workgroups} */
+int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4);
 
 /* post-mortem of the in-launch exchange (csrc/dp_dev.h) on stderr: the communicator's state words and, per parity and source block of the
  * receive region, the slots that hold words.  Trainer::check_comm calls it under TAPER_DP_POSTMORTEM=1 when a time-out is reported. */

@@ -151,10 +151,21 @@ int tp_module_set_training(tp_module *m, int on);
  * Sigmoid have twins; any other module (Dropout) fails with "Quantization not implemented for this module type" (nn.rs:15) before
  * anything is allocated.  The codes are made on the device; the source model is not touched and can keep training. */
 int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **out);
+/* Static int8 quantization: weights and biases packed exactly as tp_module_quantize(m, 0, 1) packs them (tp_qmodule_tensor returns the same
+ * bits), and every Linear additionally given ONE activation scale: the calibration tensors run through the plain float layers (a QAT layer:
+ * its inner layer) and the finite min / max of each Linear's float input over all of them give max(|min|, |max|) / 127 (all zero ->
+ * (0, 1), all equal to m -> (0.9 m, 1.1 m)), on the device.  A Linear's forward then quantizes its input with that scale and multiplies
+ * int8 by int8 on the integer matrix cores with exact int32 sums (include/taper_hip.h, th_linear_q8q8_fwd), two launches at every batch
+ * size; everything else runs as in the weight-only twin.  Refused before anything is allocated: a module tp_module_quantize refuses (same
+ * message), n_calib < 1, a null calibration tensor, a Linear with in_features > 65 536.  The source model is only read; no tape node stays. */
+int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
+/* the calibrated activation scales in layer order: *n = their count (0 for a weight-only twin), the first min(*n, cap) into h_scales (nullable) */
+int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n);
 int tp_qmodule_free(tp_qmodule *q);
 /* QuantizedModule::forward: records no tape node; the output does not require a gradient */
 int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out);
-/* code bytes of every tensor, plus 8 bytes of {min_val, scale} per int8 tensor */
+/* code bytes of every tensor (a static twin's Linear weights with their row padding), plus 8 bytes of {min_val, scale} per int8 tensor and
+ * 4 bytes per activation scale */
 int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out);
 /* the packed tensors in the order of the source's parameters(): length, then codes (n int8 or n uint16; h_codes nullable),
  * {min_val, scale} (int8; {0, 0} for Float16; nullable) and the qtype (nullable) */

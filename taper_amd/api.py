@@ -318,6 +318,16 @@ class Module:
         tp_check(host.tp_module_quantize(self._h, code, 1 if enabled else 0, C.byref(h)), "Module::quantize")
         return QuantizedModule(h.value)
 
+    def quantize_static(self, calib):
+        """Static int8 post-training quantization -> QuantizedModule: the weights packed as quantize("int8") packs them, and one activation
+        scale per Linear from the float model's activations on `calib` (a Tensor or a sequence of them).  Linear layers then run
+        int8 x int8 on the integer matrix cores at every batch size; this model is only read."""
+        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
+        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
+        h = _p()
+        tp_check(host.tp_module_quantize_static(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static")
+        return QuantizedModule(h.value)
+
 
 class QuantizedModule:
     """nn.rs:20-23: forward from the packed codes (no tape node, the output needs no gradient)"""
@@ -342,6 +352,15 @@ class QuantizedModule:
         n = C.c_size_t()
         tp_check(host.tp_qmodule_storage_bytes(self._h, C.byref(n)), "QuantizedModule::storage_bytes")
         return n.value
+
+    def act_scales(self) -> np.ndarray:
+        """the calibrated activation scale of every Linear of a quantize_static twin, in layer order (empty for a weight-only twin)"""
+        n = C.c_int()
+        tp_check(host.tp_qmodule_act_scales(self._h, None, 0, C.byref(n)), "QuantizedModule::act_scales")
+        out = np.zeros(n.value, np.float32)
+        if n.value:
+            tp_check(host.tp_qmodule_act_scales(self._h, out.ctypes.data, n.value, C.byref(n)), "QuantizedModule::act_scales")
+        return out
 
     def tensors(self):
         """[(qtype, codes, (min_val, scale))] in parameter order: codes int8 with its pair for "int8", uint16 half bits and

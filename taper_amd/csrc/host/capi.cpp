@@ -15,7 +15,7 @@ struct tp_loader { std::unique_ptr<DataLoader> l; };
 struct tp_trainer { std::unique_ptr<Trainer> t; };
 struct tp_comm { std::shared_ptr<Communicator> c; };
 struct tp_sched { std::shared_ptr<LRScheduler> s; };
-struct tp_qmodule { std::unique_ptr<QuantizedModule> q; std::vector<const QTensor *> tensors; };
+struct tp_qmodule { std::unique_ptr<QuantizedModule> q; std::vector<const QTensor *> tensors; std::vector<const float *> act_scales; };
 struct tp_observer { std::unique_ptr<MinMaxObserver> minmax; std::unique_ptr<HistogramObserver> hist; };   // one of the two, by kind
 struct tp_observer_manager { ObserverManager m; };
 
@@ -286,6 +286,26 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
     *out = h.release();
     TP_END
 }
+int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
+    TP_BEGIN
+    TAPER_ASSERT(m && out, "tp_module_quantize_static: null argument");
+    std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
+    for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
+    auto h = std::make_unique<tp_qmodule>();
+    h->q = quantize_static(*m->m, c);
+    h->q->tensors(&h->tensors);
+    h->q->act_scales(&h->act_scales);
+    *out = h.release();
+    TP_END
+}
+int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n) {
+    TP_BEGIN
+    TAPER_ASSERT(q && n, "tp_qmodule_act_scales: null argument");
+    *n = (int)q->act_scales.size();
+    for (int i = 0; h_scales && i < *n && i < cap; ++i)
+        taper::th_check(th_memcpy_d2h(Device::ctx(), h_scales + i, q->act_scales[i], sizeof(float)), "th_memcpy_d2h");
+    TP_END
+}
 int tp_qmodule_free(tp_qmodule *q) { TP_BEGIN delete q; TP_END }
 int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out) {
     TP_BEGIN
@@ -298,7 +318,7 @@ int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out) {
     TP_BEGIN
     size_t s = 0;
     for (const QTensor *t : q->tensors) s += t->storage_bytes();
-    *out = s;
+    *out = s + q->act_scales.size() * sizeof(float);
     TP_END
 }
 int tp_qmodule_num_tensors(const tp_qmodule *q, int *out) { TP_BEGIN *out = (int)q->tensors.size(); TP_END }
@@ -313,7 +333,14 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
     TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor: index out of range");
     const QTensor &t = *q->tensors[i];
     th_ctx *ctx = Device::ctx();
-    if (h_codes && t.n) taper::th_check(th_memcpy_d2h(ctx, h_codes, t.codes->d, t.qtype == TH_QTYPE_INT8 ? t.n : 2 * t.n), "th_memcpy_d2h");
+    if (h_codes && t.n && t.pitch) {   // a padded matrix: the rows without their padding
+        const size_t rows = t.shape[0], k = t.shape[1];
+        std::vector<char> padded(rows * t.pitch);
+        taper::th_check(th_memcpy_d2h(ctx, padded.data(), t.codes->d, padded.size()), "th_memcpy_d2h");
+        for (size_t r = 0; r < rows; ++r) std::copy_n(padded.data() + r * t.pitch, k, (char *)h_codes + r * k);
+    } else if (h_codes && t.n) {
+        taper::th_check(th_memcpy_d2h(ctx, h_codes, t.codes->d, t.qtype == TH_QTYPE_INT8 ? t.n : 2 * t.n), "th_memcpy_d2h");
+    }
     if (h_params) {
         h_params[0] = h_params[1] = 0.f;
         if (t.params) taper::th_check(th_memcpy_d2h(ctx, h_params, t.params->d, 2 * sizeof(float)), "th_memcpy_d2h");

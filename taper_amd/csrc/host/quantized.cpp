@@ -39,8 +39,17 @@ class QPass : public QuantizedModule {
 
 class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
    public:
-    QLinear(const Linear &l, int qtype) : w_(quantize_tensor(l.weight, qtype)), k_(l.weight.shape()[1]), n_(l.weight.shape()[0]) {
+    // stat: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
+    // activation scale on the device that calibration fixes
+    QLinear(const Linear &l, int qtype, bool stat = false) : w_(quantize_tensor(l.weight, qtype)), k_(l.weight.shape()[1]), n_(l.weight.shape()[0]) {
         if (l.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(l.bias, qtype));
+        if (!stat) return;
+        const size_t step = (size_t)th_qlinear_i8_kstep();
+        w_.pitch = (k_ + step - 1) / step * step;
+        auto padded = Buffer::alloc(n_ * w_.pitch / 4);
+        TH(th_pad_rows_int8(Device::ctx(), reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, (int)k_, reinterpret_cast<int8_t *>(padded->d), (int)w_.pitch));
+        w_.codes = padded;     // (the packed copy goes back to the pool: stream order keeps it alive for the launch above)
+        act_ = Buffer::alloc(3);   // {finite min, finite max} of the calibration inputs, then the scale
     }
     Tensor forward(const Tensor &x) const override { return forward_relu(x, false); }
     // x . deq(W)^T + deq(b), and the ReLU behind it in the same launch when the Sequential twin pairs them
@@ -49,7 +58,14 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         const size_t batch = x.shape()[0];
         Tensor y = Tensor::empty({batch, n_});
         th_ctx *ctx = Device::ctx();
-        if (w_.qtype == TH_QTYPE_INT8)
+        if (act_) {   // int8 codes of x and their row sums (pooled, returned when this scope ends), then the integer product
+            const size_t pitch = (k_ + 15) / 16 * 16;
+            auto qx = Buffer::alloc(batch * pitch / 4), rs = Buffer::alloc(batch);
+            TH(th_quantize_act_int8(ctx, x.dptr(), (int)batch, (int)k_, act_->d + 2, reinterpret_cast<int8_t *>(qx->d), (int)pitch, reinterpret_cast<int *>(rs->d)));
+            TH(th_linear_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)pitch, reinterpret_cast<const int *>(rs->d), act_->d + 2, (int)batch, (int)k_,
+                                  reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d,
+                                  b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu ? 1 : 0, y.dptr()));
+        } else if (w_.qtype == TH_QTYPE_INT8)
             TH(th_linear_q8_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, w_.params->d,
                                 b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu ? 1 : 0, y.dptr()));
         else
@@ -61,11 +77,17 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         out->push_back(&w_);
         if (b_) out->push_back(b_.get());
     }
+    void act_scales(std::vector<const float *> *out) const override {
+        if (act_) out->push_back(act_->d + 2);
+    }
+    // calibration: the finite min / max of one more float input of this layer, and the scale of the range so far
+    void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, act_->d, act_->d + 2)); }
 
    private:
     QTensor w_;
     std::unique_ptr<QTensor> b_;
     size_t k_, n_;
+    std::shared_ptr<Buffer> act_;
 };
 
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
@@ -153,6 +175,9 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     void tensors(std::vector<const QTensor *> *out) const override {
         for (const auto &l : layers) l->tensors(out);
     }
+    void act_scales(std::vector<const float *> *out) const override {
+        for (const auto &l : layers) l->act_scales(out);
+    }
 };
 
 // nn.rs:15: every module without a quantize() of its own (Dropout among them) panics
@@ -174,22 +199,55 @@ std::shared_ptr<Module> copy_of(const Module &m) {
     return p ? std::make_shared<M>(*p) : nullptr;
 }
 
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype) {
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto q = std::make_unique<QSequential>();
-        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype));
+        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat));
         return q;
     }
-    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype);
+    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat);
     if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype);
     // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
-    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype);
+    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype, stat);
     if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
         !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))
         throw Error("Quantization not implemented for this module type");
     return std::make_unique<QPass>(p);
+}
+
+// the Linear layers of a model as quantize_checked meets them (a QAT layer: its inner layer)
+void linears_of(const Module &m, std::vector<const Linear *> *out) {
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        for (const auto &l : s->layers) linears_of(*l, out);
+    } else if (auto *l = dynamic_cast<const Linear *>(&m)) {
+        out->push_back(l);
+    } else if (auto *ql = dynamic_cast<const QATLinear *>(&m)) {
+        out->push_back(&ql->inner);
+    }
+}
+
+// One calibration tensor through the plain float layers of `m` (a QAT layer: its inner layer, whatever the QAT switch says), every
+// Linear twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
+Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first) {
+    auto plain = [](const Tensor &t) { return t.defined() ? Tensor::from_device(t.dptr(), t.shape()) : Tensor(); };
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        auto &qs = dynamic_cast<const QSequential &>(q);
+        Tensor h = x;
+        for (size_t i = 0; i < s->layers.size(); ++i) h = calibrate(*s->layers[i], *qs.layers[i], h, first);
+        return h;
+    }
+    const Linear *lin = dynamic_cast<const Linear *>(&m);
+    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) lin = &ql->inner;
+    if (lin) {
+        dynamic_cast<const QLinear &>(q).observe(x, first);
+        return x.linear(plain(lin->weight), plain(lin->bias), false);
+    }
+    const Conv2d *cv = dynamic_cast<const Conv2d *>(&m);
+    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) cv = &qc->inner;
+    if (cv) return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
+    return m.forward(x);
 }
 
 }  // namespace
@@ -212,6 +270,25 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
         }
     }
     return quantize_checked(m, qt);
+}
+
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib) {
+    // every refusal before anything is allocated
+    check_quantizable(m);
+    TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
+    for (const Tensor &c : calib) TAPER_ASSERT(c.defined(), "quantize_static: undefined calibration tensor");
+    std::vector<const Linear *> lins;
+    linears_of(m, &lins);
+    for (const Linear *l : lins)
+        TAPER_ASSERT(l->weight.shape()[1] <= 65536, "quantize_static: a Linear with in_features " + std::to_string(l->weight.shape()[1]) +
+                                                        " is above 65536, where the int32 sum of the int8 product can overflow");
+    auto q = quantize_checked(m, TH_QTYPE_INT8, true);
+    NoGradScope no_grad;
+    for (size_t i = 0; i < calib.size(); ++i) {
+        Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)
+        calibrate(m, *q, x, i == 0);
+    }
+    return q;
 }
 
 }  // namespace taper

@@ -482,7 +482,8 @@ struct QTensor {   // a QuantizedTensor (tensor.rs:2084-2108) on the device: cod
     size_t n = 0;
     Shape shape;
     std::shared_ptr<Buffer> codes, params;
-    size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? n + 2 * sizeof(float) : 2 * n; }
+    size_t pitch = 0;   // > 0: an int8 matrix whose rows of shape[1] codes lie `pitch` bytes apart, zero-padded (a static twin's Linear weight)
+    size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? (pitch ? shape[0] * pitch : n) + 2 * sizeof(float) : 2 * n; }
     th_qtensor item(float *d_out) const;
 };
 
@@ -491,8 +492,15 @@ class QuantizedModule {
     virtual ~QuantizedModule() = default;
     virtual Tensor forward(const Tensor &input) const = 0;
     virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
+    virtual void act_scales(std::vector<const float *> *out) const {}  // device addresses of the calibrated activation scales, in layer order
 };
 std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled);
+// Static int8 post-training quantization: weights and biases packed exactly as quantize(m, Int8) packs them, and every Linear given one
+// activation scale from the finite min / max of its FLOAT input over the calibration tensors (th_fake_quant_act's rule).  Its forward
+// quantizes the input with that scale and runs int8 x int8 on the integer matrix cores (th_linear_q8q8_fwd) at every batch size; conv
+// stages and the parameter-free layers run as in the weight-only twin.  Refusals (an unquantizable module, no or an undefined calibration
+// tensor, in_features above 65 536) come before anything is allocated; the source model is only read and no tape node is recorded.
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib);
 
 // ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
 // A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the

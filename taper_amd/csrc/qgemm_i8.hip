@@ -1,0 +1,379 @@
+// qgemm_i8.hip -- calibrated int8 inference: int8 activation codes times int8 weight codes on the integer matrix cores
+// (v_mfma_i32_32x32x32_i8), exact int32 accumulation, one f32 epilogue.
+//
+//   th_quantize_act_int8  f32 [rows, k] -> symmetric int8 codes [rows, pitch] (th_fake_quant_act's codec with a scale fixed beforehand)
+//                         and the int32 sum of each row's codes; one launch, a wave per row
+//   th_pad_rows_int8      packed [rows, k] codes -> [rows, pitch] with zero padding (once per weight)
+//   th_linear_q8q8_fwd    y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU], acc = sum_k qx qw from the MFMA;
+//                         two forms: 128 x 128 tiles through LDS, and a workgroup per 32 x 32 tile with K split over its waves for few rows
+//   th_act_range_update   calibration: the finite min / max of a tensor folded into a running device pair, and the scale they give
+//
+// The weight codec is affine with zero_point -128: w = (qw + 128) sw + mw, so x . w = sx (sw (acc + 128 rs) + mw rs) with rs the sum of
+// the row's activation codes -- every integer term is exact, and the four f32 operations round once each.  A row's result depends on
+// that row alone: nothing of the tiling reaches the arithmetic.
+#include "common.h"
+#include "quant_dev.h"
+#include "stream_dev.h"
+
+namespace th {
+
+typedef int intx4 __attribute__((ext_vector_type(4)));
+typedef int intx16 __attribute__((ext_vector_type(16)));
+
+constexpr int kQ8Tile = 128;       // macro-tile: 128 rows of x by 128 rows of W, four waves of 2 x 2 MFMA tiles
+constexpr int kQ8KStep = 64;       // bytes of K per LDS stage: two 32-k MFMA steps
+constexpr int kQ8MaxK = 65536;     // |acc + 128 rs| <= 128 * 255 * K stays below 2^31
+constexpr int kQ8Raster = 8;       // tile rows per group of the tile order (gemm.hip's sgemm_tile)
+constexpr int kQ8SkinnyMaxBatch = 256;   // up to here a workgroup per 32 x 32 tile with K split over its waves (measured: profiles/quant_static.md)
+
+__device__ __forceinline__ int act_code(float v, float scale) {
+    const int q = rust_f32_as_i32(roundf(v / scale));
+    return q < -128 ? -128 : (q > 127 ? 127 : q);
+}
+
+// ---- activations -> codes ----
+// A wave per row, four rows per workgroup; a lane takes 16 k positions at a time: four float4 loads, one 16-byte store.  Positions
+// k .. pitch - 1 get the code 0.  VEC: x rows and code rows are 16-byte aligned (the host says).
+template <bool VEC>
+__global__ __launch_bounds__(256) void quantize_act_kernel(const float *__restrict__ x, int rows, int k, const float *__restrict__ d_scale,
+                                                           int8_t *__restrict__ q, int pitch, int *__restrict__ rowsum) {
+    const int lane = threadIdx.x & 63;
+    const float scale = d_scale[0];
+    for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (long)gridDim.x * 4) {
+        const float *xr = x + (size_t)row * k;
+        int8_t *qr = q + (size_t)row * pitch;
+        int sum = 0;
+        for (int k0 = lane * 16; k0 < pitch; k0 += 64 * 16) {
+            uint32_t w[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int kk = k0 + 4 * i;
+                float v[4];
+                if (VEC && kk + 4 <= k) {
+                    const float4 f = *(const float4 *)(xr + kk);
+                    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = kk + j < k ? xr[kk + j] : 0.f;
+                }
+                uint32_t word = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c = kk + j < k ? act_code(v[j], scale) : 0;
+                    sum += c;
+                    word |= (uint32_t)(uint8_t)(int8_t)c << (8 * j);
+                }
+                w[i] = word;
+            }
+            if (VEC) {
+                *(uint4 *)(qr + k0) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) qr[k0 + i] = (int8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xFF);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);   // integers: any order gives the same bits
+        if (lane == 0) rowsum[row] = sum;
+    }
+}
+
+__global__ __launch_bounds__(256) void pad_rows_kernel(const int8_t *__restrict__ src, long rows, int k, int8_t *__restrict__ dst, int pitch) {
+    const int per_row = pitch / 16;
+    const long total = rows * per_row;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
+        const long row = c / per_row;
+        const int k0 = (int)(c - row * per_row) * 16;
+        const int8_t *s = src + (size_t)row * k;   // (packed rows are not 16-byte aligned in general: byte loads, once per weight)
+        uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (k0 + i < k) w[i >> 2] |= (uint32_t)(uint8_t)s[k0 + i] << (8 * (i & 3));
+        *(uint4 *)(dst + (size_t)row * pitch + k0) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// what the epilogue of either form needs
+struct Q8Epilogue {
+    const int *rowsum;
+    const float *xscale, *wparams;
+    const int8_t *qb;
+    const float *bparams;
+    int relu, M, N;
+    float *y;
+};
+
+// One 32 x 32 accumulator tile out: this lane holds column n (a row of W) of rows row_base + (e & 3) + 8 (e >> 2) (row_base includes the
+// lane half's 4 h).  y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU], each operation rounded once.
+__device__ __forceinline__ void store_tile(const intx16 &acc, int row_base, int n, const Q8Epilogue &ep) {
+    if (n >= ep.N) return;
+    const float sx = ep.xscale[0], mw = ep.wparams[0], sw = ep.wparams[1];
+    const float bias = ep.qb ? dequant_int8(ep.qb[n], ep.bparams[1], ep.bparams[0]) : 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int row = row_base + (e & 3) + 8 * (e >> 2);
+        if (row >= ep.M) continue;
+        const int rs = ep.rowsum[row], t = acc[e] + 128 * rs;
+        float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)t), __fmul_rn(mw, (float)rs)));
+        if (ep.qb) v = __fadd_rn(v, bias);
+        ep.y[(size_t)row * ep.N + n] = ep.relu ? (v > 0.f ? v : 0.f) : v;
+    }
+}
+
+// ---- the product ----
+// LDS image of an operand stage: 128 rows of 64 bytes, the 16-byte piece c of row r at slot c ^ ((r >> 2) & 3) -- the 16 lanes a
+// ds_read_b128 serves together (rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one piece) then land on 16 different slots.
+// Fragments: lane l (r = l & 31, h = l >> 5) holds 16 consecutive codes of row r of its operand, piece 2 s + h of the stage in MFMA
+// step s -- for BOTH operands, so that whatever order the instruction gives the 16 codes of a lane, a code of x meets the code of W at
+// the same k.  C/D: column = lane & 31 (a row of W), row = (reg & 3) + 8 (reg >> 2) + 4 h (a row of x).
+__device__ __forceinline__ int lds_slot(int row, int piece) { return row * 4 + (piece ^ ((row >> 2) & 3)); }
+
+__global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict__ qx, int pitch_x, int K, const int8_t *__restrict__ qw, int pitch_w,
+                                                       Q8Epilogue ep, int tiles_m, int tiles_n) {
+    const int M = ep.M, N = ep.N;
+    __shared__ uint4 lds[2][2][kQ8Tile * 4];   // [stage][x / W][slot]: 32 KB
+
+    // tile order: block b runs on XCD b % 8; every XCD takes a contiguous run of the tile list, and the list walks groups of 8 tile rows
+    // column by column, so the tiles an XCD has in flight share their operand panels in its L2 (gemm.hip, sgemm_tile)
+    const int nwg = tiles_m * tiles_n, bid = blockIdx.x;
+    const int xcd = bid % kNumXCD, per = nwg / kNumXCD, rmd = nwg % kNumXCD;
+    const int tile = (xcd < rmd ? xcd * (per + 1) : rmd * (per + 1) + (xcd - rmd) * per) + bid / kNumXCD;
+    const int grp = tile / (kQ8Raster * tiles_n), first = grp * kQ8Raster, gh = min(kQ8Raster, tiles_m - first), in = tile - grp * kQ8Raster * tiles_n;
+    const int row0 = (first + in % gh) * kQ8Tile, col0 = (in / gh) * kQ8Tile;
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, li = lane & 31, h = lane >> 5;
+
+    // staging: thread t brings piece t & 3 of rows (t >> 2) and (t >> 2) + 64 of each operand; rows past M / N re-read the last row (never
+    // stored), pieces that begin at or past K are zero (pitch >= K rounded up to 16: every piece that is read lies inside its row)
+    const int srow = t >> 2, piece = t & 3, pieces = (K + 15) >> 4;
+    const int8_t *pa[2], *pb[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        pa[i] = qx + (size_t)min(row0 + srow + 64 * i, M - 1) * pitch_x + piece * 16;
+        pb[i] = qw + (size_t)min(col0 + srow + 64 * i, N - 1) * pitch_w + piece * 16;
+    }
+    const int nk = (K + kQ8KStep - 1) / kQ8KStep;
+    uint4 ga[2], gb[2];
+    auto fetch = [&](int kt) {
+        const bool in_k = kt * 4 + piece < pieces;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            ga[i] = in_k ? *(const uint4 *)(pa[i] + (size_t)kt * kQ8KStep) : make_uint4(0, 0, 0, 0);
+            gb[i] = in_k ? *(const uint4 *)(pb[i] + (size_t)kt * kQ8KStep) : make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            lds[buf][0][lds_slot(srow + 64 * i, piece)] = ga[i];
+            lds[buf][1][lds_slot(srow + 64 * i, piece)] = gb[i];
+        }
+    };
+
+    intx16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0;
+
+    fetch(0);
+    stage(0);
+    lds_barrier();
+    int buf = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) fetch(kt + 1);   // in flight under this stage's MFMAs
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            intx4 a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const uint4 va = lds[buf][0][lds_slot(wm + 32 * i + li, 2 * s + h)], vb = lds[buf][1][lds_slot(wn + 32 * i + li, 2 * s + h)];
+                a[i] = intx4{(int)va.x, (int)va.y, (int)va.z, (int)va.w};
+                b[i] = intx4{(int)vb.x, (int)vb.y, (int)vb.z, (int)vb.w};
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        if (kt + 1 < nk) stage(buf ^ 1);   // (read last in step kt - 1: every wave passed that step's barrier)
+        lds_barrier();
+        buf ^= 1;
+    }
+
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) store_tile(acc[i][j], row0 + wm + 32 * i + 4 * h, col0 + wn + 32 * j + li, ep);
+}
+
+// Few rows (batch <= kQ8SkinnyMaxBatch): the 128 x 128 form would leave most CUs idle and walk K in one long chain of dependent
+// stages.  Here a workgroup owns ONE 32 x 32 tile and its four waves split K: wave v takes the 64-byte chunks v, v + 4, ... of both
+// operands straight from memory into its fragments (a lane's two 16-byte loads per row are 32 consecutive bytes; no LDS staging, no
+// barrier inside the loop, so the loads of several chunks are in flight at once), and the four int32 partial tiles are added through LDS
+// -- integers: the order does not matter -- before the same epilogue.  ceil(N / 32) * ceil(M / 32) workgroups.
+__global__ __launch_bounds__(256) void qgemm_i8_skinny_kernel(const int8_t *__restrict__ qx, int pitch_x, int K, const int8_t *__restrict__ qw,
+                                                              int pitch_w, Q8Epilogue ep, int tiles_m) {
+    __shared__ int red[3][16][64];   // 12 KB
+    // block b runs on XCD b % 8: every XCD takes a contiguous run of the tile list, row tiles fastest, so the row tiles of one W panel
+    // read it through one L2
+    const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % kNumXCD, per = nwg / kNumXCD, rmd = nwg % kNumXCD;
+    const int tile = (xcd < rmd ? xcd * (per + 1) : rmd * (per + 1) + (xcd - rmd) * per) + bid / kNumXCD;
+    const int row0 = (tile % tiles_m) * 32, col0 = (tile / tiles_m) * 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, h = lane >> 5;
+    const int8_t *pa = qx + (size_t)min(row0 + li, ep.M - 1) * pitch_x + h * 16;
+    const int8_t *pb = qw + (size_t)min(col0 + li, ep.N - 1) * pitch_w + h * 16;
+    const int pieces = (K + 15) >> 4, nk = (K + kQ8KStep - 1) / kQ8KStep;   // 16-byte pieces that begin before K; 64-byte chunks
+    intx16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0;
+    for (int kt0 = wave; kt0 < nk; kt0 += 16) {   // four chunks a trip, their sixteen loads issued before the first MFMA (a chunk past K loads nothing)
+        uint4 va[4][2], vb[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const int kt = kt0 + 4 * u;
+                const bool in_k = kt * 4 + 2 * s + h < pieces;
+                va[u][s] = in_k ? *(const uint4 *)(pa + (size_t)kt * kQ8KStep + 32 * s) : make_uint4(0, 0, 0, 0);
+                vb[u][s] = in_k ? *(const uint4 *)(pb + (size_t)kt * kQ8KStep + 32 * s) : make_uint4(0, 0, 0, 0);
+            }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(intx4{(int)va[u][s].x, (int)va[u][s].y, (int)va[u][s].z, (int)va[u][s].w},
+                                                            intx4{(int)vb[u][s].x, (int)vb[u][s].y, (int)vb[u][s].z, (int)vb[u][s].w}, acc, 0, 0, 0);
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) red[wave - 1][e][lane] = acc[e];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] += red[0][e][lane] + red[1][e][lane] + red[2][e][lane];
+    store_tile(acc, row0 + 4 * h, col0 + li, ep);
+}
+
+// ---- calibration ----
+// range = {finite min, finite max} seen so far (first: this tensor's alone); scale by fq_act_int8_kernel's rule from the running pair
+__global__ __launch_bounds__(kStreamThreads) void act_range_fold_kernel(const float *__restrict__ part, int nb, int first, float *__restrict__ range,
+                                                                        float *__restrict__ d_scale) {
+    __shared__ float s[8];
+    float mn, mx;
+    fold_parts(part, nb, &mn, &mx, s);
+    if (threadIdx.x != 0) return;
+    if (!first) {
+        mn = fminf(mn, range[0]);
+        mx = fmaxf(mx, range[1]);
+    }
+    range[0] = mn;
+    range[1] = mx;
+    if (mn == mx) {
+        if (mn == 0.0f) {
+            mn = 0.0f;
+            mx = 1.0f;
+        } else {
+            const float m = mn;
+            mn = m * 0.9f;
+            mx = m * 1.1f;
+        }
+    }
+    d_scale[0] = fmaxf(fabsf(mn), fabsf(mx)) / 127.0f;
+}
+
+// every host decision of the product (th_linear_q8q8_fwd launches from it, th_debug_q8q8_plan reports it)
+struct Q8Plan {
+    int skinny, tiles_m, tiles_n, grid;
+};
+static Q8Plan q8q8_plan(int B, int N) {
+    Q8Plan p{};
+    p.skinny = B <= kQ8SkinnyMaxBatch;
+    const int ts = p.skinny ? 32 : kQ8Tile;
+    p.tiles_m = ceil_div(B, ts);
+    p.tiles_n = ceil_div(N, ts);
+    p.grid = p.tiles_m * p.tiles_n;
+    return p;
+}
+
+constexpr int kRangeParts = 512;
+constexpr int64_t kRangePartMin = 4 * 256 * 8;
+
+}  // namespace th
+
+using namespace th;
+
+extern "C" {
+
+int th_quantize_act_int8(th_ctx *ctx, const float *d_x, int rows, int k, const float *d_scale, int8_t *d_q, int pitch, int *d_rowsum) {
+    TH_REQUIRE(ctx && d_x && d_scale && d_q && d_rowsum, "th_quantize_act_int8: null argument");
+    TH_REQUIRE(rows >= 0 && k > 0 && pitch >= k && pitch % 16 == 0, "th_quantize_act_int8: bad shape rows=%d k=%d pitch=%d (pitch >= k, a multiple of 16)",
+               rows, k, pitch);
+    if (rows == 0) return 0;
+    const dim3 grid(std::min(ceil_div(rows, 4), kNumCU * 16));
+    if (k % 4 == 0 && (((uintptr_t)d_x | (uintptr_t)d_q) & 15) == 0)
+        hipLaunchKernelGGL(quantize_act_kernel<true>, grid, dim3(256), 0, ctx->stream, d_x, rows, k, d_scale, d_q, pitch, d_rowsum);
+    else
+        hipLaunchKernelGGL(quantize_act_kernel<false>, grid, dim3(256), 0, ctx->stream, d_x, rows, k, d_scale, d_q, pitch, d_rowsum);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_pad_rows_int8(th_ctx *ctx, const int8_t *d_src, int rows, int k, int8_t *d_dst, int pitch) {
+    TH_REQUIRE(ctx && d_src && d_dst, "th_pad_rows_int8: null argument");
+    TH_REQUIRE(rows >= 0 && k > 0 && pitch >= k && pitch % 16 == 0 && ((uintptr_t)d_dst & 15) == 0,
+               "th_pad_rows_int8: bad shape rows=%d k=%d pitch=%d (pitch >= k, a multiple of 16) or a destination off a 16-byte boundary", rows, k, pitch);
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(pad_rows_kernel, dim3(ew_grid((size_t)rows * (pitch / 16), 256)), dim3(256), 0, ctx->stream, d_src, (long)rows, k, d_dst, pitch);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                       const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams, int relu,
+                       float *d_y) {
+    TH_REQUIRE(ctx && d_qx && d_rowsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "th_linear_q8q8_fwd: null argument");
+    TH_REQUIRE(batch >= 0 && in_features > 0 && out_features > 0, "th_linear_q8q8_fwd: bad shape B=%d K=%d N=%d", batch, in_features, out_features);
+    TH_REQUIRE(in_features <= kQ8MaxK, "th_linear_q8q8_fwd: in_features %d is above %d, where the int32 sum can overflow", in_features, kQ8MaxK);
+    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "th_linear_q8q8_fwd: the code pointers must be 16-byte aligned");
+    TH_REQUIRE(pitch_x % 16 == 0 && pitch_w % 16 == 0 && pitch_x >= in_features && pitch_w >= in_features,
+               "th_linear_q8q8_fwd: pitches %d / %d must be multiples of 16 and at least in_features %d", pitch_x, pitch_w, in_features);
+    if (batch == 0) return 0;
+    const Q8Plan p = q8q8_plan(batch, out_features);
+    const Q8Epilogue ep{d_rowsum, d_xscale, d_wparams, d_qb, d_bparams, relu, batch, out_features, d_y};
+    if (p.skinny)
+        hipLaunchKernelGGL(qgemm_i8_skinny_kernel, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw, pitch_w, ep, p.tiles_m);
+    else
+        hipLaunchKernelGGL(qgemm_i8_kernel, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw, pitch_w, ep, p.tiles_m, p.tiles_n);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4) {
+    TH_REQUIRE(out4 && batch >= 1 && in_features > 0 && in_features <= kQ8MaxK && out_features > 0, "th_debug_q8q8_plan: null argument or bad shape B=%d K=%d N=%d",
+               batch, in_features, out_features);
+    const Q8Plan p = q8q8_plan(batch, out_features);
+    const int out[4] = {p.skinny, p.tiles_m, p.tiles_n, p.grid};
+    std::copy(out, out + 4, out4);
+    return 0;
+}
+
+int th_qlinear_i8_kstep(void) { return kQ8KStep; }
+
+int th_act_range_update(th_ctx *ctx, const float *d_x, int64_t n, int first, float *d_range2, float *d_scale) {
+    TH_REQUIRE(ctx && n >= 0 && (n == 0 || d_x) && d_range2 && d_scale, "th_act_range_update: null argument");
+    const int nb = std::max(n <= 0 ? 0 : stream_grid(n, kRangePartMin, kRangeParts), 1);
+    void *part = nullptr;
+    if (th_malloc(ctx, (size_t)nb * 2 * sizeof(float), &part)) return 1;
+    hipLaunchKernelGGL((minmax_parts_kernel<MinMaxFinite, true>), dim3(nb), dim3(kStreamThreads), 0, ctx->stream, d_x, d_x, n, (float *)part);
+    TH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(act_range_fold_kernel, dim3(1), dim3(kStreamThreads), 0, ctx->stream, (const float *)part, nb, first, d_range2, d_scale);
+    TH_LAUNCH_CHECK();
+    return th_free(ctx, part);
+}
+
+}  // extern "C"
