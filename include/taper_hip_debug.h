@@ -44,6 +44,13 @@ int th_debug_qlinear_plan(int qtype, int batch, int in_features, int out_feature
  * form takes it (a workgroup per 32 x 32 tile, K split over its four waves; 0: the 128 x 128 form through LDS), tile rows, tile columns,
  * workgroups} */
 int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4);
+/* what th_sgemm / th_linear_fwd (trans 0, 1) would do with this shape, layout and pointers (a / b / c: bytes off a 16-byte boundary: 0, 4,
+ * 8 or 12) under a plain epilogue -- pure host code, no context, the function gemm_dispatch itself launches from: out12 = {tile class (16 /
+ * 64 / 128), load form (0: 16 x 16 tiles straight from L2; 1: whole tiles by LDS-DMA; 2: LDS-DMA with the edge quads zeroed by the
+ * descriptor's range; 3: clamped float4 register loads; 4: scalar register loads), waves per workgroup, a_vec, b_vec (16-tiles: float4 loads
+ * of that operand; else both = 16-byte rows and whole quads), K slices, k positions per slice, workgroups, 1 if a split launch hands its
+ * slices to the XCDs one by one, reduce pass (0: none; 1: splitk_reduce4; 2: splitk_reduce), tile rows, tile columns}.  k == 0 is a shape. */
+int th_debug_sgemm_plan(int trans_a, int trans_b, int m, int n, int k, int a_misalign_bytes, int b_misalign_bytes, int c_misalign_bytes, int *out12);
 
 /* post-mortem of the in-launch exchange (csrc/dp_dev.h) on stderr: the communicator's state words and, per parity and source block of the
  * receive region, the slots that hold words.  Trainer::check_comm calls it under TAPER_DP_POSTMORTEM=1 when a time-out is reported. */

@@ -295,9 +295,11 @@ __global__ __launch_bounds__(256) void splitk_reduce(const float *__restrict__ p
 }
 
 static inline bool aligned16p(const void *p) { return ((uintptr_t)p & 15) == 0; }
-// the reduce pass: four elements per thread where every pointer and the slab stride allow 16-byte accesses
-static inline void launch_splitk_reduce(hipStream_t stream, const float *partial, float *C, long mn, int n, int kz, const Epilogue &ep) {
-    const bool quad = mn % 4 == 0 && aligned16p(partial) && aligned16p(C) && !ep.mask && !ep.colpart &&
+// what the output alone decides about the reduce pass: whole quads of a slab, C on a 16-byte boundary (c_bits: the pointer; its low 4 bits matter)
+static inline bool reduce_c_quad(long mn, uintptr_t c_bits) { return mn % 4 == 0 && (c_bits & 15) == 0; }
+// the reduce pass: four elements per thread where every pointer and the slab stride allow 16-byte accesses (c_quad: reduce_c_quad of this C)
+static inline void launch_splitk_reduce(hipStream_t stream, const float *partial, float *C, long mn, int n, int kz, const Epilogue &ep, bool c_quad) {
+    const bool quad = c_quad && aligned16p(partial) && !ep.mask && !ep.colpart &&
                       (!ep.adam.p || (aligned16p(ep.adam.p) && aligned16p(ep.adam.m) && aligned16p(ep.adam.v)));
     if (quad) hipLaunchKernelGGL(splitk_reduce4, dim3(ceil_div(mn / 4, 256)), dim3(256), 0, stream, partial, C, mn, n, kz, ep);
     else hipLaunchKernelGGL(splitk_reduce, dim3(ceil_div(mn, 256)), dim3(256), 0, stream, partial, C, mn, n, kz, ep);
@@ -899,43 +901,44 @@ __global__ __launch_bounds__(256, 2) void sgemm_tile(const float *__restrict__ A
 
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
+// Every host decision of a product with a plain epilogue (gemm_dispatch launches from it; th_debug_sgemm_plan reports it): the tile class,
+// the kernel instance inside it, the K slices, the grid, the workgroup-to-tile map and the reduce pass.  gemm_plan (below the thresholds it
+// applies) fills it from the shape, the layout and the low bits of the three pointers.
+enum GemmForm { kFormSmall = 0, kFormExactDma = 1, kFormRagDma = 2, kFormGuardVec = 3, kFormGuardScalar = 4 };
+enum GemmReduce { kReduceNone = 0, kReduceQuad = 1, kReduceScalar = 2 };
+struct GemmPlan {
+    int tile;            // 16 / 64 / 128
+    int form;            // GemmForm
+    int waves;           // per workgroup: 4 or 16 on 16-tiles, 4 on the others
+    int a_vec, b_vec;    // 16-tiles: float4 loads of that operand; 64 / 128-tiles: both = 16-byte rows and whole quads (`vec`)
+    int kz, kslice;      // K slices (grid.z on 16-tiles, grid.y on the others) and k positions per slice
+    int tiles_m, tiles_n;
+    int slice_xcd;       // 64 / 128-tiles, split: the slice-per-XCD map (raster | 0x100)
+    int reduce;          // GemmReduce: the pass behind a split product (quad: as far as C decides it -- reduce_c_quad)
+};
+static GemmPlan gemm_plan(int trans_a, int trans_b, int m, int n, int k, uintptr_t a_bits, uintptr_t b_bits, uintptr_t c_bits);
+
 template <bool A_KC, bool B_KC>
-static int launch_small(th_ctx *ctx, const float *A, const float *B, float *C, int m, int n, int k, long a_rs, long a_cs,
+static int launch_small(th_ctx *ctx, const GemmPlan &pl, const float *A, const float *B, float *C, int m, int n, int k, long a_rs, long a_cs,
                         long b_rs, long b_cs, const Epilogue &ep) {
-    const int tiles_m = ceil_div(m, 16), tiles_n = ceil_div(n, 16);
-    const long tiles = (long)tiles_m * tiles_n;
+    const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, kz = pl.kz;
     SmallArgs p{A, nullptr, B, C, nullptr, m, n, k, a_rs, a_cs, b_rs, b_cs, 0, 0, 0, ep};
-    // float4 operand loads need 16-B aligned rows and slice starts
-    p.a_vec = A_KC && aligned16(A) && (a_rs % 4 == 0);
-    p.b_vec = B_KC && aligned16(B) && (b_cs % 4 == 0);
-    // Deep K on a grid that cannot fill the chip: first widen the workgroup to
-    // 16 waves (in-LDS reduction, still one launch); only very deep K goes to a
-    // grid-level split with a second reduce pass.
-    int kz = 1;
-    const bool wide = tiles < 256 && k >= 256;
-    if (tiles < 64 && k >= 2048) {   // e.g. the simple CNN's Linear(3136, 10) at batch 256: 16 tiles
-        kz = (int)((256 + tiles - 1) / tiles);
-        const int kz_max = k / 512;
-        if (kz > kz_max) kz = kz_max;
-        if (kz < 1) kz = 1;
-    }
-    int kslice = ceil_div(k, kz);
-    kslice = (kslice + 15) / 16 * 16;
-    kz = ceil_div(k, kslice);
-    p.kslice = kslice;
+    p.a_vec = pl.a_vec;
+    p.b_vec = pl.b_vec;
+    p.kslice = pl.kslice;
     if (kz > 1) {
         void *ws = nullptr;
         if (th_malloc(ctx, (size_t)kz * m * n * sizeof(float), &ws)) return 1;
         p.partial = (float *)ws;
     }
-    if (wide)
+    if (pl.waves == 16)
         hipLaunchKernelGGL((sgemm_small16<A_KC, B_KC, 16>), dim3(tiles_n, tiles_m, kz), dim3(1024), 0, ctx->stream, p);
     else
         hipLaunchKernelGGL((sgemm_small16<A_KC, B_KC, 4>), dim3(tiles_n, tiles_m, kz), dim3(256), 0, ctx->stream, p);
     TH_LAUNCH_CHECK();
     if (kz > 1) {
         const long mn = (long)m * n;
-        launch_splitk_reduce(ctx->stream, (const float *)p.partial, C, mn, n, kz, ep);
+        launch_splitk_reduce(ctx->stream, (const float *)p.partial, C, mn, n, kz, ep, pl.reduce == kReduceQuad);
         TH_LAUNCH_CHECK();
         if (th_free(ctx, p.partial)) return 1;
     }
@@ -967,27 +970,17 @@ static inline int tile64_kz(int m, int n, int k) {
     return kz < 1 ? 1 : kz;
 }
 
-template <int TS, bool A_KC, bool B_KC>
-static inline bool rag_dma(int m, int n, int k, bool vec, long lda, long ldb) {
+static inline bool rag_dma(int ts, bool a_kc, bool b_kc, int k, bool vec, long lda, long ldb) {
     // (`vec`: 16-byte aligned rows and whole quads in or out of range along each operand's contiguous axis)
-    return TS == 128 && vec && ((A_KC || B_KC) ? k % 4 == 0 : k % BK == 0) && lda < (1L << 22) && ldb < (1L << 22);
+    return ts == 128 && vec && ((a_kc || b_kc) ? k % 4 == 0 : k % BK == 0) && lda < (1L << 22) && ldb < (1L << 22);
 }
 
 template <int TS, bool A_KC, bool B_KC>
-static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, int m, int n, int k, long a_rs,
+static int launch_tile(th_ctx *ctx, const GemmPlan &pl, const float *A, const float *B, float *C, int m, int n, int k, long a_rs,
                        long a_cs, long b_rs, long b_cs, const Epilogue &ep) {
-    const int tiles_m = ceil_div(m, TS), tiles_n = ceil_div(n, TS);
+    const int tiles_m = pl.tiles_m, tiles_n = pl.tiles_n, kz = pl.kz, kslice = pl.kslice;
     const size_t lds = 4 * TileGeo<TS>::TILE_MAX * sizeof(float);
-    const long lda = A_KC ? a_rs : a_cs, ldb = B_KC ? b_cs : b_rs;
-    int kz = TS == 128 ? tile128_kz(m, n, k) : tile64_kz(m, n, k);
-    int kslice = ceil_div(ceil_div(k, kz), BK) * BK;
-    kz = ceil_div(k, kslice);
-    // dwordx4 operand loads: 16-B aligned rows, and whole quads in or out of range along the vector axis
-    // (k for a k-contiguous operand, m / n for an m/n-contiguous one); slices start on multiples of 32
-    const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) && ((A_KC ? k : m) % 4 == 0) &&
-                     ((B_KC ? k : n) % 4 == 0) && m >= 4 && n >= 4 && k >= 4;
-    // whole tiles take the LDS-DMA kernel: its 32-bit lane offsets span a tile's rows (TS x leading dimension x 4 bytes < 2^31)
-    const bool exact = (m % TS == 0) && (n % TS == 0) && (k % BK == 0) && vec && lda < (1L << 22) && ldb < (1L << 22);
+    const bool vec = pl.a_vec != 0, exact = pl.form == kFormExactDma;
     float *partial = nullptr;
     if (kz > 1) {
         void *ws = nullptr;
@@ -1011,9 +1004,7 @@ static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, in
             return 0;
         }
     }
-    // K slices of at least this many 32-k chunks are handed to the XCDs slice by slice (sgemm_tile)
-    constexpr int kSliceXcdChunks = 14;
-    const int raster = kRasterRows + ((kz > 1 && kslice >= kSliceXcdChunks * BK) ? 0x100 : 0);
+    const int raster = kRasterRows + (pl.slice_xcd ? 0x100 : 0);
     if (ep.mask || ep.colpart) {     // the dX product with the backward of the layer in front in its epilogue (th_linear_bwd_adam_ex2: unsplit by its predicate)
         if (kz != 1) { th::set_error("sgemm_tile: the masked epilogue needs an unsplit product"); return 2; }
         if (exact) {
@@ -1032,7 +1023,7 @@ static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, in
         TH_SET_MAX_LDS(ctx, kern, lds);       // (per device: ADVICE r04)
         hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, kz), dim3(256), lds, ctx->stream, A, B, C, m, n, k, a_rs, a_cs,
                            b_rs, b_cs, tiles_m, tiles_n, kep, kslice, partial, 1, raster);
-    } else if (rag_dma<TS, A_KC, B_KC>(m, n, k, vec, lda, ldb)) {
+    } else if (pl.form == kFormRagDma) {
         if constexpr (TS == 128) {      // ragged edges: LDS-DMA with the edge quads zeroed by range, guarded stores
             auto kern = sgemm_tile<TS, A_KC, B_KC, false, false, false, true>;
             TH_SET_MAX_LDS(ctx, kern, lds);
@@ -1048,7 +1039,7 @@ static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, in
     TH_LAUNCH_CHECK();
     if (kz > 1) {
         const long mn = (long)m * n;
-        launch_splitk_reduce(ctx->stream, (const float *)partial, C, mn, n, kz, ep);
+        launch_splitk_reduce(ctx->stream, (const float *)partial, C, mn, n, kz, ep, pl.reduce == kReduceQuad);
         TH_LAUNCH_CHECK();
         if (th_free(ctx, partial)) return 1;
     } else if (ep.adam.p) {
@@ -1058,9 +1049,9 @@ static int launch_tile(th_ctx *ctx, const float *A, const float *B, float *C, in
 }
 
 template <bool A_KC, bool B_KC>
-static int launch_tile128(th_ctx *ctx, const float *A, const float *B, float *C, int m, int n, int k, long a_rs,
+static int launch_tile128(th_ctx *ctx, const GemmPlan &pl, const float *A, const float *B, float *C, int m, int n, int k, long a_rs,
                           long a_cs, long b_rs, long b_cs, const Epilogue &ep) {
-    return launch_tile<128, A_KC, B_KC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
+    return launch_tile<128, A_KC, B_KC>(ctx, pl, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
 }
 
 
@@ -1090,6 +1081,73 @@ static inline TileClass gemm_tile_class(int m, int n, int k) {
     return big ? TileClass::Tile128 : TileClass::Small;
 }
 
+// 16 x 16 tiles: float4 loads of a k-contiguous operand with 16-byte rows; wide workgroups and grid-level K slices for deep K on few tiles
+static void plan_small(GemmPlan &pl, int m, int n, int k, bool a_kc, bool b_kc, long a_rs, long b_cs, uintptr_t a_bits, uintptr_t b_bits) {
+    pl.tile = 16;
+    pl.form = kFormSmall;
+    pl.tiles_m = ceil_div(m, 16);
+    pl.tiles_n = ceil_div(n, 16);
+    const long tiles = (long)pl.tiles_m * pl.tiles_n;
+    // float4 operand loads need 16-B aligned rows and slice starts
+    pl.a_vec = a_kc && (a_bits & 15) == 0 && (a_rs % 4 == 0);
+    pl.b_vec = b_kc && (b_bits & 15) == 0 && (b_cs % 4 == 0);
+    // Deep K on a grid that cannot fill the chip: first widen the workgroup to
+    // 16 waves (in-LDS reduction, still one launch); only very deep K goes to a
+    // grid-level split with a second reduce pass.
+    int kz = 1;
+    pl.waves = (tiles < 256 && k >= 256) ? 16 : 4;
+    if (tiles < 64 && k >= 2048) {   // e.g. the simple CNN's Linear(3136, 10) at batch 256: 16 tiles
+        kz = (int)((256 + tiles - 1) / tiles);
+        const int kz_max = k / 512;
+        if (kz > kz_max) kz = kz_max;
+        if (kz < 1) kz = 1;
+    }
+    if (k == 0) {   // an empty product: one slice with nothing in it, the epilogue alone (C = beta C + bias)
+        pl.kslice = 16;
+        pl.kz = 1;
+        return;
+    }
+    int kslice = ceil_div(k, kz);
+    kslice = (kslice + 15) / 16 * 16;
+    pl.kslice = kslice;
+    pl.kz = ceil_div(k, kslice);
+}
+
+// 64 x 64 and 128 x 128 tiles: the load form (whole tiles by LDS-DMA, ragged edges by the descriptor's range, clamped float4 or scalar
+// register loads), the K slices and the workgroup-to-tile map of a split launch
+static void plan_tile(GemmPlan &pl, int ts, int m, int n, int k, bool a_kc, bool b_kc, long lda, long ldb, uintptr_t a_bits, uintptr_t b_bits) {
+    pl.tile = ts;
+    pl.waves = 4;
+    pl.tiles_m = ceil_div(m, ts);
+    pl.tiles_n = ceil_div(n, ts);
+    const int kz = ts == 128 ? tile128_kz(m, n, k) : tile64_kz(m, n, k);
+    pl.kslice = ceil_div(ceil_div(k, kz), BK) * BK;
+    pl.kz = ceil_div(k, pl.kslice);
+    // dwordx4 operand loads: 16-B aligned rows, and whole quads in or out of range along the vector axis
+    // (k for a k-contiguous operand, m / n for an m/n-contiguous one); slices start on multiples of 32
+    const bool vec = (a_bits & 15) == 0 && (b_bits & 15) == 0 && (lda % 4 == 0) && (ldb % 4 == 0) && ((a_kc ? k : m) % 4 == 0) &&
+                     ((b_kc ? k : n) % 4 == 0) && m >= 4 && n >= 4 && k >= 4;
+    // whole tiles take the LDS-DMA kernel: its 32-bit lane offsets span a tile's rows (TS x leading dimension x 4 bytes < 2^31)
+    const bool exact = (m % ts == 0) && (n % ts == 0) && (k % BK == 0) && vec && lda < (1L << 22) && ldb < (1L << 22);
+    pl.a_vec = pl.b_vec = vec;
+    pl.form = exact ? kFormExactDma : rag_dma(ts, a_kc, b_kc, k, vec, lda, ldb) ? kFormRagDma : vec ? kFormGuardVec : kFormGuardScalar;
+    // K slices of at least this many 32-k chunks are handed to the XCDs slice by slice (sgemm_tile)
+    constexpr int kSliceXcdChunks = 14;
+    pl.slice_xcd = pl.kz > 1 && pl.kslice >= kSliceXcdChunks * BK;
+}
+
+static GemmPlan gemm_plan(int trans_a, int trans_b, int m, int n, int k, uintptr_t a_bits, uintptr_t b_bits, uintptr_t c_bits) {
+    const long a_rs = trans_a ? 1 : k, a_cs = trans_a ? m : 1;  // gemm.rs:88-92
+    const long b_rs = trans_b ? 1 : n, b_cs = trans_b ? k : 1;  // gemm.rs:93-97
+    const bool a_kc = !trans_a, b_kc = trans_b != 0;
+    GemmPlan pl{};
+    const TileClass tc = gemm_tile_class(m, n, k);
+    if (tc == TileClass::Small) plan_small(pl, m, n, k, a_kc, b_kc, a_rs, b_cs, a_bits, b_bits);
+    else plan_tile(pl, tc == TileClass::Tile128 ? 128 : 64, m, n, k, a_kc, b_kc, a_kc ? a_rs : a_cs, b_kc ? b_cs : b_rs, a_bits, b_bits);
+    pl.reduce = pl.kz <= 1 ? kReduceNone : reduce_c_quad((long)m * n, c_bits) ? kReduceQuad : kReduceScalar;
+    return pl;
+}
+
 // op(A)[i,k] = A[i*a_rs + k*a_cs], op(B)[k,j] = B[k*b_rs + j*b_cs]
 int gemm_dispatch(th_ctx *ctx, int trans_a, int trans_b, int m, int n, int k, const float *A, const float *B, float *C,
                   const Epilogue &ep) {
@@ -1099,12 +1157,12 @@ int gemm_dispatch(th_ctx *ctx, int trans_a, int trans_b, int m, int n, int k, co
     const bool a_kc = !trans_a, b_kc = trans_b != 0;
     // Layouts: every operand is staged in the layout it has in memory (sgemm_tile: two LDS images, one MFMA loop; r03).  r01 ran deep
     // NN / TN / TT products as NT on transposed copies, r02 transposed such operands on their way into LDS.
-    const TileClass tc = gemm_tile_class(m, n, k);
+    const GemmPlan pl = gemm_plan(trans_a, trans_b, m, n, k, (uintptr_t)A, (uintptr_t)B, (uintptr_t)C);
 #define TH_GEMM_CASE(AK, BKC)                                                                         \
     if (a_kc == AK && b_kc == BKC)                                                                          \
-        return tc == TileClass::Tile64  ? launch_tile<64, AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep) \
-             : tc == TileClass::Tile128 ? launch_tile128<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep)  \
-                                        : launch_small<AK, BKC>(ctx, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
+        return pl.tile == 64  ? launch_tile<64, AK, BKC>(ctx, pl, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep) \
+             : pl.tile == 128 ? launch_tile128<AK, BKC>(ctx, pl, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep)  \
+                              : launch_small<AK, BKC>(ctx, pl, A, B, C, m, n, k, a_rs, a_cs, b_rs, b_cs, ep);
     TH_GEMM_CASE(true, true)
     TH_GEMM_CASE(true, false)
     TH_GEMM_CASE(false, true)
@@ -1200,6 +1258,20 @@ int th_sgemm(th_ctx *ctx, int trans_a, int trans_b, int m, int n, int k, float a
     TH_REQUIRE((m == 0 || n == 0) || (d_c && (k == 0 || (d_a && d_b))), "th_sgemm: null device pointer");
     Epilogue ep = make_ep(alpha, beta);
     return gemm_dispatch(ctx, trans_a, trans_b, m, n, k, d_a, d_b, d_c, ep);
+}
+
+int th_debug_sgemm_plan(int trans_a, int trans_b, int m, int n, int k, int a_misalign_bytes, int b_misalign_bytes, int c_misalign_bytes, int *out12) {
+    TH_REQUIRE(out12, "th_debug_sgemm_plan: null argument");
+    TH_REQUIRE(m >= 1 && n >= 1 && k >= 0, "th_debug_sgemm_plan: bad shape m=%d n=%d k=%d", m, n, k);
+    TH_REQUIRE(((a_misalign_bytes | b_misalign_bytes | c_misalign_bytes) & ~12) == 0,
+               "th_debug_sgemm_plan: a float pointer lies 0, 4, 8 or 12 bytes off a 16-byte boundary (got %d %d %d)", a_misalign_bytes,
+               b_misalign_bytes, c_misalign_bytes);
+    const GemmPlan p = gemm_plan(trans_a != 0, trans_b != 0, m, n, k, (uintptr_t)a_misalign_bytes, (uintptr_t)b_misalign_bytes, (uintptr_t)c_misalign_bytes);
+    const long wgs = (long)p.tiles_m * p.tiles_n * p.kz;
+    const int out[12] = {p.tile, p.form, p.waves, p.a_vec, p.b_vec, p.kz, p.kslice, (int)std::min<long>(wgs, 0x7fffffff), p.slice_xcd, p.reduce,
+                         p.tiles_m, p.tiles_n};
+    std::copy(out, out + 12, out12);
+    return 0;
 }
 
 int th_linear_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_b, float *d_y, int batch,
@@ -1418,7 +1490,7 @@ int th_linear_bwd_adam_ex2(th_ctx *ctx, const float *d_x, const float *d_w, cons
             Epilogue ep = make_ep(1.0f, (accumulate_mask & 2) ? 1.0f : 0.0f);
             ep.adam = w_adam;
             const long mn = (long)out_features * in_features;
-            launch_splitk_reduce(ctx->stream, (const float *)dw_part, d_dw, mn, in_features, dw_kz, ep);
+            launch_splitk_reduce(ctx->stream, (const float *)dw_part, d_dw, mn, in_features, dw_kz, ep, reduce_c_quad(mn, (uintptr_t)d_dw));
             TH_LAUNCH_CHECK();
             return th_free(ctx, dw_part);
         }

@@ -42,14 +42,33 @@ ODD_SHAPES = [(0, 0, 1, 1, 1), (0, 0, 2, 3, 2), (1, 1, 17, 5, 33), (0, 1, 33, 65
               (0, 0, 16, 16, 2000), (1, 0, 40, 24, 4100), (0, 0, 3, 200, 7)]
 BIG_SHAPES = [(0, 0, 1024, 1024, 256), (0, 1, 1024, 1152, 96), (1, 0, 1280, 1024, 64), (1, 1, 1024, 1024, 40),
               (0, 0, 1100, 1030, 70),
-              # deep K on a narrow output: split-K slices of the 128x128 kernel + the fixed-order reduce
+              # deep K on a narrow output: split-K slices of the 64x64 kernel + the fixed-order reduce; 256 x 256 x 3000 and 130 x 200 x 2050
+              # have 64 or more 16x16 tiles and stay there, unsplit (4 / 16 waves)
               (1, 0, 128, 784, 4096), (1, 0, 128, 784, 5000), (0, 1, 4096, 128, 784), (0, 0, 256, 256, 3000), (1, 1, 130, 200, 2050),
-              # ragged weight gradients (dW = dZ^T X with in = 784, out = 256 / 200 / 132): LDS-DMA with the edge quads zeroed by the descriptor's
-              # range and guarded stores (sgemm_tile<.., RAG>, r06); 1300: m % 4 != 0 keeps the clamped register loads
+              # ragged weight gradients (dW = dZ^T X with in = 784, out = 256 / 200 / 132): too few 128-tiles, so 64-tiles with clamped float4
+              # loads, split (132 x 784 x 8192: on the slice-per-XCD map); 784 x 200 x 1024 falls below the 3e8 multiply-adds of the 64-tiles:
+              # 16x16 tiles; 1300: m % 4 != 0 keeps the scalar register loads
               (1, 0, 784, 256, 4096), (1, 0, 256, 784, 2048), (1, 0, 784, 200, 1024), (1, 0, 132, 784, 8192), (1, 0, 1300, 1026, 512),
-              # ... and k-contiguous operands: rows past m / n, and in the last k chunk the quads past k (forward X W^T and dX = dZ W at in = 784)
+              # ... and k-contiguous operands (forward X W^T and dX = dZ W at in = 784): 64-tiles with clamped float4 loads; LDS-DMA with the
+              # edge quads zeroed by the descriptor's range and guarded stores (sgemm_tile<.., RAG>, r06) where there are enough 128-tiles:
+              # 1000 x 1028 x 200 (rows past m, quads past k) and 16384 x 256 x 784 (two K slices)
               (0, 1, 2048, 256, 784), (0, 1, 1000, 260, 784), (0, 0, 2048, 784, 256), (0, 0, 1100, 784, 260), (1, 1, 1000, 1028, 200),
               (0, 1, 16384, 256, 784)]
+
+# what the comments above say, asserted through th_debug_sgemm_plan (the host function the launch itself consumes; tests/sgemm_ref.py):
+# shape -> (tile class, load form, K slices, slice-per-XCD map)
+_SMALL, _EXACT, _RAG, _GVEC, _GSCALAR = range(5)
+BIG_FORMS = {
+    (0, 0, 1024, 1024, 256): (128, _EXACT, 1, 0), (0, 1, 1024, 1152, 96): (128, _EXACT, 1, 0), (1, 0, 1280, 1024, 64): (128, _EXACT, 1, 0),
+    (1, 1, 1024, 1024, 40): (128, _RAG, 1, 0), (0, 0, 1100, 1030, 70): (128, _GSCALAR, 1, 0),
+    (1, 0, 128, 784, 4096): (64, _GVEC, 19, 0), (1, 0, 128, 784, 5000): (64, _GVEC, 20, 0), (0, 1, 4096, 128, 784): (64, _GVEC, 4, 0),
+    (0, 0, 256, 256, 3000): (16, _SMALL, 1, 0), (1, 1, 130, 200, 2050): (16, _SMALL, 1, 0),
+    (1, 0, 784, 256, 4096): (64, _GVEC, 10, 0), (1, 0, 256, 784, 2048): (64, _GVEC, 10, 0), (1, 0, 784, 200, 1024): (16, _SMALL, 1, 0),
+    (1, 0, 132, 784, 8192): (64, _GVEC, 14, 1), (1, 0, 1300, 1026, 512): (64, _GSCALAR, 2, 0),
+    (0, 1, 2048, 256, 784): (64, _GVEC, 4, 0), (0, 1, 1000, 260, 784): (16, _SMALL, 1, 0), (0, 0, 2048, 784, 256): (64, _GVEC, 1, 0),
+    (0, 0, 1100, 784, 260): (16, _SMALL, 1, 0), (1, 1, 1000, 1028, 200): (128, _RAG, 1, 0), (0, 1, 16384, 256, 784): (128, _RAG, 2, 0),
+}
+assert set(BIG_FORMS) == set(BIG_SHAPES)
 
 
 # (alpha, beta) = (0.5, -2.0) on every shape but the big ones (> 5e7 multiply-adds): two variants of those are enough
@@ -60,6 +79,10 @@ SGEMM_CASES = [(s, ab) for ab in [(1.0, 0.0), (1.0, 1.0), (0.5, -2.0)] for s in 
 @pytest.mark.parametrize("shape,ab", SGEMM_CASES, ids=[f"{ab[0]}-{ab[1]}-" + "-".join(map(str, s)) for s, ab in SGEMM_CASES])
 def test_sgemm(ctx, O, shape, ab):
     (ta, tb, m, n, k), (alpha, beta) = shape, ab
+    if shape in BIG_FORMS:
+        from tests.sgemm_ref import plan
+        p = plan(*shape)
+        assert (p["tile"], p["form"], p["slices"], p["xcd"]) == BIG_FORMS[shape], p
     rng = np.random.default_rng(m * 31 + n * 7 + k)
     a = rng.uniform(-1, 1, (k, m) if ta else (m, k)).astype(np.float32)
     b = rng.uniform(-1, 1, (n, k) if tb else (k, n)).astype(np.float32)
@@ -91,7 +114,10 @@ def test_sgemm_transpose_detecting(ctx):
     dc = ctx.empty(n * n)
     ctx.call("th_sgemm", 0, 0, n, n, n, 1.0, ctx.upload(a), ctx.upload(b), 0.0, dc)
     np.testing.assert_array_equal(ctx.download(dc, (n, n)), b)
-    big = 1024  # through the 128x128 MFMA kernel
+    big = 1024  # through the 64x64 MFMA kernel, whole tiles by LDS-DMA, two K slices (64 128-tiles x 2 slices are too few workgroups for the 128x128 one)
+    from tests.sgemm_ref import plan
+    p = plan(0, 0, big, big, big)
+    assert (p["tile"], p["form"], p["slices"]) == (64, 1, 2), p
     a = np.eye(big, dtype=np.float32)
     b = ((np.arange(big * big, dtype=np.int64).reshape(big, big) * 7919) % 1013).astype(np.float32)
     dc = ctx.empty(big * big)
