@@ -22,9 +22,25 @@ __device__ __forceinline__ float powi_f32(float a, int b) {
 }
 
 // step_size = lr * sqrt(1 - b2^t) / (1 - b1^t)   (optim.rs:87-90)
+// Both powers in ONE walk over the bits of t: two independent multiply chains, each the very sequence of multiplies powi_f32 makes
+// (same bits), sharing the loop control -- one lone wave issues the pair in little more than the time of one, and every kernel that fuses
+// Adam runs this block in every wave.
 __device__ __forceinline__ float adam_step_size(float lr, float beta1, float beta2, int t) {
-    const float bc1 = 1.0f - powi_f32(beta1, t);
-    const float bc2 = 1.0f - powi_f32(beta2, t);
+    const bool recip = t < 0;
+    float r1 = 1.0f, r2 = 1.0f, a1 = beta1, a2 = beta2;
+    int b = t;
+    while (true) {
+        if (b & 1) {
+            r1 *= a1;
+            r2 *= a2;
+        }
+        b /= 2;
+        if (b == 0) break;
+        a1 *= a1;
+        a2 *= a2;
+    }
+    const float bc1 = 1.0f - (recip ? 1.0f / r1 : r1);
+    const float bc2 = 1.0f - (recip ? 1.0f / r2 : r2);
     return lr * (sqrtf(bc2) / bc1);
 }
 
@@ -149,6 +165,9 @@ __device__ __forceinline__ void adam_slices_block(const AdamSlices &x, int b) {
 // ALL slices in ONE workgroup, with the step counter as it stands at entry; afterwards `tick`
 // (nullable) is advanced by one (optim.rs:84).  For th_linear_fwd_ex: the slices belong to the
 // PREVIOUS step, the tick opens the next one; nothing else in that launch touches the counter.
+// A chain of dependent round trips per slice (t / lr, the powers, g / p / m / v, stores) and two more for the tick, yet NOT the
+// launch's longest workgroup: 0.08-0.11 us over plain tiles (profiles/mlp_step_tails.md).  The barrier is needed in any form of this
+// role: `tick` is usually the word the slices read as t, and thread 0 may advance it only when every wave is done reading.
 __device__ __forceinline__ void adam_slices_then_tick(const AdamSlices &x, int32_t *tick) {
     if (x.guard && sload(x.guard) != 0u) return;   // (uniform: the whole workgroup leaves before the barrier below)
 #pragma unroll

@@ -191,7 +191,9 @@ __global__ __launch_bounds__(64 * NW) void sgemm_small16(SmallArgs p) {
 }
 
 // th_linear_fwd_ex: the same tiles on rows [0, gridDim.y - 1) of the grid; block (0, gridDim.y - 1) applies the
-// carried Adam slices with the step counter as it stands and then opens the next step (t += 1)
+// carried Adam slices with the step counter as it stands and then opens the next step (t += 1).
+// The tiles are this launch's tail, not that spare workgroup: measured in situ it adds 0.08-0.11 us to the step over plain tiles
+// (tools/step_tails_probe.py, profiles/mlp_step_tails.md), and a one-round-trip rewrite of it gained nothing that probe can tell from noise -- not kept.
 template <bool A_KC, bool B_KC, int NW>
 __global__ __launch_bounds__(64 * NW) void sgemm_small16_tick(SmallArgs p, AdamSlices x, int32_t *tick) {
     __shared__ float red[NW][64][4];

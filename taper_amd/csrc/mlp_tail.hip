@@ -19,8 +19,10 @@
 //   dW1[hid][in] += dH^T . X                 A = dH[row 4g+s][hid r] (= register s), B = X[row 4g+s][in r]
 // Workgroup roles by block index:
 //   [0, n_head)      "head" workgroups, one per 16 hidden units hm: db1[16 hm ..] (+ fused Adam of b1),
-//                    dW2[:, 16 hm ..]; hm == 0 also db2, loss, hit count, the step log
-//   next n_dw        one 16-hidden x (16*TN)-input block of dW1 (+ fused Adam of W1), XCD-aware order
+//                    dW2[:, 16 hm ..]; hm == 0 (the "lead") also db2, loss, hit count, the step log -- the most work of any
+//                    workgroup, so what of it needs no result of this launch (the log slot with its remainder, the next state
+//                    words) is formed in the prologue under the operand loads; behind the final barrier only sums and stores
+//   next n_dw       one 16-hidden x (16*TN)-input block of dW1 (+ fused Adam of W1), XCD-aware order
 // W2 / b2 are READ by every workgroup, so their update cannot run here: the caller defers it
 // (th_adam_slice) to the next launch that does not read them (th_linear_fwd_ex of the next step).
 #include "tail_dev.h"
@@ -49,17 +51,29 @@ struct TailArgs {
 
 #ifdef TH_PROFILE
 __device__ long long g_tail_prof[2][16];   // [0] lead head workgroup, [1] first dW1 workgroup
+__device__ long long g_tail_prof_all[256][8];   // stamps 0..7 of every workgroup (blocks 0..255): who ends last (tools/prof_tail.py)
 #define TAIL_STAMP(i)                                                                         \
     do {                                                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == a.n_head))                  \
-            g_tail_prof[blockIdx.x == 0 ? 0 : 1][i] = wall_clock64();                         \
+        if (threadIdx.x == 0) {                                                               \
+            const long long now_ = wall_clock64();                                            \
+            if (blockIdx.x == 0 || blockIdx.x == a.n_head) g_tail_prof[blockIdx.x == 0 ? 0 : 1][i] = now_; \
+            if (blockIdx.x < 256 && (i) < 8) g_tail_prof_all[blockIdx.x][i] = now_;           \
+        }                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
 __global__ void tail_prof_mark_kernel(int i) { g_tail_prof[0][i] = g_tail_prof[1][i] = wall_clock64(); }
 #else
 #define TAIL_STAMP(i) do { } while (0)
 #endif
+
+// th_log_step's slot for step number state0: state0 mod capacity (capacity > 0), 32-bit when both fit -- the 64-bit remainder is a
+// 140-instruction routine.  Uniform; the lead head workgroup forms it in its prologue, under the operand loads.
+__device__ __forceinline__ int64_t tail_log_slot(int64_t state0, int64_t capacity) {
+    if (state0 < capacity) return state0;
+    if ((((uint64_t)state0 | (uint64_t)capacity) >> 32) == 0) return (int64_t)((uint32_t)state0 % (uint32_t)capacity);
+    return state0 % capacity;
+}
 
 template <int KS, int TN>
 __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
@@ -138,6 +152,7 @@ __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
     }
     const bool fuse_b = own_b1 && fuse_b1;
     const int64_t state0 = (lead && a.metrics) ? sload(a.state) : 0, state1 = (lead && a.metrics) ? sload(a.state + 1) : 0;
+    int64_t log_slot = 0, state0_next = 0, state1_next = 0;
 
     floatx4 accdw[TN];
 #pragma unroll
@@ -172,6 +187,12 @@ __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
             // step sizes of the fused updates (optim.rs:87-90): uniform ALU work that runs while the vector loads are in flight
             if (fuse_w) w_step = adam_step_size(w_lr, a.w1_adam.beta1, a.w1_adam.beta2, w_t);
             if (fuse_b1) b_step = adam_step_size(b_lr, a.b1_adam.beta1, a.b1_adam.beta2, b_t);
+            // ... and the lead's step-log slot and next state words: nothing of them depends on this launch's results
+            if (lead && a.metrics) {
+                log_slot = tail_log_slot(state0, a.capacity);
+                state0_next = state0 + 1;
+                state1_next = state1 + a.advance;
+            }
         }
         TAIL_STAMP(2);
         // ---- zero what lies outside the problem ----
@@ -334,11 +355,10 @@ __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
             a.loss[0] = l;
             if (a.ncorrect) a.ncorrect[0] = hsum;
             if (a.metrics) {                // the step log of th_log_step
-                const int64_t log_slot = state0 < a.capacity ? state0 : state0 % a.capacity;
                 a.metrics[2 * log_slot] = l;
                 a.metrics[2 * log_slot + 1] = hsum;
-                a.state[0] = state0 + 1;
-                a.state[1] = state1 + a.advance;
+                a.state[0] = state0_next;
+                a.state[1] = state1_next;
             }
         }
     }
@@ -567,6 +587,15 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
     // step sizes of the fused updates (optim.rs:87-90): ALU work under the loads' latency (every wave: all finish elements)
     if (fuse_w) w_step = adam_step_size(w_lr, a.w1_adam.beta1, a.w1_adam.beta2, w_t);
     if (fuse_b1) b_step = adam_step_size(b_lr, a.b1_adam.beta1, a.b1_adam.beta2, b_t);
+    // The lead's step-log slot and next state words, here too: they depend on state0 / state1 / capacity / advance alone (scalar loads
+    // of the prologue), and behind the final barrier the lead is the launch's last workgroup -- there only the wave-ordered sums,
+    // n / B and the stores are left.
+    int64_t log_slot = 0, state0_next = 0, state1_next = 0;
+    if (lead && a.metrics) {
+        log_slot = tail_log_slot(state0, a.capacity);
+        state0_next = state0 + 1;
+        state1_next = state1 + a.advance;
+    }
     TAIL_STAMP(2);
 
     for (int c0 = 0;;) {
@@ -779,11 +808,10 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
             a.loss[0] = l;
             if (a.ncorrect) a.ncorrect[0] = hsum;
             if (a.metrics) {                // the step log of th_log_step
-                const int64_t log_slot = state0 < a.capacity ? state0 : state0 % a.capacity;
                 a.metrics[2 * log_slot] = l;
                 a.metrics[2 * log_slot + 1] = hsum;
-                a.state[0] = state0 + 1;
-                a.state[1] = state1 + a.advance;
+                a.state[0] = state0_next;
+                a.state[1] = state1_next;
             }
         }
     }
@@ -933,6 +961,11 @@ extern "C" int th_debug_tail_mark(th_ctx *ctx, int i) {
 extern "C" int th_debug_tail_prof(th_ctx *ctx, long long *h_out32) {
     TH_HIP(hipStreamSynchronize(ctx->stream));
     TH_HIP(hipMemcpyFromSymbol(h_out32, HIP_SYMBOL(g_tail_prof), 32 * sizeof(long long)));
+    return 0;
+}
+extern "C" int th_debug_tail_prof_all(th_ctx *ctx, long long *h_out2048) {
+    TH_HIP(hipStreamSynchronize(ctx->stream));
+    TH_HIP(hipMemcpyFromSymbol(h_out2048, HIP_SYMBOL(g_tail_prof_all), 256 * 8 * sizeof(long long)));
     return 0;
 }
 #endif
