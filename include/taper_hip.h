@@ -419,6 +419,36 @@ int th_qlinear_i8_kstep(void);   /* bytes of K the product stages at a time (64)
  * Two launches on th_quantize_int8's min / max partials. */
 int th_act_range_update(th_ctx *ctx, const float *d_x, int64_t n, int first, float *d_range2, float *d_scale);
 
+/* ---- calibrated int8 convolution: the same arithmetic over a window, an implicit GEMM on the integer matrix cores (csrc/qconv_i8.hip) ----
+ * Codes are channel-last: qx[n][h][w][cpitch] and qw[c_out][k_h k_w][cpitch], cpitch a multiple of 16 and >= c_in, the bytes
+ * c_in .. cpitch - 1 zero -- a 16-byte piece of K is 16 consecutive channels of one tap for both operands.  For an output pixel
+ * (b, oh, ow), over the taps (kh, kw) whose input pixel (oh s_h - pad_h + kh, ow s_w - pad_w + kw) lies inside the image:
+ *     acc = sum over (ci, kh, kw) of qx * qw[co][ci][kh][kw], rs = sum over the same taps of qx, t = acc + 128 * rs    (int32, exact)
+ *     y[b][co][oh][ow] = sx * (sw * (float)t + mw * (float)rs)  [+ (float)(qb[co] + 128) * sb + mb]  [max(y, 0)]  (f32, each operation rounded once)
+ * Padding contributes nothing to either sum (code 0 is value 0), so rs depends on the pixel: a border window has fewer taps.  A pixel's
+ * result depends on its window alone, not on the batch around it.  None of the calls allocates, synchronises or reads anything back:
+ * all can be captured.
+ *
+ * th_quantize_act_nhwc_int8: f32 [n, c, h, w] -> codes [n, h, w, cpitch] (d_q 16-byte aligned; th_quantize_act_int8's codec: NaN -> 0,
+ * +-inf saturate) and d_pixsum[n, h, w] = the int32 sum of each pixel's codes over its channels.  One launch; the NCHW -> NHWC turn goes
+ * through LDS: a wave reads 64 consecutive floats of a channel plane and stores 16-byte pieces of consecutive pixels. */
+int th_quantize_act_nhwc_int8(th_ctx *ctx, const float *d_x, int n, int c, int h, int w, const float *d_scale, int8_t *d_q, int cpitch, int *d_pixsum);
+/* packed codes [c_out, c_in, k_h, k_w] (th_quantize_int8's) -> [c_out][k_h k_w][cpitch] with zero padding (d_dst 16-byte aligned): once
+ * per weight, at quantize time */
+int th_pack_conv_weight_int8(th_ctx *ctx, const int8_t *d_src, int c_out, int c_in, int k_h, int k_w, int8_t *d_dst, int cpitch);
+/* The same from the codes of a weight that the float conv kernels read with weight_layout 0 (taper's reinterpretation of the
+ * [c_out, c_in, k_h, k_w] buffer as [c_in k_h k_w][c_out], tensor.rs:1262): the code of w_eff[co][ci][kh][kw] lies at
+ * d_src[((ci k_h + kh) k_w + kw) c_out + co].  What a twin of a model's Conv2d needs, so that it multiplies by the filters the model has. */
+int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, int c_in, int k_h, int k_w, int8_t *d_dst, int cpitch);
+int th_qconv_i8_cpitch(int c_in);   /* the channel pitch a caller should use: c_in rounded up to 16 */
+/* The product, into f32 NCHW [n, c_out, h_out, w_out] with h_out = (h + 2 pad_h - k_h) / s_h + 1.  M = n h_out w_out pixels by N = c_out
+ * by K = k_h k_w cpitch; the im2col matrix exists only as addresses.  Refused before a launch: a null argument (d_qb / d_bparams are
+ * nullable, together), code pointers off a 16-byte boundary, a cpitch that is no multiple of 16 or below c_in, a shape, kernel or stride
+ * below 1, an empty output map, c_in k_h k_w > 65 536 (|t| < 2^31).  n == 0 returns 0. */
+int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                       const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                       const int8_t *d_qb, const float *d_bparams, int relu, float *d_y);
+
 /* ---- quantization-aware training: fake quantization (src/quantization/fake_quantize.rs, csrc/fake_quant.hip) ---- */
 /* A weight list through the storage codecs and back: TH_QTYPE_INT8 is th_quantize_int8 + th_dequantize_int8 (finite min / max ->
  * d_params = {min_val, scale}, written on the device; nullable), TH_QTYPE_F16 the half codec both ways -- bit for bit.  d_y must not

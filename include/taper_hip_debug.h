@@ -44,6 +44,10 @@ int th_debug_qlinear_plan(int qtype, int batch, int in_features, int out_feature
  * form takes it (a workgroup per 32 x 32 tile, K split over its four waves; 0: the 128 x 128 form through LDS), tile rows, tile columns,
  * workgroups} */
 int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4);
+/* what th_conv2d_q8q8_fwd would do with this shape -- pure host code, the function the launch itself consumes: out8 = {32-channel MFMA
+ * tiles per workgroup (1 / 2 / 4, by c_out alone), pixels per workgroup tile (128), channels per workgroup tile (32 times the first),
+ * pixel tiles, channel tiles, workgroups, h_out, w_out}.  Refuses what the launch refuses of a shape, and n < 1. */
+int th_debug_qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, int *out8);
 /* what th_sgemm / th_linear_fwd (trans 0, 1) would do with this shape, layout and pointers (a / b / c: bytes off a 16-byte boundary: 0, 4,
  * 8 or 12) under a plain epilogue -- pure host code, no context, the function gemm_dispatch itself launches from: out12 = {tile class (16 /
  * 64 / 128), load form (0: 16 x 16 tiles straight from L2; 1: whole tiles by LDS-DMA; 2: LDS-DMA with the edge quads zeroed by the

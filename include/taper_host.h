@@ -159,6 +159,14 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
  * size; everything else runs as in the weight-only twin.  Refused before anything is allocated: a module tp_module_quantize refuses (same
  * message), n_calib < 1, a null calibration tensor, a Linear with in_features > 65 536.  The source model is only read; no tape node stays. */
 int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
+/* tp_module_quantize_static with the convolutions static too: every 3x3, stride-1 Conv2d / Conv2dReLU with one group and no dilation (a
+ * QAT conv: its inner layer) gets one activation scale from its float input in the same calibration pass, and its forward is two
+ * launches -- channel-last int8 codes, then an implicit GEMM on the integer matrix cores (th_quantize_act_nhwc_int8, th_conv2d_q8q8_fwd)
+ * with the layer's own or a following ReLU in the epilogue.  Any other conv (grouped, dilated, 1x1, strided or another kernel: the float
+ * paths that are not plain convolutions) stays weight-only inside the same twin and has no scale.  tp_qmodule_tensor still returns the
+ * packed codes of tp_module_quantize (the channel-last copy is internal); tp_qmodule_act_scales lists one scale per static layer, Linear
+ * or conv, in layer order.  Refused in addition, before anything is allocated: in_channels * k_h * k_w > 65 536. */
+int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
 /* the calibrated activation scales in layer order: *n = their count (0 for a weight-only twin), the first min(*n, cap) into h_scales (nullable) */
 int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n);
 int tp_qmodule_free(tp_qmodule *q);

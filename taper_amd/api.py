@@ -328,6 +328,16 @@ class Module:
         tp_check(host.tp_module_quantize_static(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static")
         return QuantizedModule(h.value)
 
+    def quantize_static_conv(self, calib):
+        """quantize_static with the convolutions static too: every 3x3, stride-1 Conv2d / Conv2dReLU with one group gets its own activation
+        scale and runs int8 x int8 as an implicit GEMM on the integer matrix cores (any other conv stays weight-only).
+        act_scales() lists one scale per static layer, Linear or conv, in layer order; tensors() is quantize("int8")'s."""
+        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
+        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
+        h = _p()
+        tp_check(host.tp_module_quantize_static_conv(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_conv")
+        return QuantizedModule(h.value)
+
 
 class QuantizedModule:
     """nn.rs:20-23: forward from the packed codes (no tape node, the output needs no gradient)"""
@@ -354,7 +364,8 @@ class QuantizedModule:
         return n.value
 
     def act_scales(self) -> np.ndarray:
-        """the calibrated activation scale of every Linear of a quantize_static twin, in layer order (empty for a weight-only twin)"""
+        """the calibrated activation scale of every static layer of a quantize_static / quantize_static_conv twin, in layer order (empty for
+        a weight-only twin)"""
         n = C.c_int()
         tp_check(host.tp_qmodule_act_scales(self._h, None, 0, C.byref(n)), "QuantizedModule::act_scales")
         out = np.zeros(n.value, np.float32)

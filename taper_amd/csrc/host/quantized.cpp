@@ -92,12 +92,53 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
 
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
    public:
-    QConv(const Conv2d &c, int qtype) : geom_(std::make_shared<Conv2d>(c)), w_(quantize_tensor(c.weight, qtype)) {
+    // The integer product is a convolution, so it stands in for the float layer only where the float path is one: 3x3, stride 1, one
+    // group, no dilation (th_conv3x3_fwd, with the weight buffer read as [c_in k_h k_w][c_out]: tensor.rs:1262).  The float 1x1 and general
+    // paths keep the reference's scrambled gathers (tensor.rs:1799-1801, 1931): a twin of those stays weight-only, on the same kernels.
+    static bool can_be_static(const Conv2d &c) {
+        const Shape &ws = c.weight.shape();
+        return c.groups == 1 && c.dilation == std::make_pair(1, 1) && c.stride == std::make_pair(1, 1) && ws[2] == 3 && ws[3] == 3;
+    }
+    // stat: the static int8 twin (quantize_static with convs) -- the weight codes re-laid once channel-last for the product (an internal
+    // copy: tensors() keeps reporting the packed codes), and one activation scale on the device that calibration fixes
+    QConv(const Conv2d &c, int qtype, bool stat = false) : geom_(std::make_shared<Conv2d>(c)), w_(quantize_tensor(c.weight, qtype)) {
         if (c.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(c.bias, qtype));
         geom_->weight = Tensor();   // the twin keeps the geometry only, not the source's f32 storage
         geom_->bias = Tensor();
+        if (!stat || !can_be_static(c)) return;
+        const Shape &ws = w_.shape;   // [c_out, c_in, k_h, k_w]
+        cpitch_ = (size_t)th_qconv_i8_cpitch((int)ws[1]);
+        relaid_ = Buffer::alloc(ws[0] * ws[2] * ws[3] * cpitch_ / 4);
+        TH(th_pack_conv_weight_taper_int8(Device::ctx(), reinterpret_cast<const int8_t *>(w_.codes->d), (int)ws[0], (int)ws[1], (int)ws[2], (int)ws[3],
+                                    reinterpret_cast<int8_t *>(relaid_->d), (int)cpitch_));
+        act_ = Buffer::alloc(3);   // {finite min, finite max} of the calibration inputs, then the scale
     }
+    bool is_static() const { return act_ != nullptr; }
+    // codes and pixel sums of x (pooled, returned when this scope ends), then the integer product; relu: the layer's own or a following one
+    Tensor forward_static(const Tensor &x, bool relu) const {
+        const Shape &ws = w_.shape;
+        TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == ws[1], "QuantizedConv2d: input must be [batch, in_channels, h, w]");
+        const size_t n = x.shape()[0], h = x.shape()[2], w = x.shape()[3];
+        const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
+        TAPER_ASSERT(h + 2 * ph >= ws[2] && w + 2 * pw >= ws[3], "QuantizedConv2d: the kernel is larger than the padded input");
+        const size_t ho = (h + 2 * ph - ws[2]) / sh + 1, wo = (w + 2 * pw - ws[3]) / sw + 1;
+        Tensor y = Tensor::empty({n, ws[0], ho, wo});
+        auto qx = Buffer::alloc(std::max<size_t>(n * h * w * cpitch_ / 4, 1)), ps = Buffer::alloc(std::max<size_t>(n * h * w, 1));
+        th_ctx *ctx = Device::ctx();
+        TH(th_quantize_act_nhwc_int8(ctx, x.dptr(), (int)n, (int)ws[1], (int)h, (int)w, act_->d + 2, reinterpret_cast<int8_t *>(qx->d), (int)cpitch_,
+                                     reinterpret_cast<int *>(ps->d)));
+        TH(th_conv2d_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)cpitch_, reinterpret_cast<const int *>(ps->d), act_->d + 2, (int)n, (int)ws[1],
+                              (int)h, (int)w, reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d,
+                              b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu || geom_->fuse_relu ? 1 : 0,
+                              y.dptr()));
+        return y;
+    }
+    void act_scales(std::vector<const float *> *out) const override {
+        if (act_) out->push_back(act_->d + 2);
+    }
+    void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, act_->d, act_->d + 2)); }
     Tensor forward(const Tensor &x) const override {   // alone: dequantize its own two tensors
+        if (is_static()) return forward_static(x, false);
         std::vector<const QConv *> one{this};
         std::vector<std::pair<float *, float *>> at;
         auto ws = dequantize(one, &at);
@@ -138,16 +179,19 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     std::shared_ptr<Conv2d> geom_;
     QTensor w_;
     std::unique_ptr<QTensor> b_;
+    std::shared_ptr<Buffer> relaid_, act_;   // static only: [c_out][k_h k_w][cpitch] codes; the activation range and scale
+    size_t cpitch_ = 0;
 };
 
 class QSequential : public QuantizedModule {   // nn.rs:153-177
    public:
     std::vector<std::unique_ptr<QuantizedModule>> layers;
     Tensor forward(const Tensor &input) const override {
-        // every conv stage's weights in one dequantize launch, into one workspace that lives for this call
+        // every weight-only conv stage's weights in one dequantize launch, into one workspace that lives for this call
         std::vector<const QConv *> convs;
         for (const auto &l : layers)
-            if (auto *c = dynamic_cast<const QConv *>(l.get())) convs.push_back(c);
+            if (auto *c = dynamic_cast<const QConv *>(l.get()))
+                if (!c->is_static()) convs.push_back(c);
         std::vector<std::pair<float *, float *>> at;
         std::shared_ptr<Buffer> ws;
         if (!convs.empty()) ws = QConv::dequantize(convs, &at);
@@ -164,6 +208,13 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
                     x = lin->forward(x);
                 }
             } else if (auto *cv = dynamic_cast<const QConv *>(l)) {
+                if (cv->is_static()) {   // conv + ReLU: the ReLU in the product's epilogue
+                    auto *next = i + 1 < layers.size() ? dynamic_cast<const QPass *>(layers[i + 1].get()) : nullptr;
+                    const bool relu = next && next->is_relu();
+                    x = cv->forward_static(x, relu);
+                    if (relu) ++i;
+                    continue;
+                }
                 x = cv->forward_with(x, at[ci].first, at[ci].second);
                 ++ci;
             } else {
@@ -199,17 +250,18 @@ std::shared_ptr<Module> copy_of(const Module &m) {
     return p ? std::make_shared<M>(*p) : nullptr;
 }
 
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false) {
+// stat: the Linear layers static; stat_convs: the plain convolutions too
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto q = std::make_unique<QSequential>();
-        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat));
+        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs));
         return q;
     }
     if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat);
-    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype);
+    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype, stat_convs);
     // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
     if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype, stat);
-    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype);
+    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype, stat_convs);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
         !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))
@@ -228,8 +280,19 @@ void linears_of(const Module &m, std::vector<const Linear *> *out) {
     }
 }
 
+// the convolutions of a model, likewise
+void convs_of(const Module &m, std::vector<const Conv2d *> *out) {
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        for (const auto &l : s->layers) convs_of(*l, out);
+    } else if (auto *c = dynamic_cast<const Conv2d *>(&m)) {
+        out->push_back(c);
+    } else if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) {
+        out->push_back(&qc->inner);
+    }
+}
+
 // One calibration tensor through the plain float layers of `m` (a QAT layer: its inner layer, whatever the QAT switch says), every
-// Linear twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
+// Linear twin and every static conv twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
 Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first) {
     auto plain = [](const Tensor &t) { return t.defined() ? Tensor::from_device(t.dptr(), t.shape()) : Tensor(); };
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
@@ -246,7 +309,11 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
     }
     const Conv2d *cv = dynamic_cast<const Conv2d *>(&m);
     if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) cv = &qc->inner;
-    if (cv) return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
+    if (cv) {
+        auto &qcv = dynamic_cast<const QConv &>(q);
+        if (qcv.is_static()) qcv.observe(x, first);
+        return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
+    }
     return m.forward(x);
 }
 
@@ -272,7 +339,7 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
     return quantize_checked(m, qt);
 }
 
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib) {
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs) {
     // every refusal before anything is allocated
     check_quantizable(m);
     TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
@@ -282,7 +349,17 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
     for (const Linear *l : lins)
         TAPER_ASSERT(l->weight.shape()[1] <= 65536, "quantize_static: a Linear with in_features " + std::to_string(l->weight.shape()[1]) +
                                                         " is above 65536, where the int32 sum of the int8 product can overflow");
-    auto q = quantize_checked(m, TH_QTYPE_INT8, true);
+    if (convs) {
+        std::vector<const Conv2d *> cvs;
+        convs_of(m, &cvs);
+        for (const Conv2d *c : cvs) {
+            const Shape &ws = c->weight.shape();
+            TAPER_ASSERT(!QConv::can_be_static(*c) || ws[1] * ws[2] * ws[3] <= 65536,
+                         "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) +
+                             " is above 65536, where the int32 sum of the int8 product can overflow");
+        }
+    }
+    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs);
     NoGradScope no_grad;
     for (size_t i = 0; i < calib.size(); ++i) {
         Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)

@@ -500,7 +500,12 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // quantizes the input with that scale and runs int8 x int8 on the integer matrix cores (th_linear_q8q8_fwd) at every batch size; conv
 // stages and the parameter-free layers run as in the weight-only twin.  Refusals (an unquantizable module, no or an undefined calibration
 // tensor, in_features above 65 536) come before anything is allocated; the source model is only read and no tape node is recorded.
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib);
+// convs: every 3x3, stride-1 Conv2d / Conv2dReLU with one group and no dilation (where the float path is a convolution) becomes static
+// too -- one scale from its float input, then its forward is two launches, channel-last codes (th_quantize_act_nhwc_int8) and the
+// implicit-GEMM product (th_conv2d_q8q8_fwd) with its own or a following ReLU in the epilogue; any other conv stays weight-only inside the
+// same twin.  in_channels * k_h * k_w above 65 536 is refused with the other refusals.  act_scales() then lists one scale per static
+// layer, Linear or conv, in layer order.
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false);
 
 // ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
 // A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the

@@ -1,0 +1,322 @@
+// qconv_i8.hip -- calibrated int8 convolution: qgemm_i8.hip's arithmetic restated for a window, as an implicit GEMM on the
+// integer matrix cores (v_mfma_i32_32x32x32_i8) over channel-last codes.
+//
+//   th_quantize_act_nhwc_int8  f32 [n, c, h, w] -> int8 codes [n, h, w, cpitch] (th_quantize_act_int8's codec) and the int32 sum of each
+//                              pixel's codes; one launch, the NCHW -> NHWC turn through LDS
+//   th_pack_conv_weight_int8   packed codes [c_out, c_in, k_h, k_w] -> [c_out][k_h k_w][cpitch] with zero padding (once per weight);
+//                              th_pack_conv_weight_taper_int8: the same from a weight in the float conv kernels' weight_layout 0
+//   th_conv2d_q8q8_fwd         y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU] into f32 NCHW; acc = the sum
+//                              over the in-image taps of qx qw from the MFMA, rs = the sum of d_pixsum over the same taps
+//
+// With both operands channel-last a 16-byte piece of K is 16 consecutive channels of one tap: M = n h_out w_out output pixels, N = c_out,
+// K = k_h k_w cpitch.  The im2col matrix exists only as addresses; an out-of-image tap is a zero piece, and code 0 IS value 0, so padding
+// adds nothing to acc or rs.  A pixel's result depends on its own window alone: nothing of the tiling reaches the arithmetic.
+#include "common.h"
+#include "quant_dev.h"
+
+namespace th {
+
+typedef int intx4 __attribute__((ext_vector_type(4)));
+typedef int intx16 __attribute__((ext_vector_type(16)));
+
+constexpr int kQcPix = 128;        // output pixels per workgroup: four waves of 32
+constexpr int kQcChan = 32;        // channels per MFMA tile; a workgroup takes NT of them (1, 2 or 4)
+constexpr int kQcMaxK = 65536;     // c_in k_h k_w: |acc + 128 rs| <= 128 * 255 * K stays below 2^31 (qgemm_i8.hip's kQ8MaxK)
+constexpr int kQcTurnPix = 64;     // th_quantize_act_nhwc_int8: pixels ...
+constexpr int kQcTurnChan = 64;    // ... by channels of one LDS turn
+constexpr int kQcTurnPitch = 20;   // words per pixel row of the turn: 16 of codes, 4 of padding (a row stays 16-byte aligned)
+
+// ---- activations -> channel-last codes ----
+// A workgroup turns 64 consecutive pixels of one image, 64 channels at a time.  In: lane = pixel, so a wave's load is 64 consecutive
+// floats of one channel plane; a thread packs four consecutive channels into one LDS word.  Out: four lanes per pixel, one 16-byte piece
+// each -- 64 consecutive bytes per pixel, the whole wave contiguous when cpitch == 64.  Channels c .. cpitch - 1 get the code 0.
+__global__ __launch_bounds__(256) void quantize_act_nhwc_kernel(const float *__restrict__ x, int n, int c, int hw, const float *__restrict__ d_scale,
+                                                                int8_t *__restrict__ q, int cpitch, int *__restrict__ pixsum, int tiles_per_img) {
+    __shared__ uint4 turn[kQcTurnPix * kQcTurnPitch / 4];   // 5 KB
+    uint32_t *turn_w = (uint32_t *)turn;
+    const int t = threadIdx.x, pin = t & 63, cq = t >> 6, pout = t >> 2, piece = t & 3;
+    const float scale = d_scale[0];
+    const long tiles = (long)n * tiles_per_img;
+    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int img = (int)(tile / tiles_per_img), p0 = (int)(tile - (long)img * tiles_per_img) * kQcTurnPix;
+        const float *xi = x + (size_t)img * c * hw;
+        int sum = 0;
+        for (int cb = 0; cb < cpitch; cb += kQcTurnChan) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                uint32_t word = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ch = cb + 16 * i + 4 * cq + j;
+                    if (ch < c && p0 + pin < hw) word |= (uint32_t)(uint8_t)(int8_t)act_code(xi[(size_t)ch * hw + p0 + pin], scale) << (8 * j);
+                }
+                turn_w[pin * kQcTurnPitch + 4 * i + cq] = word;
+            }
+            __syncthreads();
+            if (p0 + pout < hw && cb + 16 * piece < cpitch) {
+                const uint4 v = turn[pout * (kQcTurnPitch / 4) + piece];
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) sum += (int)(int8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xFF);
+                *(uint4 *)(q + ((size_t)img * hw + p0 + pout) * cpitch + cb + 16 * piece) = v;
+            }
+            __syncthreads();
+        }
+        sum += __shfl_xor(sum, 1, 64);   // the four lanes of a pixel (integers: any order gives the same bits)
+        sum += __shfl_xor(sum, 2, 64);
+        if (piece == 0 && p0 + pout < hw) pixsum[(size_t)img * hw + p0 + pout] = sum;
+    }
+}
+
+// a thread per 16-byte piece of the destination (packed sources are not aligned in general: byte loads, once per weight).  TAPER: the
+// source is a weight the float conv kernels read in the reference's reinterpretation (weight_layout 0, tensor.rs:1262): the code of
+// w_eff[co][ci][tap] lies at src[(ci taps + tap) c_out + co]
+template <bool TAPER>
+__global__ __launch_bounds__(256) void pack_conv_weight_kernel(const int8_t *__restrict__ src, long rows, int c_in, int taps, int8_t *__restrict__ dst,
+                                                               int cpitch) {
+    const int cp16 = cpitch / 16;
+    const long total = rows * taps * cp16;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long rt = i / cp16;   // row * taps + tap
+        const int c0 = (int)(i - rt * cp16) * 16;
+        const long row = rt / taps;
+        const int tap = (int)(rt - row * taps);
+        const int8_t *s = TAPER ? src + (size_t)tap * rows + row : src + (size_t)row * c_in * taps + tap;
+        const size_t step = TAPER ? (size_t)taps * rows : (size_t)taps;   // from one input channel to the next
+        uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (c0 + j < c_in) w[j >> 2] |= (uint32_t)(uint8_t)s[(size_t)(c0 + j) * step] << (8 * (j & 3));
+        *(uint4 *)(dst + (size_t)i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// ---- the product ----
+struct QcArgs {
+    const int8_t *qx, *qw;
+    const int *pixsum;
+    const float *xscale, *wparams;
+    const int8_t *qb;
+    const float *bparams;
+    float *y;
+    int cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, h_out, w_out, M, relu, tiles_n;
+};
+
+// qgemm_i8_kernel's LDS image: rows of 64 bytes, the 16-byte piece c of row r at slot c ^ ((r >> 2) & 3)
+__device__ __forceinline__ int qc_slot(int row, int piece) { return row * 4 + (piece ^ ((row >> 2) & 3)); }
+
+// A workgroup owns 128 output pixels (any run of the n h_out w_out list: it may span map rows and images) by 32 NT channels; wave v
+// owns pixels 32 v .. 32 v + 31 against every channel tile.  A stage is 64 bytes of K = four pieces; piece g of K is channels
+// 16 (g % cp16) .. + 15 of tap g / cp16 for BOTH operands, so the fragments pair code with code as in qgemm_i8_kernel.  The weights are
+// the A operand and the pixels the B operand: C column = lane & 31 is a pixel, C row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) a
+// channel, and a wave's store of one register is 32 consecutive pixels of one channel plane.
+template <int NT>
+__global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
+    __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
+    __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, h = lane >> 5;
+    const int tile_m = blockIdx.x / a.tiles_n, tile_n = blockIdx.x - tile_m * a.tiles_n;
+    const int m0 = tile_m * kQcPix, col0 = tile_n * kQcChan * NT;
+    const int cp16 = a.cpitch >> 4, taps = a.k_h * a.k_w, pieces = taps * cp16, nk = (pieces + 3) >> 2, hw_out = a.h_out * a.w_out;
+
+    // staging: thread t brings piece t & 3 of pixel rows t >> 2 and (t >> 2) + 64, and of weight rows (t >> 2) + 64 i below 32 NT
+    const int srow = t >> 2, piece = t & 3;
+    const int8_t *px[2];
+    int ih0[2], iw0[2];   // the window's first tap in the image; a pixel past M gets a window that no tap of is inside any image
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int m = m0 + srow + 64 * i;
+        const bool live = m < a.M;
+        const int img = live ? m / hw_out : 0, p = live ? m - img * hw_out : 0, oh = p / a.w_out, ow = p - oh * a.w_out;
+        ih0[i] = live ? oh * a.s_h - a.pad_h : -a.k_h;
+        iw0[i] = ow * a.s_w - a.pad_w;
+        px[i] = a.qx + (size_t)img * a.h * a.w * a.cpitch;
+    }
+    constexpr int WL = (NT + 1) / 2;   // weight pieces a thread stages
+    const size_t wrow_bytes = (size_t)pieces * 16;
+    uint4 gx[2], gw[WL];
+    auto fetch = [&](int kt) {
+        const int g = kt * 4 + piece;
+        const bool in_k = g < pieces;
+        const int tap = g / cp16, cpiece = g - tap * cp16, kh = tap / a.k_w, kw = tap - kh * a.k_w;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int ih = ih0[i] + kh, iw = iw0[i] + kw;
+            const bool inside = in_k && ih >= 0 && ih < a.h && iw >= 0 && iw < a.w;
+            gx[i] = inside ? *(const uint4 *)(px[i] + ((size_t)ih * a.w + iw) * a.cpitch + cpiece * 16) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < WL; ++i) {
+            const int row = srow + 64 * i;   // (rows past c_out re-read the last row: never stored)
+            gw[i] = in_k && row < kQcChan * NT ? *(const uint4 *)(a.qw + (size_t)min(col0 + row, a.c_out - 1) * wrow_bytes + (size_t)g * 16)
+                                               : make_uint4(0, 0, 0, 0);
+        }
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) lds_x[buf][qc_slot(srow + 64 * i, piece)] = gx[i];
+#pragma unroll
+        for (int i = 0; i < WL; ++i)
+            if (srow + 64 * i < kQcChan * NT) lds_w[buf][qc_slot(srow + 64 * i, piece)] = gw[i];
+    };
+
+    intx16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0;
+
+    fetch(0);
+    stage(0);
+    lds_barrier();
+    int buf = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) fetch(kt + 1);   // in flight under this stage's MFMAs
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const uint4 vx = lds_x[buf][qc_slot(wave * 32 + li, 2 * s + h)];
+            const intx4 xf{(int)vx.x, (int)vx.y, (int)vx.z, (int)vx.w};
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const uint4 vw = lds_w[buf][qc_slot(32 * j + li, 2 * s + h)];
+                acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(intx4{(int)vw.x, (int)vw.y, (int)vw.z, (int)vw.w}, xf, acc[j], 0, 0, 0);
+            }
+        }
+        if (kt + 1 < nk) stage(buf ^ 1);   // (read last in step kt - 1: every wave passed that step's barrier)
+        lds_barrier();
+        buf ^= 1;
+    }
+
+    // epilogue: this lane's pixel, its window's sum of pixel sums (integer; border windows have fewer taps), then store_tile's four operations
+    const int m = m0 + wave * 32 + li;
+    if (m >= a.M) return;
+    const int img = m / hw_out, p = m - img * hw_out, oh = p / a.w_out, ow = p - oh * a.w_out;
+    const int *ps = a.pixsum + (size_t)img * a.h * a.w;
+    int rs = 0;
+    for (int kh = 0; kh < a.k_h; ++kh) {
+        const int ih = oh * a.s_h - a.pad_h + kh;
+        if (ih < 0 || ih >= a.h) continue;
+        for (int kw = 0; kw < a.k_w; ++kw) {
+            const int iw = ow * a.s_w - a.pad_w + kw;
+            if (iw >= 0 && iw < a.w) rs += ps[ih * a.w + iw];
+        }
+    }
+    const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1];
+    const float rterm = __fmul_rn(mw, (float)rs);
+    float *yp = a.y + (size_t)img * a.c_out * hw_out + p;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
+            if (co >= a.c_out) continue;
+            const int tt = acc[j][e] + 128 * rs;
+            float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
+            if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
+            yp[(size_t)co * hw_out] = a.relu ? (v > 0.f ? v : 0.f) : v;
+        }
+}
+
+// every host decision of the product (th_conv2d_q8q8_fwd launches from it, th_debug_qconv_plan reports it)
+struct QcPlan {
+    int nt, tiles_m, tiles_n, grid, h_out, w_out;
+};
+// nullptr, or why the shape is refused
+static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, QcPlan *p) {
+    if (n < 0 || c_in <= 0 || h <= 0 || w <= 0 || c_out <= 0 || k_h <= 0 || k_w <= 0 || s_h <= 0 || s_w <= 0 || pad_h < 0 || pad_w < 0)
+        return "a shape, kernel or stride below 1, or a negative padding";
+    if ((long)h + 2L * pad_h < k_h || (long)w + 2L * pad_w < k_w) return "an empty output map";
+    if ((long)h + 2L * pad_h > 0x7fffffffL || (long)w + 2L * pad_w > 0x7fffffffL) return "a padded map side above 2^31";
+    if ((long)c_in * k_h * k_w > kQcMaxK) return "c_in * k_h * k_w above 65536, where the int32 sum can overflow";
+    p->h_out = (h + 2 * pad_h - k_h) / s_h + 1;
+    p->w_out = (w + 2 * pad_w - k_w) / s_w + 1;
+    const long M = (long)n * p->h_out * p->w_out;
+    if (M > 0x7fffffffL - kQcPix || (long)n * h * w > 0x7fffffffL) return "more than 2^31 pixels";
+    p->nt = c_out <= kQcChan ? 1 : c_out <= 2 * kQcChan ? 2 : 4;   // a 128-wide channel tile on a 4- or 32-channel layer is mostly waste
+    p->tiles_m = ceil_div(M, kQcPix);
+    p->tiles_n = ceil_div(c_out, kQcChan * p->nt);
+    if ((long)p->tiles_m * p->tiles_n > 0x7fffffffL) return "more than 2^31 workgroups";
+    p->grid = p->tiles_m * p->tiles_n;
+    return nullptr;
+}
+
+}  // namespace th
+
+using namespace th;
+
+extern "C" {
+
+int th_qconv_i8_cpitch(int c_in) { return c_in > 0 ? (c_in + 15) / 16 * 16 : 0; }
+
+int th_quantize_act_nhwc_int8(th_ctx *ctx, const float *d_x, int n, int c, int h, int w, const float *d_scale, int8_t *d_q, int cpitch, int *d_pixsum) {
+    TH_REQUIRE(ctx && d_x && d_scale && d_q && d_pixsum, "th_quantize_act_nhwc_int8: null argument");
+    TH_REQUIRE(n >= 0 && c > 0 && h > 0 && w > 0 && cpitch >= c && cpitch % 16 == 0 && (long)h * w <= 0x7fffffffL && (long)n * h * w <= 0x7fffffffL,
+               "th_quantize_act_nhwc_int8: bad shape n=%d c=%d h=%d w=%d cpitch=%d (cpitch >= c, a multiple of 16)", n, c, h, w, cpitch);
+    TH_REQUIRE(((uintptr_t)d_q & 15) == 0, "th_quantize_act_nhwc_int8: the code pointer must be 16-byte aligned");
+    if (n == 0) return 0;
+    const int hw = h * w, tiles_per_img = ceil_div(hw, kQcTurnPix);
+    const long tiles = (long)n * tiles_per_img;
+    hipLaunchKernelGGL(quantize_act_nhwc_kernel, dim3((unsigned)std::min(tiles, (long)kNumCU * 32)), dim3(256), 0, ctx->stream, d_x, n, c, hw, d_scale, d_q,
+                       cpitch, d_pixsum, tiles_per_img);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+static int pack_conv_weight(const char *fn, bool taper, th_ctx *ctx, const int8_t *d_src, int c_out, int c_in, int k_h, int k_w, int8_t *d_dst, int cpitch) {
+    TH_REQUIRE(ctx && d_src && d_dst, "%s: null argument", fn);
+    TH_REQUIRE(c_out >= 0 && c_in > 0 && k_h > 0 && k_w > 0 && cpitch >= c_in && cpitch % 16 == 0 && (long)k_h * k_w <= 0x7fffffffL && ((uintptr_t)d_dst & 15) == 0,
+               "%s: bad shape c_out=%d c_in=%d k=%dx%d cpitch=%d (cpitch >= c_in, a multiple of 16) or a destination off a 16-byte boundary", fn, c_out, c_in,
+               k_h, k_w, cpitch);
+    if (c_out == 0) return 0;
+    const dim3 grid(ew_grid((size_t)c_out * k_h * k_w * (cpitch / 16), 256));
+    if (taper)
+        hipLaunchKernelGGL(pack_conv_weight_kernel<true>, grid, dim3(256), 0, ctx->stream, d_src, (long)c_out, c_in, k_h * k_w, d_dst, cpitch);
+    else
+        hipLaunchKernelGGL(pack_conv_weight_kernel<false>, grid, dim3(256), 0, ctx->stream, d_src, (long)c_out, c_in, k_h * k_w, d_dst, cpitch);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_pack_conv_weight_int8(th_ctx *ctx, const int8_t *d_src, int c_out, int c_in, int k_h, int k_w, int8_t *d_dst, int cpitch) {
+    return pack_conv_weight("th_pack_conv_weight_int8", false, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
+}
+
+int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, int c_in, int k_h, int k_w, int8_t *d_dst, int cpitch) {
+    return pack_conv_weight("th_pack_conv_weight_taper_int8", true, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
+}
+
+int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                       const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
+                       const float *d_bparams, int relu, float *d_y) {
+    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "th_conv2d_q8q8_fwd: null argument");
+    QcPlan p{};
+    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
+    TH_REQUIRE(!why, "th_conv2d_q8q8_fwd: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w,
+               pad_h, pad_w);
+    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "th_conv2d_q8q8_fwd: the code pointers must be 16-byte aligned");
+    TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "th_conv2d_q8q8_fwd: cpitch %d must be a multiple of 16 and at least c_in %d", cpitch, c_in);
+    if (n == 0) return 0;
+    const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+                   p.h_out, p.w_out, n * p.h_out * p.w_out, relu, p.tiles_n};
+    if (p.nt == 1)
+        hipLaunchKernelGGL(qconv_i8_kernel<1>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    else if (p.nt == 2)
+        hipLaunchKernelGGL(qconv_i8_kernel<2>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(qconv_i8_kernel<4>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_debug_qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, int *out8) {
+    TH_REQUIRE(out8 && n >= 1, "th_debug_qconv_plan: null argument or n=%d below 1", n);
+    QcPlan p{};
+    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
+    TH_REQUIRE(!why, "th_debug_qconv_plan: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w,
+               pad_h, pad_w);
+    const int out[8] = {p.nt, kQcPix, kQcChan * p.nt, p.tiles_m, p.tiles_n, p.grid, p.h_out, p.w_out};
+    std::copy(out, out + 8, out8);
+    return 0;
+}
+
+}  // extern "C"

@@ -26,11 +26,6 @@ constexpr int kQ8MaxK = 65536;     // |acc + 128 rs| <= 128 * 255 * K stays belo
 constexpr int kQ8Raster = 8;       // tile rows per group of the tile order (gemm.hip's sgemm_tile)
 constexpr int kQ8SkinnyMaxBatch = 256;   // up to here a workgroup per 32 x 32 tile with K split over its waves (measured: profiles/quant_static.md)
 
-__device__ __forceinline__ int act_code(float v, float scale) {
-    const int q = rust_f32_as_i32(roundf(v / scale));
-    return q < -128 ? -128 : (q > 127 ? 127 : q);
-}
-
 // ---- activations -> codes ----
 // A wave per row, four rows per workgroup; a lane takes 16 k positions at a time: four float4 loads, one 16-byte store.  Positions
 // k .. pitch - 1 get the code 0.  VEC: x rows and code rows are 16-byte aligned (the host says).

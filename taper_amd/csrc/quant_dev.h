@@ -67,6 +67,13 @@ __device__ __forceinline__ int quant_int8(float x, float min_val, float scale) {
     return (int)(w < -128 ? -128 : (w > 127 ? 127 : w));
 }
 
+// the symmetric int8 activation code of calibrated inference (qgemm_i8.hip, qconv_i8.hip): th_fake_quant_act's code with a scale fixed
+// beforehand -- clamp(round(v / scale) as i32, -128, 127), NaN -> 0, +-inf saturate
+__device__ __forceinline__ int act_code(float v, float scale) {
+    const int q = rust_f32_as_i32(roundf(v / scale));
+    return q < -128 ? -128 : (q > 127 ? 127 : q);
+}
+
 // (q - zero_point) * scale + min_val with zero_point = -128: two roundings, never contracted (tensor.rs:357)
 __device__ __forceinline__ float dequant_int8(int q, float scale, float min_val) { return __fadd_rn(__fmul_rn((float)(q + 128), scale), min_val); }
 
