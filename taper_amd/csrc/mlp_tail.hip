@@ -23,6 +23,9 @@
 //                    workgroup, so what of it needs no result of this launch (the log slot with its remainder, the next state
 //                    words) is formed in the prologue under the operand loads; behind the final barrier only sums and stores
 //   next n_dw       one 16-hidden x (16*TN)-input block of dW1 (+ fused Adam of W1), XCD-aware order
+// The whole-tile kernel's 4-wave instances up to hidden 128 (not the data-parallel ones) run a fifth, HELPER wave per workgroup (tail_helper_wave): it forms the step
+// size of the workgroup's fused update and, in the lead, does the lead's own work (step log, loss, hit count, db2), so that the four
+// working waves -- one per SIMD, issue-bound -- carry nothing that is uniform or needed once (profiles/mlp_tail_helper.md).
 // W2 / b2 are READ by every workgroup, so their update cannot run here: the caller defers it
 // (th_adam_slice) to the next launch that does not read them (th_linear_fwd_ex of the next step).
 #include "tail_dev.h"
@@ -52,13 +55,21 @@ struct TailArgs {
 #ifdef TH_PROFILE
 __device__ long long g_tail_prof[2][16];   // [0] lead head workgroup, [1] first dW1 workgroup
 __device__ long long g_tail_prof_all[256][8];   // stamps 0..7 of every workgroup (blocks 0..255): who ends last (tools/prof_tail.py)
+// stamp 7 of the lead: the later of thread 0's and the helper wave's (the clock only rises, so no reset between launches)
+__device__ __forceinline__ void tail_prof_end(long long now) {
+    atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof[0][7]), (unsigned long long)now);
+    atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof_all[0][7]), (unsigned long long)now);
+}
 #define TAIL_STAMP(i)                                                                         \
     do {                                                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                    \
         if (threadIdx.x == 0) {                                                               \
             const long long now_ = wall_clock64();                                            \
-            if (blockIdx.x == 0 || blockIdx.x == a.n_head) g_tail_prof[blockIdx.x == 0 ? 0 : 1][i] = now_; \
-            if (blockIdx.x < 256 && (i) < 8) g_tail_prof_all[blockIdx.x][i] = now_;           \
+            if ((i) == 7 && blockIdx.x == 0) tail_prof_end(now_);                             \
+            else {                                                                            \
+                if (blockIdx.x == 0 || blockIdx.x == a.n_head) g_tail_prof[blockIdx.x == 0 ? 0 : 1][i] = now_; \
+                if (blockIdx.x < 256 && (i) < 8) g_tail_prof_all[blockIdx.x][i] = now_;       \
+            }                                                                                 \
         }                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
@@ -463,14 +474,84 @@ __device__ __forceinline__ void tail_dx_role(const TailArgs &a, int rb) {
     }
 }
 
+// loss, hit count and the step log from the waves' partial sums, in wave order (one thread of the lead head workgroup)
+template <int NW>
+__device__ __forceinline__ void tail_lead_log(const TailArgs &a, const float (*sc)[36], int64_t log_slot, int64_t state0_next, int64_t state1_next) {
+    float n = sc[0][32], hsum = sc[0][33];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+        n += sc[w][32];
+        hsum += sc[w][33];
+    }
+    const float l = n / (float)a.batch;   // loss.rs:164
+    a.loss[0] = l;
+    if (a.ncorrect) a.ncorrect[0] = hsum;
+    if (a.metrics) {                // the step log of th_log_step
+        a.metrics[2 * log_slot] = l;
+        a.metrics[2 * log_slot + 1] = hsum;
+        a.state[0] = state0_next;
+        a.state[1] = state1_next;
+    }
+}
+
+// The HELPER wave (wave NW of the 4-wave instances up to hidden 128: 200 VGPRs, so a second wave fits on SIMD 0; NW = 8 would put three
+// waves on a SIMD, KS = 16 needs 264 VGPRs).  A lone wave per SIMD is issue-bound and 12 of the CU's 16 wave slots are empty, so what is
+// wave-uniform and needs no result of the launch leaves the four working waves: the helper loads nothing but scalars, forms the step size
+// of the workgroup's fused update (w_step in a dW1 workgroup, b_step in a head workgroup) and hands it over through LDS at the final
+// barrier; in the lead it also forms the step-log slot and the next state words and, behind the barrier, does the lead's own stretch
+// (loss, hit count, step log, db2), so waves 0..3 of the lead do what a plain head workgroup does.  It touches
+// none of red / tr / rowv / sc[wave], and meets every workgroup barrier the working waves meet.
+// Not in the data-parallel instances: their workgroups WAIT for the peers' slices, and ranks that share a device rely on a waiting 4-wave
+// workgroup (168 VGPRs on each SIMD) leaving room on its CU for a 1 024-thread workgroup of the late rank's first launch (4 waves of 64
+// VGPRs per SIMD: 168 + 256 <= 512).  A second wave on SIMD 0 (2 x 144 + 256 > 512) closes every CU that holds a waiting workgroup to that
+// launch, and four ranks of the 784-64-10 model on one device (3 x 108 waiting workgroups on 256 CUs) then starve the late rank.
+constexpr int tail_helper_waves(int KS, int NW, int DPNR) { return (NW == 4 && KS <= 8 && DPNR == 0) ? 1 : 0; }
+
+template <int NW>
+__device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_role, bool lead, bool any_w, bool any_b, float *h_step,
+                                                 const float (*sc)[36]) {
+    const int lane = threadIdx.x & 63;
+    // the counter / learning rate of the workgroup's fused update: plain scalar loads (nobody writes the counter in this launch)
+    float step = 0.f;
+    if (head_role ? any_b : any_w) {
+        const AdamDev &ad = head_role ? a.b1_adam : a.w1_adam;
+        step = adam_step_size(sload(ad.lr), ad.beta1, ad.beta2, sload(ad.t));   // optim.rs:87-90
+    }
+    // the lead's step-log slot and next state words: they depend on state0 / state1 / capacity / advance alone
+    const bool log = lead && a.metrics;
+    int64_t log_slot = 0, state0_next = 0, state1_next = 0;
+    if (log) {
+        const int64_t state0 = sload(a.state), state1 = sload(a.state + 1);
+        log_slot = tail_log_slot(state0, a.capacity);
+        state0_next = state0 + 1;
+        state1_next = state1 + a.advance;
+    }
+    if (lane == 0) *h_step = step;
+    __syncthreads();                      // the working waves' final barrier
+    if (lead) {
+        if (a.db2 && lane < a.c) {
+            float sum = sc[0][16 + lane];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) sum += sc[w][16 + lane];
+            a.db2[lane] = sum;
+        }
+        if (lane == 0) tail_lead_log<NW>(a, sc, log_slot, state0_next, state1_next);
+#ifdef TH_PROFILE
+        if (lane == 0) tail_prof_end(wall_clock64());
+#endif
+    }
+}
+
 // NW waves per workgroup (4 / 8): the 64-row chunks of a batch are a serial chain per wave (2.7 us each), so batches
 // above 64 rows get more waves instead of more iterations; waves 0..3 finish the tile.
 // DPNR > 0 (th_mlp_tail_dp): data parallel, DPNR >= the communicator's rank count -- every finished slice (a dW1 block; a head workgroup's
 // dW2 tile, db1 and, in the lead, db2) goes through dp_exchange() before it is stored or fed to Adam: what is applied is the MEAN over the
 // ranks, formed in rank order.  Loss and hit count stay this rank's own (the host averages the step logs).
 template <int KS, int TN, bool HAS_DX, int NW, int DPNR = 0>
-__global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
+__global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void mlp_tail_exact_kernel(TailArgs a) {
     constexpr unsigned HID = 16 * KS;
+    constexpr bool HELPER = tail_helper_waves(KS, NW, DPNR) != 0;
+    __shared__ float h_step;                         // HELPER: the step size of the workgroup's fused update
     __shared__ float red[NW][TN][64][4];
     __shared__ float tr[NW][16][17];
     __shared__ float rowv[NW][2][16];
@@ -487,7 +568,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
     DpTicket dp_tk{0u, 0u};
     if constexpr (DPNR > 0) dp_tk = dp_begin(a.dp);   // (two scalar loads, looked at when the slice is ready)
     if (HAS_DX && bid >= a.n_head + a.n_dw) {   // (its own instantiation: the code of a role nobody runs still costs instruction fetches)
-        tail_dx_role<KS, NW>(a, bid - a.n_head - a.n_dw);
+        if (!HELPER || wave < NW) tail_dx_role<KS, NW>(a, bid - a.n_head - a.n_dw);   // (no barriers in this role: the helper just leaves)
         return;
     }
     const bool head_role = bid < a.n_head;
@@ -511,8 +592,15 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
     const unsigned col0 = grp * 16 * TN;
     const bool lead = head_role && tile_m == 0;
     const bool any_w = a.w1_adam.p != nullptr, any_b = a.db1 && a.b1_adam.p != nullptr;
-    const int32_t w_t = any_w ? sload(a.w1_adam.t) : 1, b_t = any_b ? sload(a.b1_adam.t) : 1;
-    const float w_lr = any_w ? sload(a.w1_adam.lr) : 0.f, b_lr = any_b ? sload(a.b1_adam.lr) : 0.f;
+    if constexpr (HELPER) {
+        if (__builtin_amdgcn_readfirstlane(wave) == NW) {
+            tail_helper_wave<NW>(a, head_role, lead, any_w, any_b, &h_step, sc);
+            return;
+        }
+    }
+    // (the instances with a helper wave: the counters / learning rates are the helper's to load)
+    const int32_t w_t = (!HELPER && any_w) ? sload(a.w1_adam.t) : 1, b_t = (!HELPER && any_b) ? sload(a.b1_adam.t) : 1;
+    const float w_lr = (!HELPER && any_w) ? sload(a.w1_adam.lr) : 0.f, b_lr = (!HELPER && any_b) ? sload(a.b1_adam.lr) : 0.f;
 
     // ---- chunk-independent operands ----
     float4 wv[KS];                                   // W2[class r16][16 ks + 4 g4 ..]; rows >= C: a copy of row C-1, masked at the logits
@@ -551,7 +639,8 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
         bm_ = ldg_b(a.b1_adam.m, b1_off);
         bv_ = ldg_b(a.b1_adam.v, b1_off);
     }
-    const int64_t state0 = (lead && a.metrics) ? sload(a.state) : 0, state1 = (lead && a.metrics) ? sload(a.state + 1) : 0;
+    const bool log_here = !HELPER && lead && a.metrics;
+    const int64_t state0 = log_here ? sload(a.state) : 0, state1 = log_here ? sload(a.state + 1) : 0;
 
     floatx4 accdw[TN];
 #pragma unroll
@@ -584,14 +673,15 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
     };
     load_chunk(0);
     TAIL_STAMP(1);
-    // step sizes of the fused updates (optim.rs:87-90): ALU work under the loads' latency (every wave: all finish elements)
-    if (fuse_w) w_step = adam_step_size(w_lr, a.w1_adam.beta1, a.w1_adam.beta2, w_t);
-    if (fuse_b1) b_step = adam_step_size(b_lr, a.b1_adam.beta1, a.b1_adam.beta2, b_t);
+    // step sizes of the fused updates (optim.rs:87-90): ALU work under the loads' latency (every wave: all finish elements) -- NOT hidden
+    // under it (profiles/mlp_step_tails.md), so the instances with a helper wave leave the block to it and read h_step behind the barrier
+    if (!HELPER && fuse_w) w_step = adam_step_size(w_lr, a.w1_adam.beta1, a.w1_adam.beta2, w_t);
+    if (!HELPER && fuse_b1) b_step = adam_step_size(b_lr, a.b1_adam.beta1, a.b1_adam.beta2, b_t);
     // The lead's step-log slot and next state words, here too: they depend on state0 / state1 / capacity / advance alone (scalar loads
     // of the prologue), and behind the final barrier the lead is the launch's last workgroup -- there only the wave-ordered sums,
     // n / B and the stores are left.
     int64_t log_slot = 0, state0_next = 0, state1_next = 0;
-    if (lead && a.metrics) {
+    if (log_here) {
         log_slot = tail_log_slot(state0, a.capacity);
         state0_next = state0 + 1;
         state1_next = state1 + a.advance;
@@ -677,6 +767,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
             for (int i = 0; i < 4; ++i) red[wave][tn][lane][i] = accdw[tn][i];
         __syncthreads();
         TAIL_STAMP(6);
+        if (HELPER && fuse_w) w_step = h_step;
         float outv[TN];
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn) {
@@ -722,6 +813,7 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
     }
     __syncthreads();
     TAIL_STAMP(6);
+    if (HELPER && fuse_b1) b_step = h_step;
     if constexpr (DPNR > 0) {
         // slice tile_m of the launch, two values per thread of waves 0..3: [0] this thread's dW2 element, [1] db1 (threads 0..15) or, in the
         // lead workgroup, db2 (threads 16..16 + C - 1).  Reduced over the ranks, then exactly the single-GPU epilogue on the means.
@@ -791,13 +883,13 @@ __global__ __launch_bounds__(64 * NW) void mlp_tail_exact_kernel(TailArgs a) {
         }
     }
     if (lead) {
-        if (DPNR == 0 && a.db2 && t < C) {
+        if (DPNR == 0 && !HELPER && a.db2 && t < C) {
             float sum = sc[0][16 + t];
 #pragma unroll
             for (int w = 1; w < NW; ++w) sum += sc[w][16 + t];
             a.db2[t] = sum;
         }
-        if (t == 0) {
+        if (!HELPER && t == 0) {
             float n = sc[0][32], hsum = sc[0][33];
 #pragma unroll
             for (int w = 1; w < NW; ++w) {
@@ -847,6 +939,8 @@ static const void *tail_dp_instance(int n_ranks) {
     if (n_ranks <= 4) return (const void *)mlp_tail_exact_kernel<KS, 2, false, NW, 4>;
     return (const void *)mlp_tail_exact_kernel<KS, 2, false, NW, 8>;
 }
+// threads per workgroup of the whole-tile kernel: nw working waves + the helper wave of the instances that have one
+static int tail_exact_threads(int ks, int nw, bool dp) { return 64 * (nw + tail_helper_waves(ks, nw, dp ? 2 : 0)); }
 static const void *tail_dp_kernel(int batch, int hidden, int n_ranks) {
     const bool nw8 = batch > 64;
     if (hidden == 64) return nw8 ? tail_dp_instance<4, 8>(n_ranks) : tail_dp_instance<4, 4>(n_ranks);
@@ -860,7 +954,7 @@ extern "C" int th_mlp_tail_dp_supported(const th_comm *comm, th_ctx *ctx, int ba
     if (grid > DP_MAX_SLOTS) return 0;
     if (comm_dp_sharing(comm) > 1) {       // ranks on ONE device (a test box): comm_dp_shared_fits (comm.hip) has the two conditions and why
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tail_dp_kernel(batch, hidden, dp->n_ranks), batch > 64 ? 512 : 256, 0) != hipSuccess) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tail_dp_kernel(batch, hidden, dp->n_ranks), tail_exact_threads(hidden / 16, batch > 64 ? 8 : 4, true), 0) != hipSuccess) {
             (void)hipGetLastError();
             return 0;
         }
@@ -913,16 +1007,16 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
         a.dp_tick = d_tick;
         const void *fn = tail_dp_kernel(batch, hidden, dp->n_ranks);
         void *args[] = {&a};
-        TH_HIP(hipLaunchKernel(fn, dim3(grid), dim3(64 * nw), args, 0, ctx->stream));
+        TH_HIP(hipLaunchKernel(fn, dim3(grid), dim3(tail_exact_threads(hidden / 16, nw, true)), args, 0, ctx->stream));
         comm_dp_count_launch(comm);
         return 0;
     }
 #define TH_TAIL_LAUNCH(KS)                                                                                            \
     do {                                                                                                              \
         if (exact && d_dx && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
-        else if (exact && d_dx) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 4>), dim3(grid), dim3(256), 0, ctx->stream, a);     \
+        else if (exact && d_dx) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 4>), dim3(grid), dim3(tail_exact_threads(KS, 4, false)), 0, ctx->stream, a);     \
         else if (exact && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
-        else if (exact) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 4>), dim3(grid), dim3(256), 0, ctx->stream, a);     \
+        else if (exact) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 4>), dim3(grid), dim3(tail_exact_threads(KS, 4, false)), 0, ctx->stream, a);     \
         else hipLaunchKernelGGL((mlp_tail_kernel<KS, TN>), dim3(grid), dim3(256), 0, ctx->stream, a);                 \
     } while (0)
     if (exact && hidden == 32) TH_TAIL_LAUNCH(2);

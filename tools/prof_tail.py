@@ -8,6 +8,11 @@ Per role (lead head workgroup = block 0, plain head workgroups = blocks 1..7, dW
   body   stamp 7 - stamp 0 of the workgroup
   end    stamp 7 - the earliest stamp 0 of the launch (when the workgroup is done, on the launch's own clock)
   step   stamp 2 - stamp 1 (the step-size block: what of it is NOT hidden under the loads shows up as body time)
+  issue  stamp 1 - stamp 0 (roles, addresses and the issue of every load)
+  wait   stamp 3 - stamp 2 (the load wait that is left behind the step-size block)
+  math   stamp 5 - stamp 3 (logits, softmax, dH, the dW1 / dW2 products)
+  sync   stamp 6 - stamp 5 (partial sums to LDS and the final barrier)
+In the instances with a helper wave the lead's stamp 7 is the later of thread 0's and the helper's.
 
 The shape is fixed (784-128-10, batch 64: 8 head + 200 dW1 workgroups); the role split below and the profile build's 256-workgroup
 stamp table hold for that launch only.
@@ -81,7 +86,11 @@ for it in range(args.samples + 10):
     start = s[:, 0].min()
     body, end, stepsz = s[:, 7] - s[:, 0], s[:, 7] - start, s[:, 2] - s[:, 1]
     dw = slice(N_HEAD, N_BLOCKS)
-    rows.append(dict(lead_body=body[0], lead_end=end[0], lead_step=stepsz[0], lead_behind_barrier=s[0, 7] - s[0, 6],
+    row = {}
+    for name, hi, lo in (("issue", 1, 0), ("wait", 3, 2), ("math", 5, 3), ("sync", 6, 5)):
+        d = s[:, hi] - s[:, lo]
+        row.update({f"lead_{name}": d[0], f"head_{name}": np.median(d[1:N_HEAD]), f"dw_{name}": np.median(d[dw])})
+    rows.append(dict(row, lead_body=body[0], lead_end=end[0], lead_step=stepsz[0], lead_behind_barrier=s[0, 7] - s[0, 6],
                      head_body=np.median(body[1:N_HEAD]), head_end=np.median(end[1:N_HEAD]), head_behind_barrier=np.median(s[1:N_HEAD, 7] - s[1:N_HEAD, 6]),
                      dw_body=np.median(body[dw]), dw_end=np.median(end[dw]), dw_end_max=end[dw].max(), dw_step=np.median(stepsz[dw]),
                      launch=end.max(), last_is_lead=float(end.argmax() == 0)))
