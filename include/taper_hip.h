@@ -125,6 +125,10 @@ int th_linear_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *
 int th_linear_fwd_ex(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_b, float *d_y,
                      int batch, int in_features, int out_features, int relu,
                      const th_adam_slice *extra, int n_extra, int32_t *d_tick);
+/* th_linear_fwd_ex's latency-bound launch may give a workgroup a SUB-TILE of a 16 x 16 MFMA tile (more workgroups, fewer bytes through each
+ * CU's L1; same bits).  on = 0: the 16 x 16 launch whatever the shape -- for contexts whose device is shared by several ranks' waiting
+ * workgroups (th_comm_sharing), where nothing measures a gain.  Default 1. */
+int th_linear_fwd_ex_set_subtiles(th_ctx *ctx, int on);
 /* backward of the three reference nodes at once (ops.rs:238-294,
  * tensor.rs:574-587, 674-694); any of d_dx, d_dw, d_db may be NULL (input
  * without requires_grad: ops.rs:243).  d_relu_y (nullable): the layer's

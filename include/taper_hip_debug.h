@@ -55,6 +55,11 @@ int th_debug_qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k
  * of that operand; else both = 16-byte rows and whole quads), K slices, k positions per slice, workgroups, 1 if a split launch hands its
  * slices to the XCDs one by one, reduce pass (0: none; 1: splitk_reduce4; 2: splitk_reduce), tile rows, tile columns}.  k == 0 is a shape. */
 int th_debug_sgemm_plan(int trans_a, int trans_b, int m, int n, int k, int a_misalign_bytes, int b_misalign_bytes, int c_misalign_bytes, int *out12);
+/* what th_linear_fwd_ex would launch for this shape with the context's sub-tile switch on (1) or off (0) -- pure host code, no context, the
+ * function the launch itself consumes: out8 = {1 if the one-launch path takes it (0: slices, tick and th_linear_fwd as launches of their own;
+ * the rest is 0 then), sub-tile rows, sub-tile columns (16 x 16: the whole MFMA tile), waves per workgroup, K chunks per wave (1), grid.x
+ * (sub-tile columns), grid.y (sub-tile rows + the spare row), 1 if every XCD takes the sub-tiles of one 32 x 32 block of the output}. */
+int th_debug_linear_fwd_ex_plan(int batch, int in_features, int out_features, int subtiles, int *out8);
 
 /* post-mortem of the in-launch exchange (csrc/dp_dev.h) on stderr: the communicator's state words and, per parity and source block of the
  * receive region, the slots that hold words.  Trainer::check_comm calls it under TAPER_DP_POSTMORTEM=1 when a time-out is reported. */

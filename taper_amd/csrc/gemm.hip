@@ -63,24 +63,55 @@ struct SmallArgs {
     int xcd_blocks = 0;   // sgemm_small16_tick only: 8 x 4 tiles handed out as one 2 x 2 block per XCD
 };
 
-template <bool A_KC, bool B_KC, int NW, bool MASKED>
+#ifdef TH_PROFILE
+// stamps 0..5 of th_linear_fwd_ex's launch (tools/prof_fwd.py): per workgroup, lane 0 of wave 0 ([0]) and of the last wave that owns a whole
+// chunk ([1]); 100 MHz wall clock.  Nothing else reads the buffer.
+constexpr int kFwdProfBlocks = 320;
+__device__ long long g_fwd_prof[kFwdProfBlocks][2][6];
+#define FWD_STAMP(i)                                                                          \
+    do {                                                                                      \
+        if constexpr (STAMPED) {                                                              \
+            __builtin_amdgcn_sched_barrier(0);                                                \
+            if (stamp_slot >= 0) g_fwd_prof[stamp_blk][stamp_slot][i] = wall_clock64();       \
+            __builtin_amdgcn_sched_barrier(0);                                                \
+        }                                                                                     \
+    } while (0)
+// the value must be in its register: the compiler waits for the load (or the MFMA) that writes it in front of this point
+#define FWD_LANDED(v) do { if constexpr (STAMPED) asm volatile("" ::"v"(v)); } while (0)
+#else
+#define FWD_STAMP(i) do { } while (0)
+#define FWD_LANDED(v) do { } while (0)
+#endif
+
+// RM x RN (powers of two up to 16): the workgroup owns that SUB-TILE of a 16 x 16 MFMA tile (th_linear_fwd_ex).  Every output element of
+// v_mfma_f32_16x16x4_f32 is its own FMA chain over k (experiments/mfma_fma_chain.hip), so feeding RM rows of A and RN of B into the same
+// MFMAs over the same chunks, and dropping the C/D elements outside, gives the bits of the 16 x 16 form.  Lanes past the sub-tile alias one of
+// its rows (no further cache line) and supply zeros; the C/D elements outside the sub-tile are neither summed nor stored.
+template <bool A_KC, bool B_KC, int NW, bool MASKED, int RM = 16, int RN = 16, bool STAMPED = false>
 __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, int tile_col, int zslice, float (*red)[64][4]) {
+    constexpr bool SUB = RM < 16 || RN < 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
-    const int row0 = tile_row * 16, col0 = tile_col * 16;
+    const int row0 = tile_row * RM, col0 = tile_col * RN;
     const int kbeg_slice = zslice * p.kslice;
     const int kend_slice = min(p.k, kbeg_slice + p.kslice);
     // split the slice between the NW waves in multiples of 16
     const int kwave = ((kend_slice - kbeg_slice + 16 * NW - 1) / (16 * NW)) * 16;
     const int kbeg = kbeg_slice + wave * kwave;
     const int kend = min(kend_slice, kbeg + kwave);
+#ifdef TH_PROFILE
+    const int stamp_blk = blockIdx.x + gridDim.x * blockIdx.y;
+    const int stamp_last = max((kend_slice - kbeg_slice) / kwave - 1, 0) % NW;
+    const int stamp_slot = (lane != 0 || stamp_blk >= kFwdProfBlocks) ? -1 : wave == 0 ? 0 : wave == stamp_last ? 1 : -1;
+#endif
+    FWD_STAMP(0);
 
-    const int arow = row0 + r, bcol = col0 + r;
-    const bool a_ok = arow < p.m, b_ok = bcol < p.n;
-    const long a_off = (long)(a_ok ? arow : 0) * p.a_rs;
+    const int arow = row0 + (SUB ? r & (RM - 1) : r), bcol = col0 + (SUB ? r & (RN - 1) : r);
+    const bool a_ok = (!SUB || r < RM) && arow < p.m, b_ok = (!SUB || r < RN) && bcol < p.n;
+    const long a_off = (long)(a_ok ? arow : SUB ? row0 : 0) * p.a_rs;
     const float *ap = p.A + a_off;
     const float *mp = MASKED ? p.Amask + a_off : nullptr;
-    const float *bp = p.B + (long)(b_ok ? bcol : 0) * p.b_cs;
+    const float *bp = p.B + (long)(b_ok ? bcol : SUB ? col0 : 0) * p.b_cs;
 
     // These shapes are latency-bound: after a kernel boundary every dependent
     // global round trip costs ~0.5-1 us.  So (a) everything the epilogue will
@@ -94,7 +125,8 @@ __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, i
     const int ecol = col0 + (lane & 15);
     const bool fuse_adam = p.ep.adam.p != nullptr && p.partial == nullptr;
     const int erow = row0 + (lane >> 4) * 4 + wave;     // meaningful for wave < 4
-    const bool e_ok = wave < 4 && erow < p.m && ecol < p.n;
+    const bool e_sub = !SUB || ((lane >> 4) * 4 + wave < RM && (lane & 15) < RN);   // the C/D elements of the sub-tile
+    const bool e_ok = wave < 4 && erow < p.m && ecol < p.n && e_sub;
     const long e_ix = e_ok ? (long)erow * p.n + ecol : 0;
     float e_bias = 0.f, e_cold = 0.f, e_p = 0.f, e_m = 0.f, e_v = 0.f, e_step = 0.f;
     if (e_ok) {
@@ -139,6 +171,12 @@ __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, i
                 for (int s = 0; s < 4; ++s) bv[c][s] = (kb + s < kend) ? bp[(long)(kb + s) * p.b_rs] : 0.f;
             }
         }
+        if (kk0 == kbeg) {
+            FWD_STAMP(1);
+            FWD_LANDED(av[0][0]);
+            FWD_LANDED(bv[0][0]);
+            FWD_STAMP(2);
+        }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             if (kk0 + 16 * c >= kend) break;  // wave-uniform
@@ -150,13 +188,18 @@ __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, i
             }
         }
     }
+    FWD_LANDED(acc[0]);
+    FWD_STAMP(3);
 
     // deterministic in-workgroup reduction: every wave parks its 4 partial sums; wave e adds element e
     // of waves 0..NW-1 in wave order
+    if (!SUB || (g * 4 < RM && r < RN)) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
+        for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
+    }
     __syncthreads();
-    if (wave < 4) {
+    FWD_STAMP(4);
+    if (wave < 4 && e_sub) {
         float sum = red[0][lane][wave];
         for (int w = 1; w < NW; ++w) sum += red[w][lane][wave];
         // C/D map of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + i  (here i = wave)
@@ -181,6 +224,10 @@ __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, i
             }
         }
     }
+#ifdef TH_PROFILE
+    if constexpr (STAMPED) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): stamp 5 is the store's return, not its issue
+#endif
+    FWD_STAMP(5);
 }
 
 // grid = (tiles_n, tiles_m, kz); block = 64 * NW
@@ -194,19 +241,25 @@ __global__ __launch_bounds__(64 * NW) void sgemm_small16(SmallArgs p) {
 // carried Adam slices with the step counter as it stands and then opens the next step (t += 1).
 // The tiles are this launch's tail, not that spare workgroup: measured in situ it adds 0.08-0.11 us to the step over plain tiles
 // (tools/step_tails_probe.py, profiles/mlp_step_tails.md), and a one-round-trip rewrite of it gained nothing that probe can tell from noise -- not kept.
-template <bool A_KC, bool B_KC, int NW>
+template <bool A_KC, bool B_KC, int NW, int RM = 16, int RN = 16>
 __global__ __launch_bounds__(64 * NW) void sgemm_small16_tick(SmallArgs p, AdamSlices x, int32_t *tick) {
     __shared__ float red[NW][64][4];
     if (blockIdx.y + 1 < gridDim.y) {
         int tm = blockIdx.y, tn = blockIdx.x;
         if (p.xcd_blocks) {
-            // 8 x 4 tiles (the MNIST MLP's layer 1 at batch 64): block b runs on XCD b % 8; give every XCD a 2 x 2 block of tiles instead of
-            // one column of 4, so its L2 fetches 2 row tiles of X and 2 of W (200 KB) instead of all of X and 1 of W (250 KB)
+            // 64 x 128 outputs (the MNIST MLP's layer 1 at batch 64): block b runs on XCD b % 8; give every XCD the (sub-)tiles of one 32 x 32
+            // block of H instead of a column of them, so its L2 fetches 32 rows of X and 32 of W (200 KB) instead of all of X and 16 of W (250 KB)
+            constexpr int SBM = 32 / RM, SBN = 32 / RN;
+            static_assert(SBN == 2 || SBN == 4, "sub-tiles of 16 or 8 columns");
             const int b = blockIdx.x + gridDim.x * blockIdx.y, q = b & 7, j = b >> 3;
-            tm = 2 * (q >> 2) + (j >> 1);
-            tn = 2 * (q & 3) + (j & 1);
+            tm = SBM * (q >> 2) + (j >> (SBN == 4 ? 2 : 1));
+            tn = SBN * (q & 3) + (j & (SBN - 1));
         }
-        small16_body<A_KC, B_KC, NW, false>(p, tm, tn, 0, red);
+#ifdef TH_PROFILE
+        small16_body<A_KC, B_KC, NW, false, RM, RN, true>(p, tm, tn, 0, red);
+#else
+        small16_body<A_KC, B_KC, NW, false, RM, RN>(p, tm, tn, 0, red);
+#endif
         return;
     }
     if (blockIdx.x == 0) adam_slices_then_tick(x, tick);
@@ -1239,6 +1292,32 @@ int linear_fwd_partials(th_ctx *ctx, const float *x, const float *w, int m, int 
     return 0;
 }
 
+// Every host decision of th_linear_fwd_ex's one-launch path (the launch consumes it; th_debug_linear_fwd_ex_plan reports it): the sub-tile a
+// workgroup owns, its waves, the grid (tile rows + the spare row) and the XCD map.
+struct FwdExPlan {
+    int one_launch;      // 0: the slices, the tick and th_linear_fwd as launches of their own (the rest is 0)
+    int rm, rn;          // sub-tile rows x columns (16 x 16: the whole MFMA tile)
+    int waves;           // per workgroup: 4 or 16; every wave owns one K chunk
+    int grid_x, grid_y;  // grid_y - 1 rows of (sub-)tiles and the spare row
+    int xcd_blocks;      // 64 x 128 outputs: every XCD takes the (sub-)tiles of one 32 x 32 block
+};
+static FwdExPlan fwd_ex_plan(int m, int n, int k, bool subtiles) {
+    FwdExPlan pl{};
+    const long tiles = (long)ceil_div(m, 16) * ceil_div(n, 16);
+    if (!(m > 0 && n > 0 && k > 0 && !gemm_is_big(m, n, k) && !(tiles < 64 && k >= 2048))) return pl;
+    pl.one_launch = 1;
+    pl.rm = pl.rn = 16;
+    pl.waves = (tiles < 256 && k >= 256) ? 16 : 4;
+    // 8 x 8 sub-tiles: four times the workgroups, half the bytes through each CU's L1 -- where it was measured to gain
+    // (profiles/mlp_fwd_subtiles.md): the 16-wave instance with ONE round of loads per wave (k <= 1024) on at most 64 x 128 outputs, i.e.
+    // up to 128 sub-tiles.  4-row sub-tiles (256 of them at 64 x 128) lost 2.7 us there; batch 128 is not measured and keeps 16 x 16.
+    if (subtiles && pl.waves == 16 && k <= 1024 && m <= 64 && n <= 128) pl.rm = pl.rn = 8;
+    pl.grid_x = ceil_div(n, pl.rn);
+    pl.grid_y = ceil_div(m, pl.rm) + 1;
+    pl.xcd_blocks = pl.grid_x == 128 / pl.rn && pl.grid_y == 64 / pl.rm + 1;
+    return pl;
+}
+
 }  // namespace th
 
 using namespace th;
@@ -1291,16 +1370,17 @@ int th_linear_fwd_ex(th_ctx *ctx, const float *d_x, const float *d_w, const floa
     for (int i = 0; i < n_extra; ++i)
         TH_REQUIRE(extra[i].f.d_p != d_w && extra[i].f.d_p != d_b, "th_linear_fwd_ex: a carried slice must not alias what this launch reads");
     const int m = batch, n = out_features, k = in_features;
-    const long tiles = (long)ceil_div(m, 16) * ceil_div(n, 16);
-    // the latency-bound case this entry exists for: 16x16 tiles, no grid-level K split -> ONE launch
-    if (m > 0 && n > 0 && k > 0 && !gemm_is_big(m, n, k) && !(tiles < 64 && k >= 2048)) {
+    const FwdExPlan pl = fwd_ex_plan(m, n, k, ctx->fwd_subtiles != 0);
+    // the latency-bound case this entry exists for: 16x16 MFMA tiles, no grid-level K split -> ONE launch
+    if (pl.one_launch) {
         SmallArgs p{d_x, nullptr, d_w, d_y, nullptr, m, n, k, k, 1, 1, k, (k + 15) / 16 * 16, 0, 0, make_ep(1.0f, 0.0f, d_b, relu)};
         p.a_vec = aligned16(d_x) && (k % 4 == 0);
         p.b_vec = aligned16(d_w) && (k % 4 == 0);
         const AdamSlices x = make_adam_slices(extra, n_extra, ctx);
-        const dim3 grid(ceil_div(n, 16), ceil_div(m, 16) + 1, 1);
-        p.xcd_blocks = grid.x == 8 && grid.y == 5;
-        if (tiles < 256 && k >= 256) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
+        const dim3 grid(pl.grid_x, pl.grid_y, 1);
+        p.xcd_blocks = pl.xcd_blocks;
+        if (pl.rm == 8) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16, 8, 8>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
+        else if (pl.waves == 16) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
         else hipLaunchKernelGGL((sgemm_small16_tick<true, true, 4>), grid, dim3(256), 0, ctx->stream, p, x, d_tick);
         TH_LAUNCH_CHECK();
         return 0;
@@ -1311,6 +1391,31 @@ int th_linear_fwd_ex(th_ctx *ctx, const float *d_x, const float *d_w, const floa
         if (int rc = th_adam_tick(ctx, d_tick)) return rc;
     return th_linear_fwd(ctx, d_x, d_w, d_b, d_y, batch, in_features, out_features, relu);
 }
+
+int th_linear_fwd_ex_set_subtiles(th_ctx *ctx, int on) {
+    TH_REQUIRE(ctx, "th_linear_fwd_ex_set_subtiles: null ctx");
+    ctx->fwd_subtiles = on != 0;
+    return 0;
+}
+
+int th_debug_linear_fwd_ex_plan(int batch, int in_features, int out_features, int subtiles, int *out8) {
+    TH_REQUIRE(out8, "th_debug_linear_fwd_ex_plan: null argument");
+    TH_REQUIRE(batch >= 1 && in_features >= 1 && out_features >= 1, "th_debug_linear_fwd_ex_plan: bad shape batch=%d in=%d out=%d", batch,
+               in_features, out_features);
+    const FwdExPlan pl = fwd_ex_plan(batch, out_features, in_features, subtiles != 0);
+    const int out[8] = {pl.one_launch, pl.rm, pl.rn, pl.waves, 1, pl.grid_x, pl.grid_y, pl.xcd_blocks};
+    std::copy(out, out + 8, out8);
+    return 0;
+}
+
+#ifdef TH_PROFILE
+int th_debug_fwd_prof(th_ctx *ctx, long long *h_out, int n_blocks) {
+    TH_REQUIRE(ctx && h_out && n_blocks >= 1 && n_blocks <= th::kFwdProfBlocks, "th_debug_fwd_prof: bad argument");
+    TH_HIP(hipStreamSynchronize(ctx->stream));
+    TH_HIP(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(th::g_fwd_prof), (size_t)n_blocks * 12 * sizeof(long long)));
+    return 0;
+}
+#endif
 
 }  // extern "C" (reopened below)
 

@@ -463,6 +463,8 @@ void Trainer::enqueue_steps(const float *d_images, const float *d_labels, const 
         Guard(const uint32_t *w, uint32_t *step) { TH(th_ctx_set_update_guard(Device::ctx(), w, step)); }
         ~Guard() { th_ctx_set_update_guard(Device::ctx(), nullptr, nullptr); }
     } guard(comm && comm->is_p2p() ? comm->error_word() : nullptr, comm && comm->is_p2p() ? comm->step_word() : nullptr);
+    // ranks sharing this device: their waiting workgroups occupy CUs, and the forward launch's sub-tile forms were measured on a free chip only
+    TH(th_linear_fwd_ex_set_subtiles(Device::ctx(), !(comm && comm->ranks_on_this_device() > 1)));
     const StepPlan plan = plan_step(batch, d_indices ? n_indices : (int64_t)batch);
     if (plan.form == StepForm::Mlp2Rows) {
         // the step reads its rows where they lie: through the index vector at the device cursor (every step's log advances it), or the
