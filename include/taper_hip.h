@@ -452,6 +452,25 @@ int th_qconv_i8_cpitch(int c_in);   /* the channel pitch a caller should use: c_
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                        const int8_t *d_qb, const float *d_bparams, int relu, float *d_y);
+/* ---- activations that stay int8 between two static convolutions ----
+ * th_conv2d_q8q8_fwd_codes: th_conv2d_q8q8_fwd's product and its f32 value v (the same operations, bias and ReLU included), then the
+ * activation codec with the NEXT layer's scale instead of a store of v:
+ *     d_qy[b][oh][ow][co] = clamp(round(v / *d_yscale) as i32, -128, 127)   (NaN -> 0; bytes c_out .. cpitch_y - 1 of every pixel are 0)
+ *     d_ypixsum[b][oh][ow] = the int32 sum of the pixel's c_out codes        (nullable: a pool that follows makes its own)
+ * -- bit for bit what th_quantize_act_nhwc_int8 makes of th_conv2d_q8q8_fwd's output.  One workgroup must see every channel of a pixel:
+ * c_out above th_qconv_i8_chain_max_cout() (128) is refused before the launch, with th_conv2d_q8q8_fwd's refusals, a d_qy off a 16-byte
+ * boundary and a cpitch_y that is no multiple of 16 or below c_out. */
+int th_qconv_i8_chain_max_cout(void);
+int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                             const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                             const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum);
+/* The max-pool on channel-last codes [n][h][w][cpitch] -> [n][h_out][w_out][cpitch], h_out = (h + 2 pad_h - k_h) / s_h + 1: every byte the
+ * maximum over the in-image taps from -128 (the code of the float pool's -inf start), bytes c .. cpitch - 1 written 0, d_ypixsum the sum
+ * over the c channels.  The codec never decreases in its argument, so this is the code of th_maxpool2d_fwd's result on finite values.
+ * Refused before a launch: a null argument, code pointers off a 16-byte boundary, a cpitch that is no multiple of 16 or below c, a shape,
+ * window or stride below 1, a negative padding, an empty output map.  n == 0 returns 0.  Neither call allocates, synchronises or reads back. */
+int th_maxpool2d_nhwc_int8(th_ctx *ctx, const int8_t *d_q, int n, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w,
+                           int8_t *d_qy, int *d_ypixsum);
 
 /* ---- quantization-aware training: fake quantization (src/quantization/fake_quantize.rs, csrc/fake_quant.hip) ---- */
 /* A weight list through the storage codecs and back: TH_QTYPE_INT8 is th_quantize_int8 + th_dequantize_int8 (finite min / max ->

@@ -167,6 +167,15 @@ int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib,
  * packed codes of tp_module_quantize (the channel-last copy is internal); tp_qmodule_act_scales lists one scale per static layer, Linear
  * or conv, in layer order.  Refused in addition, before anything is allocated: in_channels * k_h * k_w > 65 536. */
 int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
+/* tp_module_quantize_static_conv with the activations int8 from one static conv to the next: calibration, packing, refusals, tensors, scales
+ * and storage bytes are the same, and so is every output bit on finite activations; only the launches differ.  A link is a static conv A
+ * of at most th_qconv_i8_chain_max_cout() output channels (its own or a following ReLU folded in), optionally ONE MaxPool2d, then a
+ * static conv B inside the same Sequential: A's product writes B's codes (th_conv2d_q8q8_fwd_codes with B's scale), the pool runs on the
+ * codes (th_maxpool2d_nhwc_int8) and B skips its codec -- no f32 tensor exists at the boundary.  Anything else between two convs (a ReLU
+ * behind the pool, a second pool, any other layer, a weight-only conv, a wider A) runs as in tp_module_quantize_static_conv's twin. */
+int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
+/* the layer boundaries a forward crosses in int8 (the links above); 0 for every twin but tp_module_quantize_static_chain's */
+int tp_qmodule_chain_links(const tp_qmodule *q, int *out);
 /* the calibrated activation scales in layer order: *n = their count (0 for a weight-only twin), the first min(*n, cap) into h_scales (nullable) */
 int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n);
 int tp_qmodule_free(tp_qmodule *q);

@@ -338,6 +338,16 @@ class Module:
         tp_check(host.tp_module_quantize_static_conv(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_conv")
         return QuantizedModule(h.value)
 
+    def quantize_static_chain(self, calib):
+        """quantize_static_conv whose activations stay int8 from one static conv to the next: a conv of at most 128 output channels writes
+        the next conv's codes from its epilogue, and one MaxPool2d between the two runs on the codes.  The same scales, tensors and, on
+        finite activations, the same output bits as quantize_static_conv's twin; chain_links() counts the boundaries crossed in int8."""
+        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
+        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
+        h = _p()
+        tp_check(host.tp_module_quantize_static_chain(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_chain")
+        return QuantizedModule(h.value)
+
 
 class QuantizedModule:
     """nn.rs:20-23: forward from the packed codes (no tape node, the output needs no gradient)"""
@@ -361,6 +371,12 @@ class QuantizedModule:
     def storage_bytes(self) -> int:
         n = C.c_size_t()
         tp_check(host.tp_qmodule_storage_bytes(self._h, C.byref(n)), "QuantizedModule::storage_bytes")
+        return n.value
+
+    def chain_links(self) -> int:
+        """the layer boundaries a forward crosses in int8: 0 for every twin but quantize_static_chain's"""
+        n = C.c_int()
+        tp_check(host.tp_qmodule_chain_links(self._h, C.byref(n)), "QuantizedModule::chain_links")
         return n.value
 
     def act_scales(self) -> np.ndarray:

@@ -310,6 +310,24 @@ int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *c
     *out = h.release();
     TP_END
 }
+int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
+    TP_BEGIN
+    TAPER_ASSERT(m && out, "tp_module_quantize_static_chain: null argument");
+    std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
+    for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
+    auto h = std::make_unique<tp_qmodule>();
+    h->q = quantize_static(*m->m, c, /*convs=*/true, /*chain=*/true);
+    h->q->tensors(&h->tensors);
+    h->q->act_scales(&h->act_scales);
+    *out = h.release();
+    TP_END
+}
+int tp_qmodule_chain_links(const tp_qmodule *q, int *out) {
+    TP_BEGIN
+    TAPER_ASSERT(q && out, "tp_qmodule_chain_links: null argument");
+    *out = q->q->chain_links();
+    TP_END
+}
 int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n) {
     TP_BEGIN
     TAPER_ASSERT(q && n, "tp_qmodule_act_scales: null argument");

@@ -32,6 +32,7 @@ class QPass : public QuantizedModule {
     explicit QPass(std::shared_ptr<Module> m) : m_(std::move(m)) {}
     Tensor forward(const Tensor &x) const override { return m_->forward(x); }
     bool is_relu() const { return dynamic_cast<const ReLU *>(m_.get()) != nullptr; }
+    const MaxPool2d *max_pool() const { return dynamic_cast<const MaxPool2d *>(m_.get()); }
 
    private:
     std::shared_ptr<Module> m_;
@@ -90,6 +91,17 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
     std::shared_ptr<Buffer> act_;
 };
 
+// an activation as channel-last int8 codes [n][h][w][cpitch] with the int32 sum of every pixel's codes: what a static conv's product reads
+struct QCodes {
+    std::shared_ptr<Buffer> q, sums;   // (pooled: they go back when the last holder lets go)
+    size_t n = 0, c = 0, h = 0, w = 0, cpitch = 0;
+    int8_t *codes() const { return reinterpret_cast<int8_t *>(q->d); }
+    int *pixsum() const { return reinterpret_cast<int *>(sums->d); }
+    static QCodes alloc(size_t n, size_t c, size_t h, size_t w, size_t cpitch) {
+        return QCodes{Buffer::alloc(std::max<size_t>(n * h * w * cpitch / 4, 1)), Buffer::alloc(std::max<size_t>(n * h * w, 1)), n, c, h, w, cpitch};
+    }
+};
+
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
    public:
     // The integer product is a convolution, so it stands in for the float layer only where the float path is one: 3x3, stride 1, one
@@ -114,23 +126,44 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         act_ = Buffer::alloc(3);   // {finite min, finite max} of the calibration inputs, then the scale
     }
     bool is_static() const { return act_ != nullptr; }
-    // codes and pixel sums of x (pooled, returned when this scope ends), then the integer product; relu: the layer's own or a following one
-    Tensor forward_static(const Tensor &x, bool relu) const {
+    size_t out_channels() const { return w_.shape[0]; }
+    // the codec: codes and pixel sums of x with this layer's scale
+    QCodes encode(const Tensor &x) const {
         const Shape &ws = w_.shape;
         TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == ws[1], "QuantizedConv2d: input must be [batch, in_channels, h, w]");
-        const size_t n = x.shape()[0], h = x.shape()[2], w = x.shape()[3];
+        QCodes in = QCodes::alloc(x.shape()[0], ws[1], x.shape()[2], x.shape()[3], cpitch_);
+        TH(th_quantize_act_nhwc_int8(Device::ctx(), x.dptr(), (int)in.n, (int)in.c, (int)in.h, (int)in.w, act_->d + 2, in.codes(), (int)cpitch_, in.pixsum()));
+        return in;
+    }
+    // The integer product on codes made with this layer's scale; relu: the layer's own or a following one.  next == nullptr: f32 NCHW
+    // into *y.  Otherwise the output as the codes of `next` (its scale, its pitch) into *qy, without pixel sums when `sums` is false (a
+    // pool that follows makes them).
+    void product(const QCodes &in, bool relu, Tensor *y, const QConv *next = nullptr, QCodes *qy = nullptr, bool sums = true) const {
+        const Shape &ws = w_.shape;
+        TAPER_ASSERT(in.c == ws[1] && in.cpitch == cpitch_, "QuantizedConv2d: input must be [batch, in_channels, h, w]");
         const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
-        TAPER_ASSERT(h + 2 * ph >= ws[2] && w + 2 * pw >= ws[3], "QuantizedConv2d: the kernel is larger than the padded input");
-        const size_t ho = (h + 2 * ph - ws[2]) / sh + 1, wo = (w + 2 * pw - ws[3]) / sw + 1;
-        Tensor y = Tensor::empty({n, ws[0], ho, wo});
-        auto qx = Buffer::alloc(std::max<size_t>(n * h * w * cpitch_ / 4, 1)), ps = Buffer::alloc(std::max<size_t>(n * h * w, 1));
+        TAPER_ASSERT(in.h + 2 * ph >= ws[2] && in.w + 2 * pw >= ws[3], "QuantizedConv2d: the kernel is larger than the padded input");
+        const size_t ho = (in.h + 2 * ph - ws[2]) / sh + 1, wo = (in.w + 2 * pw - ws[3]) / sw + 1;
+        const int8_t *qb = b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr;
+        const float *bp = b_ ? b_->params->d : nullptr;
+        const int fold = relu || geom_->fuse_relu ? 1 : 0;
         th_ctx *ctx = Device::ctx();
-        TH(th_quantize_act_nhwc_int8(ctx, x.dptr(), (int)n, (int)ws[1], (int)h, (int)w, act_->d + 2, reinterpret_cast<int8_t *>(qx->d), (int)cpitch_,
-                                     reinterpret_cast<int *>(ps->d)));
-        TH(th_conv2d_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)cpitch_, reinterpret_cast<const int *>(ps->d), act_->d + 2, (int)n, (int)ws[1],
-                              (int)h, (int)w, reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d,
-                              b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu || geom_->fuse_relu ? 1 : 0,
-                              y.dptr()));
+        if (!next) {
+            *y = Tensor::empty({in.n, ws[0], ho, wo});
+            TH(th_conv2d_q8q8_fwd(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_->d + 2, (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                  reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, qb, bp, fold,
+                                  y->dptr()));
+            return;
+        }
+        *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
+        TH(th_conv2d_q8q8_fwd_codes(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_->d + 2, (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                    reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, qb, bp, fold,
+                                    next->act_->d + 2, qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
+    }
+    // two launches: the codec (its buffers pooled, returned when this scope ends), then the product
+    Tensor forward_static(const Tensor &x, bool relu) const {
+        Tensor y;
+        product(encode(x), relu, &y);
         return y;
     }
     void act_scales(std::vector<const float *> *out) const override {
@@ -183,9 +216,44 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     size_t cpitch_ = 0;
 };
 
+// MaxPool2d on codes: a maximum commutes with the codec, so these are the codes of the pooled float map
+QCodes max_pool_codes(const QCodes &in, const MaxPool2d &mp) {
+    const std::pair<int, int> k = mp.kernel, s = mp.stride.first == 0 ? mp.kernel : mp.stride, p = mp.padding;   // (Tensor::max_pool2d's default)
+    TAPER_ASSERT(k.first > 0 && k.second > 0 && in.h + 2 * p.first >= (size_t)k.first && in.w + 2 * p.second >= (size_t)k.second, "max_pool2d: bad geometry");
+    QCodes out = QCodes::alloc(in.n, in.c, (in.h + 2 * p.first - k.first) / s.first + 1, (in.w + 2 * p.second - k.second) / s.second + 1, in.cpitch);
+    TH(th_maxpool2d_nhwc_int8(Device::ctx(), in.codes(), (int)in.n, (int)in.c, (int)in.h, (int)in.w, (int)in.cpitch, k.first, k.second, s.first, s.second,
+                              p.first, p.second, out.codes(), out.pixsum()));
+    return out;
+}
+
 class QSequential : public QuantizedModule {   // nn.rs:153-177
    public:
     std::vector<std::unique_ptr<QuantizedModule>> layers;
+    bool chain = false;   // quantize_static's chain: activations stay int8 across a link
+    // A static conv's place in the list: `after` = the first layer behind it and its folded ReLU; with `chain`, whether a link starts
+    // here -- `pool` (or nullptr) and the static conv `next` at index `next_at` that takes the codes.
+    struct Stage {
+        bool relu = false;
+        size_t after = 0, next_at = 0;
+        const MaxPool2d *pool = nullptr;
+        const QConv *next = nullptr;
+    };
+    Stage stage_at(size_t i) const {
+        auto pass = [&](size_t j) { return j < layers.size() ? dynamic_cast<const QPass *>(layers[j].get()) : nullptr; };
+        auto stat = [&](size_t j) {
+            auto *c = j < layers.size() ? dynamic_cast<const QConv *>(layers[j].get()) : nullptr;
+            return c && c->is_static() ? c : nullptr;
+        };
+        Stage st;
+        st.relu = pass(i + 1) && pass(i + 1)->is_relu();
+        st.after = i + (st.relu ? 2 : 1);
+        if (!chain || stat(i)->out_channels() > (size_t)th_qconv_i8_chain_max_cout()) return st;
+        size_t j = st.after;
+        if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
+        if ((st.next = stat(j))) st.next_at = j;
+        else st.pool = nullptr;
+        return st;
+    }
     Tensor forward(const Tensor &input) const override {
         // every weight-only conv stage's weights in one dequantize launch, into one workspace that lives for this call
         std::vector<const QConv *> convs;
@@ -209,10 +277,21 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
                 }
             } else if (auto *cv = dynamic_cast<const QConv *>(l)) {
                 if (cv->is_static()) {   // conv + ReLU: the ReLU in the product's epilogue
-                    auto *next = i + 1 < layers.size() ? dynamic_cast<const QPass *>(layers[i + 1].get()) : nullptr;
-                    const bool relu = next && next->is_relu();
-                    x = cv->forward_static(x, relu);
-                    if (relu) ++i;
+                    Stage st = stage_at(i);
+                    if (!st.next) {
+                        x = cv->forward_static(x, st.relu);
+                    } else {   // a run of links: one codec, then codes from product to product; the run's last conv writes f32
+                        QCodes cur = cv->encode(x);
+                        while (st.next) {
+                            QCodes out;
+                            cv->product(cur, st.relu, nullptr, st.next, &out, /*sums=*/!st.pool);
+                            cur = st.pool ? max_pool_codes(out, *st.pool) : out;
+                            cv = st.next;
+                            st = stage_at(st.next_at);
+                        }
+                        cv->product(cur, st.relu, &x);
+                    }
+                    i = st.after - 1;
                     continue;
                 }
                 x = cv->forward_with(x, at[ci].first, at[ci].second);
@@ -228,6 +307,14 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     }
     void act_scales(std::vector<const float *> *out) const override {
         for (const auto &l : layers) l->act_scales(out);
+    }
+    int chain_links() const override {
+        int links = 0;
+        for (size_t i = 0; i < layers.size(); ++i) {
+            auto *c = dynamic_cast<const QConv *>(layers[i].get());
+            links += c && c->is_static() ? (stage_at(i).next != nullptr) : layers[i]->chain_links();
+        }
+        return links;
     }
 };
 
@@ -250,11 +337,12 @@ std::shared_ptr<Module> copy_of(const Module &m) {
     return p ? std::make_shared<M>(*p) : nullptr;
 }
 
-// stat: the Linear layers static; stat_convs: the plain convolutions too
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false) {
+// stat: the Linear layers static; stat_convs: the plain convolutions too; chain: codes from one static conv to the next
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false, bool chain = false) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto q = std::make_unique<QSequential>();
-        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs));
+        q->chain = chain;
+        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain));
         return q;
     }
     if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat);
@@ -339,7 +427,8 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
     return quantize_checked(m, qt);
 }
 
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs) {
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs, bool chain) {
+    convs = convs || chain;
     // every refusal before anything is allocated
     check_quantizable(m);
     TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
@@ -359,7 +448,7 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
                              " is above 65536, where the int32 sum of the int8 product can overflow");
         }
     }
-    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs);
+    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs, chain);
     NoGradScope no_grad;
     for (size_t i = 0; i < calib.size(); ++i) {
         Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)

@@ -493,6 +493,7 @@ class QuantizedModule {
     virtual Tensor forward(const Tensor &input) const = 0;
     virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
     virtual void act_scales(std::vector<const float *> *out) const {}  // device addresses of the calibrated activation scales, in layer order
+    virtual int chain_links() const { return 0; }                      // layer boundaries a forward crosses in int8 (quantize_static's chain)
 };
 std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled);
 // Static int8 post-training quantization: weights and biases packed exactly as quantize(m, Int8) packs them, and every Linear given one
@@ -505,7 +506,12 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // implicit-GEMM product (th_conv2d_q8q8_fwd) with its own or a following ReLU in the epilogue; any other conv stays weight-only inside the
 // same twin.  in_channels * k_h * k_w above 65 536 is refused with the other refusals.  act_scales() then lists one scale per static
 // layer, Linear or conv, in layer order.
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false);
+// chain (with convs): the same twin -- scales, tensors and, on finite activations, every output bit -- whose activations stay int8 across
+// a link: a static conv A of at most th_qconv_i8_chain_max_cout() output channels (ReLU folded in as above), optionally one MaxPool2d,
+// then a static conv B of the same Sequential.  A's product writes B's codes and pixel sums (th_conv2d_q8q8_fwd_codes with B's scale), the
+// pool runs on codes (th_maxpool2d_nhwc_int8: the codec is monotone, so it commutes with a maximum) and B skips its codec.  Anything else
+// between two convs takes the path above.  chain_links() counts the links.
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false, bool chain = false);
 
 // ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
 // A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the

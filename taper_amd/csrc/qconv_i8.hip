@@ -7,6 +7,9 @@
 //                              th_pack_conv_weight_taper_int8: the same from a weight in the float conv kernels' weight_layout 0
 //   th_conv2d_q8q8_fwd         y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU] into f32 NCHW; acc = the sum
 //                              over the in-image taps of qx qw from the MFMA, rs = the sum of d_pixsum over the same taps
+//   th_conv2d_q8q8_fwd_codes   the same product, its f32 value coded at once with the NEXT layer's scale: int8 [n, h_out, w_out, cpitch_y]
+//                              and the pixel sums, what th_quantize_act_nhwc_int8 would make of th_conv2d_q8q8_fwd's output
+//   th_maxpool2d_nhwc_int8     the max-pool on channel-last codes (the codec is monotone: the maximum of the codes is the code of the maximum)
 //
 // With both operands channel-last a 16-byte piece of K is 16 consecutive channels of one tap: M = n h_out w_out output pixels, N = c_out,
 // K = k_h k_w cpitch.  The im2col matrix exists only as addresses; an out-of-image tap is a zero piece, and code 0 IS value 0, so padding
@@ -102,16 +105,42 @@ struct QcArgs {
     int cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, h_out, w_out, M, relu, tiles_n;
 };
 
+struct QcCodesArgs : QcArgs {   // th_conv2d_q8q8_fwd_codes: y stays null
+    const float *yscale;
+    int8_t *qy;
+    int *ypixsum;
+    int cpitch_y;
+};
+
 // qgemm_i8_kernel's LDS image: rows of 64 bytes, the 16-byte piece c of row r at slot c ^ ((r >> 2) & 3)
 __device__ __forceinline__ int qc_slot(int row, int piece) { return row * 4 + (piece ^ ((row >> 2) & 3)); }
+
+// the sum of the input's pixel sums over the in-image taps of output pixel (oh, ow)
+__device__ __forceinline__ int qc_window_sum(const QcArgs &a, int img, int oh, int ow) {
+    const int *ps = a.pixsum + (size_t)img * a.h * a.w;
+    int rs = 0;
+    for (int kh = 0; kh < a.k_h; ++kh) {
+        const int ih = oh * a.s_h - a.pad_h + kh;
+        if (ih < 0 || ih >= a.h) continue;
+        for (int kw = 0; kw < a.k_w; ++kw) {
+            const int iw = ow * a.s_w - a.pad_w + kw;
+            if (iw >= 0 && iw < a.w) rs += ps[ih * a.w + iw];
+        }
+    }
+    return rs;
+}
 
 // A workgroup owns 128 output pixels (any run of the n h_out w_out list: it may span map rows and images) by 32 NT channels; wave v
 // owns pixels 32 v .. 32 v + 31 against every channel tile.  A stage is 64 bytes of K = four pieces; piece g of K is channels
 // 16 (g % cp16) .. + 15 of tap g / cp16 for BOTH operands, so the fragments pair code with code as in qgemm_i8_kernel.  The weights are
 // the A operand and the pixels the B operand: C column = lane & 31 is a pixel, C row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) a
 // channel, and a wave's store of one register is 32 consecutive pixels of one channel plane.
-template <int NT>
-__global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
+// CODES (tiles_n == 1: the workgroup sees every channel of its pixels): the epilogue's f32 value goes through the activation codec with the
+// next layer's scale instead of to memory.  An accumulator group (reg >> 2) is four consecutive channels = one word of the pixel's
+// channel-last row, the lane's at byte 8 (reg >> 2) + 4 (lane >> 5) of a 32-channel tile; two half-wave swaps (v_permlane32_swap) with
+// the lane that holds the other half of the same pixel leave 16 consecutive bytes in each, so a tile of a pixel is two 16-byte stores.
+template <int NT, bool CODES>
+__global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional<CODES, QcCodesArgs, QcArgs>::type a) {
     __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
     __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, h = lane >> 5;
@@ -189,32 +218,62 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
 
     // epilogue: this lane's pixel, its window's sum of pixel sums (integer; border windows have fewer taps), then store_tile's four operations
     const int m = m0 + wave * 32 + li;
-    if (m >= a.M) return;
-    const int img = m / hw_out, p = m - img * hw_out, oh = p / a.w_out, ow = p - oh * a.w_out;
-    const int *ps = a.pixsum + (size_t)img * a.h * a.w;
-    int rs = 0;
-    for (int kh = 0; kh < a.k_h; ++kh) {
-        const int ih = oh * a.s_h - a.pad_h + kh;
-        if (ih < 0 || ih >= a.h) continue;
-        for (int kw = 0; kw < a.k_w; ++kw) {
-            const int iw = ow * a.s_w - a.pad_w + kw;
-            if (iw >= 0 && iw < a.w) rs += ps[ih * a.w + iw];
+    if constexpr (!CODES) {
+        if (m >= a.M) return;
+        const int img = m / hw_out, p = m - img * hw_out, oh = p / a.w_out, ow = p - oh * a.w_out;
+        const int rs = qc_window_sum(a, img, oh, ow);
+        const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1];
+        const float rterm = __fmul_rn(mw, (float)rs);
+        float *yp = a.y + (size_t)img * a.c_out * hw_out + p;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (co >= a.c_out) continue;
+                const int tt = acc[j][e] + 128 * rs;
+                float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
+                if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
+                yp[(size_t)co * hw_out] = a.relu ? (v > 0.f ? v : 0.f) : v;
+            }
+    } else {
+        // (both lanes of a pixel share m: a pixel past M keeps its two lanes in the swaps and stores nothing)
+        const bool live = m < a.M;
+        const int img = live ? m / hw_out : 0, p = live ? m - img * hw_out : 0, oh = p / a.w_out, ow = p - oh * a.w_out;
+        const int rs = live ? qc_window_sum(a, img, oh, ow) : 0;
+        const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1], sy = a.yscale[0];
+        const float rterm = __fmul_rn(mw, (float)rs);
+        int8_t *row = a.qy + (size_t)m * a.cpitch_y + 16 * h;   // this lane's 16 bytes of a 32-channel tile
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            uint32_t word[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                word[g] = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int co = 32 * j + 8 * g + 4 * h + i;   // (col0 == 0)
+                    if (co >= a.c_out) continue;                 // the code 0: the row's padding
+                    const int tt = acc[j][4 * g + i] + 128 * rs;
+                    float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
+                    if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
+                    if (a.relu) v = v > 0.f ? v : 0.f;
+                    const int q = act_code(v, sy);
+                    sum += q;
+                    word[g] |= (uint32_t)(uint8_t)(int8_t)q << (8 * i);
+                }
+            }
+            // lower half: {own 0, upper's 0, own 1, upper's 1} = bytes 0 .. 15; upper half: {lower's 2, own 2, lower's 3, own 3} = bytes 16 .. 31
+            const auto r02 = __builtin_amdgcn_permlane32_swap(word[0], word[2], false, false);
+            const auto r13 = __builtin_amdgcn_permlane32_swap(word[1], word[3], false, false);
+            if (live && 32 * j + 16 * h < a.cpitch_y) *(uint4 *)(row + 32 * j) = make_uint4(r02[0], r02[1], r13[0], r13[1]);
         }
+        for (int off = 32 * NT + 16 * h; off < a.cpitch_y; off += 32)   // a pitch beyond the channel tile: zeros
+            if (live) *(uint4 *)(a.qy + (size_t)m * a.cpitch_y + off) = make_uint4(0, 0, 0, 0);
+        sum += __shfl_xor(sum, 32, 64);   // the pixel's other half (integers: no order to keep)
+        if (a.ypixsum && live && h == 0) a.ypixsum[m] = sum;
     }
-    const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1];
-    const float rterm = __fmul_rn(mw, (float)rs);
-    float *yp = a.y + (size_t)img * a.c_out * hw_out + p;
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (co >= a.c_out) continue;
-            const int tt = acc[j][e] + 128 * rs;
-            float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
-            if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
-            yp[(size_t)co * hw_out] = a.relu ? (v > 0.f ? v : 0.f) : v;
-        }
 }
 
 // every host decision of the product (th_conv2d_q8q8_fwd launches from it, th_debug_qconv_plan reports it)
@@ -238,6 +297,53 @@ static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h,
     if ((long)p->tiles_m * p->tiles_n > 0x7fffffffL) return "more than 2^31 workgroups";
     p->grid = p->tiles_m * p->tiles_n;
     return nullptr;
+}
+
+// ---- the max-pool on codes ----
+// G lanes (a power of two, at most 64) share an output pixel and take its 16-byte pieces in turn; a piece's 16 maxima start from -128,
+// the code of the float pool's -inf start (maxpool_fwd_kernel), and run over the in-image taps.  Channels c .. cpitch - 1 come out 0.
+__global__ __launch_bounds__(256) void maxpool_nhwc_i8_kernel(const int8_t *__restrict__ q, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w,
+                                                              int pad_h, int pad_w, int h_out, int w_out, long pixels, int8_t *__restrict__ qy,
+                                                              int *__restrict__ ypixsum, int G) {
+    const int t = threadIdx.x, gl = t & (G - 1), per_block = 256 / G, cp16 = cpitch >> 4;
+    const long hw_out = (long)h_out * w_out;
+    for (long base = (long)blockIdx.x * per_block; base < pixels; base += (long)gridDim.x * per_block) {
+        const long o = base + t / G;
+        const bool live = o < pixels;
+        int sum = 0;
+        if (live) {
+            const long img = o / hw_out;
+            const int p = (int)(o - img * hw_out), oh = p / w_out, ow = p - oh * w_out;
+            const int8_t *xi = q + (size_t)img * h * w * cpitch;
+            for (int piece = gl; piece < cp16; piece += G) {
+                int best[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) best[i] = -128;
+                for (int kh = 0; kh < k_h; ++kh) {
+                    const int ih = oh * s_h - pad_h + kh;
+                    if (ih < 0 || ih >= h) continue;
+                    for (int kw = 0; kw < k_w; ++kw) {
+                        const int iw = ow * s_w - pad_w + kw;
+                        if (iw < 0 || iw >= w) continue;
+                        const uint4 v = *(const uint4 *)(xi + ((size_t)ih * w + iw) * cpitch + piece * 16);
+                        const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) best[i] = max(best[i], (int)(int8_t)((wd[i >> 2] >> (8 * (i & 3))) & 0xFF));
+                    }
+                }
+                uint32_t out[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if (piece * 16 + i < c) {
+                        sum += best[i];
+                        out[i >> 2] |= (uint32_t)(uint8_t)(int8_t)best[i] << (8 * (i & 3));
+                    }
+                *(uint4 *)(qy + (size_t)o * cpitch + piece * 16) = make_uint4(out[0], out[1], out[2], out[3]);
+            }
+        }
+        for (int off = G >> 1; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);   // the pixel's lanes (integers: no order to keep)
+        if (live && gl == 0) ypixsum[o] = sum;
+    }
 }
 
 }  // namespace th
@@ -285,25 +391,81 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
     return pack_conv_weight("th_pack_conv_weight_taper_int8", true, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
 }
 
+// the checks both products share; fn: the caller's name for the message
+static int qconv_check(const char *fn, int cpitch, int n, int c_in, int h, int w, const void *d_qx, const void *d_qw, int c_out, int k_h, int k_w, int s_h,
+                       int s_w, int pad_h, int pad_w, QcPlan *p) {
+    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, p);
+    TH_REQUIRE(!why, "%s: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", fn, why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w);
+    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", fn);
+    TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", fn, cpitch, c_in);
+    return 0;
+}
+
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                        const float *d_bparams, int relu, float *d_y) {
     TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "th_conv2d_q8q8_fwd: null argument");
     QcPlan p{};
-    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
-    TH_REQUIRE(!why, "th_conv2d_q8q8_fwd: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w,
-               pad_h, pad_w);
-    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "th_conv2d_q8q8_fwd: the code pointers must be 16-byte aligned");
-    TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "th_conv2d_q8q8_fwd: cpitch %d must be a multiple of 16 and at least c_in %d", cpitch, c_in);
+    if (int rc = qconv_check("th_conv2d_q8q8_fwd", cpitch, n, c_in, h, w, d_qx, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p)) return rc;
     if (n == 0) return 0;
     const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
                    p.h_out, p.w_out, n * p.h_out * p.w_out, relu, p.tiles_n};
     if (p.nt == 1)
-        hipLaunchKernelGGL(qconv_i8_kernel<1>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((qconv_i8_kernel<1, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
     else if (p.nt == 2)
-        hipLaunchKernelGGL(qconv_i8_kernel<2>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((qconv_i8_kernel<2, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
     else
-        hipLaunchKernelGGL(qconv_i8_kernel<4>, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+        hipLaunchKernelGGL((qconv_i8_kernel<4, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
+
+int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                             const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                             const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
+    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && d_yscale && d_qy && (!d_qb || d_bparams), "th_conv2d_q8q8_fwd_codes: null argument");
+    QcPlan p{};
+    if (int rc = qconv_check("th_conv2d_q8q8_fwd_codes", cpitch, n, c_in, h, w, d_qx, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p)) return rc;
+    TH_REQUIRE(p.tiles_n == 1, "th_conv2d_q8q8_fwd_codes: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd)",
+               c_out, th_qconv_i8_chain_max_cout());
+    TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "th_conv2d_q8q8_fwd_codes: the output code pointer must be 16-byte aligned");
+    TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "th_conv2d_q8q8_fwd_codes: cpitch_y %d must be a multiple of 16 and at least c_out %d", cpitch_y, c_out);
+    if (n == 0) return 0;
+    QcCodesArgs a{};
+    static_cast<QcArgs &>(a) = QcArgs{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, nullptr, cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+                                      p.h_out, p.w_out, n * p.h_out * p.w_out, relu, p.tiles_n};
+    a.yscale = d_yscale, a.qy = d_qy, a.ypixsum = d_ypixsum, a.cpitch_y = cpitch_y;
+    if (p.nt == 1)
+        hipLaunchKernelGGL((qconv_i8_kernel<1, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    else if (p.nt == 2)
+        hipLaunchKernelGGL((qconv_i8_kernel<2, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((qconv_i8_kernel<4, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_maxpool2d_nhwc_int8(th_ctx *ctx, const int8_t *d_q, int n, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w,
+                           int8_t *d_qy, int *d_ypixsum) {
+    TH_REQUIRE(ctx && d_q && d_qy && d_ypixsum, "th_maxpool2d_nhwc_int8: null argument");
+    TH_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_qy) & 15) == 0, "th_maxpool2d_nhwc_int8: the code pointers must be 16-byte aligned");
+    TH_REQUIRE(n >= 0 && c > 0 && h > 0 && w > 0 && k_h > 0 && k_w > 0 && s_h > 0 && s_w > 0 && pad_h >= 0 && pad_w >= 0,
+               "th_maxpool2d_nhwc_int8: a shape, window or stride below 1, or a negative padding (n=%d c=%d %dx%d, k=%dx%d stride %dx%d pad %dx%d)", n, c, h, w,
+               k_h, k_w, s_h, s_w, pad_h, pad_w);
+    TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c, "th_maxpool2d_nhwc_int8: cpitch %d must be a multiple of 16 and at least c %d", cpitch, c);
+    TH_REQUIRE((long)h + 2L * pad_h >= k_h && (long)w + 2L * pad_w >= k_w && (long)h + 2L * pad_h <= 0x7fffffffL && (long)w + 2L * pad_w <= 0x7fffffffL,
+               "th_maxpool2d_nhwc_int8: an empty output map (%dx%d, k=%dx%d pad %dx%d)", h, w, k_h, k_w, pad_h, pad_w);
+    const int h_out = (h + 2 * pad_h - k_h) / s_h + 1, w_out = (w + 2 * pad_w - k_w) / s_w + 1;
+    const long pixels = (long)n * h_out * w_out;
+    TH_REQUIRE(pixels <= 0x7fffffffL && (long)n * h * w <= 0x7fffffffL, "th_maxpool2d_nhwc_int8: more than 2^31 pixels");
+    if (n == 0) return 0;
+    int G = 1;   // lanes per pixel: the pieces of a pixel row rounded up to a power of two, a wave at the most
+    while (G < cpitch / 16 && G < kWave) G *= 2;
+    const long blocks = (pixels + 256 / G - 1) / (256 / G);
+    hipLaunchKernelGGL(maxpool_nhwc_i8_kernel, dim3((unsigned)std::min(blocks, (long)kNumCU * 32)), dim3(256), 0, ctx->stream, d_q, c, h, w, cpitch, k_h, k_w, s_h, s_w,
+                       pad_h, pad_w, h_out, w_out, pixels, d_qy, d_ypixsum, G);
     TH_LAUNCH_CHECK();
     return 0;
 }

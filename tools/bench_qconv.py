@@ -6,14 +6,20 @@ two states -- cold (a 512 MiB buffer written elsewhere before every timed call) 
 launched back to back) -- and, for the static rows, the share of the two bounds of DESIGN 6k: integer operations against the i8 MFMA rate and
 algorithmic bytes against 8 TB/s.
 
-Model rows: the whole forward of both models at B = 1, 64 and 256 for the float model, quantize("int8"), quantize_static and
-quantize_static_conv, through the host library as a user calls it: cold as above, and "back to back" = the mean of eager calls issued without
+Pair rows: two consecutive static convs of the reference CNN at B = 256 (with the MaxPool2d(2) between them where the model has one), from
+the first conv's codes to the second conv's f32 output, graph-replayed and cold as the layer rows: unchained = product, [f32 pool,] codec,
+product; chained = product that writes codes (th_conv2d_q8q8_fwd_codes), [pool on codes (th_maxpool2d_nhwc_int8),] product.
+
+Model rows: the whole forward of both models at B = 1, 64 and 256 for the float model, quantize("int8"), quantize_static,
+quantize_static_conv and quantize_static_chain (checked bit-identical to quantize_static_conv's output on the timed input), through the
+host library as a user calls it: cold as above, and "back to back" = the mean of eager calls issued without
 a wait between them.  These rows are NOT graph replays: they time what a caller of the host library gets, tensor allocation and launch
-work included, for all four models alike, so at B = 1 and 64 they say more about launches than about kernels; the layer rows are the
-kernel comparison.
+work included, for all five models alike, so at B = 1 and 64 they say more about launches than about kernels; the layer and pair rows are
+the kernel comparison.
 
     python tools/bench_qconv.py [--reps 30] [--out profiles/quant_static_conv.json]
-    python tools/bench_qconv.py --trace-only      # a few static-conv B = 256 forwards of the reference CNN, for rocprofv3 --kernel-trace --stats
+    python tools/bench_qconv.py --trace-only [--trace-kind "int8 static chain"]      # a few B = 256 forwards of the reference CNN's static-conv
+                                                  # (or another) twin, for rocprofv3 --kernel-trace --stats
 
 writes the rows as JSON to --out and the table beside it (same name, .md).
 """
@@ -42,6 +48,9 @@ I8_OPS = 2 * 2.5e15      # MI355X_MICROARCH: the i8 MFMA forms run at twice the 
 LAYERS = [("cnn_reference", 1, 32, 28), ("cnn_reference", 32, 32, 28), ("cnn_reference", 32, 64, 14), ("cnn_reference", 64, 64, 14),
           ("cnn_reference", 64, 128, 7), ("cnn_simple", 1, 32, 28), ("cnn_simple", 32, 64, 14)]
 KINDS = ("f32", "int8 weight-only", "int8 static")
+# (c_in, c_mid, c_out, map side of the first conv, a MaxPool2d(2) between the two): the reference CNN's consecutive static convs
+PAIRS = [(1, 32, 32, 28, False), (32, 32, 64, 28, True), (32, 64, 64, 14, False), (64, 64, 128, 14, True)]
+PAIR_KINDS = ("int8 static", "int8 static chain")
 
 
 class Layer:
@@ -86,6 +95,38 @@ class Layer:
 
     def ops(self):
         return 2 * self.B * self.side * self.side * 9 * self.c_in * self.c_out
+
+
+class Pair:
+    """conv A, [MaxPool2d(2),] conv B on the device: A's codes are made once, the timed part runs from them to B's f32 output"""
+
+    def __init__(self, ctx, rng, c_in, c_mid, c_out, side, pool, B):
+        self.a = Layer(ctx, rng, c_in, c_mid, side, B)
+        self.b = Layer(ctx, rng, c_mid, c_out, side // 2 if pool else side, B)
+        self.pool, self.B, self.side = pool, B, side
+        self.b.sx = ctx.upload(np.array([2.0 / 127], np.float32))      # ReLU outputs of a He-initialised layer on N(0, 1) inputs: about 4 sigma
+        ctx.call("th_quantize_act_nhwc_int8", self.a.x, B, c_in, side, side, self.a.sx, self.a.qx, self.a.cpitch, self.a.ps)
+        if pool:
+            self.mid_f32, self.argmax = ctx.empty(B * c_mid * (side // 2) ** 2), ctx.empty(B * c_mid * (side // 2) ** 2, np.int64)
+            self.mid_q = ctx.empty(B * side * side * self.b.cpitch, np.uint8)
+
+    def run(self, ctx, kind):
+        a, b, B, s = self.a, self.b, self.B, self.side
+        head = (a.qx, a.cpitch, a.ps, a.sx, B, a.c_in, s, s, a.qw_nhwc, a.c_out, 3, 3, 1, 1, 1, 1, a.qwp, a.qb, a.qbp, 1)
+        if kind == "int8 static":
+            ctx.call("th_conv2d_q8q8_fwd", *head, a.y)
+            if self.pool:
+                ctx.call("th_maxpool2d_fwd", a.y, self.mid_f32, self.argmax, B, a.c_out, s, s, 2, 2, 2, 2, 0, 0)
+            ctx.call("th_quantize_act_nhwc_int8", self.mid_f32 if self.pool else a.y, B, b.c_in, b.side, b.side, b.sx, b.qx, b.cpitch, b.ps)
+        elif self.pool:
+            ctx.call("th_conv2d_q8q8_fwd_codes", *head, b.sx, self.mid_q, b.cpitch, None)
+            ctx.call("th_maxpool2d_nhwc_int8", self.mid_q, B, b.c_in, s, s, b.cpitch, 2, 2, 2, 2, 0, 0, b.qx, b.ps)
+        else:
+            ctx.call("th_conv2d_q8q8_fwd_codes", *head, b.sx, b.qx, b.cpitch, b.ps)
+        ctx.call("th_conv2d_q8q8_fwd", b.qx, b.cpitch, b.ps, b.sx, B, b.c_in, b.side, b.side, b.qw_nhwc, b.c_out, 3, 3, 1, 1, 1, 1, b.qwp, b.qb, b.qbp, 1, b.y)
+
+    def output(self, ctx):
+        return ctx.download(self.b.y, (self.B * self.b.c_out * self.b.side ** 2,)).view(np.uint32)
 
 
 def timed(ctx, fn, reps, flush):
@@ -139,13 +180,15 @@ def timed_eager(ctx, fn, reps, flush):
 
 
 def model_forwards(key, B, rng):
-    """-> {kind: a call that runs one forward} for the four models of one network, calibrated on inputs like the timed ones"""
+    """-> {kind: a call that runs one forward} for the five models of one network, calibrated on inputs like the timed ones"""
     model = bench.build_model(T, key)
     shape = (B, 1, 28, 28)
     calib = T.Tensor(rng.standard_normal((64, 1, 28, 28)).astype(np.float32), (64, 1, 28, 28))
     x = T.Tensor(rng.standard_normal(shape).astype(np.float32), shape)
     twins = {"int8 weight-only": model.quantize("int8"), "int8 static (Linear)": model.quantize_static(calib),
-             "int8 static (conv + Linear)": model.quantize_static_conv(calib)}
+             "int8 static (conv + Linear)": model.quantize_static_conv(calib), "int8 static chain": model.quantize_static_chain(calib)}
+    same = np.array_equal(twins["int8 static chain"](x).data().view(np.uint32), twins["int8 static (conv + Linear)"](x).data().view(np.uint32))
+    assert same, f"{key} B={B}: the chained twin's output differs from quantize_static_conv's"
 
     def float_forward():
         model.forward(x)
@@ -162,13 +205,14 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="profiles/quant_static_conv.json")
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--trace-kind", default="int8 static (conv + Linear)")
     a = ap.parse_args()
     ctx = H.Ctx(handle=T.Device.ctx_handle())
     rng = np.random.default_rng(0)
     if a.trace_only:
         calls, keep = model_forwards("cnn_reference", 256, rng)
         for _ in range(5):
-            calls["int8 static (conv + Linear)"]()
+            calls[a.trace_kind]()
         ctx.sync()
         return
     flush = ctx.empty(128 << 20)
@@ -189,6 +233,16 @@ def main():
                          replay_share_of_hbm=round(layer.static_bytes() / (warm * 1e-6) / HBM, 4))
             report(r)
         del layer
+    for c_in, c_mid, c_out, side, pool in PAIRS:
+        pair = Pair(ctx, rng, c_in, c_mid, c_out, side, pool, B)
+        outs = {}
+        for kind in PAIR_KINDS:
+            cold, warm = timed(ctx, lambda: pair.run(ctx, kind), a.reps, flush)
+            outs[kind] = pair.output(ctx)
+            report(dict(case=f"cnn_reference pair {c_in}->{c_mid} @ {side}x{side}{' -> pool' if pool else ''} -> {c_mid}->{c_out}", kind=kind, B=B,
+                        cold_us=round(cold, 2), replay_us=round(warm, 2)))
+        assert np.array_equal(*outs.values()), "the chained pair's output differs from the unchained pair's"
+        del pair
     for key in ("cnn_reference", "cnn_simple"):
         for B in (1, 64, 256):
             calls, keep = model_forwards(key, B, rng)
@@ -207,8 +261,10 @@ def table(rows, reps):
     lines = [f"# Calibrated int8 convolution on MI355X (`tools/bench_qconv.py`, {reps} reps; cold = median after writing 512 MiB elsewhere)", "",
              "Layer rows (C ABI, replay = the captured forward launched back to back): static = `th_quantize_act_nhwc_int8` + `th_conv2d_q8q8_fwd`; "
              "weight-only = `th_dequantize_multi` + `th_conv3x3_fwd`; f32 = `th_conv3x3_fwd`.",
+             "Pair rows (C ABI, replay, from the first conv's codes to the second conv's f32 output): static = product, [f32 pool,] codec, product; "
+             "static chain = `th_conv2d_q8q8_fwd_codes`, [`th_maxpool2d_nhwc_int8`,] product -- the same output bits, asserted.",
              "Shares (static rows, replay): integer operations / time / 5 POPS (twice the bf16 matrix peak), algorithmic bytes / time / 8 TB/s.",
-             "Model rows (host library, eager, not graph replays: tensor allocation and launch work included for all four models alike): back to back = "
+             "Model rows (host library, eager, not graph replays: tensor allocation and launch work included for all models alike): back to back = "
              "the mean of calls issued without a wait between them.",
              "", "| case | kind | B | cold µs | replay / back-to-back µs | share of i8 MFMA | share of HBM |", "|---|---|---|---|---|---|---|"]
     for r in rows:
