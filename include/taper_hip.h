@@ -418,6 +418,7 @@ int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *
                        const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams,
                        int relu, float *d_y);
 int th_qlinear_i8_kstep(void);   /* bytes of K the product stages at a time (64): the pitch a caller should round in_features up to */
+int th_q8q8_max_k(void);         /* the longest K (in_features; c_in k_h k_w of a conv) the int8 products take: 65 536 */
 /* Calibration: d_range2 = {min, max} over the FINITE elements of every tensor shown so far (first != 0: of this tensor alone) and
  * d_scale = the scale th_fake_quant_act gives that range: max(|min|, |max|) / 127, all zero -> (0, 1), all equal to m -> (0.9 m, 1.1 m).
  * Two launches on th_quantize_int8's min / max partials. */

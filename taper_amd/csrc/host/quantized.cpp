@@ -38,6 +38,30 @@ class QPass : public QuantizedModule {
     std::shared_ptr<Module> m_;
 };
 
+// The calibrated activation of a static twin, on the device: {finite min, finite max} of the calibration inputs, then the scale they
+// give.  Empty in a weight-only twin.
+struct ActScale {
+    std::shared_ptr<Buffer> buf;
+    explicit operator bool() const { return buf != nullptr; }
+    void alloc() { buf = Buffer::alloc(3); }
+    const float *scale() const { return buf->d + 2; }
+    // calibration: the finite min / max of one more float input of the layer, and the scale of the range so far
+    void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, buf->d, buf->d + 2)); }
+    void list(std::vector<const float *> *out) const {
+        if (buf) out->push_back(scale());
+    }
+};
+
+// a twin's bias as the kernels take it: codes and codec parameters, both null without one (f16 codes have no parameters)
+struct BiasPtrs {
+    const void *codes = nullptr;
+    const float *params = nullptr;
+    explicit BiasPtrs(const std::unique_ptr<QTensor> &b) {
+        if (b) codes = b->codes->d, params = b->params ? b->params->d : nullptr;
+    }
+    const int8_t *i8() const { return static_cast<const int8_t *>(codes); }
+};
+
 class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
    public:
     // stat: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
@@ -50,7 +74,7 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         auto padded = Buffer::alloc(n_ * w_.pitch / 4);
         TH(th_pad_rows_int8(Device::ctx(), reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, (int)k_, reinterpret_cast<int8_t *>(padded->d), (int)w_.pitch));
         w_.codes = padded;     // (the packed copy goes back to the pool: stream order keeps it alive for the launch above)
-        act_ = Buffer::alloc(3);   // {finite min, finite max} of the calibration inputs, then the scale
+        act_.alloc();
     }
     Tensor forward(const Tensor &x) const override { return forward_relu(x, false); }
     // x . deq(W)^T + deq(b), and the ReLU behind it in the same launch when the Sequential twin pairs them
@@ -59,36 +83,33 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         const size_t batch = x.shape()[0];
         Tensor y = Tensor::empty({batch, n_});
         th_ctx *ctx = Device::ctx();
+        const BiasPtrs b(b_);
         if (act_) {   // int8 codes of x and their row sums (pooled, returned when this scope ends), then the integer product
             const size_t pitch = (k_ + 15) / 16 * 16;
             auto qx = Buffer::alloc(batch * pitch / 4), rs = Buffer::alloc(batch);
-            TH(th_quantize_act_int8(ctx, x.dptr(), (int)batch, (int)k_, act_->d + 2, reinterpret_cast<int8_t *>(qx->d), (int)pitch, reinterpret_cast<int *>(rs->d)));
-            TH(th_linear_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)pitch, reinterpret_cast<const int *>(rs->d), act_->d + 2, (int)batch, (int)k_,
-                                  reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d,
-                                  b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu ? 1 : 0, y.dptr()));
+            TH(th_quantize_act_int8(ctx, x.dptr(), (int)batch, (int)k_, act_.scale(), reinterpret_cast<int8_t *>(qx->d), (int)pitch, reinterpret_cast<int *>(rs->d)));
+            TH(th_linear_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)pitch, reinterpret_cast<const int *>(rs->d), act_.scale(), (int)batch, (int)k_,
+                                  reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d, b.i8(), b.params, relu ? 1 : 0, y.dptr()));
         } else if (w_.qtype == TH_QTYPE_INT8)
-            TH(th_linear_q8_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, w_.params->d,
-                                b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr, b_ ? b_->params->d : nullptr, relu ? 1 : 0, y.dptr()));
+            TH(th_linear_q8_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, w_.params->d, b.i8(), b.params,
+                                relu ? 1 : 0, y.dptr()));
         else
             TH(th_linear_h16_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const uint16_t *>(w_.codes->d), (int)n_,
-                                 b_ ? reinterpret_cast<const uint16_t *>(b_->codes->d) : nullptr, relu ? 1 : 0, y.dptr()));
+                                 static_cast<const uint16_t *>(b.codes), relu ? 1 : 0, y.dptr()));
         return y;
     }
     void tensors(std::vector<const QTensor *> *out) const override {
         out->push_back(&w_);
         if (b_) out->push_back(b_.get());
     }
-    void act_scales(std::vector<const float *> *out) const override {
-        if (act_) out->push_back(act_->d + 2);
-    }
-    // calibration: the finite min / max of one more float input of this layer, and the scale of the range so far
-    void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, act_->d, act_->d + 2)); }
+    void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
+    const ActScale &act() const { return act_; }
 
    private:
     QTensor w_;
     std::unique_ptr<QTensor> b_;
     size_t k_, n_;
-    std::shared_ptr<Buffer> act_;
+    ActScale act_;   // static only
 };
 
 // an activation as channel-last int8 codes [n][h][w][cpitch] with the int32 sum of every pixel's codes: what a static conv's product reads
@@ -123,16 +144,16 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         relaid_ = Buffer::alloc(ws[0] * ws[2] * ws[3] * cpitch_ / 4);
         TH(th_pack_conv_weight_taper_int8(Device::ctx(), reinterpret_cast<const int8_t *>(w_.codes->d), (int)ws[0], (int)ws[1], (int)ws[2], (int)ws[3],
                                     reinterpret_cast<int8_t *>(relaid_->d), (int)cpitch_));
-        act_ = Buffer::alloc(3);   // {finite min, finite max} of the calibration inputs, then the scale
+        act_.alloc();
     }
-    bool is_static() const { return act_ != nullptr; }
+    bool is_static() const { return (bool)act_; }
     size_t out_channels() const { return w_.shape[0]; }
     // the codec: codes and pixel sums of x with this layer's scale
     QCodes encode(const Tensor &x) const {
         const Shape &ws = w_.shape;
         TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == ws[1], "QuantizedConv2d: input must be [batch, in_channels, h, w]");
         QCodes in = QCodes::alloc(x.shape()[0], ws[1], x.shape()[2], x.shape()[3], cpitch_);
-        TH(th_quantize_act_nhwc_int8(Device::ctx(), x.dptr(), (int)in.n, (int)in.c, (int)in.h, (int)in.w, act_->d + 2, in.codes(), (int)cpitch_, in.pixsum()));
+        TH(th_quantize_act_nhwc_int8(Device::ctx(), x.dptr(), (int)in.n, (int)in.c, (int)in.h, (int)in.w, act_.scale(), in.codes(), (int)cpitch_, in.pixsum()));
         return in;
     }
     // The integer product on codes made with this layer's scale; relu: the layer's own or a following one.  next == nullptr: f32 NCHW
@@ -144,21 +165,20 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
         TAPER_ASSERT(in.h + 2 * ph >= ws[2] && in.w + 2 * pw >= ws[3], "QuantizedConv2d: the kernel is larger than the padded input");
         const size_t ho = (in.h + 2 * ph - ws[2]) / sh + 1, wo = (in.w + 2 * pw - ws[3]) / sw + 1;
-        const int8_t *qb = b_ ? reinterpret_cast<const int8_t *>(b_->codes->d) : nullptr;
-        const float *bp = b_ ? b_->params->d : nullptr;
+        const BiasPtrs b(b_);
         const int fold = relu || geom_->fuse_relu ? 1 : 0;
         th_ctx *ctx = Device::ctx();
         if (!next) {
             *y = Tensor::empty({in.n, ws[0], ho, wo});
-            TH(th_conv2d_q8q8_fwd(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_->d + 2, (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                  reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, qb, bp, fold,
-                                  y->dptr()));
+            TH(th_conv2d_q8q8_fwd(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                  reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params,
+                                  fold, y->dptr()));
             return;
         }
         *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
-        TH(th_conv2d_q8q8_fwd_codes(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_->d + 2, (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                    reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, qb, bp, fold,
-                                    next->act_->d + 2, qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
+        TH(th_conv2d_q8q8_fwd_codes(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                    reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params,
+                                    fold, next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
     }
     // two launches: the codec (its buffers pooled, returned when this scope ends), then the product
     Tensor forward_static(const Tensor &x, bool relu) const {
@@ -166,10 +186,8 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         product(encode(x), relu, &y);
         return y;
     }
-    void act_scales(std::vector<const float *> *out) const override {
-        if (act_) out->push_back(act_->d + 2);
-    }
-    void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, act_->d, act_->d + 2)); }
+    void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
+    const ActScale &act() const { return act_; }
     Tensor forward(const Tensor &x) const override {   // alone: dequantize its own two tensors
         if (is_static()) return forward_static(x, false);
         std::vector<const QConv *> one{this};
@@ -212,7 +230,8 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     std::shared_ptr<Conv2d> geom_;
     QTensor w_;
     std::unique_ptr<QTensor> b_;
-    std::shared_ptr<Buffer> relaid_, act_;   // static only: [c_out][k_h k_w][cpitch] codes; the activation range and scale
+    std::shared_ptr<Buffer> relaid_;   // static only: [c_out][k_h k_w][cpitch] codes
+    ActScale act_;                     // static only
     size_t cpitch_ = 0;
 };
 
@@ -392,14 +411,14 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
     const Linear *lin = dynamic_cast<const Linear *>(&m);
     if (auto *ql = dynamic_cast<const QATLinear *>(&m)) lin = &ql->inner;
     if (lin) {
-        dynamic_cast<const QLinear &>(q).observe(x, first);
+        dynamic_cast<const QLinear &>(q).act().observe(x, first);
         return x.linear(plain(lin->weight), plain(lin->bias), false);
     }
     const Conv2d *cv = dynamic_cast<const Conv2d *>(&m);
     if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) cv = &qc->inner;
     if (cv) {
         auto &qcv = dynamic_cast<const QConv &>(q);
-        if (qcv.is_static()) qcv.observe(x, first);
+        if (qcv.is_static()) qcv.act().observe(x, first);
         return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
     }
     return m.forward(x);
@@ -435,17 +454,17 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
     for (const Tensor &c : calib) TAPER_ASSERT(c.defined(), "quantize_static: undefined calibration tensor");
     std::vector<const Linear *> lins;
     linears_of(m, &lins);
+    const size_t max_k = (size_t)th_q8q8_max_k();
+    const std::string above = " is above " + std::to_string(max_k) + ", where the int32 sum of the int8 product can overflow";
     for (const Linear *l : lins)
-        TAPER_ASSERT(l->weight.shape()[1] <= 65536, "quantize_static: a Linear with in_features " + std::to_string(l->weight.shape()[1]) +
-                                                        " is above 65536, where the int32 sum of the int8 product can overflow");
+        TAPER_ASSERT(l->weight.shape()[1] <= max_k, "quantize_static: a Linear with in_features " + std::to_string(l->weight.shape()[1]) + above);
     if (convs) {
         std::vector<const Conv2d *> cvs;
         convs_of(m, &cvs);
         for (const Conv2d *c : cvs) {
             const Shape &ws = c->weight.shape();
-            TAPER_ASSERT(!QConv::can_be_static(*c) || ws[1] * ws[2] * ws[3] <= 65536,
-                         "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) +
-                             " is above 65536, where the int32 sum of the int8 product can overflow");
+            TAPER_ASSERT(!QConv::can_be_static(*c) || ws[1] * ws[2] * ws[3] <= max_k,
+                         "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) + above);
         }
     }
     auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs, chain);

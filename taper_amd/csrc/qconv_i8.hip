@@ -1,5 +1,5 @@
-// qconv_i8.hip -- calibrated int8 convolution: qgemm_i8.hip's arithmetic restated for a window, as an implicit GEMM on the
-// integer matrix cores (v_mfma_i32_32x32x32_i8) over channel-last codes.
+// qconv_i8.hip -- calibrated int8 convolution: an implicit GEMM on the integer matrix cores (v_mfma_i32_32x32x32_i8) over
+// channel-last codes, on qi8_dev.h's piece, stage image, epilogue value and window -- the ones qgemm_i8.hip's product uses.
 //
 //   th_quantize_act_nhwc_int8  f32 [n, c, h, w] -> int8 codes [n, h, w, cpitch] (th_quantize_act_int8's codec) and the int32 sum of each
 //                              pixel's codes; one launch, the NCHW -> NHWC turn through LDS
@@ -15,16 +15,12 @@
 // K = k_h k_w cpitch.  The im2col matrix exists only as addresses; an out-of-image tap is a zero piece, and code 0 IS value 0, so padding
 // adds nothing to acc or rs.  A pixel's result depends on its own window alone: nothing of the tiling reaches the arithmetic.
 #include "common.h"
-#include "quant_dev.h"
+#include "qi8_dev.h"
 
 namespace th {
 
-typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef int intx16 __attribute__((ext_vector_type(16)));
-
 constexpr int kQcPix = 128;        // output pixels per workgroup: four waves of 32
 constexpr int kQcChan = 32;        // channels per MFMA tile; a workgroup takes NT of them (1, 2 or 4)
-constexpr int kQcMaxK = 65536;     // c_in k_h k_w: |acc + 128 rs| <= 128 * 255 * K stays below 2^31 (qgemm_i8.hip's kQ8MaxK)
 constexpr int kQcTurnPix = 64;     // th_quantize_act_nhwc_int8: pixels ...
 constexpr int kQcTurnChan = 64;    // ... by channels of one LDS turn
 constexpr int kQcTurnPitch = 20;   // words per pixel row of the turn: 16 of codes, 4 of padding (a row stays 16-byte aligned)
@@ -51,16 +47,14 @@ __global__ __launch_bounds__(256) void quantize_act_nhwc_kernel(const float *__r
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int ch = cb + 16 * i + 4 * cq + j;
-                    if (ch < c && p0 + pin < hw) word |= (uint32_t)(uint8_t)(int8_t)act_code(xi[(size_t)ch * hw + p0 + pin], scale) << (8 * j);
+                    if (ch < c && p0 + pin < hw) word |= code_at(act_code(xi[(size_t)ch * hw + p0 + pin], scale), j);
                 }
                 turn_w[pin * kQcTurnPitch + 4 * i + cq] = word;
             }
             __syncthreads();
             if (p0 + pout < hw && cb + 16 * piece < cpitch) {
                 const uint4 v = turn[pout * (kQcTurnPitch / 4) + piece];
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sum += (int)(int8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xFF);
+                sum += piece_sum(v);
                 *(uint4 *)(q + ((size_t)img * hw + p0 + pout) * cpitch + cb + 16 * piece) = v;
             }
             __syncthreads();
@@ -71,29 +65,6 @@ __global__ __launch_bounds__(256) void quantize_act_nhwc_kernel(const float *__r
     }
 }
 
-// a thread per 16-byte piece of the destination (packed sources are not aligned in general: byte loads, once per weight).  TAPER: the
-// source is a weight the float conv kernels read in the reference's reinterpretation (weight_layout 0, tensor.rs:1262): the code of
-// w_eff[co][ci][tap] lies at src[(ci taps + tap) c_out + co]
-template <bool TAPER>
-__global__ __launch_bounds__(256) void pack_conv_weight_kernel(const int8_t *__restrict__ src, long rows, int c_in, int taps, int8_t *__restrict__ dst,
-                                                               int cpitch) {
-    const int cp16 = cpitch / 16;
-    const long total = rows * taps * cp16;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long rt = i / cp16;   // row * taps + tap
-        const int c0 = (int)(i - rt * cp16) * 16;
-        const long row = rt / taps;
-        const int tap = (int)(rt - row * taps);
-        const int8_t *s = TAPER ? src + (size_t)tap * rows + row : src + (size_t)row * c_in * taps + tap;
-        const size_t step = TAPER ? (size_t)taps * rows : (size_t)taps;   // from one input channel to the next
-        uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (c0 + j < c_in) w[j >> 2] |= (uint32_t)(uint8_t)s[(size_t)(c0 + j) * step] << (8 * (j & 3));
-        *(uint4 *)(dst + (size_t)i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
 // ---- the product ----
 struct QcArgs {
     const int8_t *qx, *qw;
@@ -101,38 +72,18 @@ struct QcArgs {
     const float *xscale, *wparams;
     const int8_t *qb;
     const float *bparams;
-    float *y;
-    int cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, h_out, w_out, M, relu, tiles_n;
-};
-
-struct QcCodesArgs : QcArgs {   // th_conv2d_q8q8_fwd_codes: y stays null
+    float *y;   // the f32 form's output; the codes form's are the next four (null / 0 in the f32 form)
     const float *yscale;
     int8_t *qy;
     int *ypixsum;
     int cpitch_y;
+    QWindow win;
+    int cpitch, c_out, M, relu, tiles_n;
 };
-
-// qgemm_i8_kernel's LDS image: rows of 64 bytes, the 16-byte piece c of row r at slot c ^ ((r >> 2) & 3)
-__device__ __forceinline__ int qc_slot(int row, int piece) { return row * 4 + (piece ^ ((row >> 2) & 3)); }
-
-// the sum of the input's pixel sums over the in-image taps of output pixel (oh, ow)
-__device__ __forceinline__ int qc_window_sum(const QcArgs &a, int img, int oh, int ow) {
-    const int *ps = a.pixsum + (size_t)img * a.h * a.w;
-    int rs = 0;
-    for (int kh = 0; kh < a.k_h; ++kh) {
-        const int ih = oh * a.s_h - a.pad_h + kh;
-        if (ih < 0 || ih >= a.h) continue;
-        for (int kw = 0; kw < a.k_w; ++kw) {
-            const int iw = ow * a.s_w - a.pad_w + kw;
-            if (iw >= 0 && iw < a.w) rs += ps[ih * a.w + iw];
-        }
-    }
-    return rs;
-}
 
 // A workgroup owns 128 output pixels (any run of the n h_out w_out list: it may span map rows and images) by 32 NT channels; wave v
 // owns pixels 32 v .. 32 v + 31 against every channel tile.  A stage is 64 bytes of K = four pieces; piece g of K is channels
-// 16 (g % cp16) .. + 15 of tap g / cp16 for BOTH operands, so the fragments pair code with code as in qgemm_i8_kernel.  The weights are
+// 16 (g % cp16) .. + 15 of tap g / cp16 for BOTH operands, so the fragments pair code with code (qi8_dev.h).  The weights are
 // the A operand and the pixels the B operand: C column = lane & 31 is a pixel, C row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) a
 // channel, and a wave's store of one register is 32 consecutive pixels of one channel plane.
 // CODES (tiles_n == 1: the workgroup sees every channel of its pixels): the epilogue's f32 value goes through the activation codec with the
@@ -140,13 +91,13 @@ __device__ __forceinline__ int qc_window_sum(const QcArgs &a, int img, int oh, i
 // channel-last row, the lane's at byte 8 (reg >> 2) + 4 (lane >> 5) of a 32-channel tile; two half-wave swaps (v_permlane32_swap) with
 // the lane that holds the other half of the same pixel leave 16 consecutive bytes in each, so a tile of a pixel is two 16-byte stores.
 template <int NT, bool CODES>
-__global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional<CODES, QcCodesArgs, QcArgs>::type a) {
+__global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
     __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, h = lane >> 5;
     const int tile_m = blockIdx.x / a.tiles_n, tile_n = blockIdx.x - tile_m * a.tiles_n;
-    const int m0 = tile_m * kQcPix, col0 = tile_n * kQcChan * NT;
-    const int cp16 = a.cpitch >> 4, taps = a.k_h * a.k_w, pieces = taps * cp16, nk = (pieces + 3) >> 2, hw_out = a.h_out * a.w_out;
+    const int m0 = tile_m * kQcPix, col0 = CODES ? 0 : tile_n * kQcChan * NT;   // (CODES: tiles_n == 1)
+    const int cp16 = a.cpitch >> 4, taps = a.win.k_h * a.win.k_w, pieces = taps * cp16, nk = (pieces + 3) >> 2, hw_out = a.win.h_out * a.win.w_out;
 
     // staging: thread t brings piece t & 3 of pixel rows t >> 2 and (t >> 2) + 64, and of weight rows (t >> 2) + 64 i below 32 NT
     const int srow = t >> 2, piece = t & 3;
@@ -156,10 +107,10 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional
     for (int i = 0; i < 2; ++i) {
         const int m = m0 + srow + 64 * i;
         const bool live = m < a.M;
-        const int img = live ? m / hw_out : 0, p = live ? m - img * hw_out : 0, oh = p / a.w_out, ow = p - oh * a.w_out;
-        ih0[i] = live ? oh * a.s_h - a.pad_h : -a.k_h;
-        iw0[i] = ow * a.s_w - a.pad_w;
-        px[i] = a.qx + (size_t)img * a.h * a.w * a.cpitch;
+        const QWindow::Pixel o = a.win.split(live ? m : 0);
+        ih0[i] = live ? a.win.top(o.oh) : -a.win.k_h;
+        iw0[i] = a.win.left(o.ow);
+        px[i] = a.qx + (size_t)o.img * a.win.h * a.win.w * a.cpitch;
     }
     constexpr int WL = (NT + 1) / 2;   // weight pieces a thread stages
     const size_t wrow_bytes = (size_t)pieces * 16;
@@ -167,12 +118,12 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional
     auto fetch = [&](int kt) {
         const int g = kt * 4 + piece;
         const bool in_k = g < pieces;
-        const int tap = g / cp16, cpiece = g - tap * cp16, kh = tap / a.k_w, kw = tap - kh * a.k_w;
+        const int tap = g / cp16, cpiece = g - tap * cp16, kh = tap / a.win.k_w, kw = tap - kh * a.win.k_w;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int ih = ih0[i] + kh, iw = iw0[i] + kw;
-            const bool inside = in_k && ih >= 0 && ih < a.h && iw >= 0 && iw < a.w;
-            gx[i] = inside ? *(const uint4 *)(px[i] + ((size_t)ih * a.w + iw) * a.cpitch + cpiece * 16) : make_uint4(0, 0, 0, 0);
+            const bool inside = in_k && ih >= 0 && ih < a.win.h && iw >= 0 && iw < a.win.w;
+            gx[i] = inside ? *(const uint4 *)(px[i] + ((size_t)ih * a.win.w + iw) * a.cpitch + cpiece * 16) : make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < WL; ++i) {
@@ -183,10 +134,10 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional
     };
     auto stage = [&](int buf) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) lds_x[buf][qc_slot(srow + 64 * i, piece)] = gx[i];
+        for (int i = 0; i < 2; ++i) lds_x[buf][stage_slot(srow + 64 * i, piece)] = gx[i];
 #pragma unroll
         for (int i = 0; i < WL; ++i)
-            if (srow + 64 * i < kQcChan * NT) lds_w[buf][qc_slot(srow + 64 * i, piece)] = gw[i];
+            if (srow + 64 * i < kQcChan * NT) lds_w[buf][stage_slot(srow + 64 * i, piece)] = gw[i];
     };
 
     intx16 acc[NT];
@@ -203,72 +154,53 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional
         if (kt + 1 < nk) fetch(kt + 1);   // in flight under this stage's MFMAs
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const uint4 vx = lds_x[buf][qc_slot(wave * 32 + li, 2 * s + h)];
-            const intx4 xf{(int)vx.x, (int)vx.y, (int)vx.z, (int)vx.w};
+            const intx4 xf = stage_frag(lds_x[buf], wave * 32 + li, s, h);
 #pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const uint4 vw = lds_w[buf][qc_slot(32 * j + li, 2 * s + h)];
-                acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(intx4{(int)vw.x, (int)vw.y, (int)vw.z, (int)vw.w}, xf, acc[j], 0, 0, 0);
-            }
+            for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(stage_frag(lds_w[buf], 32 * j + li, s, h), xf, acc[j], 0, 0, 0);
         }
         if (kt + 1 < nk) stage(buf ^ 1);   // (read last in step kt - 1: every wave passed that step's barrier)
         lds_barrier();
         buf ^= 1;
     }
 
-    // epilogue: this lane's pixel, its window's sum of pixel sums (integer; border windows have fewer taps), then store_tile's four operations
+    // epilogue: this lane's pixel, its window's sum of pixel sums (integer; border windows have fewer taps), then q8_value of the lane's 16 NT
+    // channels.  A pixel past M: the f32 form is done; the codes form keeps both its lanes (they share m) in the swaps and stores nothing.
     const int m = m0 + wave * 32 + li;
-    if constexpr (!CODES) {
-        if (m >= a.M) return;
-        const int img = m / hw_out, p = m - img * hw_out, oh = p / a.w_out, ow = p - oh * a.w_out;
-        const int rs = qc_window_sum(a, img, oh, ow);
-        const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1];
-        const float rterm = __fmul_rn(mw, (float)rs);
-        float *yp = a.y + (size_t)img * a.c_out * hw_out + p;
+    const bool live = m < a.M;
+    if (!CODES && !live) return;
+    const QWindow::Pixel o = a.win.split(live ? m : 0);
+    const int *ps = a.pixsum + (size_t)o.img * a.win.h * a.win.w;
+    int rs = 0;
+    if (live) a.win.for_taps(o.oh, o.ow, [&](int ih, int iw) { rs += ps[ih * a.win.w + iw]; });
+    const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1], rterm = q8_rterm(mw, rs), sy = CODES ? a.yscale[0] : 0.f;
+    float *yp = CODES ? nullptr : a.y + ((size_t)o.img * a.c_out + col0 + 4 * h) * hw_out + o.p;   // the f32 form: this pixel in the lane's first channel plane
+    int sum = 0;
 #pragma unroll
-        for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < NT; ++j) {
+        int q[16];   // CODES: the lane's channels of this tile through the activation codec with the next layer's scale; past c_out the code 0
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (co >= a.c_out) continue;
-                const int tt = acc[j][e] + 128 * rs;
-                float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
-                if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
-                yp[(size_t)co * hw_out] = a.relu ? (v > 0.f ? v : 0.f) : v;
+        for (int e = 0; e < 16; ++e) {
+            const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
+            q[e] = 0;
+            if (co >= a.c_out) continue;
+            const float v = q8_value(acc[j][e], rs, rterm, sx, sw, a.qb != nullptr, [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, a.relu);
+            if constexpr (CODES) {
+                q[e] = act_code(v, sy);
+                sum += q[e];
+            } else {
+                yp[(size_t)(32 * j + (e & 3) + 8 * (e >> 2)) * hw_out] = v;
             }
-    } else {
-        // (both lanes of a pixel share m: a pixel past M keeps its two lanes in the swaps and stores nothing)
-        const bool live = m < a.M;
-        const int img = live ? m / hw_out : 0, p = live ? m - img * hw_out : 0, oh = p / a.w_out, ow = p - oh * a.w_out;
-        const int rs = live ? qc_window_sum(a, img, oh, ow) : 0;
-        const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1], sy = a.yscale[0];
-        const float rterm = __fmul_rn(mw, (float)rs);
-        int8_t *row = a.qy + (size_t)m * a.cpitch_y + 16 * h;   // this lane's 16 bytes of a 32-channel tile
-        int sum = 0;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            uint32_t word[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                word[g] = 0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int co = 32 * j + 8 * g + 4 * h + i;   // (col0 == 0)
-                    if (co >= a.c_out) continue;                 // the code 0: the row's padding
-                    const int tt = acc[j][4 * g + i] + 128 * rs;
-                    float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)tt), rterm));
-                    if (a.qb) v = __fadd_rn(v, dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]));
-                    if (a.relu) v = v > 0.f ? v : 0.f;
-                    const int q = act_code(v, sy);
-                    sum += q;
-                    word[g] |= (uint32_t)(uint8_t)(int8_t)q << (8 * i);
-                }
-            }
-            // lower half: {own 0, upper's 0, own 1, upper's 1} = bytes 0 .. 15; upper half: {lower's 2, own 2, lower's 3, own 3} = bytes 16 .. 31
-            const auto r02 = __builtin_amdgcn_permlane32_swap(word[0], word[2], false, false);
-            const auto r13 = __builtin_amdgcn_permlane32_swap(word[1], word[3], false, false);
-            if (live && 32 * j + 16 * h < a.cpitch_y) *(uint4 *)(row + 32 * j) = make_uint4(r02[0], r02[1], r13[0], r13[1]);
         }
+        if constexpr (CODES) {
+            // q[4 g ..] is the word at byte 8 g + 4 h of the tile.  Swapped, the lower half holds {own 0, upper's 0, own 1, upper's 1}
+            // = bytes 0 .. 15 and the upper half {lower's 2, own 2, lower's 3, own 3} = bytes 16 .. 31
+            const uint4 w = piece_pack(q);
+            const auto r02 = __builtin_amdgcn_permlane32_swap(w.x, w.z, false, false);
+            const auto r13 = __builtin_amdgcn_permlane32_swap(w.y, w.w, false, false);
+            if (live && 32 * j + 16 * h < a.cpitch_y) *(uint4 *)(a.qy + (size_t)m * a.cpitch_y + 16 * h + 32 * j) = make_uint4(r02[0], r02[1], r13[0], r13[1]);
+        }
+    }
+    if constexpr (CODES) {
         for (int off = 32 * NT + 16 * h; off < a.cpitch_y; off += 32)   // a pitch beyond the channel tile: zeros
             if (live) *(uint4 *)(a.qy + (size_t)m * a.cpitch_y + off) = make_uint4(0, 0, 0, 0);
         sum += __shfl_xor(sum, 32, 64);   // the pixel's other half (integers: no order to keep)
@@ -278,18 +210,17 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(typename std::conditional
 
 // every host decision of the product (th_conv2d_q8q8_fwd launches from it, th_debug_qconv_plan reports it)
 struct QcPlan {
-    int nt, tiles_m, tiles_n, grid, h_out, w_out;
+    int nt, tiles_m, tiles_n, grid;
+    QWindow win;
 };
 // nullptr, or why the shape is refused
 static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, QcPlan *p) {
-    if (n < 0 || c_in <= 0 || h <= 0 || w <= 0 || c_out <= 0 || k_h <= 0 || k_w <= 0 || s_h <= 0 || s_w <= 0 || pad_h < 0 || pad_w < 0)
-        return "a shape, kernel or stride below 1, or a negative padding";
-    if ((long)h + 2L * pad_h < k_h || (long)w + 2L * pad_w < k_w) return "an empty output map";
-    if ((long)h + 2L * pad_h > 0x7fffffffL || (long)w + 2L * pad_w > 0x7fffffffL) return "a padded map side above 2^31";
-    if ((long)c_in * k_h * k_w > kQcMaxK) return "c_in * k_h * k_w above 65536, where the int32 sum can overflow";
-    p->h_out = (h + 2 * pad_h - k_h) / s_h + 1;
-    p->w_out = (w + 2 * pad_w - k_w) / s_w + 1;
-    const long M = (long)n * p->h_out * p->w_out;
+    const int bad = window_check(h, w, k_h, k_w, s_h, s_w, pad_h, pad_w, &p->win);
+    if (n < 0 || c_in <= 0 || c_out <= 0 || bad == kWinBelowOne) return "a shape, kernel or stride below 1, or a negative padding";
+    if (bad == kWinEmpty) return "an empty output map";
+    if (bad == kWinSide) return "a padded map side above 2^31";
+    if ((long)c_in * k_h * k_w > kQ8MaxK) return "c_in * k_h * k_w above " TH_Q8_STR(TH_Q8_MAX_K) ", where the int32 sum can overflow";
+    const long M = (long)n * p->win.h_out * p->win.w_out;
     if (M > 0x7fffffffL - kQcPix || (long)n * h * w > 0x7fffffffL) return "more than 2^31 pixels";
     p->nt = c_out <= kQcChan ? 1 : c_out <= 2 * kQcChan ? 2 : 4;   // a 128-wide channel tile on a 4- or 32-channel layer is mostly waste
     p->tiles_m = ceil_div(M, kQcPix);
@@ -302,43 +233,28 @@ static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h,
 // ---- the max-pool on codes ----
 // G lanes (a power of two, at most 64) share an output pixel and take its 16-byte pieces in turn; a piece's 16 maxima start from -128,
 // the code of the float pool's -inf start (maxpool_fwd_kernel), and run over the in-image taps.  Channels c .. cpitch - 1 come out 0.
-__global__ __launch_bounds__(256) void maxpool_nhwc_i8_kernel(const int8_t *__restrict__ q, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w,
-                                                              int pad_h, int pad_w, int h_out, int w_out, long pixels, int8_t *__restrict__ qy,
+__global__ __launch_bounds__(256) void maxpool_nhwc_i8_kernel(const int8_t *__restrict__ q, int c, int cpitch, QWindow win, long pixels, int8_t *__restrict__ qy,
                                                               int *__restrict__ ypixsum, int G) {
     const int t = threadIdx.x, gl = t & (G - 1), per_block = 256 / G, cp16 = cpitch >> 4;
-    const long hw_out = (long)h_out * w_out;
     for (long base = (long)blockIdx.x * per_block; base < pixels; base += (long)gridDim.x * per_block) {
         const long o = base + t / G;
         const bool live = o < pixels;
         int sum = 0;
         if (live) {
-            const long img = o / hw_out;
-            const int p = (int)(o - img * hw_out), oh = p / w_out, ow = p - oh * w_out;
-            const int8_t *xi = q + (size_t)img * h * w * cpitch;
+            const QWindow::Pixel px = win.split((int)o);   // (the host refuses 2^31 pixels)
+            const int8_t *xi = q + (size_t)px.img * win.h * win.w * cpitch;
             for (int piece = gl; piece < cp16; piece += G) {
                 int best[16];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) best[i] = -128;
-                for (int kh = 0; kh < k_h; ++kh) {
-                    const int ih = oh * s_h - pad_h + kh;
-                    if (ih < 0 || ih >= h) continue;
-                    for (int kw = 0; kw < k_w; ++kw) {
-                        const int iw = ow * s_w - pad_w + kw;
-                        if (iw < 0 || iw >= w) continue;
-                        const uint4 v = *(const uint4 *)(xi + ((size_t)ih * w + iw) * cpitch + piece * 16);
-                        const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+                win.for_taps(px.oh, px.ow, [&](int ih, int iw) {
+                    const uint4 v = *(const uint4 *)(xi + ((size_t)ih * win.w + iw) * cpitch + piece * 16);
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) best[i] = max(best[i], (int)(int8_t)((wd[i >> 2] >> (8 * (i & 3))) & 0xFF));
-                    }
-                }
-                uint32_t out[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if (piece * 16 + i < c) {
-                        sum += best[i];
-                        out[i >> 2] |= (uint32_t)(uint8_t)(int8_t)best[i] << (8 * (i & 3));
-                    }
-                *(uint4 *)(qy + (size_t)o * cpitch + piece * 16) = make_uint4(out[0], out[1], out[2], out[3]);
+                    for (int i = 0; i < 16; ++i) best[i] = max(best[i], piece_code(v, i));
+                });
+                const uint4 out = piece_pack(best, c - piece * 16);
+                sum += piece_sum(out);
+                *(uint4 *)(qy + (size_t)o * cpitch + piece * 16) = out;
             }
         }
         for (int off = G >> 1; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);   // the pixel's lanes (integers: no order to keep)
@@ -375,10 +291,8 @@ static int pack_conv_weight(const char *fn, bool taper, th_ctx *ctx, const int8_
                k_h, k_w, cpitch);
     if (c_out == 0) return 0;
     const dim3 grid(ew_grid((size_t)c_out * k_h * k_w * (cpitch / 16), 256));
-    if (taper)
-        hipLaunchKernelGGL(pack_conv_weight_kernel<true>, grid, dim3(256), 0, ctx->stream, d_src, (long)c_out, c_in, k_h * k_w, d_dst, cpitch);
-    else
-        hipLaunchKernelGGL(pack_conv_weight_kernel<false>, grid, dim3(256), 0, ctx->stream, d_src, (long)c_out, c_in, k_h * k_w, d_dst, cpitch);
+    hipLaunchKernelGGL(taper ? pack_conv_weight_kernel<true> : pack_conv_weight_kernel<false>, grid, dim3(256), 0, ctx->stream, d_src, (long)c_out, c_in, k_h * k_w,
+                       d_dst, cpitch);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -391,33 +305,37 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
     return pack_conv_weight("th_pack_conv_weight_taper_int8", true, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
 }
 
-// the checks both products share; fn: the caller's name for the message
-static int qconv_check(const char *fn, int cpitch, int n, int c_in, int h, int w, const void *d_qx, const void *d_qw, int c_out, int k_h, int k_w, int s_h,
-                       int s_w, int pad_h, int pad_w, QcPlan *p) {
-    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, p);
+// Both products: their checks (fn: the caller's name for the message), then the launch; the other form's outputs come null
+static int qconv_run(const char *fn, bool codes, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
+                     int w, const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
+                     const float *d_bparams, int relu, float *d_y, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
+    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && (codes ? d_yscale && d_qy : d_y != nullptr) && (!d_qb || d_bparams), "%s: null argument", fn);
+    QcPlan p{};
+    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
     TH_REQUIRE(!why, "%s: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", fn, why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w);
     TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", fn);
     TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", fn, cpitch, c_in);
+    if (codes) {
+        TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd)", fn, c_out,
+                   th_qconv_i8_chain_max_cout());
+        TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", fn);
+        TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", fn, cpitch_y, c_out);
+    }
+    if (n == 0) return 0;
+    const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, d_yscale, d_qy, d_ypixsum, cpitch_y, p.win, cpitch, c_out,
+                   n * p.win.h_out * p.win.w_out, relu, p.tiles_n};
+    auto kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true> : p.nt == 2 ? qconv_i8_kernel<2, true> : qconv_i8_kernel<4, true>)
+                        : (p.nt == 1 ? qconv_i8_kernel<1, false> : p.nt == 2 ? qconv_i8_kernel<2, false> : qconv_i8_kernel<4, false>);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    TH_LAUNCH_CHECK();
     return 0;
 }
 
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                        const float *d_bparams, int relu, float *d_y) {
-    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "th_conv2d_q8q8_fwd: null argument");
-    QcPlan p{};
-    if (int rc = qconv_check("th_conv2d_q8q8_fwd", cpitch, n, c_in, h, w, d_qx, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p)) return rc;
-    if (n == 0) return 0;
-    const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
-                   p.h_out, p.w_out, n * p.h_out * p.w_out, relu, p.tiles_n};
-    if (p.nt == 1)
-        hipLaunchKernelGGL((qconv_i8_kernel<1, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    else if (p.nt == 2)
-        hipLaunchKernelGGL((qconv_i8_kernel<2, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((qconv_i8_kernel<4, false>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    TH_LAUNCH_CHECK();
-    return 0;
+    return qconv_run("th_conv2d_q8q8_fwd", false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
+                     d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
 }
 
 int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
@@ -425,47 +343,29 @@ int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
 int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                              const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && d_yscale && d_qy && (!d_qb || d_bparams), "th_conv2d_q8q8_fwd_codes: null argument");
-    QcPlan p{};
-    if (int rc = qconv_check("th_conv2d_q8q8_fwd_codes", cpitch, n, c_in, h, w, d_qx, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p)) return rc;
-    TH_REQUIRE(p.tiles_n == 1, "th_conv2d_q8q8_fwd_codes: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd)",
-               c_out, th_qconv_i8_chain_max_cout());
-    TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "th_conv2d_q8q8_fwd_codes: the output code pointer must be 16-byte aligned");
-    TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "th_conv2d_q8q8_fwd_codes: cpitch_y %d must be a multiple of 16 and at least c_out %d", cpitch_y, c_out);
-    if (n == 0) return 0;
-    QcCodesArgs a{};
-    static_cast<QcArgs &>(a) = QcArgs{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, nullptr, cpitch, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
-                                      p.h_out, p.w_out, n * p.h_out * p.w_out, relu, p.tiles_n};
-    a.yscale = d_yscale, a.qy = d_qy, a.ypixsum = d_ypixsum, a.cpitch_y = cpitch_y;
-    if (p.nt == 1)
-        hipLaunchKernelGGL((qconv_i8_kernel<1, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    else if (p.nt == 2)
-        hipLaunchKernelGGL((qconv_i8_kernel<2, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((qconv_i8_kernel<4, true>), dim3(p.grid), dim3(256), 0, ctx->stream, a);
-    TH_LAUNCH_CHECK();
-    return 0;
+    return qconv_run("th_conv2d_q8q8_fwd_codes", true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+                     d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
 }
 
 int th_maxpool2d_nhwc_int8(th_ctx *ctx, const int8_t *d_q, int n, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w,
                            int8_t *d_qy, int *d_ypixsum) {
     TH_REQUIRE(ctx && d_q && d_qy && d_ypixsum, "th_maxpool2d_nhwc_int8: null argument");
     TH_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_qy) & 15) == 0, "th_maxpool2d_nhwc_int8: the code pointers must be 16-byte aligned");
-    TH_REQUIRE(n >= 0 && c > 0 && h > 0 && w > 0 && k_h > 0 && k_w > 0 && s_h > 0 && s_w > 0 && pad_h >= 0 && pad_w >= 0,
+    QWindow win{};
+    const int bad = window_check(h, w, k_h, k_w, s_h, s_w, pad_h, pad_w, &win);
+    TH_REQUIRE(n >= 0 && c > 0 && bad != kWinBelowOne,
                "th_maxpool2d_nhwc_int8: a shape, window or stride below 1, or a negative padding (n=%d c=%d %dx%d, k=%dx%d stride %dx%d pad %dx%d)", n, c, h, w,
                k_h, k_w, s_h, s_w, pad_h, pad_w);
     TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c, "th_maxpool2d_nhwc_int8: cpitch %d must be a multiple of 16 and at least c %d", cpitch, c);
-    TH_REQUIRE((long)h + 2L * pad_h >= k_h && (long)w + 2L * pad_w >= k_w && (long)h + 2L * pad_h <= 0x7fffffffL && (long)w + 2L * pad_w <= 0x7fffffffL,
-               "th_maxpool2d_nhwc_int8: an empty output map (%dx%d, k=%dx%d pad %dx%d)", h, w, k_h, k_w, pad_h, pad_w);
-    const int h_out = (h + 2 * pad_h - k_h) / s_h + 1, w_out = (w + 2 * pad_w - k_w) / s_w + 1;
-    const long pixels = (long)n * h_out * w_out;
+    TH_REQUIRE(bad == kWinOk, "th_maxpool2d_nhwc_int8: an empty output map (%dx%d, k=%dx%d pad %dx%d)", h, w, k_h, k_w, pad_h, pad_w);
+    const long pixels = (long)n * win.h_out * win.w_out;
     TH_REQUIRE(pixels <= 0x7fffffffL && (long)n * h * w <= 0x7fffffffL, "th_maxpool2d_nhwc_int8: more than 2^31 pixels");
     if (n == 0) return 0;
     int G = 1;   // lanes per pixel: the pieces of a pixel row rounded up to a power of two, a wave at the most
     while (G < cpitch / 16 && G < kWave) G *= 2;
     const long blocks = (pixels + 256 / G - 1) / (256 / G);
-    hipLaunchKernelGGL(maxpool_nhwc_i8_kernel, dim3((unsigned)std::min(blocks, (long)kNumCU * 32)), dim3(256), 0, ctx->stream, d_q, c, h, w, cpitch, k_h, k_w, s_h, s_w,
-                       pad_h, pad_w, h_out, w_out, pixels, d_qy, d_ypixsum, G);
+    hipLaunchKernelGGL(maxpool_nhwc_i8_kernel, dim3((unsigned)std::min(blocks, (long)kNumCU * 32)), dim3(256), 0, ctx->stream, d_q, c, cpitch, win, pixels, d_qy,
+                       d_ypixsum, G);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -476,7 +376,7 @@ int th_debug_qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h, int k
     const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
     TH_REQUIRE(!why, "th_debug_qconv_plan: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w,
                pad_h, pad_w);
-    const int out[8] = {p.nt, kQcPix, kQcChan * p.nt, p.tiles_m, p.tiles_n, p.grid, p.h_out, p.w_out};
+    const int out[8] = {p.nt, kQcPix, kQcChan * p.nt, p.tiles_m, p.tiles_n, p.grid, p.win.h_out, p.win.w_out};
     std::copy(out, out + 8, out8);
     return 0;
 }

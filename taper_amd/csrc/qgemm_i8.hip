@@ -3,26 +3,22 @@
 //
 //   th_quantize_act_int8  f32 [rows, k] -> symmetric int8 codes [rows, pitch] (th_fake_quant_act's codec with a scale fixed beforehand)
 //                         and the int32 sum of each row's codes; one launch, a wave per row
-//   th_pad_rows_int8      packed [rows, k] codes -> [rows, pitch] with zero padding (once per weight)
+//   th_pad_rows_int8      packed [rows, k] codes -> [rows, pitch] with zero padding (once per weight): the conv weight pack with one tap
 //   th_linear_q8q8_fwd    y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU], acc = sum_k qx qw from the MFMA;
 //                         two forms: 128 x 128 tiles through LDS, and a workgroup per 32 x 32 tile with K split over its waves for few rows
 //   th_act_range_update   calibration: the finite min / max of a tensor folded into a running device pair, and the scale they give
 //
-// The weight codec is affine with zero_point -128: w = (qw + 128) sw + mw, so x . w = sx (sw (acc + 128 rs) + mw rs) with rs the sum of
-// the row's activation codes -- every integer term is exact, and the four f32 operations round once each.  A row's result depends on
-// that row alone: nothing of the tiling reaches the arithmetic.
+// The piece of 16 codes, the LDS image of a stage, the fragment pairing and the epilogue's arithmetic are qi8_dev.h's, shared with
+// qconv_i8.hip; rs is the sum of the row's activation codes.  A row's result depends on that row alone: nothing of the tiling reaches
+// the arithmetic.
 #include "common.h"
-#include "quant_dev.h"
+#include "qi8_dev.h"
 #include "stream_dev.h"
 
 namespace th {
 
-typedef int intx4 __attribute__((ext_vector_type(4)));
-typedef int intx16 __attribute__((ext_vector_type(16)));
-
 constexpr int kQ8Tile = 128;       // macro-tile: 128 rows of x by 128 rows of W, four waves of 2 x 2 MFMA tiles
 constexpr int kQ8KStep = 64;       // bytes of K per LDS stage: two 32-k MFMA steps
-constexpr int kQ8MaxK = 65536;     // |acc + 128 rs| <= 128 * 255 * K stays below 2^31
 constexpr int kQ8Raster = 8;       // tile rows per group of the tile order (gemm.hip's sgemm_tile)
 constexpr int kQ8SkinnyMaxBatch = 256;   // up to here a workgroup per 32 x 32 tile with K split over its waves (measured: profiles/quant_static.md)
 
@@ -39,7 +35,7 @@ __global__ __launch_bounds__(256) void quantize_act_kernel(const float *__restri
         int8_t *qr = q + (size_t)row * pitch;
         int sum = 0;
         for (int k0 = lane * 16; k0 < pitch; k0 += 64 * 16) {
-            uint32_t w[4];
+            int c[16];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int kk = k0 + 4 * i;
@@ -51,40 +47,23 @@ __global__ __launch_bounds__(256) void quantize_act_kernel(const float *__restri
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = kk + j < k ? xr[kk + j] : 0.f;
                 }
-                uint32_t word = 0;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int c = kk + j < k ? act_code(v[j], scale) : 0;
-                    sum += c;
-                    word |= (uint32_t)(uint8_t)(int8_t)c << (8 * j);
+                    c[4 * i + j] = kk + j < k ? act_code(v[j], scale) : 0;
+                    sum += c[4 * i + j];
                 }
-                w[i] = word;
             }
+            const uint4 p = piece_pack(c);
             if (VEC) {
-                *(uint4 *)(qr + k0) = make_uint4(w[0], w[1], w[2], w[3]);
+                *(uint4 *)(qr + k0) = p;
             } else {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) qr[k0 + i] = (int8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xFF);
+                for (int i = 0; i < 16; ++i) qr[k0 + i] = (int8_t)piece_code(p, i);
             }
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);   // integers: any order gives the same bits
         if (lane == 0) rowsum[row] = sum;
-    }
-}
-
-__global__ __launch_bounds__(256) void pad_rows_kernel(const int8_t *__restrict__ src, long rows, int k, int8_t *__restrict__ dst, int pitch) {
-    const int per_row = pitch / 16;
-    const long total = rows * per_row;
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
-        const long row = c / per_row;
-        const int k0 = (int)(c - row * per_row) * 16;
-        const int8_t *s = src + (size_t)row * k;   // (packed rows are not 16-byte aligned in general: byte loads, once per weight)
-        uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (k0 + i < k) w[i >> 2] |= (uint32_t)(uint8_t)s[k0 + i] << (8 * (i & 3));
-        *(uint4 *)(dst + (size_t)row * pitch + k0) = make_uint4(w[0], w[1], w[2], w[3]);
     }
 }
 
@@ -99,7 +78,7 @@ struct Q8Epilogue {
 };
 
 // One 32 x 32 accumulator tile out: this lane holds column n (a row of W) of rows row_base + (e & 3) + 8 (e >> 2) (row_base includes the
-// lane half's 4 h).  y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU], each operation rounded once.
+// lane half's 4 h), each through q8_value.
 __device__ __forceinline__ void store_tile(const intx16 &acc, int row_base, int n, const Q8Epilogue &ep) {
     if (n >= ep.N) return;
     const float sx = ep.xscale[0], mw = ep.wparams[0], sw = ep.wparams[1];
@@ -108,21 +87,14 @@ __device__ __forceinline__ void store_tile(const intx16 &acc, int row_base, int 
     for (int e = 0; e < 16; ++e) {
         const int row = row_base + (e & 3) + 8 * (e >> 2);
         if (row >= ep.M) continue;
-        const int rs = ep.rowsum[row], t = acc[e] + 128 * rs;
-        float v = __fmul_rn(sx, __fadd_rn(__fmul_rn(sw, (float)t), __fmul_rn(mw, (float)rs)));
-        if (ep.qb) v = __fadd_rn(v, bias);
-        ep.y[(size_t)row * ep.N + n] = ep.relu ? (v > 0.f ? v : 0.f) : v;
+        const int rs = ep.rowsum[row];
+        ep.y[(size_t)row * ep.N + n] = q8_value(acc[e], rs, q8_rterm(mw, rs), sx, sw, ep.qb != nullptr, [&] { return bias; }, ep.relu);
     }
 }
 
 // ---- the product ----
-// LDS image of an operand stage: 128 rows of 64 bytes, the 16-byte piece c of row r at slot c ^ ((r >> 2) & 3) -- the 16 lanes a
-// ds_read_b128 serves together (rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one piece) then land on 16 different slots.
-// Fragments: lane l (r = l & 31, h = l >> 5) holds 16 consecutive codes of row r of its operand, piece 2 s + h of the stage in MFMA
-// step s -- for BOTH operands, so that whatever order the instruction gives the 16 codes of a lane, a code of x meets the code of W at
-// the same k.  C/D: column = lane & 31 (a row of W), row = (reg & 3) + 8 (reg >> 2) + 4 h (a row of x).
-__device__ __forceinline__ int lds_slot(int row, int piece) { return row * 4 + (piece ^ ((row >> 2) & 3)); }
-
+// Each operand's stage is 128 rows in qi8_dev.h's image; x is the MFMA's A operand and W its B: C/D column = lane & 31 is a row of W,
+// C/D row = (reg & 3) + 8 (reg >> 2) + 4 h a row of x.
 __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict__ qx, int pitch_x, int K, const int8_t *__restrict__ qw, int pitch_w,
                                                        Q8Epilogue ep, int tiles_m, int tiles_n) {
     const int M = ep.M, N = ep.N;
@@ -161,8 +133,8 @@ __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict_
     auto stage = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            lds[buf][0][lds_slot(srow + 64 * i, piece)] = ga[i];
-            lds[buf][1][lds_slot(srow + 64 * i, piece)] = gb[i];
+            lds[buf][0][stage_slot(srow + 64 * i, piece)] = ga[i];
+            lds[buf][1][stage_slot(srow + 64 * i, piece)] = gb[i];
         }
     };
 
@@ -185,9 +157,8 @@ __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict_
             intx4 a[2], b[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const uint4 va = lds[buf][0][lds_slot(wm + 32 * i + li, 2 * s + h)], vb = lds[buf][1][lds_slot(wn + 32 * i + li, 2 * s + h)];
-                a[i] = intx4{(int)va.x, (int)va.y, (int)va.z, (int)va.w};
-                b[i] = intx4{(int)vb.x, (int)vb.y, (int)vb.z, (int)vb.w};
+                a[i] = stage_frag(lds[buf][0], wm + 32 * i + li, s, h);
+                b[i] = stage_frag(lds[buf][1], wn + 32 * i + li, s, h);
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -240,8 +211,7 @@ __global__ __launch_bounds__(256) void qgemm_i8_skinny_kernel(const int8_t *__re
         for (int u = 0; u < 4; ++u)
 #pragma unroll
             for (int s = 0; s < 2; ++s)
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(intx4{(int)va[u][s].x, (int)va[u][s].y, (int)va[u][s].z, (int)va[u][s].w},
-                                                            intx4{(int)vb[u][s].x, (int)vb[u][s].y, (int)vb[u][s].z, (int)vb[u][s].w}, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(as_frag(va[u][s]), as_frag(vb[u][s]), acc, 0, 0, 0);
     }
     if (wave > 0) {
 #pragma unroll
@@ -310,10 +280,8 @@ int th_quantize_act_int8(th_ctx *ctx, const float *d_x, int rows, int k, const f
                rows, k, pitch);
     if (rows == 0) return 0;
     const dim3 grid(std::min(ceil_div(rows, 4), kNumCU * 16));
-    if (k % 4 == 0 && (((uintptr_t)d_x | (uintptr_t)d_q) & 15) == 0)
-        hipLaunchKernelGGL(quantize_act_kernel<true>, grid, dim3(256), 0, ctx->stream, d_x, rows, k, d_scale, d_q, pitch, d_rowsum);
-    else
-        hipLaunchKernelGGL(quantize_act_kernel<false>, grid, dim3(256), 0, ctx->stream, d_x, rows, k, d_scale, d_q, pitch, d_rowsum);
+    const bool vec = k % 4 == 0 && (((uintptr_t)d_x | (uintptr_t)d_q) & 15) == 0;
+    hipLaunchKernelGGL(vec ? quantize_act_kernel<true> : quantize_act_kernel<false>, grid, dim3(256), 0, ctx->stream, d_x, rows, k, d_scale, d_q, pitch, d_rowsum);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -323,7 +291,8 @@ int th_pad_rows_int8(th_ctx *ctx, const int8_t *d_src, int rows, int k, int8_t *
     TH_REQUIRE(rows >= 0 && k > 0 && pitch >= k && pitch % 16 == 0 && ((uintptr_t)d_dst & 15) == 0,
                "th_pad_rows_int8: bad shape rows=%d k=%d pitch=%d (pitch >= k, a multiple of 16) or a destination off a 16-byte boundary", rows, k, pitch);
     if (rows == 0) return 0;
-    hipLaunchKernelGGL(pad_rows_kernel, dim3(ew_grid((size_t)rows * (pitch / 16), 256)), dim3(256), 0, ctx->stream, d_src, (long)rows, k, d_dst, pitch);
+    hipLaunchKernelGGL(pack_conv_weight_kernel<false>, dim3(ew_grid((size_t)rows * (pitch / 16), 256)), dim3(256), 0, ctx->stream, d_src, (long)rows, k, 1, d_dst,
+                       pitch);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -358,6 +327,7 @@ int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4) 
 }
 
 int th_qlinear_i8_kstep(void) { return kQ8KStep; }
+int th_q8q8_max_k(void) { return kQ8MaxK; }
 
 int th_act_range_update(th_ctx *ctx, const float *d_x, int64_t n, int first, float *d_range2, float *d_scale) {
     TH_REQUIRE(ctx && n >= 0 && (n == 0 || d_x) && d_range2 && d_scale, "th_act_range_update: null argument");

@@ -203,7 +203,7 @@ def test_channel_last_codes_and_pixel_sums(ctx, shape):
 
 def test_weight_pack_is_a_transpose_and_pad(ctx):
     rng = np.random.default_rng(2)
-    for co, ci, kh, kw, pitch in ((1, 1, 1, 1, 16), (4, 1, 3, 3, 16), (5, 17, 3, 2, 32), (33, 16, 5, 5, 16), (8, 70, 3, 3, 96)):
+    for co, ci, kh, kw, pitch in ((1, 1, 1, 1, 16), (4, 1, 3, 3, 16), (5, 17, 3, 2, 32), (33, 16, 5, 5, 16), (8, 70, 3, 3, 96), (5, 33, 1, 1, 96)):
         src = rng.integers(-128, 128, (co, ci, kh, kw)).astype(np.int8)
         n = co * kh * kw * pitch
         dst = ctx.upload(np.concatenate([np.full(64, 0xA5, np.uint8), np.full(n, 0x7F, np.uint8), np.full(64, 0xA5, np.uint8)]))
@@ -211,6 +211,10 @@ def test_weight_pack_is_a_transpose_and_pad(ctx):
         raw = ctx.download(dst, (n + 128,), np.uint8)
         assert (raw[:64] == 0xA5).all() and (raw[64 + n:] == 0xA5).all()
         np.testing.assert_array_equal(raw[64:64 + n].view(np.int8).reshape(co, kh * kw, pitch), Q.pack_weight(src, pitch))
+        if (kh, kw) == (1, 1):      # one tap: the rows of a Linear's weight, th_pad_rows_int8's (rows, k, pitch) -- the same bytes from either entry point
+            rows = ctx.upload(np.full(n, 0x7F, np.uint8))
+            ctx.call("th_pad_rows_int8", ctx.upload(src.view(np.uint8)), co, ci, rows, pitch)
+            np.testing.assert_array_equal(ctx.download(rows, (n,), np.uint8), raw[64:64 + n])
         # the same buffer as a model's Conv2d reads it (weight_layout 0)
         ctx.call("th_pack_conv_weight_taper_int8", ctx.upload(src.view(np.uint8)), co, ci, kh, kw, dst.offset(64), pitch)
         raw = ctx.download(dst, (n + 128,), np.uint8)

@@ -205,12 +205,18 @@ def test_a_row_of_the_lowest_code_at_the_largest_k(ctx):
 
 
 def test_pad_rows(ctx):
+    """k below, at and above a 16-byte piece and a pitch looser than the tight one; the packed source at an odd byte offset (its rows are not
+    16-byte aligned in general), the destination between two guard regions that must come back untouched"""
     rng = np.random.default_rng(2)
-    for rows, k, pitch in ((1, 1, 16), (7, 17, 64), (10, 784, 832), (3, 64, 64)):
+    for rows, k, pitch in ((1, 1, 16), (7, 17, 64), (10, 784, 832), (3, 64, 64), (1, 15, 16), (2, 16, 16), (3, 17, 32), (5, 33, 96)):
         src = rng.integers(-128, 128, (rows, k)).astype(np.int8)
-        dst = ctx.upload(np.full(rows * pitch, 0x7F, np.uint8))
-        ctx.call("th_pad_rows_int8", ctx.upload(src.view(np.uint8)), rows, k, dst, pitch)
-        np.testing.assert_array_equal(ctx.download(dst, (rows, pitch), np.int8), _padded(src, pitch))
+        n = rows * pitch
+        sbuf = ctx.upload(np.concatenate([np.full(3, 0x33, np.uint8), src.reshape(-1).view(np.uint8), np.full(13, 0x33, np.uint8)]))
+        dst = ctx.upload(np.concatenate([np.full(64, 0xA5, np.uint8), np.full(n, 0x7F, np.uint8), np.full(64, 0xA5, np.uint8)]))
+        ctx.call("th_pad_rows_int8", sbuf.offset(3), rows, k, dst.offset(64), pitch)
+        raw = ctx.download(dst, (n + 128,), np.uint8)
+        assert (raw[:64] == 0xA5).all() and (raw[64 + n:] == 0xA5).all(), "bytes around the padded rows were written"
+        np.testing.assert_array_equal(raw[64:64 + n].view(np.int8).reshape(rows, pitch), _padded(src, pitch))
 
 
 # ---------------------------------------------------------------- 3: refusals (host checks before any launch)
