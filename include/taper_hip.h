@@ -370,6 +370,16 @@ int th_f16_to_f32(th_ctx *ctx, const uint16_t *d_x, float *d_y, size_t n);
  * {min_val, scale} on the device; zero_point is -128.  Dequantise (tensor.rs:353-360): (q - zero_point) * scale + min_val. */
 int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params);
 int th_dequantize_int8(th_ctx *ctx, const int8_t *d_q, float *d_y, size_t n, float scale, int zero_point, float min_val);
+/* The same codec with one {min_val, scale} pair per channel: element k of channel c is d_x[c * chan_stride + k * elem_stride],
+ * its code goes to the same index of d_q, and d_params[2 c], d_params[2 c + 1] receive the pair of the finite min / max of channel c
+ * alone -- bit for bit th_quantize_int8 applied to the gathered channel.  Two geometries, both read coalesced: rows (chan_stride == len,
+ * elem_stride == 1: a Linear weight [out, in]; one launch, a workgroup per row) and columns (chan_stride == 1, elem_stride == channels: a
+ * Conv2d buffer as the float kernels read it, [c_in k_h k_w][c_out]; two launches, lanes across channels and the K walk split over waves
+ * and workgroups).  channels == 1 with elem_stride == 1 is th_quantize_int8 itself.  Min / max folds are compares: no float atomics,
+ * nothing read back, no host synchronisation (capturable).  Refused before a launch: a null argument, channels or len below 1, any other
+ * stride pair. */
+int th_quantize_int8_channels(th_ctx *ctx, const float *d_x, int channels, int64_t len, int64_t chan_stride, int64_t elem_stride, int8_t *d_q,
+                              float *d_params);
 
 /* ---- quantized inference: QuantizedLinear / QuantizedConv2d forward of src/nn.rs:88-120, 336-429 (csrc/qlinear.hip) ---- */
 /* Every weight takes exactly the value the codecs above give it -- int8: (float)(q + 128) * scale + min_val, two roundings, with
@@ -417,6 +427,12 @@ int th_pad_rows_int8(th_ctx *ctx, const int8_t *d_src, int rows, int k, int8_t *
 int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
                        const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams,
                        int relu, float *d_y);
+/* th_linear_q8q8_fwd with one weight pair per output row: d_wparams is [out_features][2], {mw, sw} of row n at d_wparams[2 n],
+ * d_wparams[2 n + 1] (th_quantize_int8_channels' rows), y = sx * (sw[n] * (float)t + mw[n] * (float)rs) ...; the bias pair stays one.
+ * The same kernels, tile forms, plan (th_debug_q8q8_plan) and refusals. */
+int th_linear_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                          const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams,
+                          int relu, float *d_y);
 int th_qlinear_i8_kstep(void);   /* bytes of K the product stages at a time (64): the pitch a caller should round in_features up to */
 int th_q8q8_max_k(void);         /* the longest K (in_features; c_in k_h k_w of a conv) the int8 products take: 65 536 */
 /* Calibration: d_range2 = {min, max} over the FINITE elements of every tensor shown so far (first != 0: of this tensor alone) and
@@ -453,6 +469,12 @@ int th_qconv_i8_cpitch(int c_in);   /* the channel pitch a caller should use: c_
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                        const int8_t *d_qb, const float *d_bparams, int relu, float *d_y);
+/* th_conv2d_q8q8_fwd with one weight pair per output channel: d_wparams is [c_out][2], {mw, sw} of channel co at d_wparams[2 co],
+ * d_wparams[2 co + 1] (th_quantize_int8_channels' columns on the model's buffer); the bias pair stays one.  The same kernel body, forms
+ * (th_debug_qconv_plan) and refusals. */
+int th_conv2d_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                          const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                          const int8_t *d_qb, const float *d_bparams, int relu, float *d_y);
 /* ---- activations that stay int8 between two static convolutions ----
  * th_conv2d_q8q8_fwd_codes: th_conv2d_q8q8_fwd's product and its f32 value v (the same operations, bias and ReLU included), then the
  * activation codec with the NEXT layer's scale instead of a store of v:
@@ -465,6 +487,10 @@ int th_qconv_i8_chain_max_cout(void);
 int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                              const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum);
+/* th_conv2d_q8q8_fwd_codes with d_wparams [c_out][2] as in th_conv2d_q8q8_fwd_pc: the same codec, swaps, stores and refusals */
+int th_conv2d_q8q8_fwd_codes_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum);
 /* The max-pool on channel-last codes [n][h][w][cpitch] -> [n][h_out][w_out][cpitch], h_out = (h + 2 pad_h - k_h) / s_h + 1: every byte the
  * maximum over the in-image taps from -128 (the code of the float pool's -inf start), bytes c .. cpitch - 1 written 0, d_ypixsum the sum
  * over the c channels.  The codec never decreases in its argument, so this is the code of th_maxpool2d_fwd's result on finite values.

@@ -174,6 +174,17 @@ int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *c
  * codes (th_maxpool2d_nhwc_int8) and B skips its codec -- no f32 tensor exists at the boundary.  Anything else between two convs (a ReLU
  * behind the pool, a second pool, any other layer, a weight-only conv, a wider A) runs as in tp_module_quantize_static_conv's twin. */
 int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out);
+/* The three calls above as one, by flags, and per-channel weight pairs: TP_QSTATIC_CONVS is tp_module_quantize_static_conv, with
+ * TP_QSTATIC_CHAIN tp_module_quantize_static_chain (CHAIN without CONVS, and any unknown bit, is refused).  TP_QSTATIC_PER_CHANNEL gives the
+ * weight of every static layer one {min_val, scale} pair per output channel instead of one for the tensor -- a Linear's rows; a static
+ * conv's effective output channels, the columns of its buffer as the float kernels read it ([c_in k_h k_w][c_out]) -- each pair from the
+ * finite min / max of that channel alone (th_quantize_int8_channels), and the products read them (th_linear_q8q8_fwd_pc,
+ * th_conv2d_q8q8_fwd_pc, th_conv2d_q8q8_fwd_codes_pc).  Biases and every layer that stays weight-only keep one pair; calibration, scales,
+ * links and refusals are those of the per-tensor twin. */
+#define TP_QSTATIC_CONVS 1
+#define TP_QSTATIC_CHAIN 2
+#define TP_QSTATIC_PER_CHANNEL 4
+int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out);
 /* the layer boundaries a forward crosses in int8 (the links above); 0 for every twin but tp_module_quantize_static_chain's */
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out);
 /* the calibrated activation scales in layer order: *n = their count (0 for a weight-only twin), the first min(*n, cap) into h_scales (nullable) */
@@ -181,14 +192,20 @@ int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n)
 int tp_qmodule_free(tp_qmodule *q);
 /* QuantizedModule::forward: records no tape node; the output does not require a gradient */
 int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out);
-/* code bytes of every tensor (a static twin's Linear weights with their row padding), plus 8 bytes of {min_val, scale} per int8 tensor and
- * 4 bytes per activation scale */
+/* code bytes of every tensor (a static twin's Linear weights with their row padding), plus 8 bytes of {min_val, scale} per int8 tensor
+ * (per channel of a per-channel tensor) and 4 bytes per activation scale */
 int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out);
 /* the packed tensors in the order of the source's parameters(): length, then codes (n int8 or n uint16; h_codes nullable),
  * {min_val, scale} (int8; {0, 0} for Float16; nullable) and the qtype (nullable) */
 int tp_qmodule_num_tensors(const tp_qmodule *q, int *out);
 int tp_qmodule_tensor_len(const tp_qmodule *q, int i, size_t *out);
 int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params, int *qtype);
+/* Per-channel tensors (TP_QSTATIC_PER_CHANNEL): element k of channel c is code c * chan_stride + k * elem_stride of the packed tensor; a
+ * tensor with one pair returns 1, 0, 1.  tp_qmodule_tensor_params: *n_pairs = the tensor's pairs (its channels; 1 for a per-tensor int8
+ * tensor, 0 for Float16), the first min(*n_pairs, cap_pairs) as {min_val, scale} into h_pairs (nullable).  tp_qmodule_tensor refuses a
+ * non-null h_params on a per-channel tensor; its codes and qtype work as before. */
+int tp_qmodule_tensor_channels(const tp_qmodule *q, int i, size_t *channels, size_t *chan_stride, size_t *elem_stride);
+int tp_qmodule_tensor_params(const tp_qmodule *q, int i, float *h_pairs, size_t cap_pairs, size_t *n_pairs);
 
 /* ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager}.rs) ----
  * config: qtype 0 Int8 / 1 Float16 (2..4 refused like tp_module_quantize), activations (fake-quantize each layer's output, before any

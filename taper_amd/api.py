@@ -348,6 +348,18 @@ class Module:
         tp_check(host.tp_module_quantize_static_chain(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_chain")
         return QuantizedModule(h.value)
 
+    def quantize_static_per_channel(self, calib, convs=True, chain=True):
+        """quantize_static / quantize_static_conv / quantize_static_chain (by `convs` and `chain`) with one {min_val, scale} pair per output
+        channel for the weight of every static layer: a Linear's rows, a static conv's effective output channels.  Biases and every layer
+        that stays weight-only keep one pair; act_scales() and chain_links() are the per-tensor twin's.  tensors() gives such a weight's
+        pairs as an ndarray of shape (channels, 2), channel_layout(i) where a channel's codes lie."""
+        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
+        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
+        h = _p()
+        flags = (1 if convs or chain else 0) | (2 if chain else 0) | 4
+        tp_check(host.tp_module_quantize_static_ex(self._h, arr, len(tensors), flags, C.byref(h)), "Module::quantize_static_per_channel")
+        return QuantizedModule(h.value)
+
 
 class QuantizedModule:
     """nn.rs:20-23: forward from the packed codes (no tape node, the output needs no gradient)"""
@@ -391,7 +403,7 @@ class QuantizedModule:
 
     def tensors(self):
         """[(qtype, codes, (min_val, scale))] in parameter order: codes int8 with its pair for "int8", uint16 half bits and
-        (0, 0) for "float16"."""
+        (0, 0) for "float16".  A per-channel tensor (quantize_static_per_channel) has an ndarray of shape (channels, 2) as its third element."""
         n = C.c_int()
         tp_check(host.tp_qmodule_num_tensors(self._h, C.byref(n)), "QuantizedModule::tensors")
         out = []
@@ -401,11 +413,25 @@ class QuantizedModule:
             qt = C.c_int()
             tp_check(host.tp_qmodule_tensor(self._h, i, None, None, C.byref(qt)), "QuantizedModule::tensors")
             codes = np.zeros(ln.value, np.int8 if qt.value == 0 else np.uint16)
+            channels, chan_stride, _ = self.channel_layout(i)
+            if chan_stride:
+                pairs, n_pairs = np.zeros((channels, 2), np.float32), C.c_size_t()
+                tp_check(host.tp_qmodule_tensor(self._h, i, codes.ctypes.data if ln.value else None, None, None), "QuantizedModule::tensors")
+                tp_check(host.tp_qmodule_tensor_params(self._h, i, pairs.ctypes.data, channels, C.byref(n_pairs)), "QuantizedModule::tensors")
+                out.append(("int8", codes, pairs))
+                continue
             params = np.zeros(2, np.float32)
             tp_check(host.tp_qmodule_tensor(self._h, i, codes.ctypes.data if ln.value else None, params.ctypes.data, None),
                      "QuantizedModule::tensors")
             out.append(("int8" if qt.value == 0 else "float16", codes, (params[0], params[1])))
         return out
+
+    def channel_layout(self, i):
+        """(channels, chan_stride, elem_stride) of tensor i: element k of channel c is code c * chan_stride + k * elem_stride; (1, 0, 1) for
+        a tensor with one pair"""
+        ch, cs, es = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        tp_check(host.tp_qmodule_tensor_channels(self._h, int(i), C.byref(ch), C.byref(cs), C.byref(es)), "QuantizedModule::channel_layout")
+        return ch.value, cs.value, es.value
 
 
 def _mk(fn, name, *args):

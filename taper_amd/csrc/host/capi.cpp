@@ -286,40 +286,39 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
     *out = h.release();
     TP_END
 }
-int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
-    TP_BEGIN
-    TAPER_ASSERT(m && out, "tp_module_quantize_static: null argument");
+// every static twin: `fn` is the caller's name for the message
+static void quantize_static_into(const char *fn, const tp_module *m, const tp_tensor *const *calib, int n_calib, bool convs, bool chain, bool per_channel,
+                                 tp_qmodule **out) {
+    TAPER_ASSERT(m && out, std::string(fn) + ": null argument");
     std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
     for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
     auto h = std::make_unique<tp_qmodule>();
-    h->q = quantize_static(*m->m, c);
+    h->q = quantize_static(*m->m, c, convs, chain, per_channel);
     h->q->tensors(&h->tensors);
     h->q->act_scales(&h->act_scales);
     *out = h.release();
+}
+int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
+    TP_BEGIN
+    quantize_static_into("tp_module_quantize_static", m, calib, n_calib, false, false, false, out);
     TP_END
 }
 int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
-    TAPER_ASSERT(m && out, "tp_module_quantize_static_conv: null argument");
-    std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
-    for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
-    auto h = std::make_unique<tp_qmodule>();
-    h->q = quantize_static(*m->m, c, /*convs=*/true);
-    h->q->tensors(&h->tensors);
-    h->q->act_scales(&h->act_scales);
-    *out = h.release();
+    quantize_static_into("tp_module_quantize_static_conv", m, calib, n_calib, /*convs=*/true, false, false, out);
     TP_END
 }
 int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
-    TAPER_ASSERT(m && out, "tp_module_quantize_static_chain: null argument");
-    std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
-    for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
-    auto h = std::make_unique<tp_qmodule>();
-    h->q = quantize_static(*m->m, c, /*convs=*/true, /*chain=*/true);
-    h->q->tensors(&h->tensors);
-    h->q->act_scales(&h->act_scales);
-    *out = h.release();
+    quantize_static_into("tp_module_quantize_static_chain", m, calib, n_calib, /*convs=*/true, /*chain=*/true, false, out);
+    TP_END
+}
+int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
+    TP_BEGIN
+    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL)) == 0, "tp_module_quantize_static_ex: unknown flag bits");
+    TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), "tp_module_quantize_static_ex: TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
+    quantize_static_into("tp_module_quantize_static_ex", m, calib, n_calib, (flags & TP_QSTATIC_CONVS) != 0, (flags & TP_QSTATIC_CHAIN) != 0,
+                         (flags & TP_QSTATIC_PER_CHANNEL) != 0, out);
     TP_END
 }
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out) {
@@ -362,6 +361,7 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
     TP_BEGIN
     TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor: index out of range");
     const QTensor &t = *q->tensors[i];
+    TAPER_ASSERT(!h_params || !t.per_channel(), "tp_qmodule_tensor: a per-channel tensor has a pair per channel: read them with tp_qmodule_tensor_params");
     th_ctx *ctx = Device::ctx();
     if (h_codes && t.n && t.pitch) {   // a padded matrix: the rows without their padding
         const size_t rows = t.shape[0], k = t.shape[1];
@@ -376,6 +376,24 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
         if (t.params) taper::th_check(th_memcpy_d2h(ctx, h_params, t.params->d, 2 * sizeof(float)), "th_memcpy_d2h");
     }
     if (qtype) *qtype = t.qtype;
+    TP_END
+}
+int tp_qmodule_tensor_channels(const tp_qmodule *q, int i, size_t *channels, size_t *chan_stride, size_t *elem_stride) {
+    TP_BEGIN
+    TAPER_ASSERT(q && channels && chan_stride && elem_stride, "tp_qmodule_tensor_channels: null argument");
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor_channels: index out of range");
+    const QTensor &t = *q->tensors[i];
+    *channels = t.channels, *chan_stride = t.chan_stride, *elem_stride = t.elem_stride;
+    TP_END
+}
+int tp_qmodule_tensor_params(const tp_qmodule *q, int i, float *h_pairs, size_t cap_pairs, size_t *n_pairs) {
+    TP_BEGIN
+    TAPER_ASSERT(q && n_pairs, "tp_qmodule_tensor_params: null argument");
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->tensors.size(), "tp_qmodule_tensor_params: index out of range");
+    const QTensor &t = *q->tensors[i];
+    *n_pairs = t.params ? t.channels : 0;
+    const size_t take = std::min(*n_pairs, cap_pairs);
+    if (h_pairs && take) taper::th_check(th_memcpy_d2h(Device::ctx(), h_pairs, t.params->d, take * 2 * sizeof(float)), "th_memcpy_d2h");
     TP_END
 }
 static QATConfig qat_config(int qtype, int activations, int symmetric, int per_channel) {

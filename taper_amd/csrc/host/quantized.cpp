@@ -26,6 +26,19 @@ QTensor quantize_tensor(const Tensor &t, int qtype) {   // tensor.rs:2084-2108 f
     return q;
 }
 
+// An int8 weight with one pair per channel (th_quantize_int8_channels): element k of channel c at t[c * chan_stride + k * elem_stride]
+QTensor quantize_channels(const Tensor &t, size_t channels, size_t chan_stride, size_t elem_stride) {
+    QTensor q;
+    q.n = t.len();
+    q.shape = t.shape();
+    q.channels = channels, q.chan_stride = chan_stride, q.elem_stride = elem_stride;
+    q.codes = Buffer::alloc((q.n + 3) / 4);
+    q.params = Buffer::alloc(2 * channels);
+    TH(th_quantize_int8_channels(Device::ctx(), t.dptr(), (int)channels, (int64_t)(q.n / channels), (int64_t)chan_stride, (int64_t)elem_stride,
+                                 reinterpret_cast<int8_t *>(q.codes->d), q.params->d));
+    return q;
+}
+
 // the reference's parameter-free layers: their twins run the float layer itself (values pass through unchanged)
 class QPass : public QuantizedModule {
    public:
@@ -65,8 +78,11 @@ struct BiasPtrs {
 class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
    public:
     // stat: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
-    // activation scale on the device that calibration fixes
-    QLinear(const Linear &l, int qtype, bool stat = false) : w_(quantize_tensor(l.weight, qtype)), k_(l.weight.shape()[1]), n_(l.weight.shape()[0]) {
+    // activation scale on the device that calibration fixes; per_channel (static only): one weight pair per row
+    QLinear(const Linear &l, int qtype, bool stat = false, bool per_channel = false)
+        : w_(stat && per_channel ? quantize_channels(l.weight, l.weight.shape()[0], l.weight.shape()[1], 1) : quantize_tensor(l.weight, qtype)),
+          k_(l.weight.shape()[1]),
+          n_(l.weight.shape()[0]) {
         if (l.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(l.bias, qtype));
         if (!stat) return;
         const size_t step = (size_t)th_qlinear_i8_kstep();
@@ -88,8 +104,9 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
             const size_t pitch = (k_ + 15) / 16 * 16;
             auto qx = Buffer::alloc(batch * pitch / 4), rs = Buffer::alloc(batch);
             TH(th_quantize_act_int8(ctx, x.dptr(), (int)batch, (int)k_, act_.scale(), reinterpret_cast<int8_t *>(qx->d), (int)pitch, reinterpret_cast<int *>(rs->d)));
-            TH(th_linear_q8q8_fwd(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)pitch, reinterpret_cast<const int *>(rs->d), act_.scale(), (int)batch, (int)k_,
-                                  reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d, b.i8(), b.params, relu ? 1 : 0, y.dptr()));
+            const auto product = w_.per_channel() ? th_linear_q8q8_fwd_pc : th_linear_q8q8_fwd;   // (a pair per row, or one)
+            TH(product(ctx, reinterpret_cast<const int8_t *>(qx->d), (int)pitch, reinterpret_cast<const int *>(rs->d), act_.scale(), (int)batch, (int)k_,
+                       reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d, b.i8(), b.params, relu ? 1 : 0, y.dptr()));
         } else if (w_.qtype == TH_QTYPE_INT8)
             TH(th_linear_q8_fwd(ctx, x.dptr(), (int)batch, (int)k_, reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, w_.params->d, b.i8(), b.params,
                                 relu ? 1 : 0, y.dptr()));
@@ -133,8 +150,11 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         return c.groups == 1 && c.dilation == std::make_pair(1, 1) && c.stride == std::make_pair(1, 1) && ws[2] == 3 && ws[3] == 3;
     }
     // stat: the static int8 twin (quantize_static with convs) -- the weight codes re-laid once channel-last for the product (an internal
-    // copy: tensors() keeps reporting the packed codes), and one activation scale on the device that calibration fixes
-    QConv(const Conv2d &c, int qtype, bool stat = false) : geom_(std::make_shared<Conv2d>(c)), w_(quantize_tensor(c.weight, qtype)) {
+    // copy: tensors() keeps reporting the packed codes), and one activation scale on the device that calibration fixes; per_channel
+    // (static only): one weight pair per effective output channel co, whose elements lie at (ci taps + tap) c_out + co of the buffer
+    QConv(const Conv2d &c, int qtype, bool stat = false, bool per_channel = false)
+        : geom_(std::make_shared<Conv2d>(c)),
+          w_(stat && per_channel && can_be_static(c) ? quantize_channels(c.weight, c.weight.shape()[0], 1, c.weight.shape()[0]) : quantize_tensor(c.weight, qtype)) {
         if (c.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(c.bias, qtype));
         geom_->weight = Tensor();   // the twin keeps the geometry only, not the source's f32 storage
         geom_->bias = Tensor();
@@ -170,15 +190,17 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         th_ctx *ctx = Device::ctx();
         if (!next) {
             *y = Tensor::empty({in.n, ws[0], ho, wo});
-            TH(th_conv2d_q8q8_fwd(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                  reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params,
-                                  fold, y->dptr()));
+            const auto product = w_.per_channel() ? th_conv2d_q8q8_fwd_pc : th_conv2d_q8q8_fwd;   // (a pair per output channel, or one)
+            TH(product(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                       reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold,
+                       y->dptr()));
             return;
         }
         *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
-        TH(th_conv2d_q8q8_fwd_codes(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                    reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params,
-                                    fold, next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
+        const auto product = w_.per_channel() ? th_conv2d_q8q8_fwd_codes_pc : th_conv2d_q8q8_fwd_codes;
+        TH(product(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                   reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold,
+                   next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
     }
     // two launches: the codec (its buffers pooled, returned when this scope ends), then the product
     Tensor forward_static(const Tensor &x, bool relu) const {
@@ -356,19 +378,21 @@ std::shared_ptr<Module> copy_of(const Module &m) {
     return p ? std::make_shared<M>(*p) : nullptr;
 }
 
-// stat: the Linear layers static; stat_convs: the plain convolutions too; chain: codes from one static conv to the next
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false, bool chain = false) {
+// stat: the Linear layers static; stat_convs: the plain convolutions too; chain: codes from one static conv to the next; per_channel: a
+// weight pair per output channel in every static layer
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false, bool chain = false,
+                                                  bool per_channel = false) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto q = std::make_unique<QSequential>();
         q->chain = chain;
-        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain));
+        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain, per_channel));
         return q;
     }
-    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat);
-    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype, stat_convs);
+    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat, per_channel);
+    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype, stat_convs, per_channel);
     // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
-    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype, stat);
-    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype, stat_convs);
+    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype, stat, per_channel);
+    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype, stat_convs, per_channel);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
         !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))
@@ -446,7 +470,7 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
     return quantize_checked(m, qt);
 }
 
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs, bool chain) {
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs, bool chain, bool per_channel) {
     convs = convs || chain;
     // every refusal before anything is allocated
     check_quantizable(m);
@@ -467,7 +491,7 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
                          "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) + above);
         }
     }
-    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs, chain);
+    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs, chain, per_channel);
     NoGradScope no_grad;
     for (size_t i = 0; i < calib.size(); ++i) {
         Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)

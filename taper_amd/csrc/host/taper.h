@@ -483,7 +483,11 @@ struct QTensor {   // a QuantizedTensor (tensor.rs:2084-2108) on the device: cod
     Shape shape;
     std::shared_ptr<Buffer> codes, params;
     size_t pitch = 0;   // > 0: an int8 matrix whose rows of shape[1] codes lie `pitch` bytes apart, zero-padded (a static twin's Linear weight)
-    size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? (pitch ? shape[0] * pitch : n) + 2 * sizeof(float) : 2 * n; }
+    // channels > 1: one {min_val, scale} pair per channel (params holds 2 * channels floats), element k of channel c at index
+    // c * chan_stride + k * elem_stride of the packed codes (th_quantize_int8_channels); 1, 0, 1: one pair for the tensor
+    size_t channels = 1, chan_stride = 0, elem_stride = 1;
+    bool per_channel() const { return chan_stride != 0; }
+    size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? (pitch ? shape[0] * pitch : n) + channels * 2 * sizeof(float) : 2 * n; }
     th_qtensor item(float *d_out) const;
 };
 
@@ -511,7 +515,12 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // then a static conv B of the same Sequential.  A's product writes B's codes and pixel sums (th_conv2d_q8q8_fwd_codes with B's scale), the
 // pool runs on codes (th_maxpool2d_nhwc_int8: the codec is monotone, so it commutes with a maximum) and B skips its codec.  Anything else
 // between two convs takes the path above.  chain_links() counts the links.
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false, bool chain = false);
+// per_channel: the weight of every static layer gets one {min_val, scale} pair per output channel instead of one for the tensor
+// (th_quantize_int8_channels: a Linear's rows; a static conv's effective output channels, the columns of the buffer as the float kernels
+// read it) and its product reads them (th_linear_q8q8_fwd_pc, th_conv2d_q8q8_fwd_pc / _codes_pc).  Biases, every layer that stays
+// weight-only, calibration (so act_scales()), the links and the refusals are the per-tensor twin's.
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false, bool chain = false,
+                                                 bool per_channel = false);
 
 // ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
 // A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the

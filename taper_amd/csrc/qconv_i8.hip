@@ -9,6 +9,7 @@
 //                              over the in-image taps of qx qw from the MFMA, rs = the sum of d_pixsum over the same taps
 //   th_conv2d_q8q8_fwd_codes   the same product, its f32 value coded at once with the NEXT layer's scale: int8 [n, h_out, w_out, cpitch_y]
 //                              and the pixel sums, what th_quantize_act_nhwc_int8 would make of th_conv2d_q8q8_fwd's output
+//   th_conv2d_q8q8_fwd_pc, th_conv2d_q8q8_fwd_codes_pc: both with one {mw, sw} per output channel, a template flag of the kernel
 //   th_maxpool2d_nhwc_int8     the max-pool on channel-last codes (the codec is monotone: the maximum of the codes is the code of the maximum)
 //
 // With both operands channel-last a 16-byte piece of K is 16 consecutive channels of one tap: M = n h_out w_out output pixels, N = c_out,
@@ -90,7 +91,10 @@ struct QcArgs {
 // next layer's scale instead of to memory.  An accumulator group (reg >> 2) is four consecutive channels = one word of the pixel's
 // channel-last row, the lane's at byte 8 (reg >> 2) + 4 (lane >> 5) of a 32-channel tile; two half-wave swaps (v_permlane32_swap) with
 // the lane that holds the other half of the same pixel leave 16 consecutive bytes in each, so a tile of a pixel is two 16-byte stores.
-template <int NT, bool CODES>
+// PC: wparams holds one {mw, sw} per output channel.  A lane needs the pairs of its 16 NT channels: the workgroup's 32 NT
+// pairs are staged once in the LDS the K loop has released (its last barrier is behind every read of a stage), one pair a thread, and
+// the epilogue reads them from there -- 16 NT dependent loads from memory a lane cost 2.6 - 7.5 us a layer, measured; this costs 0.0 - 0.6.
+template <int NT, bool CODES, bool PC>
 __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
     __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
@@ -165,6 +169,14 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
 
     // epilogue: this lane's pixel, its window's sum of pixel sums (integer; border windows have fewer taps), then q8_value of the lane's 16 NT
     // channels.  A pixel past M: the f32 form is done; the codes form keeps both its lanes (they share m) in the swaps and stores nothing.
+    float2 *pairs = (float2 *)lds_w;   // PC: {mw, sw} of channel col0 + i at pairs[i] (channels past c_out re-read the last: never used)
+    if constexpr (PC) {
+        if (t < kQcChan * NT) {
+            const int co = min(col0 + t, a.c_out - 1);
+            pairs[t] = make_float2(a.wparams[2 * co], a.wparams[2 * co + 1]);
+        }
+        lds_barrier();
+    }
     const int m = m0 + wave * 32 + li;
     const bool live = m < a.M;
     if (!CODES && !live) return;
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     const int *ps = a.pixsum + (size_t)o.img * a.win.h * a.win.w;
     int rs = 0;
     if (live) a.win.for_taps(o.oh, o.ow, [&](int ih, int iw) { rs += ps[ih * a.win.w + iw]; });
-    const float sx = a.xscale[0], mw = a.wparams[0], sw = a.wparams[1], rterm = q8_rterm(mw, rs), sy = CODES ? a.yscale[0] : 0.f;
+    const float sx = a.xscale[0], mw = PC ? 0.f : a.wparams[0], sw = PC ? 0.f : a.wparams[1], rterm = q8_rterm(mw, rs), sy = CODES ? a.yscale[0] : 0.f;
     float *yp = CODES ? nullptr : a.y + ((size_t)o.img * a.c_out + col0 + 4 * h) * hw_out + o.p;   // the f32 form: this pixel in the lane's first channel plane
     int sum = 0;
 #pragma unroll
@@ -183,7 +195,8 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
             const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
             q[e] = 0;
             if (co >= a.c_out) continue;
-            const float v = q8_value(acc[j][e], rs, rterm, sx, sw, a.qb != nullptr, [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, a.relu);
+            const float v = q8_value(acc[j][e], rs, PC ? q8_rterm(pairs[co - col0].x, rs) : rterm, sx, PC ? pairs[co - col0].y : sw, a.qb != nullptr,
+                                     [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, a.relu);
             if constexpr (CODES) {
                 q[e] = act_code(v, sy);
                 sum += q[e];
@@ -305,8 +318,9 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
     return pack_conv_weight("th_pack_conv_weight_taper_int8", true, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
 }
 
-// Both products: their checks (fn: the caller's name for the message), then the launch; the other form's outputs come null
-static int qconv_run(const char *fn, bool codes, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
+// Both products: their checks (fn: the caller's name for the message), then the launch; the other form's outputs come null; pc:
+// d_wparams holds a pair per output channel
+static int qconv_run(const char *fn, bool codes, bool pc, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
                      int w, const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                      const float *d_bparams, int relu, float *d_y, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
     TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && (codes ? d_yscale && d_qy : d_y != nullptr) && (!d_qb || d_bparams), "%s: null argument", fn);
@@ -316,16 +330,19 @@ static int qconv_run(const char *fn, bool codes, th_ctx *ctx, const int8_t *d_qx
     TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", fn);
     TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", fn, cpitch, c_in);
     if (codes) {
-        TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd)", fn, c_out,
-                   th_qconv_i8_chain_max_cout());
+        TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd%s)", fn, c_out,
+                   th_qconv_i8_chain_max_cout(), pc ? "_pc" : "");
         TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", fn);
         TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", fn, cpitch_y, c_out);
     }
     if (n == 0) return 0;
     const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, d_yscale, d_qy, d_ypixsum, cpitch_y, p.win, cpitch, c_out,
                    n * p.win.h_out * p.win.w_out, relu, p.tiles_n};
-    auto kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true> : p.nt == 2 ? qconv_i8_kernel<2, true> : qconv_i8_kernel<4, true>)
-                        : (p.nt == 1 ? qconv_i8_kernel<1, false> : p.nt == 2 ? qconv_i8_kernel<2, false> : qconv_i8_kernel<4, false>);
+    auto kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true, false> : p.nt == 2 ? qconv_i8_kernel<2, true, false> : qconv_i8_kernel<4, true, false>)
+                        : (p.nt == 1 ? qconv_i8_kernel<1, false, false> : p.nt == 2 ? qconv_i8_kernel<2, false, false> : qconv_i8_kernel<4, false, false>);
+    if (pc)
+        kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true, true> : p.nt == 2 ? qconv_i8_kernel<2, true, true> : qconv_i8_kernel<4, true, true>)
+                       : (p.nt == 1 ? qconv_i8_kernel<1, false, true> : p.nt == 2 ? qconv_i8_kernel<2, false, true> : qconv_i8_kernel<4, false, true>);
     hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, ctx->stream, a);
     TH_LAUNCH_CHECK();
     return 0;
@@ -334,7 +351,7 @@ static int qconv_run(const char *fn, bool codes, th_ctx *ctx, const int8_t *d_qx
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                        const float *d_bparams, int relu, float *d_y) {
-    return qconv_run("th_conv2d_q8q8_fwd", false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
+    return qconv_run("th_conv2d_q8q8_fwd", false, false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
                      d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
 }
 
@@ -343,7 +360,21 @@ int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
 int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                              const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes", true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+    return qconv_run("th_conv2d_q8q8_fwd_codes", true, false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+                     d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
+}
+
+int th_conv2d_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                          const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
+                          const float *d_bparams, int relu, float *d_y) {
+    return qconv_run("th_conv2d_q8q8_fwd_pc", false, true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
+                     d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
+}
+
+int th_conv2d_q8q8_fwd_codes_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
+    return qconv_run("th_conv2d_q8q8_fwd_codes_pc", true, true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
                      d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
 }
 

@@ -6,6 +6,7 @@
 //   th_pad_rows_int8      packed [rows, k] codes -> [rows, pitch] with zero padding (once per weight): the conv weight pack with one tap
 //   th_linear_q8q8_fwd    y = sx * (sw * (float)(acc + 128 rs) + mw * (float)rs) [+ deq(bias)] [ReLU], acc = sum_k qx qw from the MFMA;
 //                         two forms: 128 x 128 tiles through LDS, and a workgroup per 32 x 32 tile with K split over its waves for few rows
+//   th_linear_q8q8_fwd_pc the same with one {mw, sw} per output row: the same kernels, a template flag in store_tile
 //   th_act_range_update   calibration: the finite min / max of a tensor folded into a running device pair, and the scale they give
 //
 // The piece of 16 codes, the LDS image of a stage, the fragment pairing and the epilogue's arithmetic are qi8_dev.h's, shared with
@@ -78,10 +79,11 @@ struct Q8Epilogue {
 };
 
 // One 32 x 32 accumulator tile out: this lane holds column n (a row of W) of rows row_base + (e & 3) + 8 (e >> 2) (row_base includes the
-// lane half's 4 h), each through q8_value.
+// lane half's 4 h), each through q8_value.  PC: wparams holds one {mw, sw} per column, this lane's at 2 n; else one for all.
+template <bool PC>
 __device__ __forceinline__ void store_tile(const intx16 &acc, int row_base, int n, const Q8Epilogue &ep) {
     if (n >= ep.N) return;
-    const float sx = ep.xscale[0], mw = ep.wparams[0], sw = ep.wparams[1];
+    const float sx = ep.xscale[0], mw = ep.wparams[PC ? 2 * (size_t)n : 0], sw = ep.wparams[PC ? 2 * (size_t)n + 1 : 1];
     const float bias = ep.qb ? dequant_int8(ep.qb[n], ep.bparams[1], ep.bparams[0]) : 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -95,6 +97,7 @@ __device__ __forceinline__ void store_tile(const intx16 &acc, int row_base, int 
 // ---- the product ----
 // Each operand's stage is 128 rows in qi8_dev.h's image; x is the MFMA's A operand and W its B: C/D column = lane & 31 is a row of W,
 // C/D row = (reg & 3) + 8 (reg >> 2) + 4 h a row of x.
+template <bool PC>
 __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict__ qx, int pitch_x, int K, const int8_t *__restrict__ qw, int pitch_w,
                                                        Q8Epilogue ep, int tiles_m, int tiles_n) {
     const int M = ep.M, N = ep.N;
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict_
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) store_tile(acc[i][j], row0 + wm + 32 * i + 4 * h, col0 + wn + 32 * j + li, ep);
+        for (int i = 0; i < 2; ++i) store_tile<PC>(acc[i][j], row0 + wm + 32 * i + 4 * h, col0 + wn + 32 * j + li, ep);
 }
 
 // Few rows (batch <= kQ8SkinnyMaxBatch): the 128 x 128 form would leave most CUs idle and walk K in one long chain of dependent
@@ -181,6 +184,7 @@ __global__ __launch_bounds__(256) void qgemm_i8_kernel(const int8_t *__restrict_
 // operands straight from memory into its fragments (a lane's two 16-byte loads per row are 32 consecutive bytes; no LDS staging, no
 // barrier inside the loop, so the loads of several chunks are in flight at once), and the four int32 partial tiles are added through LDS
 // -- integers: the order does not matter -- before the same epilogue.  ceil(N / 32) * ceil(M / 32) workgroups.
+template <bool PC>
 __global__ __launch_bounds__(256) void qgemm_i8_skinny_kernel(const int8_t *__restrict__ qx, int pitch_x, int K, const int8_t *__restrict__ qw,
                                                               int pitch_w, Q8Epilogue ep, int tiles_m) {
     __shared__ int red[3][16][64];   // 12 KB
@@ -221,7 +225,7 @@ __global__ __launch_bounds__(256) void qgemm_i8_skinny_kernel(const int8_t *__re
     if (wave > 0) return;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] += red[0][e][lane] + red[1][e][lane] + red[2][e][lane];
-    store_tile(acc, row0 + 4 * h, col0 + li, ep);
+    store_tile<PC>(acc, row0 + 4 * h, col0 + li, ep);
 }
 
 // ---- calibration ----
@@ -297,24 +301,40 @@ int th_pad_rows_int8(th_ctx *ctx, const int8_t *d_src, int rows, int k, int8_t *
     return 0;
 }
 
-int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
-                       const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams, int relu,
-                       float *d_y) {
-    TH_REQUIRE(ctx && d_qx && d_rowsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "th_linear_q8q8_fwd: null argument");
-    TH_REQUIRE(batch >= 0 && in_features > 0 && out_features > 0, "th_linear_q8q8_fwd: bad shape B=%d K=%d N=%d", batch, in_features, out_features);
-    TH_REQUIRE(in_features <= kQ8MaxK, "th_linear_q8q8_fwd: in_features %d is above %d, where the int32 sum can overflow", in_features, kQ8MaxK);
-    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "th_linear_q8q8_fwd: the code pointers must be 16-byte aligned");
+// Both products: their checks (fn: the caller's name for the message), then the launch; pc: d_wparams holds a pair per output row
+static int q8q8_run(const char *fn, bool pc, th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                    const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams, int relu, float *d_y) {
+    TH_REQUIRE(ctx && d_qx && d_rowsum && d_xscale && d_qw && d_wparams && d_y && (!d_qb || d_bparams), "%s: null argument", fn);
+    TH_REQUIRE(batch >= 0 && in_features > 0 && out_features > 0, "%s: bad shape B=%d K=%d N=%d", fn, batch, in_features, out_features);
+    TH_REQUIRE(in_features <= kQ8MaxK, "%s: in_features %d is above %d, where the int32 sum can overflow", fn, in_features, kQ8MaxK);
+    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", fn);
     TH_REQUIRE(pitch_x % 16 == 0 && pitch_w % 16 == 0 && pitch_x >= in_features && pitch_w >= in_features,
-               "th_linear_q8q8_fwd: pitches %d / %d must be multiples of 16 and at least in_features %d", pitch_x, pitch_w, in_features);
+               "%s: pitches %d / %d must be multiples of 16 and at least in_features %d", fn, pitch_x, pitch_w, in_features);
     if (batch == 0) return 0;
     const Q8Plan p = q8q8_plan(batch, out_features);
     const Q8Epilogue ep{d_rowsum, d_xscale, d_wparams, d_qb, d_bparams, relu, batch, out_features, d_y};
     if (p.skinny)
-        hipLaunchKernelGGL(qgemm_i8_skinny_kernel, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw, pitch_w, ep, p.tiles_m);
+        hipLaunchKernelGGL(pc ? qgemm_i8_skinny_kernel<true> : qgemm_i8_skinny_kernel<false>, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw,
+                           pitch_w, ep, p.tiles_m);
     else
-        hipLaunchKernelGGL(qgemm_i8_kernel, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw, pitch_w, ep, p.tiles_m, p.tiles_n);
+        hipLaunchKernelGGL(pc ? qgemm_i8_kernel<true> : qgemm_i8_kernel<false>, dim3(p.grid), dim3(256), 0, ctx->stream, d_qx, pitch_x, in_features, d_qw, pitch_w, ep,
+                           p.tiles_m, p.tiles_n);
     TH_LAUNCH_CHECK();
     return 0;
+}
+
+int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                       const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams, int relu,
+                       float *d_y) {
+    return q8q8_run("th_linear_q8q8_fwd", false, ctx, d_qx, pitch_x, d_rowsum, d_xscale, batch, in_features, d_qw, pitch_w, out_features, d_wparams, d_qb, d_bparams,
+                    relu, d_y);
+}
+
+int th_linear_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
+                          const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams, int relu,
+                          float *d_y) {
+    return q8q8_run("th_linear_q8q8_fwd_pc", true, ctx, d_qx, pitch_x, d_rowsum, d_xscale, batch, in_features, d_qw, pitch_w, out_features, d_wparams, d_qb, d_bparams,
+                    relu, d_y);
 }
 
 int th_debug_q8q8_plan(int batch, int in_features, int out_features, int *out4) {

@@ -34,6 +34,79 @@ __global__ __launch_bounds__(256) void quantize_int8_kernel(const float *__restr
     }
 }
 
+// ---- one pair per channel ----
+// Rows: channel c is len consecutive floats.  A workgroup per channel, lanes along the row: the min / max walk (stream_dev.h's span, from
+// the row's own address), the workgroup fold, then the codes -- the row's second read comes from the cache.  One launch.
+__global__ __launch_bounds__(kStreamThreads) void quantize_int8_rows_kernel(const float *__restrict__ x, int8_t *__restrict__ q, int channels, int64_t len,
+                                                                            float *__restrict__ params) {
+    __shared__ float s[8];
+    for (int64_t c = blockIdx.x; c < channels; c += gridDim.x) {
+        const float *xr = x + (size_t)c * len;
+        int8_t *qr = q + (size_t)c * len;
+        float mn, mx, min_val, scale;
+        minmax_span<MinMaxFinite, true>(xr, xr, len, threadIdx.x, kStreamThreads, &mn, &mx);
+        block_minmax(&mn, &mx, s);
+        int8_params(mn, mx, &min_val, &scale);
+        if (threadIdx.x == 0) {
+            params[2 * c] = min_val;
+            params[2 * c + 1] = scale;
+        }
+        for (int64_t i = threadIdx.x; i < len; i += kStreamThreads) qr[i] = (int8_t)quant_int8(xr[i], min_val, scale);
+    }
+}
+
+// Columns: element k of channel c lies at x[k channels + c].  Lane = channel, so a wave reads 64 consecutive floats; workgroup
+// (bx, by) owns channels 64 bx .. + 63 and its wave v the elements k = 4 by + v, + 4 gridDim.y, ...: the K walk is split over waves and
+// workgroups.  The first pass leaves part[by][c] = {min, max} of a workgroup's share; the second folds a channel's gridDim.y partials
+// (compares: any order gives the same bits), writes the pair and codes the same share.
+constexpr int kQuantColSplit = 32;   // workgroups along K at most, 16 elements of every channel each at least
+
+__device__ __forceinline__ void cols_fold(float *mn, float *mx, float (*s)[4][64], int lane, int wave) {   // the four waves' values of a channel
+    s[0][wave][lane] = *mn;
+    s[1][wave][lane] = *mx;
+    __syncthreads();
+    *mn = fminf(fminf(s[0][0][lane], s[0][1][lane]), fminf(s[0][2][lane], s[0][3][lane]));
+    *mx = fmaxf(fmaxf(s[1][0][lane], s[1][1][lane]), fmaxf(s[1][2][lane], s[1][3][lane]));
+}
+
+__global__ __launch_bounds__(256) void minmax_cols_kernel(const float *__restrict__ x, int channels, int64_t len, float *__restrict__ part) {
+    __shared__ float s[2][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+    float mn = INFINITY, mx = -INFINITY;
+    if (c < channels)
+        for (int64_t k = blockIdx.y * 4 + wave; k < len; k += 4 * gridDim.y) {
+            const float v = x[(size_t)k * channels + c];
+            MinMaxFinite::take(mn, mx, v, v);
+        }
+    cols_fold(&mn, &mx, s, lane, wave);
+    if (wave == 0 && c < channels) {
+        part[((size_t)blockIdx.y * channels + c) * 2] = mn;
+        part[((size_t)blockIdx.y * channels + c) * 2 + 1] = mx;
+    }
+}
+
+__global__ __launch_bounds__(256) void quantize_int8_cols_kernel(const float *__restrict__ x, int8_t *__restrict__ q, int channels, int64_t len,
+                                                                 const float *__restrict__ part, float *__restrict__ params) {
+    __shared__ float s[2][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+    float mn = INFINITY, mx = -INFINITY, min_val, scale;
+    if (c < channels)
+        for (int p = wave; p < (int)gridDim.y; p += 4) {
+            mn = fminf(mn, part[((size_t)p * channels + c) * 2]);
+            mx = fmaxf(mx, part[((size_t)p * channels + c) * 2 + 1]);
+        }
+    cols_fold(&mn, &mx, s, lane, wave);
+    if (c >= channels) return;
+    int8_params(mn, mx, &min_val, &scale);
+    if (blockIdx.y == 0 && wave == 0) {
+        params[2 * c] = min_val;
+        params[2 * c + 1] = scale;
+    }
+    for (int64_t k = blockIdx.y * 4 + wave; k < len; k += 4 * gridDim.y) q[(size_t)k * channels + c] = (int8_t)quant_int8(x[(size_t)k * channels + c], min_val, scale);
+}
+
 __global__ __launch_bounds__(256) void dequantize_int8_kernel(const int8_t *__restrict__ q, float *__restrict__ y, size_t n, float scale,
                                                               int zero_point, float min_val) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
@@ -62,8 +135,9 @@ int th_f16_to_f32(th_ctx *ctx, const uint16_t *d_x, float *d_y, size_t n) {
     return 0;
 }
 
-int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params) {
-    TH_REQUIRE(ctx && d_params && (n == 0 || (d_x && d_q)), "th_quantize_int8: null argument");
+// th_quantize_int8, and th_quantize_int8_channels' single channel (fn: the caller's name for the message)
+static int quantize_int8_run(const char *fn, th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params) {
+    TH_REQUIRE(ctx && d_params && (n == 0 || (d_x && d_q)), "%s: null argument", fn);
     const int nb = n == 0 ? 0 : stream_grid((int64_t)n, 256, kQuantParts);
     void *part = nullptr;
     if (th_malloc(ctx, (size_t)std::max(nb, 1) * 2 * sizeof(float), &part)) return 1;
@@ -72,6 +146,35 @@ int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float
         TH_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(quantize_int8_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, ctx->stream, d_x, d_q, n, (const float *)part, nb, d_params);
+    TH_LAUNCH_CHECK();
+    return th_free(ctx, part);
+}
+
+int th_quantize_int8(th_ctx *ctx, const float *d_x, int8_t *d_q, size_t n, float *d_params) {
+    return quantize_int8_run("th_quantize_int8", ctx, d_x, d_q, n, d_params);
+}
+
+int th_quantize_int8_channels(th_ctx *ctx, const float *d_x, int channels, int64_t len, int64_t chan_stride, int64_t elem_stride, int8_t *d_q,
+                              float *d_params) {
+    TH_REQUIRE(ctx && d_x && d_q && d_params, "th_quantize_int8_channels: null argument");
+    TH_REQUIRE(channels >= 1 && len >= 1, "th_quantize_int8_channels: channels=%d or len=%lld below 1", channels, (long long)len);
+    const bool rows = elem_stride == 1 && (chan_stride == len || channels == 1), cols = chan_stride == 1 && elem_stride == channels;
+    TH_REQUIRE(rows || cols,
+               "th_quantize_int8_channels: chan_stride=%lld elem_stride=%lld is neither rows (chan_stride == len, elem_stride == 1) nor columns "
+               "(chan_stride == 1, elem_stride == channels)",
+               (long long)chan_stride, (long long)elem_stride);
+    if (rows && channels == 1) return quantize_int8_run("th_quantize_int8_channels", ctx, d_x, d_q, (size_t)len, d_params);
+    if (rows) {
+        hipLaunchKernelGGL(quantize_int8_rows_kernel, dim3(std::min(channels, kNumCU * 32)), dim3(kStreamThreads), 0, ctx->stream, d_x, d_q, channels, len, d_params);
+        TH_LAUNCH_CHECK();
+        return 0;
+    }
+    const dim3 grid(ceil_div(channels, 64), stream_grid(len, 16, kQuantColSplit));
+    void *part = nullptr;
+    if (th_malloc(ctx, (size_t)grid.y * channels * 2 * sizeof(float), &part)) return 1;
+    hipLaunchKernelGGL(minmax_cols_kernel, grid, dim3(256), 0, ctx->stream, d_x, channels, len, (float *)part);
+    TH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(quantize_int8_cols_kernel, grid, dim3(256), 0, ctx->stream, d_x, d_q, channels, len, (const float *)part, d_params);
     TH_LAUNCH_CHECK();
     return th_free(ctx, part);
 }

@@ -1,6 +1,9 @@
 """Calibrated int8 convolution (th_quantize_act_nhwc_int8 + th_conv2d_q8q8_fwd) beside the weight-only int8 convolution (th_dequantize_multi +
 th_conv3x3_fwd) and the f32 convolution (th_conv3x3_fwd), MI355X, timed in one process.
 
+"int8 static per-channel" / "... chain per-channel" are the static rows with one weight pair per output channel (th_conv2d_q8q8_fwd_pc,
+th_conv2d_q8q8_fwd_codes_pc, Module.quantize_static_per_channel: DESIGN 6m).
+
 Layer rows: every Conv2dReLU(3x3, pad 1) of the reference CNN and of the simple CNN at B = 256, on its own, through the C ABI: us per forward in
 two states -- cold (a 512 MiB buffer written elsewhere before every timed call) and graph-replayed (the forward captured once, the graph
 launched back to back) -- and, for the static rows, the share of the two bounds of DESIGN 6k: integer operations against the i8 MFMA rate and
@@ -18,6 +21,7 @@ work included, for all five models alike, so at B = 1 and 64 they say more about
 the kernel comparison.
 
     python tools/bench_qconv.py [--reps 30] [--out profiles/quant_static_conv.json]
+    python tools/bench_qconv.py --kinds "int8 static,int8 static per-channel" --models cnn_reference      # a part of the rows
     python tools/bench_qconv.py --trace-only [--trace-kind "int8 static chain"]      # a few B = 256 forwards of the reference CNN's static-conv
                                                   # (or another) twin, for rocprofv3 --kernel-trace --stats
 
@@ -47,10 +51,10 @@ I8_OPS = 2 * 2.5e15      # MI355X_MICROARCH: the i8 MFMA forms run at twice the 
 # (model, c_in, c_out, map side): the 3x3 / pad 1 layers of bench.build_model's two CNNs on 28 x 28 inputs
 LAYERS = [("cnn_reference", 1, 32, 28), ("cnn_reference", 32, 32, 28), ("cnn_reference", 32, 64, 14), ("cnn_reference", 64, 64, 14),
           ("cnn_reference", 64, 128, 7), ("cnn_simple", 1, 32, 28), ("cnn_simple", 32, 64, 14)]
-KINDS = ("f32", "int8 weight-only", "int8 static")
+KINDS = ("f32", "int8 weight-only", "int8 static", "int8 static per-channel")
 # (c_in, c_mid, c_out, map side of the first conv, a MaxPool2d(2) between the two): the reference CNN's consecutive static convs
 PAIRS = [(1, 32, 32, 28, False), (32, 32, 64, 28, True), (32, 64, 64, 14, False), (64, 64, 128, 14, True)]
-PAIR_KINDS = ("int8 static", "int8 static chain")
+PAIR_KINDS = ("int8 static", "int8 static chain", "int8 static per-channel", "int8 static chain per-channel")
 
 
 class Layer:
@@ -75,6 +79,16 @@ class Layer:
         self.items = (H.QTensor * 2)(H.QTensor(int(self.qw), int(self.qwp), int(self.wf), w.size, 0), H.QTensor(int(self.qb), int(self.qbp), int(self.bf), b.size, 0))
         self.x = ctx.upload(rng.standard_normal((B, c_in, side, side)).astype(np.float32))
         self.y = ctx.empty(B * c_out * side * side)
+        self.qw_nhwc_pc = None
+
+    def per_channel(self, ctx):
+        """the weight packed again with a pair per effective output channel, on the device (once, when a per-channel row is first timed)"""
+        if self.qw_nhwc_pc is None:
+            qw = ctx.empty(self.c_out * self.c_in * 9, np.uint8)
+            self.qwp_pc, self.qw_nhwc_pc = ctx.empty(2 * self.c_out), ctx.empty(self.c_out * 9 * self.cpitch, np.uint8)
+            ctx.call("th_quantize_int8_channels", self.w, self.c_out, self.c_in * 9, 1, self.c_out, qw, self.qwp_pc)
+            ctx.call("th_pack_conv_weight_taper_int8", qw, self.c_out, self.c_in, 3, 3, self.qw_nhwc_pc, self.cpitch)
+            ctx.sync()
 
     def run(self, ctx, kind):
         B, s = self.B, self.side
@@ -83,6 +97,11 @@ class Layer:
         elif kind == "int8 weight-only":
             ctx.call("th_dequantize_multi", C.addressof(self.items), 2)
             ctx.call("th_conv3x3_fwd", self.x, self.wf, self.bf, self.y, B, self.c_in, s, s, self.c_out, 1, 0, 1)
+        elif kind == "int8 static per-channel":
+            self.per_channel(ctx)
+            ctx.call("th_quantize_act_nhwc_int8", self.x, B, self.c_in, s, s, self.sx, self.qx, self.cpitch, self.ps)
+            ctx.call("th_conv2d_q8q8_fwd_pc", self.qx, self.cpitch, self.ps, self.sx, B, self.c_in, s, s, self.qw_nhwc_pc, self.c_out, 3, 3, 1, 1, 1, 1, self.qwp_pc,
+                     self.qb, self.qbp, 1, self.y)
         else:
             ctx.call("th_quantize_act_nhwc_int8", self.x, B, self.c_in, s, s, self.sx, self.qx, self.cpitch, self.ps)
             ctx.call("th_conv2d_q8q8_fwd", self.qx, self.cpitch, self.ps, self.sx, B, self.c_in, s, s, self.qw_nhwc, self.c_out, 3, 3, 1, 1, 1, 1, self.qwp,
@@ -112,18 +131,22 @@ class Pair:
 
     def run(self, ctx, kind):
         a, b, B, s = self.a, self.b, self.B, self.side
-        head = (a.qx, a.cpitch, a.ps, a.sx, B, a.c_in, s, s, a.qw_nhwc, a.c_out, 3, 3, 1, 1, 1, 1, a.qwp, a.qb, a.qbp, 1)
-        if kind == "int8 static":
-            ctx.call("th_conv2d_q8q8_fwd", *head, a.y)
+        pc = "_pc" if kind.endswith("per-channel") else ""
+        if pc:
+            a.per_channel(ctx), b.per_channel(ctx)
+        (qwa, qwpa), (qwb, qwpb) = ((l.qw_nhwc_pc, l.qwp_pc) if pc else (l.qw_nhwc, l.qwp) for l in (a, b))
+        head = (a.qx, a.cpitch, a.ps, a.sx, B, a.c_in, s, s, qwa, a.c_out, 3, 3, 1, 1, 1, 1, qwpa, a.qb, a.qbp, 1)
+        if "chain" not in kind:
+            ctx.call("th_conv2d_q8q8_fwd" + pc, *head, a.y)
             if self.pool:
                 ctx.call("th_maxpool2d_fwd", a.y, self.mid_f32, self.argmax, B, a.c_out, s, s, 2, 2, 2, 2, 0, 0)
             ctx.call("th_quantize_act_nhwc_int8", self.mid_f32 if self.pool else a.y, B, b.c_in, b.side, b.side, b.sx, b.qx, b.cpitch, b.ps)
         elif self.pool:
-            ctx.call("th_conv2d_q8q8_fwd_codes", *head, b.sx, self.mid_q, b.cpitch, None)
+            ctx.call("th_conv2d_q8q8_fwd_codes" + pc, *head, b.sx, self.mid_q, b.cpitch, None)
             ctx.call("th_maxpool2d_nhwc_int8", self.mid_q, B, b.c_in, s, s, b.cpitch, 2, 2, 2, 2, 0, 0, b.qx, b.ps)
         else:
-            ctx.call("th_conv2d_q8q8_fwd_codes", *head, b.sx, b.qx, b.cpitch, b.ps)
-        ctx.call("th_conv2d_q8q8_fwd", b.qx, b.cpitch, b.ps, b.sx, B, b.c_in, b.side, b.side, b.qw_nhwc, b.c_out, 3, 3, 1, 1, 1, 1, b.qwp, b.qb, b.qbp, 1, b.y)
+            ctx.call("th_conv2d_q8q8_fwd_codes" + pc, *head, b.sx, b.qx, b.cpitch, b.ps)
+        ctx.call("th_conv2d_q8q8_fwd" + pc, b.qx, b.cpitch, b.ps, b.sx, B, b.c_in, b.side, b.side, qwb, b.c_out, 3, 3, 1, 1, 1, 1, qwpb, b.qb, b.qbp, 1, b.y)
 
     def output(self, ctx):
         return ctx.download(self.b.y, (self.B * self.b.c_out * self.b.side ** 2,)).view(np.uint32)
@@ -186,9 +209,13 @@ def model_forwards(key, B, rng):
     calib = T.Tensor(rng.standard_normal((64, 1, 28, 28)).astype(np.float32), (64, 1, 28, 28))
     x = T.Tensor(rng.standard_normal(shape).astype(np.float32), shape)
     twins = {"int8 weight-only": model.quantize("int8"), "int8 static (Linear)": model.quantize_static(calib),
-             "int8 static (conv + Linear)": model.quantize_static_conv(calib), "int8 static chain": model.quantize_static_chain(calib)}
+             "int8 static (conv + Linear)": model.quantize_static_conv(calib), "int8 static chain": model.quantize_static_chain(calib),
+             "int8 static chain per-channel": model.quantize_static_per_channel(calib)}
     same = np.array_equal(twins["int8 static chain"](x).data().view(np.uint32), twins["int8 static (conv + Linear)"](x).data().view(np.uint32))
     assert same, f"{key} B={B}: the chained twin's output differs from quantize_static_conv's"
+    same = np.array_equal(twins["int8 static chain per-channel"](x).data().view(np.uint32),
+                          model.quantize_static_per_channel(calib, chain=False)(x).data().view(np.uint32))
+    assert same, f"{key} B={B}: the chained per-channel twin's output differs from the unchained one's"
 
     def float_forward():
         model.forward(x)
@@ -206,7 +233,14 @@ def main():
     ap.add_argument("--out", default="profiles/quant_static_conv.json")
     ap.add_argument("--trace-only", action="store_true")
     ap.add_argument("--trace-kind", default="int8 static (conv + Linear)")
+    ap.add_argument("--kinds", default="", help="comma-separated kinds to time (default: all)")
+    ap.add_argument("--models", default="cnn_reference,cnn_simple", help="the models of the layer and model rows")
+    ap.add_argument("--batches", default="1,64,256", help="the batch sizes of the model rows")
     a = ap.parse_args()
+
+    def chosen(kind):
+        return not a.kinds or kind in a.kinds.split(",")
+
     ctx = H.Ctx(handle=T.Device.ctx_handle())
     rng = np.random.default_rng(0)
     if a.trace_only:
@@ -223,12 +257,12 @@ def main():
         print(json.dumps(r), flush=True)
 
     B = 256
-    for key, c_in, c_out, side in LAYERS:
+    for key, c_in, c_out, side in (l for l in LAYERS if l[0] in a.models.split(",")):
         layer = Layer(ctx, rng, c_in, c_out, side, B)
-        for kind in KINDS:
+        for kind in filter(chosen, KINDS):
             cold, warm = timed(ctx, lambda: layer.run(ctx, kind), a.reps, flush)
             r = dict(case=f"{key} conv {c_in}->{c_out} @ {side}x{side}", kind=kind, B=B, cold_us=round(cold, 2), replay_us=round(warm, 2))
-            if kind == "int8 static":
+            if kind.startswith("int8 static"):
                 r.update(replay_share_of_i8_mfma=round(layer.ops() / (warm * 1e-6) / I8_OPS, 4),
                          replay_share_of_hbm=round(layer.static_bytes() / (warm * 1e-6) / HBM, 4))
             report(r)
@@ -236,17 +270,19 @@ def main():
     for c_in, c_mid, c_out, side, pool in PAIRS:
         pair = Pair(ctx, rng, c_in, c_mid, c_out, side, pool, B)
         outs = {}
-        for kind in PAIR_KINDS:
+        for kind in filter(chosen, PAIR_KINDS):
             cold, warm = timed(ctx, lambda: pair.run(ctx, kind), a.reps, flush)
             outs[kind] = pair.output(ctx)
             report(dict(case=f"cnn_reference pair {c_in}->{c_mid} @ {side}x{side}{' -> pool' if pool else ''} -> {c_mid}->{c_out}", kind=kind, B=B,
                         cold_us=round(cold, 2), replay_us=round(warm, 2)))
-        assert np.array_equal(*outs.values()), "the chained pair's output differs from the unchained pair's"
+        for pc in (False, True):      # per codec, a chained pair computes what its unchained pair computes
+            same = [o for k, o in outs.items() if k.endswith("per-channel") == pc]
+            assert all(np.array_equal(same[0], o) for o in same), "the chained pair's output differs from the unchained pair's"
         del pair
-    for key in ("cnn_reference", "cnn_simple"):
-        for B in (1, 64, 256):
+    for key in a.models.split(","):
+        for B in map(int, a.batches.split(",")):
             calls, keep = model_forwards(key, B, rng)
-            for kind, fn in calls.items():
+            for kind, fn in ((k, f) for k, f in calls.items() if chosen(k)):
                 cold, warm = timed_eager(ctx, fn, a.reps, flush)
                 report(dict(case=f"{key} forward", kind=kind, B=B, cold_us=round(cold, 2), back_to_back_us=round(warm, 2)))
             del calls, keep
@@ -262,7 +298,8 @@ def table(rows, reps):
              "Layer rows (C ABI, replay = the captured forward launched back to back): static = `th_quantize_act_nhwc_int8` + `th_conv2d_q8q8_fwd`; "
              "weight-only = `th_dequantize_multi` + `th_conv3x3_fwd`; f32 = `th_conv3x3_fwd`.",
              "Pair rows (C ABI, replay, from the first conv's codes to the second conv's f32 output): static = product, [f32 pool,] codec, product; "
-             "static chain = `th_conv2d_q8q8_fwd_codes`, [`th_maxpool2d_nhwc_int8`,] product -- the same output bits, asserted.",
+             "static chain = `th_conv2d_q8q8_fwd_codes`, [`th_maxpool2d_nhwc_int8`,] product -- the same output bits, asserted.  per-channel: the "
+             "same launches through the `_pc` entry points, one weight pair per output channel.",
              "Shares (static rows, replay): integer operations / time / 5 POPS (twice the bf16 matrix peak), algorithmic bytes / time / 8 TB/s.",
              "Model rows (host library, eager, not graph replays: tensor allocation and launch work included for all models alike): back to back = "
              "the mean of calls issued without a wait between them.",
