@@ -1,8 +1,10 @@
-// adam_dev.h -- device-side Adam arithmetic shared by the stand-alone optimizer
-// kernel (optim.hip) and the kernels that apply the update in their epilogue
-// (gemm.hip: linear backward; head.hip: classifier head).  Literal restatement of
-// src/optim.rs:83-113: eps is added to sqrt(v) before the bias
-// correction is folded into the step size (quirk Q10).
+// adam_dev.h -- device-side Adam arithmetic of the stand-alone optimizer kernels (optim.hip, comm.hip) and of every kernel that
+// applies the update in its epilogue.  Literal restatement of src/optim.rs:83-113.  The element update and quirk Q10
+// (eps is added to sqrt(v) before the bias correction is folded into the step size) are stated below in two parts, adam_moments() and
+// adam_param() -- adam_next() is both at once: a kernel keeps its own loads and stores, where it wants them, and calls them on the
+// registers in between.  (Five epilogues still write the same lines out -- head.hip's two, mlp_tail_kernel's two, wide_grads_kernel's
+// dW: their kernels came out of the compiler differently with the calls, DESIGN.md section 3.  tests/test_gpu_adam_sites.py holds
+// every fused entry, those included, to th_adam_slices bit for bit.)
 #pragma once
 #include "common.h"
 
@@ -44,16 +46,37 @@ __device__ __forceinline__ float adam_step_size(float lr, float beta1, float bet
     return lr * (sqrtf(bc2) / bc1);
 }
 
-// one element of optim.rs:99-110
+// One element of optim.rs:99-110 on registers, in the two parts a kernel wants apart: the new moments first, so that their stores can go
+// out in front of the division, then the parameter.  No load, no store.
+struct AdamMV {
+    float m, v;
+};
+__device__ __forceinline__ AdamMV adam_moments(float p, float m, float v, float grad, float beta1, float beta2, float wd) {
+    const float g = grad + wd * p;                                            // optim.rs:101
+    return AdamMV{beta1 * m + (1.0f - beta1) * g,                             // optim.rs:104
+                  beta2 * v + (1.0f - beta2) * g * g};                        // optim.rs:107
+}
+__device__ __forceinline__ float adam_param(float p, const AdamMV &x, float step, float eps) {
+    return p - step * x.m / (sqrtf(x.v) + eps);                               // optim.rs:110 (Q10)
+}
+// both parts at once: old p / m / v and the complete gradient in, the new p / m / v out
+struct AdamPMV {
+    float p, m, v;
+};
+__device__ __forceinline__ AdamPMV adam_next(float p, float m, float v, float grad, float step, float beta1, float beta2, float eps,
+                                             float wd) {
+    const AdamMV x = adam_moments(p, m, v, grad, beta1, beta2, wd);
+    return AdamPMV{adam_param(p, x, step, eps), x.m, x.v};
+}
+
+// the same element with its loads and stores
 __device__ __forceinline__ void adam_update(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v, long i, float grad,
                                             float step, float beta1, float beta2, float eps, float wd) {
     const float pv = p[i];
-    const float gv = grad + wd * pv;                       // optim.rs:101
-    const float mv = beta1 * m[i] + (1.0f - beta1) * gv;   // optim.rs:104
-    const float vv = beta2 * v[i] + (1.0f - beta2) * gv * gv;  // optim.rs:107
-    m[i] = mv;
-    v[i] = vv;
-    p[i] = pv - step * mv / (sqrtf(vv) + eps);             // optim.rs:110
+    const AdamMV x = adam_moments(pv, m[i], v[i], grad, beta1, beta2, wd);
+    m[i] = x.m;
+    v[i] = x.v;
+    p[i] = adam_param(pv, x, step, eps);
 }
 
 // th_adam_fuse on the device side (p == nullptr: no fused update)
@@ -63,6 +86,17 @@ struct AdamDev {
     const float *lr;
     float beta1, beta2, eps, wd;
 };
+
+__device__ __forceinline__ AdamMV adam_moments(const AdamDev &a, float p, float m, float v, float grad) {
+    return adam_moments(p, m, v, grad, a.beta1, a.beta2, a.wd);
+}
+__device__ __forceinline__ float adam_param(const AdamDev &a, float p, const AdamMV &x, float step) { return adam_param(p, x, step, a.eps); }
+__device__ __forceinline__ AdamPMV adam_next(const AdamDev &a, float p, float m, float v, float grad, float step) {
+    return adam_next(p, m, v, grad, step, a.beta1, a.beta2, a.eps, a.wd);
+}
+__device__ __forceinline__ void adam_update(const AdamDev &a, long i, float grad, float step) {
+    adam_update(a.p, a.m, a.v, i, grad, step, a.beta1, a.beta2, a.eps, a.wd);
+}
 
 // A uniform value from global memory through the scalar unit (s_load): it travels on lgkmcnt, so waiting for it does
 // not drain the vector loads in flight.  (As a vector load + readfirstlane the compiler parks an s_waitcnt vmcnt(0)
@@ -133,10 +167,8 @@ __device__ __forceinline__ void adam_slice_quad(const AdamDev &a, const float *_
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float gj = gv[j] + a.wd * pv[j];
-        mv[j] = a.beta1 * mv[j] + (1.0f - a.beta1) * gj;
-        vv[j] = a.beta2 * vv[j] + (1.0f - a.beta2) * gj * gj;
-        pv[j] = pv[j] - step * mv[j] / (sqrtf(vv[j]) + a.eps);
+        const AdamPMV x = adam_next(a, pv[j], mv[j], vv[j], gv[j], step);
+        pv[j] = x.p; mv[j] = x.m; vv[j] = x.v;
     }
     if (vec) {
         *reinterpret_cast<float4 *>(a.p + i0) = make_float4(pv[0], pv[1], pv[2], pv[3]);

@@ -300,19 +300,13 @@ __global__ __launch_bounds__(256) void p2p_allreduce_adam_kernel(P2PDev c, long 
             const float4 pv = *reinterpret_cast<const float4 *>(p + i), mv = *reinterpret_cast<const float4 *>(m + i),
                          vv = *reinterpret_cast<const float4 *>(v + i);
             const float4 g = p2p_sum_quad<NR>(c, i, scale);
-            float4 po, mo, vo;
-#define TH_ADAM_LANE(k)                                                  \
-            {                                                            \
-                const float gg = g.k + wd * pv.k;                        \
-                mo.k = beta1 * mv.k + (1.0f - beta1) * gg;               \
-                vo.k = beta2 * vv.k + (1.0f - beta2) * gg * gg;          \
-                po.k = pv.k - step_size * mo.k / (sqrtf(vo.k) + eps);    \
-            }
-            TH_ADAM_LANE(x) TH_ADAM_LANE(y) TH_ADAM_LANE(z) TH_ADAM_LANE(w)
-#undef TH_ADAM_LANE
-            *reinterpret_cast<float4 *>(m + i) = mo;
-            *reinterpret_cast<float4 *>(v + i) = vo;
-            *reinterpret_cast<float4 *>(p + i) = po;
+            const AdamPMV x = adam_next(pv.x, mv.x, vv.x, g.x, step_size, beta1, beta2, eps, wd);
+            const AdamPMV y = adam_next(pv.y, mv.y, vv.y, g.y, step_size, beta1, beta2, eps, wd);
+            const AdamPMV z = adam_next(pv.z, mv.z, vv.z, g.z, step_size, beta1, beta2, eps, wd);
+            const AdamPMV w = adam_next(pv.w, mv.w, vv.w, g.w, step_size, beta1, beta2, eps, wd);
+            *reinterpret_cast<float4 *>(m + i) = make_float4(x.m, y.m, z.m, w.m);
+            *reinterpret_cast<float4 *>(v + i) = make_float4(x.v, y.v, z.v, w.v);
+            *reinterpret_cast<float4 *>(p + i) = make_float4(x.p, y.p, z.p, w.p);
         }
     }
     if (!ok) {      // READY timed out: nothing was read, nothing moved, the counter stays; the error word is up

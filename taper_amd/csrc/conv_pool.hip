@@ -828,10 +828,7 @@ __global__ __launch_bounds__(1024) void bias_grad_counts_adam_kernel(const float
 #pragma unroll
         for (int i = 1; i < 64; ++i) tot += sh[i][q];
         gb[ch] = tot;
-        if (ad.p) {
-            const float step = adam_dev_step(ad);
-            adam_update(ad.p, ad.m, ad.v, ch, tot, step, ad.beta1, ad.beta2, ad.eps, ad.wd);
-        }
+        if (ad.p) adam_update(ad, ch, tot, adam_dev_step(ad));
     }
 }
 
@@ -992,12 +989,10 @@ __global__ __launch_bounds__(1024) void bias_grad_adam_kernel(const float *__res
         for (int w = 1; w < 16; ++w) tot += sh[w];
         gb[ch] = tot;
         if (ad.p) {
-            const float gv = tot + ad.wd * pv;
-            const float mn = ad.beta1 * mv + (1.0f - ad.beta1) * gv;
-            const float vn = ad.beta2 * vv + (1.0f - ad.beta2) * gv * gv;
-            ad.m[ch] = mn;
-            ad.v[ch] = vn;
-            ad.p[ch] = pv - step * mn / (sqrtf(vn) + ad.eps);
+            const AdamPMV x = adam_next(ad, pv, mv, vv, tot, step);
+            ad.m[ch] = x.m;
+            ad.v[ch] = x.v;
+            ad.p[ch] = x.p;
         }
     }
 }
@@ -1033,12 +1028,10 @@ __global__ __launch_bounds__(1024) void bias_from_colsum_adam_kernel(const float
             gb[ch] = tot;
             if (ad.p) {
                 const float step = adam_dev_step(ad), pv = ad.p[ch];
-                const float gv = tot + ad.wd * pv;
-                const float mn = ad.beta1 * ad.m[ch] + (1.0f - ad.beta1) * gv;
-                const float vn = ad.beta2 * ad.v[ch] + (1.0f - ad.beta2) * gv * gv;
-                ad.m[ch] = mn;
-                ad.v[ch] = vn;
-                ad.p[ch] = pv - step * mn / (sqrtf(vn) + ad.eps);
+                const AdamMV x = adam_moments(ad, pv, ad.m[ch], ad.v[ch], tot);
+                ad.m[ch] = x.m;
+                ad.v[ch] = x.v;
+                ad.p[ch] = adam_param(ad, pv, x, step);
             }
         }
     }

@@ -214,12 +214,10 @@ __device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, i
                 p.C[e_ix] = out;
                 if (fuse_adam) {  // th_linear_bwd_adam: C is a complete gradient (optim.rs:99-110)
                     const AdamDev &ad = p.ep.adam;
-                    const float gv = out + ad.wd * e_p;
-                    const float mn = ad.beta1 * e_m + (1.0f - ad.beta1) * gv;
-                    const float vn = ad.beta2 * e_v + (1.0f - ad.beta2) * gv * gv;
-                    ad.m[e_ix] = mn;
-                    ad.v[e_ix] = vn;
-                    ad.p[e_ix] = e_p - e_step * mn / (sqrtf(vn) + ad.eps);
+                    const AdamMV x = adam_moments(ad, e_p, e_m, e_v, out);
+                    ad.m[e_ix] = x.m;
+                    ad.v[e_ix] = x.v;
+                    ad.p[e_ix] = adam_param(ad, e_p, x, e_step);
                 }
             }
         }
@@ -307,17 +305,12 @@ __global__ __launch_bounds__(256) void splitk_reduce4(const float *__restrict__ 
     if (fuse) {
         const AdamDev &ad = ep.adam;
         const float p4[4] = {pv.x, pv.y, pv.z, pv.w}, m4[4] = {mv.x, mv.y, mv.z, mv.w}, v4[4] = {vv.x, vv.y, vv.z, vv.w};
-        float pn[4], mo[4], vo[4];
+        AdamPMV x[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gv = out[e] + ad.wd * p4[e];
-            mo[e] = ad.beta1 * m4[e] + (1.0f - ad.beta1) * gv;
-            vo[e] = ad.beta2 * v4[e] + (1.0f - ad.beta2) * gv * gv;
-            pn[e] = p4[e] - step * mo[e] / (sqrtf(vo[e]) + ad.eps);
-        }
-        *reinterpret_cast<float4 *>(ad.m + i) = make_float4(mo[0], mo[1], mo[2], mo[3]);
-        *reinterpret_cast<float4 *>(ad.v + i) = make_float4(vo[0], vo[1], vo[2], vo[3]);
-        *reinterpret_cast<float4 *>(ad.p + i) = make_float4(pn[0], pn[1], pn[2], pn[3]);
+        for (int e = 0; e < 4; ++e) x[e] = adam_next(ad, p4[e], m4[e], v4[e], out[e], step);
+        *reinterpret_cast<float4 *>(ad.m + i) = make_float4(x[0].m, x[1].m, x[2].m, x[3].m);
+        *reinterpret_cast<float4 *>(ad.v + i) = make_float4(x[0].v, x[1].v, x[2].v, x[3].v);
+        *reinterpret_cast<float4 *>(ad.p + i) = make_float4(x[0].p, x[1].p, x[2].p, x[3].p);
     }
 }
 
@@ -340,12 +333,10 @@ __global__ __launch_bounds__(256) void splitk_reduce(const float *__restrict__ p
     C[i] = out;
     if (fuse) {
         const AdamDev &ad = ep.adam;
-        const float gv = out + ad.wd * pv;
-        const float mn_ = ad.beta1 * mv + (1.0f - ad.beta1) * gv;
-        const float vn = ad.beta2 * vv + (1.0f - ad.beta2) * gv * gv;
-        ad.m[i] = mn_;
-        ad.v[i] = vn;
-        ad.p[i] = pv - step * mn_ / (sqrtf(vn) + ad.eps);
+        const AdamPMV x = adam_next(ad, pv, mv, vv, out, step);
+        ad.m[i] = x.m;
+        ad.v[i] = x.v;
+        ad.p[i] = x.p;
     }
 }
 
@@ -428,12 +419,10 @@ __device__ __forceinline__ void linear_db_role(const LinearBwdArgs &q, int blk, 
         const float out = q.db_accum ? old + tot : tot;
         q.db[c] = out;
         if (fuse) {   // optim.rs:99-110
-            const float gv = out + q.db_adam.wd * pv;
-            const float mn = q.db_adam.beta1 * mv + (1.0f - q.db_adam.beta1) * gv;
-            const float vn = q.db_adam.beta2 * vv + (1.0f - q.db_adam.beta2) * gv * gv;
-            q.db_adam.m[c] = mn;
-            q.db_adam.v[c] = vn;
-            q.db_adam.p[c] = pv - step * mn / (sqrtf(vn) + q.db_adam.eps);
+            const AdamMV x = adam_moments(q.db_adam, pv, mv, vv, out);
+            q.db_adam.m[c] = x.m;
+            q.db_adam.v[c] = x.v;
+            q.db_adam.p[c] = adam_param(q.db_adam, pv, x, step);
         }
     }
 }
@@ -923,14 +912,12 @@ __global__ __launch_bounds__(256, 2) void sgemm_tile(const float *__restrict__ A
                     if (masked) v = mk[e] > 0.f ? v : 0.f;
                     C[idx] = v;
                     csum[j] += v;
-                    if constexpr (ADAMEP) {     // adam_update's arithmetic, element by element
+                    if constexpr (ADAMEP) {     // optim.rs:99-110 on the p / m / v requested eight elements ahead
                         const AdamDev &ad = ep.adam;
-                        const float gv = v + ad.wd * ap[e & 7];
-                        const float mn = ad.beta1 * am[e & 7] + (1.0f - ad.beta1) * gv;
-                        const float vn = ad.beta2 * av[e & 7] + (1.0f - ad.beta2) * gv * gv;
-                        ad.m[idx] = mn;
-                        ad.v[idx] = vn;
-                        ad.p[idx] = ap[e & 7] - adam_step * mn / (sqrtf(vn) + ad.eps);
+                        const AdamMV x = adam_moments(ad, ap[e & 7], am[e & 7], av[e & 7], v);
+                        ad.m[idx] = x.m;
+                        ad.v[idx] = x.v;
+                        ad.p[idx] = adam_param(ad, ap[e & 7], x, adam_step);
                     }
                 }
             }

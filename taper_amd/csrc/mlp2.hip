@@ -905,21 +905,13 @@ __global__ __launch_bounds__(256) void mlp2_finish_kernel(Mlp2FinishArgs a) {
             s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
         }
         *reinterpret_cast<float4 *>(a.dw1 + i0) = s;
-        if (fuse) {      // optim.rs:99-110, element by element as adam_update does
+        if (fuse) {      // optim.rs:99-110 on the operands requested at entry
             const AdamDev &ad = a.w1a;
-            float4 po, mo, vo;
-#define M2_ADAM(k)                                                       \
-            {                                                            \
-                const float gg = s.k + ad.wd * pv.k;                     \
-                mo.k = ad.beta1 * mv.k + (1.0f - ad.beta1) * gg;         \
-                vo.k = ad.beta2 * vv.k + (1.0f - ad.beta2) * gg * gg;    \
-                po.k = pv.k - step * mo.k / (sqrtf(vo.k) + ad.eps);      \
-            }
-            M2_ADAM(x) M2_ADAM(y) M2_ADAM(z) M2_ADAM(w)
-#undef M2_ADAM
-            *reinterpret_cast<float4 *>(ad.m + i0) = mo;
-            *reinterpret_cast<float4 *>(ad.v + i0) = vo;
-            *reinterpret_cast<float4 *>(ad.p + i0) = po;
+            const AdamPMV x = adam_next(ad, pv.x, mv.x, vv.x, s.x, step), y = adam_next(ad, pv.y, mv.y, vv.y, s.y, step);
+            const AdamPMV z = adam_next(ad, pv.z, mv.z, vv.z, s.z, step), w = adam_next(ad, pv.w, mv.w, vv.w, s.w, step);
+            *reinterpret_cast<float4 *>(ad.m + i0) = make_float4(x.m, y.m, z.m, w.m);
+            *reinterpret_cast<float4 *>(ad.v + i0) = make_float4(x.v, y.v, z.v, w.v);
+            *reinterpret_cast<float4 *>(ad.p + i0) = make_float4(x.p, y.p, z.p, w.p);
         }
         return;
     }

@@ -515,7 +515,7 @@ __device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_ro
     float step = 0.f;
     if (head_role ? any_b : any_w) {
         const AdamDev &ad = head_role ? a.b1_adam : a.w1_adam;
-        step = adam_step_size(sload(ad.lr), ad.beta1, ad.beta2, sload(ad.t));   // optim.rs:87-90
+        step = adam_dev_step(ad);   // optim.rs:87-90
     }
     // the lead's step-log slot and next state words: they depend on state0 / state1 / capacity / advance alone
     const bool log = lead && a.metrics;
@@ -790,12 +790,10 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
             if (DPNR == 0 || !fuse_w) *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off + tn * 64) = out;
             if (fuse_w) {
                 const AdamDev &ad = a.w1_adam;
-                const float gv = out + ad.wd * e_p[tn];
-                const float mn = ad.beta1 * e_m[tn] + (1.0f - ad.beta1) * gv;
-                const float vn = ad.beta2 * e_v[tn] + (1.0f - ad.beta2) * gv * gv;
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.m) + e_off + tn * 64) = mn;
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.v) + e_off + tn * 64) = vn;
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.p) + e_off + tn * 64) = e_p[tn] - w_step * mn / (sqrtf(vn) + ad.eps);
+                const AdamMV x = adam_moments(ad, e_p[tn], e_m[tn], e_v[tn], out);
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.m) + e_off + tn * 64) = x.m;
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.v) + e_off + tn * 64) = x.v;
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.p) + e_off + tn * 64) = adam_param(ad, e_p[tn], x, w_step);
             }
         }
         TAIL_STAMP(7);
@@ -849,12 +847,10 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
             a.db1[ix] = out;
             if (fuse_b1) {
                 const AdamDev &ad = a.b1_adam;
-                const float gv = out + ad.wd * bp_;
-                const float mn = ad.beta1 * bm_ + (1.0f - ad.beta1) * gv;
-                const float vn = ad.beta2 * bv_ + (1.0f - ad.beta2) * gv * gv;
-                ad.m[ix] = mn;
-                ad.v[ix] = vn;
-                ad.p[ix] = bp_ - b_step * mn / (sqrtf(vn) + ad.eps);
+                const AdamMV x = adam_moments(ad, bp_, bm_, bv_, out);
+                ad.m[ix] = x.m;
+                ad.v[ix] = x.v;
+                ad.p[ix] = adam_param(ad, bp_, x, b_step);
             }
         }
         if (lead && a.db2 && t >= 16 && t < 16 + C) a.db2[t - 16] = hv2[1];
@@ -874,12 +870,10 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
         a.db1[ix] = out;
         if (fuse_b1) {
             const AdamDev &ad = a.b1_adam;
-            const float gv = out + ad.wd * bp_;
-            const float mn = ad.beta1 * bm_ + (1.0f - ad.beta1) * gv;
-            const float vn = ad.beta2 * bv_ + (1.0f - ad.beta2) * gv * gv;
-            ad.m[ix] = mn;
-            ad.v[ix] = vn;
-            ad.p[ix] = bp_ - b_step * mn / (sqrtf(vn) + ad.eps);
+            const AdamPMV x = adam_next(ad, bp_, bm_, bv_, out, b_step);
+            ad.m[ix] = x.m;
+            ad.v[ix] = x.v;
+            ad.p[ix] = x.p;
         }
     }
     if (lead) {

@@ -44,19 +44,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
             const float4 pv = *reinterpret_cast<const float4 *>(p + i);
             const float4 mv = *reinterpret_cast<const float4 *>(m + i);
             const float4 vv = *reinterpret_cast<const float4 *>(v + i);
-            float4 po, mo, vo;
-#define TH_ADAM_LANE(c)                                                      \
-            {                                                                \
-                const float gg = gv.c + wd * pv.c;                           \
-                mo.c = beta1 * mv.c + (1.0f - beta1) * gg;                   \
-                vo.c = beta2 * vv.c + (1.0f - beta2) * gg * gg;              \
-                po.c = pv.c - step * mo.c / (sqrtf(vo.c) + eps);             \
-            }
-            TH_ADAM_LANE(x) TH_ADAM_LANE(y) TH_ADAM_LANE(z) TH_ADAM_LANE(w)
-#undef TH_ADAM_LANE
-            *reinterpret_cast<float4 *>(m + i) = mo;
-            *reinterpret_cast<float4 *>(v + i) = vo;
-            *reinterpret_cast<float4 *>(p + i) = po;
+            const AdamPMV x = adam_next(pv.x, mv.x, vv.x, gv.x, step, beta1, beta2, eps, wd);
+            const AdamPMV y = adam_next(pv.y, mv.y, vv.y, gv.y, step, beta1, beta2, eps, wd);
+            const AdamPMV z = adam_next(pv.z, mv.z, vv.z, gv.z, step, beta1, beta2, eps, wd);
+            const AdamPMV w = adam_next(pv.w, mv.w, vv.w, gv.w, step, beta1, beta2, eps, wd);
+            *reinterpret_cast<float4 *>(m + i) = make_float4(x.m, y.m, z.m, w.m);
+            *reinterpret_cast<float4 *>(v + i) = make_float4(x.v, y.v, z.v, w.v);
+            *reinterpret_cast<float4 *>(p + i) = make_float4(x.p, y.p, z.p, w.p);
             continue;
         }
         for (int64_t j = i; j < i + 4 && j < total; ++j) {
@@ -88,7 +82,7 @@ __global__ void adam_tick_kernel(int32_t *t_state, const uint32_t *guard, uint32
 __global__ __launch_bounds__(256) void adam_slice_kernel(AdamDev a, const float *__restrict__ g, int64_t n) {
     const float step = adam_dev_step(a);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        adam_update(a.p, a.m, a.v, i, g[i], step, a.beta1, a.beta2, a.eps, a.wd);
+        adam_update(a, i, g[i], step);
 }
 
 __global__ __launch_bounds__(256) void adam_slices_kernel(AdamSlices x) { adam_slices_block(x, blockIdx.x); }
