@@ -491,6 +491,19 @@ int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const 
 int th_conv2d_q8q8_fwd_codes_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                                 const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                                 const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum);
+/* ---- a frozen BatchNorm2d behind a static convolution ----
+ * th_conv2d_q8q8_fwd / _pc and th_conv2d_q8q8_fwd_codes / _codes_pc with one more step in the epilogue: with v the product's value, bias
+ * included and WITHOUT its ReLU, and {a, b} = d_affine[2 co], d_affine[2 co + 1] (th_fold_batchnorm2d's),
+ *     y = v * a + b   (one multiply, one add, each rounded once, never contracted), then max(y, 0) with relu
+ * and y is stored (f32 form) or coded with *d_yscale (codes form) as in the twin.  per_channel: d_wparams is [c_out][2] as in the _pc
+ * twins (!= 0) or one pair (0).  The same kernel body, forms (th_debug_qconv_plan) and refusals as the twins, and a null d_affine. */
+int th_conv2d_q8q8_fwd_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                              const int8_t *d_qb, const float *d_bparams, int relu, float *d_y, int per_channel, const float *d_affine);
+int th_conv2d_q8q8_fwd_codes_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                    const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                    const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
+                                    int per_channel, const float *d_affine);
 /* The max-pool on channel-last codes [n][h][w][cpitch] -> [n][h_out][w_out][cpitch], h_out = (h + 2 pad_h - k_h) / s_h + 1: every byte the
  * maximum over the in-image taps from -128 (the code of the float pool's -inf start), bytes c .. cpitch - 1 written 0, d_ypixsum the sum
  * over the c channels.  The codec never decreases in its argument, so this is the code of th_maxpool2d_fwd's result on finite values.
@@ -562,6 +575,16 @@ int th_batchnorm2d_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const f
                        int hw, int batch_stats, int accumulate_mask);
 /* the workgroups a channel's n * hw elements are shared among (1: every call above is a single launch); 0 for a shape that is refused */
 int th_batchnorm2d_split(int n, int c, int hw);
+/* A BatchNorm2d frozen on its running pair for the quantized twins (csrc/quant.hip): d_affine[c][2] = {a, b} with
+ *     invstd = 1 / sqrt(running_var + eps),   a = gamma * invstd,   b = beta - running_mean * a
+ * every operation rounded once (the square root too: sqrtf, where the eval path's intrinsic is good to one ulp), in this order.  One launch, nothing read back: capturable.  Refused before the launch: a null pointer,
+ * c <= 0, eps not finite or <= 0. */
+int th_fold_batchnorm2d(th_ctx *ctx, const float *d_gamma, const float *d_beta, const float *d_running_mean, const float *d_running_var, float eps, int c,
+                        float *d_affine);
+/* The frozen layer over an NCHW map [n, c, hw]: y = x * a[ch] + b[ch] (one multiply, one add, each rounded once), then max(y, 0) with
+ * relu.  One streaming launch: 16-byte accesses when hw % 4 == 0 and d_x, d_y are 16-byte aligned, single floats otherwise.
+ * Refused before the launch: a null pointer, c or hw <= 0, n < 0, n * hw >= 2^31.  n == 0 returns 0. */
+int th_channel_affine_fwd(th_ctx *ctx, const float *d_x, const float *d_affine, int n, int c, int hw, int relu, float *d_y);
 
 /* ---- broadcast / reduce / layout: src/tensor.rs ---------------------- */
 int th_transpose2d(th_ctx *ctx, const float *d_in, float *d_out, int rows, int cols);      /* tensor.rs:544-566 */

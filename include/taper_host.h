@@ -148,7 +148,7 @@ int tp_module_set_training(tp_module *m, int on);
 /* ---- post-training quantization (src/nn.rs:14-23, the quantized twins of nn.rs:62-504) ----
  * qtype: 0 Int8, 1 Float16; 2 Int4, 3 BFloat16 and 4 NF4 are placeholders in the reference (zeros) and are refused.  enabled == 0
  * gives Float16 whatever qtype says (tensor.rs:2085-2088).  Linear, Conv2d / Conv2dReLU, Sequential, the pools, Flatten, ReLU and
- * Sigmoid have twins; any other module (Dropout) fails with "Quantization not implemented for this module type" (nn.rs:15) before
+ * Sigmoid have twins; any other module (Dropout; BatchNorm2d and BasicBlock, which the static calls below take) fails with "Quantization not implemented for this module type" (nn.rs:15) before
  * anything is allocated.  The codes are made on the device; the source model is not touched and can keep training. */
 int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **out);
 /* Static int8 quantization: weights and biases packed exactly as tp_module_quantize(m, 0, 1) packs them (tp_qmodule_tensor returns the same
@@ -193,9 +193,10 @@ int tp_qmodule_free(tp_qmodule *q);
 /* QuantizedModule::forward: records no tape node; the output does not require a gradient */
 int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out);
 /* code bytes of every tensor (a static twin's Linear weights with their row padding), plus 8 bytes of {min_val, scale} per int8 tensor
- * (per channel of a per-channel tensor) and 4 bytes per activation scale */
+ * (per channel of a per-channel tensor), 4 bytes per activation scale and 8 bytes per channel of a frozen BatchNorm2d */
 int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out);
-/* the packed tensors in the order of the source's parameters(): length, then codes (n int8 or n uint16; h_codes nullable),
+/* the packed tensors in the order of the source's parameters() without those of a BatchNorm2d (its gamma and beta are not packed: see
+ * tp_qmodule_affine): length, then codes (n int8 or n uint16; h_codes nullable),
  * {min_val, scale} (int8; {0, 0} for Float16; nullable) and the qtype (nullable) */
 int tp_qmodule_num_tensors(const tp_qmodule *q, int *out);
 int tp_qmodule_tensor_len(const tp_qmodule *q, int i, size_t *out);
@@ -206,6 +207,20 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
  * non-null h_params on a per-channel tensor; its codes and qtype work as before. */
 int tp_qmodule_tensor_channels(const tp_qmodule *q, int i, size_t *channels, size_t *chan_stride, size_t *elem_stride);
 int tp_qmodule_tensor_params(const tp_qmodule *q, int i, float *h_pairs, size_t cap_pairs, size_t *n_pairs);
+/* BatchNorm2d and BasicBlock in the four tp_module_quantize_static* calls above (tp_module_quantize keeps the reference's refusal: without
+ * TP_QSTATIC_CONVS the convs of such a model stay weight-only inside a static twin).  A BatchNorm2d's twin keeps a snapshot of the layer on its running pair,
+ * whatever its training flag says: per channel {a, b} with invstd = 1 / sqrt(running_var + eps), a = gamma * invstd,
+ * b = beta - running_mean * a, made on the device (th_fold_batchnorm2d), and its forward is y = x * a + b, then max(y, 0) where the layer
+ * fuses a ReLU -- each operation rounded once.  The weights are not touched: every code of tp_qmodule_tensor is that of the same call on
+ * the same model.  A BasicBlock gives its conv twin and its BatchNorm2d twin inline to the enclosing Sequential's twin (alone: a Sequential
+ * twin of the two).  Right behind a static conv that has no ReLU of its own the layer runs in that conv's epilogue
+ * (th_conv2d_q8q8_fwd_affine / _codes_affine) with its own or a following ReLU folded in behind it, so a link of TP_QSTATIC_CHAIN is static
+ * conv, [BatchNorm2d], [ReLU], [one MaxPool2d], static conv; behind anything else (a weight-only conv such as a BasicBlock's with stride
+ * 2) it is one launch of th_channel_affine_fwd.  Calibration runs the float layer in eval mode.  Nothing of the source is modified.
+ * tp_qmodule_num_affines: the frozen layers of the twin; tp_qmodule_affine: layer i in layer order -- *n_pairs = its channels, the first
+ * min(*n_pairs, cap_pairs) pairs {a, b} into h_pairs (nullable). */
+int tp_qmodule_num_affines(const tp_qmodule *q, int *out);
+int tp_qmodule_affine(const tp_qmodule *q, int i, float *h_pairs, size_t cap_pairs, size_t *n_pairs);
 
 /* ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager}.rs) ----
  * config: qtype 0 Int8 / 1 Float16 (2..4 refused like tp_module_quantize), activations (fake-quantize each layer's output, before any

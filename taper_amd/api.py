@@ -401,8 +401,22 @@ class QuantizedModule:
             tp_check(host.tp_qmodule_act_scales(self._h, out.ctypes.data, n.value, C.byref(n)), "QuantizedModule::act_scales")
         return out
 
+    def affines(self):
+        """the frozen BatchNorm2d layers of the twin in layer order: a list of float32 arrays of shape (channels, 2) = {a, b}, the layer on
+        its running pair as y = x * a + b (empty for a model without BatchNorm2d)"""
+        n = C.c_int()
+        tp_check(host.tp_qmodule_num_affines(self._h, C.byref(n)), "QuantizedModule::affines")
+        out = []
+        for i in range(n.value):
+            k = C.c_size_t()
+            tp_check(host.tp_qmodule_affine(self._h, i, None, 0, C.byref(k)), "QuantizedModule::affines")
+            pairs = np.zeros((k.value, 2), np.float32)
+            tp_check(host.tp_qmodule_affine(self._h, i, pairs.ctypes.data, k.value, C.byref(k)), "QuantizedModule::affines")
+            out.append(pairs)
+        return out
+
     def tensors(self):
-        """[(qtype, codes, (min_val, scale))] in parameter order: codes int8 with its pair for "int8", uint16 half bits and
+        """[(qtype, codes, (min_val, scale))] in parameter order (a BatchNorm2d's gamma and beta are not packed: see affines()): codes int8 with its pair for "int8", uint16 half bits and
         (0, 0) for "float16".  A per-channel tensor (quantize_static_per_channel) has an ndarray of shape (channels, 2) as its third element."""
         n = C.c_int()
         tp_check(host.tp_qmodule_num_tensors(self._h, C.byref(n)), "QuantizedModule::tensors")

@@ -15,7 +15,12 @@ struct tp_loader { std::unique_ptr<DataLoader> l; };
 struct tp_trainer { std::unique_ptr<Trainer> t; };
 struct tp_comm { std::shared_ptr<Communicator> c; };
 struct tp_sched { std::shared_ptr<LRScheduler> s; };
-struct tp_qmodule { std::unique_ptr<QuantizedModule> q; std::vector<const QTensor *> tensors; std::vector<const float *> act_scales; };
+struct tp_qmodule {
+    std::unique_ptr<QuantizedModule> q;
+    std::vector<const QTensor *> tensors;
+    std::vector<const float *> act_scales;
+    std::vector<std::pair<const float *, size_t>> affines;
+};
 struct tp_observer { std::unique_ptr<MinMaxObserver> minmax; std::unique_ptr<HistogramObserver> hist; };   // one of the two, by kind
 struct tp_observer_manager { ObserverManager m; };
 
@@ -283,6 +288,7 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
     auto h = std::make_unique<tp_qmodule>();
     h->q = quantize(*m->m, (QType)qtype, enabled != 0);
     h->q->tensors(&h->tensors);
+    h->q->affines(&h->affines);
     *out = h.release();
     TP_END
 }
@@ -296,6 +302,7 @@ static void quantize_static_into(const char *fn, const tp_module *m, const tp_te
     h->q = quantize_static(*m->m, c, convs, chain, per_channel);
     h->q->tensors(&h->tensors);
     h->q->act_scales(&h->act_scales);
+    h->q->affines(&h->affines);
     *out = h.release();
 }
 int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
@@ -347,7 +354,23 @@ int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out) {
     TP_BEGIN
     size_t s = 0;
     for (const QTensor *t : q->tensors) s += t->storage_bytes();
+    for (const auto &a : q->affines) s += a.second * 2 * sizeof(float);
     *out = s + q->act_scales.size() * sizeof(float);
+    TP_END
+}
+int tp_qmodule_num_affines(const tp_qmodule *q, int *out) {
+    TP_BEGIN
+    TAPER_ASSERT(q && out, "tp_qmodule_num_affines: null argument");
+    *out = (int)q->affines.size();
+    TP_END
+}
+int tp_qmodule_affine(const tp_qmodule *q, int i, float *h_pairs, size_t cap_pairs, size_t *n_pairs) {
+    TP_BEGIN
+    TAPER_ASSERT(q && n_pairs, "tp_qmodule_affine: null argument");
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->affines.size(), "tp_qmodule_affine: index out of range");
+    *n_pairs = q->affines[i].second;
+    const size_t take = std::min(*n_pairs, cap_pairs);
+    if (h_pairs && take) taper::th_check(th_memcpy_d2h(Device::ctx(), h_pairs, q->affines[i].first, take * 2 * sizeof(float)), "th_memcpy_d2h");
     TP_END
 }
 int tp_qmodule_num_tensors(const tp_qmodule *q, int *out) { TP_BEGIN *out = (int)q->tensors.size(); TP_END }

@@ -129,6 +129,32 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
     ActScale act_;   // static only
 };
 
+// A BatchNorm2d frozen on its running pair: {a, b} per channel, made on the device when the twin is made -- a snapshot, the
+// source goes on training.  Behind a static conv the conv's epilogue applies it (QSequential::stage_at); anywhere else forward() does.
+class QBatchNorm : public QuantizedModule {
+   public:
+    explicit QBatchNorm(const BatchNorm2d &b) : c_(b.num_features), relu_(b.fuse_relu), affine_(Buffer::alloc(2 * b.num_features)) {
+        TH(th_fold_batchnorm2d(Device::ctx(), b.gamma.dptr(), b.beta.dptr(), b.running_mean.dptr(), b.running_var.dptr(), b.eps, (int)c_, affine_->d));
+    }
+    Tensor forward(const Tensor &x) const override {
+        TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == c_, "QuantizedBatchNorm2d: input must be [batch, num_features, h, w]");
+        const size_t hw = x.shape()[2] * x.shape()[3];
+        TAPER_ASSERT(x.shape()[0] <= 0x7fffffffu && hw <= 0x7fffffffu, "QuantizedBatchNorm2d: input too large");
+        Tensor y = Tensor::empty(x.shape());
+        TH(th_channel_affine_fwd(Device::ctx(), x.dptr(), affine_->d, (int)x.shape()[0], (int)c_, (int)hw, relu_ ? 1 : 0, y.dptr()));
+        return y;
+    }
+    void affines(std::vector<std::pair<const float *, size_t>> *out) const override { out->push_back({affine_->d, c_}); }
+    const float *pairs() const { return affine_->d; }
+    size_t channels() const { return c_; }
+    bool fuse_relu() const { return relu_; }
+
+   private:
+    size_t c_;
+    bool relu_;
+    std::shared_ptr<Buffer> affine_;   // [c][2] = {a, b}
+};
+
 // an activation as channel-last int8 codes [n][h][w][cpitch] with the int32 sum of every pixel's codes: what a static conv's product reads
 struct QCodes {
     std::shared_ptr<Buffer> q, sums;   // (pooled: they go back when the last holder lets go)
@@ -168,6 +194,7 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     }
     bool is_static() const { return (bool)act_; }
     size_t out_channels() const { return w_.shape[0]; }
+    bool own_relu() const { return geom_->fuse_relu; }
     // the codec: codes and pixel sums of x with this layer's scale
     QCodes encode(const Tensor &x) const {
         const Shape &ws = w_.shape;
@@ -178,8 +205,10 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     }
     // The integer product on codes made with this layer's scale; relu: the layer's own or a following one.  next == nullptr: f32 NCHW
     // into *y.  Otherwise the output as the codes of `next` (its scale, its pitch) into *qy, without pixel sums when `sums` is false (a
-    // pool that follows makes them).
-    void product(const QCodes &in, bool relu, Tensor *y, const QConv *next = nullptr, QCodes *qy = nullptr, bool sums = true) const {
+    // pool that follows makes them).  bn: a frozen BatchNorm2d right behind this layer (whose own ReLU is off), applied in the epilogue
+    // before `relu`.
+    void product(const QCodes &in, bool relu, Tensor *y, const QConv *next = nullptr, QCodes *qy = nullptr, bool sums = true,
+                 const QBatchNorm *bn = nullptr) const {
         const Shape &ws = w_.shape;
         TAPER_ASSERT(in.c == ws[1] && in.cpitch == cpitch_, "QuantizedConv2d: input must be [batch, in_channels, h, w]");
         const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
@@ -188,6 +217,22 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         const BiasPtrs b(b_);
         const int fold = relu || geom_->fuse_relu ? 1 : 0;
         th_ctx *ctx = Device::ctx();
+        TAPER_ASSERT(!bn || (bn->channels() == ws[0] && !geom_->fuse_relu), "QuantizedConv2d: a BatchNorm2d of another width, or behind a fused ReLU");
+        if (bn && !next) {
+            *y = Tensor::empty({in.n, ws[0], ho, wo});
+            TH(th_conv2d_q8q8_fwd_affine(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                         reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(),
+                                         b.params, fold, y->dptr(), w_.per_channel() ? 1 : 0, bn->pairs()));
+            return;
+        }
+        if (bn) {
+            *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
+            TH(th_conv2d_q8q8_fwd_codes_affine(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                                               reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d,
+                                               b.i8(), b.params, fold, next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr,
+                                               w_.per_channel() ? 1 : 0, bn->pairs()));
+            return;
+        }
         if (!next) {
             *y = Tensor::empty({in.n, ws[0], ho, wo});
             const auto product = w_.per_channel() ? th_conv2d_q8q8_fwd_pc : th_conv2d_q8q8_fwd;   // (a pair per output channel, or one)
@@ -203,9 +248,9 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
                    next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
     }
     // two launches: the codec (its buffers pooled, returned when this scope ends), then the product
-    Tensor forward_static(const Tensor &x, bool relu) const {
+    Tensor forward_static(const Tensor &x, bool relu, const QBatchNorm *bn = nullptr) const {
         Tensor y;
-        product(encode(x), relu, &y);
+        product(encode(x), relu, &y, nullptr, nullptr, true, bn);
         return y;
     }
     void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
@@ -271,11 +316,14 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
    public:
     std::vector<std::unique_ptr<QuantizedModule>> layers;
     bool chain = false;   // quantize_static's chain: activations stay int8 across a link
-    // A static conv's place in the list: `after` = the first layer behind it and its folded ReLU; with `chain`, whether a link starts
-    // here -- `pool` (or nullptr) and the static conv `next` at index `next_at` that takes the codes.
+    // A static conv's place in the list: `bn` = a frozen BatchNorm2d right behind it that its epilogue applies (a conv with a ReLU of its
+    // own leaves the layer standing: the ReLU comes first there); `relu` = the ReLU folded in behind both -- the BatchNorm's own or a ReLU
+    // layer; `after` = the first layer behind all of them; with `chain`, whether a link starts here -- `pool` (or nullptr) and the
+    // static conv `next` at index `next_at` that takes the codes.
     struct Stage {
         bool relu = false;
         size_t after = 0, next_at = 0;
+        const QBatchNorm *bn = nullptr;
         const MaxPool2d *pool = nullptr;
         const QConv *next = nullptr;
     };
@@ -286,8 +334,15 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
             return c && c->is_static() ? c : nullptr;
         };
         Stage st;
-        st.relu = pass(i + 1) && pass(i + 1)->is_relu();
-        st.after = i + (st.relu ? 2 : 1);
+        st.after = i + 1;
+        if (!stat(i)->own_relu() && st.after < layers.size() && (st.bn = dynamic_cast<const QBatchNorm *>(layers[st.after].get()))) {
+            st.relu = st.bn->fuse_relu();
+            ++st.after;
+        }
+        if (pass(st.after) && pass(st.after)->is_relu()) {   // (behind a BatchNorm with a ReLU of its own: the same ReLU a second time)
+            st.relu = true;
+            ++st.after;
+        }
         if (!chain || stat(i)->out_channels() > (size_t)th_qconv_i8_chain_max_cout()) return st;
         size_t j = st.after;
         if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
@@ -320,17 +375,17 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
                 if (cv->is_static()) {   // conv + ReLU: the ReLU in the product's epilogue
                     Stage st = stage_at(i);
                     if (!st.next) {
-                        x = cv->forward_static(x, st.relu);
+                        x = cv->forward_static(x, st.relu, st.bn);
                     } else {   // a run of links: one codec, then codes from product to product; the run's last conv writes f32
                         QCodes cur = cv->encode(x);
                         while (st.next) {
                             QCodes out;
-                            cv->product(cur, st.relu, nullptr, st.next, &out, /*sums=*/!st.pool);
+                            cv->product(cur, st.relu, nullptr, st.next, &out, /*sums=*/!st.pool, st.bn);
                             cur = st.pool ? max_pool_codes(out, *st.pool) : out;
                             cv = st.next;
                             st = stage_at(st.next_at);
                         }
-                        cv->product(cur, st.relu, &x);
+                        cv->product(cur, st.relu, &x, nullptr, nullptr, true, st.bn);
                     }
                     i = st.after - 1;
                     continue;
@@ -349,6 +404,9 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     void act_scales(std::vector<const float *> *out) const override {
         for (const auto &l : layers) l->act_scales(out);
     }
+    void affines(std::vector<std::pair<const float *, size_t>> *out) const override {
+        for (const auto &l : layers) l->affines(out);
+    }
     int chain_links() const override {
         int links = 0;
         for (size_t i = 0; i < layers.size(); ++i) {
@@ -359,15 +417,17 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     }
 };
 
-// nn.rs:15: every module without a quantize() of its own (Dropout among them) panics
-void check_quantizable(const Module &m) {
+// nn.rs:15: every module without a quantize() of its own (Dropout among them) panics.  batchnorm: whether BatchNorm2d and BasicBlock
+// have one -- in the static twins; the weight-only quantize() keeps the reference's refusal
+void check_quantizable(const Module &m, bool batchnorm) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
-        for (const auto &l : s->layers) check_quantizable(*l);
+        for (const auto &l : s->layers) check_quantizable(*l, batchnorm);
         return;
     }
     if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const QATModule *>(&m) || dynamic_cast<const ReLU *>(&m) ||
         dynamic_cast<const Sigmoid *>(&m) || dynamic_cast<const MaxPool2d *>(&m) || dynamic_cast<const AvgPool2d *>(&m) ||
-        dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m))
+        dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m) ||
+        (batchnorm && (dynamic_cast<const BatchNorm2d *>(&m) || dynamic_cast<const BasicBlock *>(&m))))
         return;
     throw Error("Quantization not implemented for this module type");
 }
@@ -385,9 +445,24 @@ std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bo
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto q = std::make_unique<QSequential>();
         q->chain = chain;
-        for (const auto &l : s->layers) q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain, per_channel));
+        for (const auto &l : s->layers) {
+            if (auto *bb = dynamic_cast<const BasicBlock *>(l.get())) {   // inline, so that a link can cross the block's boundary
+                q->layers.push_back(std::make_unique<QConv>(bb->conv, qtype, stat_convs, per_channel));
+                q->layers.push_back(std::make_unique<QBatchNorm>(bb->bn));
+            } else {
+                q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain, per_channel));
+            }
+        }
         return q;
     }
+    if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {   // alone: a Sequential of its two layers
+        auto q = std::make_unique<QSequential>();
+        q->chain = chain;
+        q->layers.push_back(std::make_unique<QConv>(bb->conv, qtype, stat_convs, per_channel));
+        q->layers.push_back(std::make_unique<QBatchNorm>(bb->bn));
+        return q;
+    }
+    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&m)) return std::make_unique<QBatchNorm>(*bn);
     if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat, per_channel);
     if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype, stat_convs, per_channel);
     // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
@@ -419,18 +494,46 @@ void convs_of(const Module &m, std::vector<const Conv2d *> *out) {
         out->push_back(c);
     } else if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) {
         out->push_back(&qc->inner);
+    } else if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {
+        out->push_back(&bb->conv);
     }
 }
 
 // One calibration tensor through the plain float layers of `m` (a QAT layer: its inner layer, whatever the QAT switch says), every
 // Linear twin and every static conv twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
+// A BasicBlock's two twins lie inline in the enclosing QSequential (quantize_checked): `qi` walks the twin's layers beside the model's.
+// A BatchNorm2d runs in eval mode on its running pair whatever its flag says, by the kernel itself: the layer is only read.
 Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first) {
     auto plain = [](const Tensor &t) { return t.defined() ? Tensor::from_device(t.dptr(), t.shape()) : Tensor(); };
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
         auto &qs = dynamic_cast<const QSequential &>(q);
         Tensor h = x;
-        for (size_t i = 0; i < s->layers.size(); ++i) h = calibrate(*s->layers[i], *qs.layers[i], h, first);
+        size_t qi = 0;
+        for (const auto &l : s->layers) {
+            if (auto *bb = dynamic_cast<const BasicBlock *>(l.get())) {
+                h = calibrate(bb->conv, *qs.layers[qi], h, first);
+                h = calibrate(bb->bn, *qs.layers[qi + 1], h, first);
+                qi += 2;
+            } else {
+                h = calibrate(*l, *qs.layers[qi++], h, first);
+            }
+        }
         return h;
+    }
+    if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {
+        auto &qs = dynamic_cast<const QSequential &>(q);
+        return calibrate(bb->bn, *qs.layers[1], calibrate(bb->conv, *qs.layers[0], x, first), first);
+    }
+    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&m)) {
+        TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == bn->num_features, "BatchNorm2d: expected a 4-D input [N, num_features, H, W]");
+        const size_t hw = x.shape()[2] * x.shape()[3];
+        TAPER_ASSERT(x.shape()[0] <= 0x7fffffffu && hw <= 0x7fffffffu, "BatchNorm2d: input too large");
+        Tensor y = Tensor::empty(x.shape());
+        auto saved = Buffer::alloc(2 * bn->num_features);
+        TH(th_batchnorm2d_fwd(Device::ctx(), x.dptr(), bn->gamma.dptr(), bn->beta.dptr(), y.dptr(), bn->running_mean.dptr(), bn->running_var.dptr(), saved->d,
+                              saved->d + bn->num_features, (int)x.shape()[0], (int)bn->num_features, (int)hw, bn->eps, bn->momentum, /*training=*/0,
+                              bn->fuse_relu ? 1 : 0));
+        return y;
     }
     const Linear *lin = dynamic_cast<const Linear *>(&m);
     if (auto *ql = dynamic_cast<const QATLinear *>(&m)) lin = &ql->inner;
@@ -453,7 +556,7 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
 th_qtensor QTensor::item(float *d_out) const { return th_qtensor{codes->d, params ? params->d : nullptr, d_out, (int64_t)n, qtype}; }
 
 std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled) {
-    check_quantizable(m);   // before anything is allocated
+    check_quantizable(m, /*batchnorm=*/false);   // before anything is allocated
     int qt = TH_QTYPE_F16;  // tensor.rs:2085-2088: disabled quantization gives Float16
     if (enabled) {
         switch (qtype) {
@@ -473,7 +576,7 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs, bool chain, bool per_channel) {
     convs = convs || chain;
     // every refusal before anything is allocated
-    check_quantizable(m);
+    check_quantizable(m, /*batchnorm=*/true);
     TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
     for (const Tensor &c : calib) TAPER_ASSERT(c.defined(), "quantize_static: undefined calibration tensor");
     std::vector<const Linear *> lins;

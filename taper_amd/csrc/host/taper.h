@@ -473,7 +473,7 @@ void set_training(Module &m, bool on);
 
 // ---- post-training quantization (src/nn.rs:14-23 Module::quantize / QuantizedModule, quantized twins nn.rs:62-504) ----
 // quantize() of Linear, Conv2d / Conv2dReLU, Sequential and the parameter-free layers (pools, Flatten, ReLU, Sigmoid); any other module
-// throws the reference's panic message (nn.rs:15).  The codes are made on the device from the live parameters (th_quantize_int8 /
+// (BatchNorm2d and BasicBlock among them: quantize_static below takes those) throws the reference's panic message (nn.rs:15).  The codes are made on the device from the live parameters (th_quantize_int8 /
 // th_f32_to_f16) and the model is not touched.  forward records no tape node; its output never requires a gradient.
 enum class QType { Int8 = 0, Float16 = 1, Int4 = 2, BFloat16 = 3, NF4 = 4 };
 
@@ -498,6 +498,8 @@ class QuantizedModule {
     virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
     virtual void act_scales(std::vector<const float *> *out) const {}  // device addresses of the calibrated activation scales, in layer order
     virtual int chain_links() const { return 0; }                      // layer boundaries a forward crosses in int8 (quantize_static's chain)
+    // every frozen BatchNorm2d in layer order: the device address of its [channels][2] = {a, b} and its channels
+    virtual void affines(std::vector<std::pair<const float *, size_t>> *out) const {}
 };
 std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool enabled);
 // Static int8 post-training quantization: weights and biases packed exactly as quantize(m, Int8) packs them, and every Linear given one
@@ -519,6 +521,14 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // (th_quantize_int8_channels: a Linear's rows; a static conv's effective output channels, the columns of the buffer as the float kernels
 // read it) and its product reads them (th_linear_q8q8_fwd_pc, th_conv2d_q8q8_fwd_pc / _codes_pc).  Biases, every layer that stays
 // weight-only, calibration (so act_scales()), the links and the refusals are the per-tensor twin's.
+// BatchNorm2d, in every form of quantize_static (not in quantize(), which keeps the reference's refusal): the twin keeps a snapshot {a, b} per channel of the layer on its running
+// pair, whatever its training flag says (th_fold_batchnorm2d: a = gamma * invstd, b = beta - running_mean * a), and computes
+// y = x * a + b [ReLU].  Its gamma and beta are not packed: tensors() is the source's parameters() without BatchNorm's, the codes those of
+// the same model without the fold; affines() lists the pairs.  A BasicBlock gives its conv twin and its BatchNorm twin inline to the
+// enclosing Sequential's twin (alone: a Sequential twin of the two).  Right behind a static conv without a ReLU of its own the layer runs
+// in that conv's epilogue (th_conv2d_q8q8_fwd_affine / _codes_affine) with its own or a following ReLU behind it, so a link of `chain` is
+// static conv, [BatchNorm2d], [ReLU], [one MaxPool2d], static conv; behind anything else it is one streaming launch
+// (th_channel_affine_fwd).  Calibration runs the float layer in eval mode; nothing of the source is modified.
 std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false, bool chain = false,
                                                  bool per_channel = false);
 

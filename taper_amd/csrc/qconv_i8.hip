@@ -10,6 +10,8 @@
 //   th_conv2d_q8q8_fwd_codes   the same product, its f32 value coded at once with the NEXT layer's scale: int8 [n, h_out, w_out, cpitch_y]
 //                              and the pixel sums, what th_quantize_act_nhwc_int8 would make of th_conv2d_q8q8_fwd's output
 //   th_conv2d_q8q8_fwd_pc, th_conv2d_q8q8_fwd_codes_pc: both with one {mw, sw} per output channel, a template flag of the kernel
+//   th_conv2d_q8q8_fwd_affine, th_conv2d_q8q8_fwd_codes_affine: both with a frozen BatchNorm2d behind the bias, y = v a[co] + b[co], then the
+//                              ReLU: one more template flag, the pairs {a, b} staged beside the weight pairs
 //   th_maxpool2d_nhwc_int8     the max-pool on channel-last codes (the codec is monotone: the maximum of the codes is the code of the maximum)
 //
 // With both operands channel-last a 16-byte piece of K is 16 consecutive channels of one tap: M = n h_out w_out output pixels, N = c_out,
@@ -80,6 +82,7 @@ struct QcArgs {
     int cpitch_y;
     QWindow win;
     int cpitch, c_out, M, relu, tiles_n;
+    const float *affine;   // AFFINE: {a, b} per output channel (null otherwise)
 };
 
 // A workgroup owns 128 output pixels (any run of the n h_out w_out list: it may span map rows and images) by 32 NT channels; wave v
@@ -94,7 +97,9 @@ struct QcArgs {
 // PC: wparams holds one {mw, sw} per output channel.  A lane needs the pairs of its 16 NT channels: the workgroup's 32 NT
 // pairs are staged once in the LDS the K loop has released (its last barrier is behind every read of a stage), one pair a thread, and
 // the epilogue reads them from there -- 16 NT dependent loads from memory a lane cost 2.6 - 7.5 us a layer, measured; this costs 0.0 - 0.6.
-template <int NT, bool CODES, bool PC>
+// AFFINE: a frozen BatchNorm2d behind the layer: the value is q8_value without its ReLU, then __fadd_rn(__fmul_rn(v, a), b) with
+// the channel's {a, b}, then the ReLU.  The workgroup's 32 NT pairs are staged like the weight pairs, behind them and the same barrier.
+template <int NT, bool CODES, bool PC, bool AFFINE = false>
 __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
     __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
@@ -175,8 +180,15 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
             const int co = min(col0 + t, a.c_out - 1);
             pairs[t] = make_float2(a.wparams[2 * co], a.wparams[2 * co + 1]);
         }
-        lds_barrier();
     }
+    float2 *ab = pairs + kQcChan * NT;   // AFFINE: {a, b} of channel col0 + i at ab[i]
+    if constexpr (AFFINE) {
+        if (t < kQcChan * NT) {
+            const int co = min(col0 + t, a.c_out - 1);
+            ab[t] = make_float2(a.affine[2 * co], a.affine[2 * co + 1]);
+        }
+    }
+    if constexpr (PC || AFFINE) lds_barrier();
     const int m = m0 + wave * 32 + li;
     const bool live = m < a.M;
     if (!CODES && !live) return;
@@ -195,8 +207,9 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
             const int co = col0 + 32 * j + (e & 3) + 8 * (e >> 2) + 4 * h;
             q[e] = 0;
             if (co >= a.c_out) continue;
-            const float v = q8_value(acc[j][e], rs, PC ? q8_rterm(pairs[co - col0].x, rs) : rterm, sx, PC ? pairs[co - col0].y : sw, a.qb != nullptr,
-                                     [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, a.relu);
+            float v = q8_value(acc[j][e], rs, PC ? q8_rterm(pairs[co - col0].x, rs) : rterm, sx, PC ? pairs[co - col0].y : sw, a.qb != nullptr,
+                               [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, AFFINE ? 0 : a.relu);
+            if constexpr (AFFINE) v = affine_value(v, ab[co - col0].x, ab[co - col0].y, a.relu);
             if constexpr (CODES) {
                 q[e] = act_code(v, sy);
                 sum += q[e];
@@ -241,6 +254,12 @@ static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h,
     if ((long)p->tiles_m * p->tiles_n > 0x7fffffffL) return "more than 2^31 workgroups";
     p->grid = p->tiles_m * p->tiles_n;
     return nullptr;
+}
+
+// the kernel of a plan's NT
+template <bool CODES, bool PC, bool AFFINE>
+static auto qconv_kernel_of(int nt) {
+    return nt == 1 ? qconv_i8_kernel<1, CODES, PC, AFFINE> : nt == 2 ? qconv_i8_kernel<2, CODES, PC, AFFINE> : qconv_i8_kernel<4, CODES, PC, AFFINE>;
 }
 
 // ---- the max-pool on codes ----
@@ -319,11 +338,12 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
 }
 
 // Both products: their checks (fn: the caller's name for the message), then the launch; the other form's outputs come null; pc:
-// d_wparams holds a pair per output channel
-static int qconv_run(const char *fn, bool codes, bool pc, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
+// d_wparams holds a pair per output channel; affine: d_affine holds {a, b} per output channel (null and unread otherwise)
+static int qconv_run(const char *fn, bool codes, bool pc, bool affine, const float *d_affine, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
                      int w, const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                      const float *d_bparams, int relu, float *d_y, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && (codes ? d_yscale && d_qy : d_y != nullptr) && (!d_qb || d_bparams), "%s: null argument", fn);
+    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && (codes ? d_yscale && d_qy : d_y != nullptr) && (!d_qb || d_bparams) && (!affine || d_affine),
+               "%s: null argument", fn);
     QcPlan p{};
     const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
     TH_REQUIRE(!why, "%s: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", fn, why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w);
@@ -331,18 +351,18 @@ static int qconv_run(const char *fn, bool codes, bool pc, th_ctx *ctx, const int
     TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", fn, cpitch, c_in);
     if (codes) {
         TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd%s)", fn, c_out,
-                   th_qconv_i8_chain_max_cout(), pc ? "_pc" : "");
+                   th_qconv_i8_chain_max_cout(), affine ? "_affine" : pc ? "_pc" : "");
         TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", fn);
         TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", fn, cpitch_y, c_out);
     }
     if (n == 0) return 0;
     const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, d_yscale, d_qy, d_ypixsum, cpitch_y, p.win, cpitch, c_out,
-                   n * p.win.h_out * p.win.w_out, relu, p.tiles_n};
-    auto kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true, false> : p.nt == 2 ? qconv_i8_kernel<2, true, false> : qconv_i8_kernel<4, true, false>)
-                        : (p.nt == 1 ? qconv_i8_kernel<1, false, false> : p.nt == 2 ? qconv_i8_kernel<2, false, false> : qconv_i8_kernel<4, false, false>);
-    if (pc)
-        kernel = codes ? (p.nt == 1 ? qconv_i8_kernel<1, true, true> : p.nt == 2 ? qconv_i8_kernel<2, true, true> : qconv_i8_kernel<4, true, true>)
-                       : (p.nt == 1 ? qconv_i8_kernel<1, false, true> : p.nt == 2 ? qconv_i8_kernel<2, false, true> : qconv_i8_kernel<4, false, true>);
+                   n * p.win.h_out * p.win.w_out, relu, p.tiles_n, affine ? d_affine : nullptr};
+    auto kernel = codes ? (pc ? qconv_kernel_of<true, true, false>(p.nt) : qconv_kernel_of<true, false, false>(p.nt))
+                        : (pc ? qconv_kernel_of<false, true, false>(p.nt) : qconv_kernel_of<false, false, false>(p.nt));
+    if (affine)
+        kernel = codes ? (pc ? qconv_kernel_of<true, true, true>(p.nt) : qconv_kernel_of<true, false, true>(p.nt))
+                       : (pc ? qconv_kernel_of<false, true, true>(p.nt) : qconv_kernel_of<false, false, true>(p.nt));
     hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, ctx->stream, a);
     TH_LAUNCH_CHECK();
     return 0;
@@ -351,7 +371,7 @@ static int qconv_run(const char *fn, bool codes, bool pc, th_ctx *ctx, const int
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                        const float *d_bparams, int relu, float *d_y) {
-    return qconv_run("th_conv2d_q8q8_fwd", false, false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
+    return qconv_run("th_conv2d_q8q8_fwd", false, false, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
                      d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
 }
 
@@ -360,22 +380,37 @@ int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
 int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                              const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes", true, false, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+    return qconv_run("th_conv2d_q8q8_fwd_codes", true, false, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
                      d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
 }
 
 int th_conv2d_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                           const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                           const float *d_bparams, int relu, float *d_y) {
-    return qconv_run("th_conv2d_q8q8_fwd_pc", false, true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
+    return qconv_run("th_conv2d_q8q8_fwd_pc", false, true, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
                      d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
 }
 
 int th_conv2d_q8q8_fwd_codes_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                                 const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                                 const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes_pc", true, true, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
+    return qconv_run("th_conv2d_q8q8_fwd_codes_pc", true, true, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
                      d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
+}
+
+int th_conv2d_q8q8_fwd_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
+                              const float *d_bparams, int relu, float *d_y, int per_channel, const float *d_affine) {
+    return qconv_run("th_conv2d_q8q8_fwd_affine", false, per_channel != 0, true, d_affine, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w,
+                     s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
+}
+
+int th_conv2d_q8q8_fwd_codes_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                    const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                    const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
+                                    int per_channel, const float *d_affine) {
+    return qconv_run("th_conv2d_q8q8_fwd_codes_affine", true, per_channel != 0, true, d_affine, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h,
+                     k_w, s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
 }
 
 int th_maxpool2d_nhwc_int8(th_ctx *ctx, const int8_t *d_q, int n, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w,

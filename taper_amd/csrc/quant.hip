@@ -2,9 +2,13 @@
 // Int4 / BFloat16 / NF4 are placeholders there): int8 affine quantisation over the finite min / max of the tensor, and the
 // hand-rolled IEEE half conversion.  Integer / bit work: restated literally (including the half-up rounding whose mantissa
 // carry is OR-ed, not added, into the exponent field) and held to bit-exact parity.  HBM-bound, one pass each.
+// Also here: a frozen BatchNorm2d for the quantized twins -- th_fold_batchnorm2d makes {a, b} per channel and
+// th_channel_affine_fwd is the layer where no static conv's epilogue takes it.
 #include "common.h"
 #include "quant_dev.h"
 #include "stream_dev.h"
+
+#include <cmath>
 
 namespace th {
 
@@ -113,6 +117,47 @@ __global__ __launch_bounds__(256) void dequantize_int8_kernel(const int8_t *__re
         y[i] = (float)((int)q[i] - zero_point) * scale + min_val;                     // tensor.rs:357 (two roundings: contraction is off)
 }
 
+// ---- a frozen BatchNorm2d ----
+// The fold: {a, b} of every channel from the layer's parameters and its running pair; a lane a channel, every operation rounded once.
+// invstd is batchnorm.hip's eval expression with sqrtf in the place of __fsqrt_rn: the intrinsic is the hardware's square root, good to
+// one ulp, where sqrtf rounds correctly -- a snapshot that a numpy restatement gives bit for bit needs the latter.
+__global__ __launch_bounds__(kStreamThreads) void batchnorm_fold_kernel(const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                                        const float *__restrict__ running_mean, const float *__restrict__ running_var,
+                                                                        float eps, int c, float *__restrict__ affine) {
+    for (int64_t ch = grid_t0(); ch < c; ch += grid_stride()) {
+        const float invstd = __fdiv_rn(1.0f, sqrtf(running_var[ch] + eps));
+        const float a = __fmul_rn(gamma[ch], invstd);
+        affine[2 * ch] = a;
+        affine[2 * ch + 1] = __fsub_rn(beta[ch], __fmul_rn(running_mean[ch], a));
+    }
+}
+
+// The standalone layer over NCHW: the tensor is one stream of `units` units of V (float4s when hw % 4 == 0 and both pointers are 16-byte
+// aligned, then no unit straddles a plane; floats otherwise), upp of them a plane.  A lane walks t0, t0 + stride, ... and keeps its place
+// {offset in the plane, channel} by additions: one 64-bit division a lane, before the walk.
+template <class V>
+__global__ __launch_bounds__(kStreamThreads) void channel_affine_kernel(const float *__restrict__ x, const float *__restrict__ affine, int64_t units, int upp,
+                                                                        int c, int relu, float *__restrict__ y) {
+    const int64_t stride = grid_stride();
+    int64_t j = grid_t0();
+    if (j >= units) return;
+    const int64_t plane = j / upp, dplane = stride / upp;
+    int off = (int)(j - plane * upp), ch = (int)(plane % c);
+    const int doff = (int)(stride - dplane * upp), dch = (int)(dplane % c);
+#pragma unroll 2
+    for (; j < units; j += stride) {
+        const float a = affine[2 * ch], b = affine[2 * ch + 1];
+        put(y, j, vmap([=](float v) { return affine_value(v, a, b, relu); }, at<V>(x, j)));
+        off += doff;
+        ch += dch;
+        if (off >= upp) {   // (off < 2 upp and ch <= 2 c - 1 here: one step back each)
+            off -= upp;
+            ++ch;
+        }
+        if (ch >= c) ch -= c;
+    }
+}
+
 }  // namespace th
 
 using namespace th;
@@ -183,6 +228,32 @@ int th_dequantize_int8(th_ctx *ctx, const int8_t *d_q, float *d_y, size_t n, flo
     TH_REQUIRE(ctx && (n == 0 || (d_q && d_y)), "th_dequantize_int8: null argument");
     if (n == 0) return 0;
     hipLaunchKernelGGL(dequantize_int8_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, ctx->stream, d_q, d_y, n, scale, zero_point, min_val);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_fold_batchnorm2d(th_ctx *ctx, const float *d_gamma, const float *d_beta, const float *d_running_mean, const float *d_running_var, float eps, int c,
+                        float *d_affine) {
+    TH_REQUIRE(ctx && d_gamma && d_beta && d_running_mean && d_running_var && d_affine, "th_fold_batchnorm2d: null argument");
+    TH_REQUIRE(c > 0, "th_fold_batchnorm2d: c must be positive (got %d)", c);
+    TH_REQUIRE(std::isfinite(eps) && eps > 0.0f, "th_fold_batchnorm2d: eps must be finite and positive (got %g)", (double)eps);
+    hipLaunchKernelGGL(batchnorm_fold_kernel, dim3(stream_grid(c, kStreamThreads, kNumCU)), dim3(kStreamThreads), 0, ctx->stream, d_gamma, d_beta, d_running_mean,
+                       d_running_var, eps, c, d_affine);
+    TH_LAUNCH_CHECK();
+    return 0;
+}
+
+int th_channel_affine_fwd(th_ctx *ctx, const float *d_x, const float *d_affine, int n, int c, int hw, int relu, float *d_y) {
+    TH_REQUIRE(ctx && d_x && d_affine && d_y, "th_channel_affine_fwd: null argument");
+    TH_REQUIRE(n >= 0 && c > 0 && hw > 0, "th_channel_affine_fwd: c and hw must be positive, n not negative (got n=%d c=%d hw=%d)", n, c, hw);
+    TH_REQUIRE((int64_t)n * hw < ((int64_t)1 << 31), "th_channel_affine_fwd: %lld elements per channel: fewer than 2^31 are supported", (long long)n * hw);
+    if (n == 0) return 0;
+    const bool wide = hw % 4 == 0 && (((uintptr_t)d_x | (uintptr_t)d_y) & 15) == 0;
+    const int upp = wide ? hw / 4 : hw;
+    const int64_t units = (int64_t)n * c * upp;
+    const dim3 grid(stream_grid(units, 2 * kStreamThreads, kNumCU * 8));   // two units a lane at least
+    hipLaunchKernelGGL(wide ? channel_affine_kernel<float4> : channel_affine_kernel<float>, grid, dim3(kStreamThreads), 0, ctx->stream, d_x, d_affine, units, upp, c,
+                       relu, d_y);
     TH_LAUNCH_CHECK();
     return 0;
 }

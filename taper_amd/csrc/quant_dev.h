@@ -77,4 +77,11 @@ __device__ __forceinline__ int act_code(float v, float scale) {
 // (q - zero_point) * scale + min_val with zero_point = -128: two roundings, never contracted (tensor.rs:357)
 __device__ __forceinline__ float dequant_int8(int q, float scale, float min_val) { return __fadd_rn(__fmul_rn((float)(q + 128), scale), min_val); }
 
+// A frozen BatchNorm2d behind a value: y = v a + b with the channel's folded pair, one multiply and one add rounded once
+// each and never contracted, then the ReLU.  The int8 conv epilogue (qconv_i8.hip) and the standalone layer (quant.hip) both call this.
+__device__ __forceinline__ float affine_value(float v, float a, float b, int relu) {
+    const float y = __fadd_rn(__fmul_rn(v, a), b);
+    return relu ? (y > 0.f ? y : 0.f) : y;
+}
+
 }  // namespace th
