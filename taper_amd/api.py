@@ -264,6 +264,9 @@ def accuracy(pred, targets) -> float:
     return float(out.value)
 
 
+_QSTATIC_CONVS, _QSTATIC_CHAIN, _QSTATIC_PER_CHANNEL = 1, 2, 4      # include/taper_host.h's TP_QSTATIC_* flags
+
+
 # -- src/nn.rs, src/activation.rs ------------------------------------------------
 class Module:
     def __init__(self, h):
@@ -322,42 +325,34 @@ class Module:
         """Static int8 post-training quantization -> QuantizedModule: the weights packed as quantize("int8") packs them, and one activation
         scale per Linear from the float model's activations on `calib` (a Tensor or a sequence of them).  Linear layers then run
         int8 x int8 on the integer matrix cores at every batch size; this model is only read."""
-        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
-        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
-        h = _p()
-        tp_check(host.tp_module_quantize_static(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static")
-        return QuantizedModule(h.value)
+        return self._quantize_static(host.tp_module_quantize_static, "quantize_static", calib)
 
     def quantize_static_conv(self, calib):
         """quantize_static with the convolutions static too: every 3x3, stride-1 Conv2d / Conv2dReLU with one group gets its own activation
         scale and runs int8 x int8 as an implicit GEMM on the integer matrix cores (any other conv stays weight-only).
         act_scales() lists one scale per static layer, Linear or conv, in layer order; tensors() is quantize("int8")'s."""
-        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
-        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
-        h = _p()
-        tp_check(host.tp_module_quantize_static_conv(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_conv")
-        return QuantizedModule(h.value)
+        return self._quantize_static(host.tp_module_quantize_static_conv, "quantize_static_conv", calib)
 
     def quantize_static_chain(self, calib):
         """quantize_static_conv whose activations stay int8 from one static conv to the next: a conv of at most 128 output channels writes
         the next conv's codes from its epilogue, and one MaxPool2d between the two runs on the codes.  The same scales, tensors and, on
         finite activations, the same output bits as quantize_static_conv's twin; chain_links() counts the boundaries crossed in int8."""
-        tensors = [calib] if isinstance(calib, Tensor) else list(calib)
-        arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
-        h = _p()
-        tp_check(host.tp_module_quantize_static_chain(self._h, arr, len(tensors), C.byref(h)), "Module::quantize_static_chain")
-        return QuantizedModule(h.value)
+        return self._quantize_static(host.tp_module_quantize_static_chain, "quantize_static_chain", calib)
 
     def quantize_static_per_channel(self, calib, convs=True, chain=True):
         """quantize_static / quantize_static_conv / quantize_static_chain (by `convs` and `chain`) with one {min_val, scale} pair per output
         channel for the weight of every static layer: a Linear's rows, a static conv's effective output channels.  Biases and every layer
         that stays weight-only keep one pair; act_scales() and chain_links() are the per-tensor twin's.  tensors() gives such a weight's
         pairs as an ndarray of shape (channels, 2), channel_layout(i) where a channel's codes lie."""
+        flags = (_QSTATIC_CONVS if convs or chain else 0) | (_QSTATIC_CHAIN if chain else 0) | _QSTATIC_PER_CHANNEL
+        return self._quantize_static(host.tp_module_quantize_static_ex, "quantize_static_per_channel", calib, flags)
+
+    def _quantize_static(self, entry, name, calib, *flags):
+        """one static quantize call of the host library: the calibration tensors marshalled, `flags` for the entry point that takes them"""
         tensors = [calib] if isinstance(calib, Tensor) else list(calib)
         arr = (C.c_void_p * max(len(tensors), 1))(*[t._h if t is not None else None for t in tensors])
         h = _p()
-        flags = (1 if convs or chain else 0) | (2 if chain else 0) | 4
-        tp_check(host.tp_module_quantize_static_ex(self._h, arr, len(tensors), flags, C.byref(h)), "Module::quantize_static_per_channel")
+        tp_check(entry(self._h, arr, len(tensors), *flags, C.byref(h)), "Module::" + name)
         return QuantizedModule(h.value)
 
 

@@ -292,14 +292,15 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
     *out = h.release();
     TP_END
 }
-// every static twin: `fn` is the caller's name for the message
-static void quantize_static_into(const char *fn, const tp_module *m, const tp_tensor *const *calib, int n_calib, bool convs, bool chain, bool per_channel,
-                                 tp_qmodule **out) {
+// every static twin, by TP_QSTATIC_* flags: `fn` is the caller's name for the message
+static void quantize_static_into(const char *fn, const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
     TAPER_ASSERT(m && out, std::string(fn) + ": null argument");
     std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
     for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
+    QuantizeOptions o;
+    o.convs = (flags & TP_QSTATIC_CONVS) != 0, o.chain = (flags & TP_QSTATIC_CHAIN) != 0, o.per_channel = (flags & TP_QSTATIC_PER_CHANNEL) != 0;
     auto h = std::make_unique<tp_qmodule>();
-    h->q = quantize_static(*m->m, c, convs, chain, per_channel);
+    h->q = quantize_static(*m->m, c, o);
     h->q->tensors(&h->tensors);
     h->q->act_scales(&h->act_scales);
     h->q->affines(&h->affines);
@@ -307,25 +308,24 @@ static void quantize_static_into(const char *fn, const tp_module *m, const tp_te
 }
 int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
-    quantize_static_into("tp_module_quantize_static", m, calib, n_calib, false, false, false, out);
+    quantize_static_into("tp_module_quantize_static", m, calib, n_calib, 0, out);
     TP_END
 }
 int tp_module_quantize_static_conv(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
-    quantize_static_into("tp_module_quantize_static_conv", m, calib, n_calib, /*convs=*/true, false, false, out);
+    quantize_static_into("tp_module_quantize_static_conv", m, calib, n_calib, TP_QSTATIC_CONVS, out);
     TP_END
 }
 int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
-    quantize_static_into("tp_module_quantize_static_chain", m, calib, n_calib, /*convs=*/true, /*chain=*/true, false, out);
+    quantize_static_into("tp_module_quantize_static_chain", m, calib, n_calib, TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN, out);
     TP_END
 }
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
     TP_BEGIN
     TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL)) == 0, "tp_module_quantize_static_ex: unknown flag bits");
     TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), "tp_module_quantize_static_ex: TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
-    quantize_static_into("tp_module_quantize_static_ex", m, calib, n_calib, (flags & TP_QSTATIC_CONVS) != 0, (flags & TP_QSTATIC_CHAIN) != 0,
-                         (flags & TP_QSTATIC_PER_CHANNEL) != 0, out);
+    quantize_static_into("tp_module_quantize_static_ex", m, calib, n_calib, flags, out);
     TP_END
 }
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out) {

@@ -77,14 +77,14 @@ struct BiasPtrs {
 
 class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
    public:
-    // stat: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
-    // activation scale on the device that calibration fixes; per_channel (static only): one weight pair per row
-    QLinear(const Linear &l, int qtype, bool stat = false, bool per_channel = false)
-        : w_(stat && per_channel ? quantize_channels(l.weight, l.weight.shape()[0], l.weight.shape()[1], 1) : quantize_tensor(l.weight, qtype)),
+    // o.linears: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
+    // activation scale on the device that calibration fixes; o.per_channel (static only): one weight pair per row
+    QLinear(const Linear &l, int qtype, QuantizeOptions o = {})
+        : w_(o.linears && o.per_channel ? quantize_channels(l.weight, l.weight.shape()[0], l.weight.shape()[1], 1) : quantize_tensor(l.weight, qtype)),
           k_(l.weight.shape()[1]),
           n_(l.weight.shape()[0]) {
         if (l.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(l.bias, qtype));
-        if (!stat) return;
+        if (!o.linears) return;
         const size_t step = (size_t)th_qlinear_i8_kstep();
         w_.pitch = (k_ + step - 1) / step * step;
         auto padded = Buffer::alloc(n_ * w_.pitch / 4);
@@ -130,7 +130,7 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
 };
 
 // A BatchNorm2d frozen on its running pair: {a, b} per channel, made on the device when the twin is made -- a snapshot, the
-// source goes on training.  Behind a static conv the conv's epilogue applies it (QSequential::stage_at); anywhere else forward() does.
+// source goes on training.  Behind a static conv the conv's epilogue applies it (QSequential::resolve); anywhere else forward() does.
 class QBatchNorm : public QuantizedModule {
    public:
     explicit QBatchNorm(const BatchNorm2d &b) : c_(b.num_features), relu_(b.fuse_relu), affine_(Buffer::alloc(2 * b.num_features)) {
@@ -166,6 +166,19 @@ struct QCodes {
     }
 };
 
+// what a static conv's product folds into its epilogue: a ReLU behind the layer (its own is added there), and a frozen BatchNorm2d right
+// behind the layer (whose own ReLU is off), applied before that ReLU
+struct QEpilogue {
+    bool relu = false;
+    const QBatchNorm *bn = nullptr;
+};
+// where the product goes: f32 NCHW (the default), or the codes of `next` (its scale, its pitch), without pixel sums when `sums` is false
+// (a pool that follows makes them)
+struct QDest {
+    const class QConv *next = nullptr;
+    bool sums = true;
+};
+
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
    public:
     // The integer product is a convolution, so it stands in for the float layer only where the float path is one: 3x3, stride 1, one
@@ -175,16 +188,16 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         const Shape &ws = c.weight.shape();
         return c.groups == 1 && c.dilation == std::make_pair(1, 1) && c.stride == std::make_pair(1, 1) && ws[2] == 3 && ws[3] == 3;
     }
-    // stat: the static int8 twin (quantize_static with convs) -- the weight codes re-laid once channel-last for the product (an internal
-    // copy: tensors() keeps reporting the packed codes), and one activation scale on the device that calibration fixes; per_channel
+    // o.convs: the static int8 twin (quantize_static with convs) -- the weight codes re-laid once channel-last for the product (an internal
+    // copy: tensors() keeps reporting the packed codes), and one activation scale on the device that calibration fixes; o.per_channel
     // (static only): one weight pair per effective output channel co, whose elements lie at (ci taps + tap) c_out + co of the buffer
-    QConv(const Conv2d &c, int qtype, bool stat = false, bool per_channel = false)
+    QConv(const Conv2d &c, int qtype, QuantizeOptions o = {})
         : geom_(std::make_shared<Conv2d>(c)),
-          w_(stat && per_channel && can_be_static(c) ? quantize_channels(c.weight, c.weight.shape()[0], 1, c.weight.shape()[0]) : quantize_tensor(c.weight, qtype)) {
+          w_(o.convs && o.per_channel && can_be_static(c) ? quantize_channels(c.weight, c.weight.shape()[0], 1, c.weight.shape()[0]) : quantize_tensor(c.weight, qtype)) {
         if (c.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(c.bias, qtype));
         geom_->weight = Tensor();   // the twin keeps the geometry only, not the source's f32 storage
         geom_->bias = Tensor();
-        if (!stat || !can_be_static(c)) return;
+        if (!o.convs || !can_be_static(c)) return;
         const Shape &ws = w_.shape;   // [c_out, c_in, k_h, k_w]
         cpitch_ = (size_t)th_qconv_i8_cpitch((int)ws[1]);
         relaid_ = Buffer::alloc(ws[0] * ws[2] * ws[3] * cpitch_ / 4);
@@ -203,60 +216,42 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         TH(th_quantize_act_nhwc_int8(Device::ctx(), x.dptr(), (int)in.n, (int)in.c, (int)in.h, (int)in.w, act_.scale(), in.codes(), (int)cpitch_, in.pixsum()));
         return in;
     }
-    // The integer product on codes made with this layer's scale; relu: the layer's own or a following one.  next == nullptr: f32 NCHW
-    // into *y.  Otherwise the output as the codes of `next` (its scale, its pitch) into *qy, without pixel sums when `sums` is false (a
-    // pool that follows makes them).  bn: a frozen BatchNorm2d right behind this layer (whose own ReLU is off), applied in the epilogue
-    // before `relu`.
-    void product(const QCodes &in, bool relu, Tensor *y, const QConv *next = nullptr, QCodes *qy = nullptr, bool sums = true,
-                 const QBatchNorm *bn = nullptr) const {
+    struct Output {   // what the QDest asked for; the other member stays empty
+        Tensor y;
+        QCodes codes;
+    };
+    // the integer product on codes made with this layer's scale
+    Output product(const QCodes &in, QEpilogue e, QDest d = {}) const {
         const Shape &ws = w_.shape;
         TAPER_ASSERT(in.c == ws[1] && in.cpitch == cpitch_, "QuantizedConv2d: input must be [batch, in_channels, h, w]");
         const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
         TAPER_ASSERT(in.h + 2 * ph >= ws[2] && in.w + 2 * pw >= ws[3], "QuantizedConv2d: the kernel is larger than the padded input");
         const size_t ho = (in.h + 2 * ph - ws[2]) / sh + 1, wo = (in.w + 2 * pw - ws[3]) / sw + 1;
         const BiasPtrs b(b_);
-        const int fold = relu || geom_->fuse_relu ? 1 : 0;
-        th_ctx *ctx = Device::ctx();
-        TAPER_ASSERT(!bn || (bn->channels() == ws[0] && !geom_->fuse_relu), "QuantizedConv2d: a BatchNorm2d of another width, or behind a fused ReLU");
-        if (bn && !next) {
-            *y = Tensor::empty({in.n, ws[0], ho, wo});
-            TH(th_conv2d_q8q8_fwd_affine(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                         reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(),
-                                         b.params, fold, y->dptr(), w_.per_channel() ? 1 : 0, bn->pairs()));
-            return;
+        const int fold = e.relu || geom_->fuse_relu ? 1 : 0, pc = w_.per_channel() ? 1 : 0;   // (pc: a pair per output channel, or one)
+        TAPER_ASSERT(!e.bn || (e.bn->channels() == ws[0] && !geom_->fuse_relu), "QuantizedConv2d: a BatchNorm2d of another width, or behind a fused ReLU");
+        // every entry point takes the same operands and then its own tail
+        auto run = [&](auto entry, auto... tail) {
+            TH(entry(Device::ctx(), in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
+                     reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold, tail...));
+        };
+        Output out;
+        if (!d.next) {
+            out.y = Tensor::empty({in.n, ws[0], ho, wo});
+            if (e.bn) run(th_conv2d_q8q8_fwd_affine, out.y.dptr(), pc, e.bn->pairs());
+            else run(pc ? th_conv2d_q8q8_fwd_pc : th_conv2d_q8q8_fwd, out.y.dptr());
+            return out;
         }
-        if (bn) {
-            *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
-            TH(th_conv2d_q8q8_fwd_codes_affine(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                                               reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d,
-                                               b.i8(), b.params, fold, next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr,
-                                               w_.per_channel() ? 1 : 0, bn->pairs()));
-            return;
-        }
-        if (!next) {
-            *y = Tensor::empty({in.n, ws[0], ho, wo});
-            const auto product = w_.per_channel() ? th_conv2d_q8q8_fwd_pc : th_conv2d_q8q8_fwd;   // (a pair per output channel, or one)
-            TH(product(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                       reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold,
-                       y->dptr()));
-            return;
-        }
-        *qy = QCodes::alloc(in.n, ws[0], ho, wo, next->cpitch_);
-        const auto product = w_.per_channel() ? th_conv2d_q8q8_fwd_codes_pc : th_conv2d_q8q8_fwd_codes;
-        TH(product(ctx, in.codes(), (int)cpitch_, in.pixsum(), act_.scale(), (int)in.n, (int)ws[1], (int)in.h, (int)in.w,
-                   reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold,
-                   next->act_.scale(), qy->codes(), (int)qy->cpitch, sums ? qy->pixsum() : nullptr));
-    }
-    // two launches: the codec (its buffers pooled, returned when this scope ends), then the product
-    Tensor forward_static(const Tensor &x, bool relu, const QBatchNorm *bn = nullptr) const {
-        Tensor y;
-        product(encode(x), relu, &y, nullptr, nullptr, true, bn);
-        return y;
+        QCodes &q = out.codes = QCodes::alloc(in.n, ws[0], ho, wo, d.next->cpitch_);
+        int *sums = d.sums ? q.pixsum() : nullptr;
+        if (e.bn) run(th_conv2d_q8q8_fwd_codes_affine, d.next->act_.scale(), q.codes(), (int)q.cpitch, sums, pc, e.bn->pairs());
+        else run(pc ? th_conv2d_q8q8_fwd_codes_pc : th_conv2d_q8q8_fwd_codes, d.next->act_.scale(), q.codes(), (int)q.cpitch, sums);
+        return out;
     }
     void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
     const ActScale &act() const { return act_; }
     Tensor forward(const Tensor &x) const override {   // alone: dequantize its own two tensors
-        if (is_static()) return forward_static(x, false);
+        if (is_static()) return product(encode(x), {}).y;   // two launches: the codec (its buffers pooled, returned with this expression), then the product
         std::vector<const QConv *> one{this};
         std::vector<std::pair<float *, float *>> at;
         auto ws = dequantize(one, &at);
@@ -315,85 +310,93 @@ QCodes max_pool_codes(const QCodes &in, const MaxPool2d &mp) {
 class QSequential : public QuantizedModule {   // nn.rs:153-177
    public:
     std::vector<std::unique_ptr<QuantizedModule>> layers;
-    bool chain = false;   // quantize_static's chain: activations stay int8 across a link
-    // A static conv's place in the list: `bn` = a frozen BatchNorm2d right behind it that its epilogue applies (a conv with a ReLU of its
-    // own leaves the layer standing: the ReLU comes first there); `relu` = the ReLU folded in behind both -- the BatchNorm's own or a ReLU
-    // layer; `after` = the first layer behind all of them; with `chain`, whether a link starts here -- `pool` (or nullptr) and the
-    // static conv `next` at index `next_at` that takes the codes.
+    // A static conv's place in a run: `fold.bn` = a frozen BatchNorm2d right behind it that its epilogue applies (a conv with a ReLU of
+    // its own leaves the layer standing: the ReLU comes first there); `fold.relu` = the ReLU folded in behind both -- the BatchNorm's own
+    // or a ReLU layer; with `chain`, whether a link starts here -- `pool` (or nullptr) and the static conv `next`, the run's next stage,
+    // that takes the codes.
     struct Stage {
-        bool relu = false;
-        size_t after = 0, next_at = 0;
-        const QBatchNorm *bn = nullptr;
+        const QConv *conv = nullptr;
+        QEpilogue fold;
         const MaxPool2d *pool = nullptr;
         const QConv *next = nullptr;
     };
-    Stage stage_at(size_t i) const {
+    // What forward runs, in order; one of four kinds.  Every layer of `layers` belongs to exactly one step: the one that runs it or folds it.
+    struct Step {
+        const QuantizedModule *plain = nullptr;   // any other layer (a nested Sequential's twin among them): its own forward
+        const QLinear *lin = nullptr;             // a Linear, `relu`: with the ReLU behind it in the same launch
+        bool relu = false;
+        const QConv *weight_only = nullptr;       // a weight-only conv, its weights at `slot` of the call's dequantize workspace
+        size_t slot = 0;
+        std::vector<Stage> run;                   // static convs: one codec, codes across every link, the last stage writes f32
+    };
+    // The steps, once `layers` is complete: nothing they depend on changes afterwards (is_static() is fixed when a conv twin is made,
+    // calibration only fills scales).  chain = quantize_static's chain: activations stay int8 across a link.
+    void resolve(bool chain) {
         auto pass = [&](size_t j) { return j < layers.size() ? dynamic_cast<const QPass *>(layers[j].get()) : nullptr; };
         auto stat = [&](size_t j) {
             auto *c = j < layers.size() ? dynamic_cast<const QConv *>(layers[j].get()) : nullptr;
             return c && c->is_static() ? c : nullptr;
         };
-        Stage st;
-        st.after = i + 1;
-        if (!stat(i)->own_relu() && st.after < layers.size() && (st.bn = dynamic_cast<const QBatchNorm *>(layers[st.after].get()))) {
-            st.relu = st.bn->fuse_relu();
-            ++st.after;
+        for (size_t i = 0; i < layers.size();) {
+            Step s;
+            if ((s.lin = dynamic_cast<const QLinear *>(layers[i].get()))) {
+                s.relu = pass(i + 1) && pass(i + 1)->is_relu();   // Linear + ReLU: one launch, the ReLU in its epilogue
+                i += s.relu ? 2 : 1;
+            } else if (stat(i)) {   // conv + ReLU: the ReLU in the product's epilogue
+                for (const QConv *cv = stat(i); cv; cv = s.run.back().next) {
+                    Stage st;
+                    st.conv = cv;
+                    size_t after = i + 1;   // the first layer behind everything the stage folds
+                    if (!cv->own_relu() && after < layers.size() && (st.fold.bn = dynamic_cast<const QBatchNorm *>(layers[after].get()))) {
+                        st.fold.relu = st.fold.bn->fuse_relu();
+                        ++after;
+                    }
+                    if (pass(after) && pass(after)->is_relu()) {   // (behind a BatchNorm with a ReLU of its own: the same ReLU a second time)
+                        st.fold.relu = true;
+                        ++after;
+                    }
+                    i = after;
+                    if (chain && cv->out_channels() <= (size_t)th_qconv_i8_chain_max_cout()) {
+                        size_t j = after;
+                        if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
+                        if ((st.next = stat(j))) i = j;   // a link: the run goes on there
+                        else st.pool = nullptr;           // (a pool counts only when a static conv follows it)
+                    }
+                    s.run.push_back(st);
+                }
+            } else if ((s.weight_only = dynamic_cast<const QConv *>(layers[i].get()))) {
+                s.slot = weight_only_.size();
+                weight_only_.push_back(s.weight_only);
+                ++i;
+            } else {
+                s.plain = layers[i++].get();
+            }
+            steps_.push_back(std::move(s));
         }
-        if (pass(st.after) && pass(st.after)->is_relu()) {   // (behind a BatchNorm with a ReLU of its own: the same ReLU a second time)
-            st.relu = true;
-            ++st.after;
-        }
-        if (!chain || stat(i)->out_channels() > (size_t)th_qconv_i8_chain_max_cout()) return st;
-        size_t j = st.after;
-        if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
-        if ((st.next = stat(j))) st.next_at = j;
-        else st.pool = nullptr;
-        return st;
     }
     Tensor forward(const Tensor &input) const override {
-        // every weight-only conv stage's weights in one dequantize launch, into one workspace that lives for this call
-        std::vector<const QConv *> convs;
-        for (const auto &l : layers)
-            if (auto *c = dynamic_cast<const QConv *>(l.get()))
-                if (!c->is_static()) convs.push_back(c);
+        // every weight-only conv step's weights in one dequantize launch, into one workspace that lives for this call
         std::vector<std::pair<float *, float *>> at;
         std::shared_ptr<Buffer> ws;
-        if (!convs.empty()) ws = QConv::dequantize(convs, &at);
+        if (!weight_only_.empty()) ws = QConv::dequantize(weight_only_, &at);
         Tensor x = input;
-        size_t ci = 0;
-        for (size_t i = 0; i < layers.size(); ++i) {
-            const QuantizedModule *l = layers[i].get();
-            if (auto *lin = dynamic_cast<const QLinear *>(l)) {
-                auto *next = i + 1 < layers.size() ? dynamic_cast<const QPass *>(layers[i + 1].get()) : nullptr;
-                if (next && next->is_relu()) {   // Linear + ReLU: one launch, the ReLU in its epilogue
-                    x = lin->forward_relu(x, true);
-                    ++i;
-                } else {
-                    x = lin->forward(x);
-                }
-            } else if (auto *cv = dynamic_cast<const QConv *>(l)) {
-                if (cv->is_static()) {   // conv + ReLU: the ReLU in the product's epilogue
-                    Stage st = stage_at(i);
+        for (const Step &s : steps_) {
+            if (s.lin) {
+                x = s.lin->forward_relu(x, s.relu);
+            } else if (s.weight_only) {
+                x = s.weight_only->forward_with(x, at[s.slot].first, at[s.slot].second);
+            } else if (s.plain) {
+                x = s.plain->forward(x);
+            } else {   // a run: one codec, then codes from product to product (pooled buffers, each returned when `cur` moves on)
+                QCodes cur = s.run[0].conv->encode(x);
+                for (const Stage &st : s.run) {
                     if (!st.next) {
-                        x = cv->forward_static(x, st.relu, st.bn);
-                    } else {   // a run of links: one codec, then codes from product to product; the run's last conv writes f32
-                        QCodes cur = cv->encode(x);
-                        while (st.next) {
-                            QCodes out;
-                            cv->product(cur, st.relu, nullptr, st.next, &out, /*sums=*/!st.pool, st.bn);
-                            cur = st.pool ? max_pool_codes(out, *st.pool) : out;
-                            cv = st.next;
-                            st = stage_at(st.next_at);
-                        }
-                        cv->product(cur, st.relu, &x, nullptr, nullptr, true, st.bn);
+                        x = st.conv->product(cur, st.fold).y;
+                    } else {
+                        QCodes out = st.conv->product(cur, st.fold, {st.next, /*sums=*/!st.pool}).codes;
+                        cur = st.pool ? max_pool_codes(out, *st.pool) : out;
                     }
-                    i = st.after - 1;
-                    continue;
                 }
-                x = cv->forward_with(x, at[ci].first, at[ci].second);
-                ++ci;
-            } else {
-                x = l->forward(x);
             }
         }
         return x;
@@ -409,12 +412,13 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     }
     int chain_links() const override {
         int links = 0;
-        for (size_t i = 0; i < layers.size(); ++i) {
-            auto *c = dynamic_cast<const QConv *>(layers[i].get());
-            links += c && c->is_static() ? (stage_at(i).next != nullptr) : layers[i]->chain_links();
-        }
+        for (const Step &s : steps_) links += s.plain ? s.plain->chain_links() : s.run.empty() ? 0 : (int)s.run.size() - 1;
         return links;
     }
+
+   private:
+    std::vector<Step> steps_;
+    std::vector<const QConv *> weight_only_;   // the weight-only conv steps, by slot
 };
 
 // nn.rs:15: every module without a quantize() of its own (Dropout among them) panics.  batchnorm: whether BatchNorm2d and BasicBlock
@@ -438,93 +442,68 @@ std::shared_ptr<Module> copy_of(const Module &m) {
     return p ? std::make_shared<M>(*p) : nullptr;
 }
 
-// stat: the Linear layers static; stat_convs: the plain convolutions too; chain: codes from one static conv to the next; per_channel: a
-// weight pair per output channel in every static layer
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, bool stat = false, bool stat_convs = false, bool chain = false,
-                                                  bool per_channel = false) {
-    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+// The leaf layers of `m` as the twin sees them, in order: a Sequential gives its children, a BasicBlock its conv and its BatchNorm2d (so
+// that a link can cross the block's boundary), a QAT layer its inner layer (it deploys as that: qat_layers.rs:126-133, the packed codes
+// are the fake-quantized weights it trained with).  A nested Sequential is one leaf: it stays a twin of its own.
+std::vector<const Module *> leaves_of(const Module &m) {
+    std::vector<const Module *> out;
+    auto leaf = [&](const Module &l) {
+        if (auto *bb = dynamic_cast<const BasicBlock *>(&l)) out.insert(out.end(), {&bb->conv, &bb->bn});
+        else if (auto *ql = dynamic_cast<const QATLinear *>(&l)) out.push_back(&ql->inner);
+        else if (auto *qc = dynamic_cast<const QATConv2d *>(&l)) out.push_back(&qc->inner);
+        else out.push_back(&l);
+    };
+    if (auto *s = dynamic_cast<const Sequential *>(&m))
+        for (const auto &l : s->layers) leaf(*l);
+    else
+        leaf(m);
+    return out;
+}
+
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, QuantizeOptions o = {}) {
+    const std::vector<const Module *> leaves = leaves_of(m);
+    if (dynamic_cast<const Sequential *>(&m) || leaves.size() > 1) {   // (more than one leaf of another module: a Sequential twin of them)
         auto q = std::make_unique<QSequential>();
-        q->chain = chain;
-        for (const auto &l : s->layers) {
-            if (auto *bb = dynamic_cast<const BasicBlock *>(l.get())) {   // inline, so that a link can cross the block's boundary
-                q->layers.push_back(std::make_unique<QConv>(bb->conv, qtype, stat_convs, per_channel));
-                q->layers.push_back(std::make_unique<QBatchNorm>(bb->bn));
-            } else {
-                q->layers.push_back(quantize_checked(*l, qtype, stat, stat_convs, chain, per_channel));
-            }
-        }
+        for (const Module *l : leaves) q->layers.push_back(quantize_checked(*l, qtype, o));
+        q->resolve(o.chain);
         return q;
     }
-    if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {   // alone: a Sequential of its two layers
-        auto q = std::make_unique<QSequential>();
-        q->chain = chain;
-        q->layers.push_back(std::make_unique<QConv>(bb->conv, qtype, stat_convs, per_channel));
-        q->layers.push_back(std::make_unique<QBatchNorm>(bb->bn));
-        return q;
-    }
-    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&m)) return std::make_unique<QBatchNorm>(*bn);
-    if (auto *l = dynamic_cast<const Linear *>(&m)) return std::make_unique<QLinear>(*l, qtype, stat, per_channel);
-    if (auto *c = dynamic_cast<const Conv2d *>(&m)) return std::make_unique<QConv>(*c, qtype, stat_convs, per_channel);
-    // a QAT layer deploys as its inner layer (qat_layers.rs:126-133): the packed codes are the fake-quantized weights it trained with
-    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) return std::make_unique<QLinear>(ql->inner, qtype, stat, per_channel);
-    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) return std::make_unique<QConv>(qc->inner, qtype, stat_convs, per_channel);
+    const Module &l = *leaves[0];
+    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) return std::make_unique<QBatchNorm>(*bn);
+    if (auto *lin = dynamic_cast<const Linear *>(&l)) return std::make_unique<QLinear>(*lin, qtype, o);
+    if (auto *c = dynamic_cast<const Conv2d *>(&l)) return std::make_unique<QConv>(*c, qtype, o);
     std::shared_ptr<Module> p;
-    if (!(p = copy_of<ReLU>(m)) && !(p = copy_of<Sigmoid>(m)) && !(p = copy_of<MaxPool2d>(m)) && !(p = copy_of<AvgPool2d>(m)) &&
-        !(p = copy_of<AdaptiveAvgPool2d>(m)) && !(p = copy_of<Flatten>(m)))
+    if (!(p = copy_of<ReLU>(l)) && !(p = copy_of<Sigmoid>(l)) && !(p = copy_of<MaxPool2d>(l)) && !(p = copy_of<AvgPool2d>(l)) &&
+        !(p = copy_of<AdaptiveAvgPool2d>(l)) && !(p = copy_of<Flatten>(l)))
         throw Error("Quantization not implemented for this module type");
     return std::make_unique<QPass>(p);
 }
 
-// the Linear layers of a model as quantize_checked meets them (a QAT layer: its inner layer)
-void linears_of(const Module &m, std::vector<const Linear *> *out) {
-    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
-        for (const auto &l : s->layers) linears_of(*l, out);
-    } else if (auto *l = dynamic_cast<const Linear *>(&m)) {
-        out->push_back(l);
-    } else if (auto *ql = dynamic_cast<const QATLinear *>(&m)) {
-        out->push_back(&ql->inner);
-    }
-}
-
-// the convolutions of a model, likewise
-void convs_of(const Module &m, std::vector<const Conv2d *> *out) {
-    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
-        for (const auto &l : s->layers) convs_of(*l, out);
-    } else if (auto *c = dynamic_cast<const Conv2d *>(&m)) {
-        out->push_back(c);
-    } else if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) {
-        out->push_back(&qc->inner);
-    } else if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {
-        out->push_back(&bb->conv);
+// the layers of type L of a model as quantize_checked meets them, nested Sequentials included
+template <class L>
+void layers_of(const Module &m, std::vector<const L *> *out) {
+    for (const Module *l : leaves_of(m)) {
+        if (auto *p = dynamic_cast<const L *>(l)) out->push_back(p);
+        else if (l != &m) layers_of(*l, out);
     }
 }
 
 // One calibration tensor through the plain float layers of `m` (a QAT layer: its inner layer, whatever the QAT switch says), every
 // Linear twin and every static conv twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
-// A BasicBlock's two twins lie inline in the enclosing QSequential (quantize_checked): `qi` walks the twin's layers beside the model's.
+// A Sequential twin's layers are the twins of leaves_of(m), one each and in that order (quantize_checked made them so).
 // A BatchNorm2d runs in eval mode on its running pair whatever its flag says, by the kernel itself: the layer is only read.
 Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first) {
     auto plain = [](const Tensor &t) { return t.defined() ? Tensor::from_device(t.dptr(), t.shape()) : Tensor(); };
-    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
-        auto &qs = dynamic_cast<const QSequential &>(q);
+    const std::vector<const Module *> leaves = leaves_of(m);
+    if (auto *qs = dynamic_cast<const QSequential *>(&q)) {
+        TAPER_ASSERT(leaves.size() == qs->layers.size(), "calibrate: the twin is not this model's");
         Tensor h = x;
-        size_t qi = 0;
-        for (const auto &l : s->layers) {
-            if (auto *bb = dynamic_cast<const BasicBlock *>(l.get())) {
-                h = calibrate(bb->conv, *qs.layers[qi], h, first);
-                h = calibrate(bb->bn, *qs.layers[qi + 1], h, first);
-                qi += 2;
-            } else {
-                h = calibrate(*l, *qs.layers[qi++], h, first);
-            }
-        }
+        auto twin = qs->layers.begin();
+        for (const Module *l : leaves) h = calibrate(*l, **twin++, h, first);
         return h;
     }
-    if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) {
-        auto &qs = dynamic_cast<const QSequential &>(q);
-        return calibrate(bb->bn, *qs.layers[1], calibrate(bb->conv, *qs.layers[0], x, first), first);
-    }
-    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&m)) {
+    const Module &l = *leaves[0];
+    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) {
         TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == bn->num_features, "BatchNorm2d: expected a 4-D input [N, num_features, H, W]");
         const size_t hw = x.shape()[2] * x.shape()[3];
         TAPER_ASSERT(x.shape()[0] <= 0x7fffffffu && hw <= 0x7fffffffu, "BatchNorm2d: input too large");
@@ -535,20 +514,16 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
                               bn->fuse_relu ? 1 : 0));
         return y;
     }
-    const Linear *lin = dynamic_cast<const Linear *>(&m);
-    if (auto *ql = dynamic_cast<const QATLinear *>(&m)) lin = &ql->inner;
-    if (lin) {
+    if (auto *lin = dynamic_cast<const Linear *>(&l)) {
         dynamic_cast<const QLinear &>(q).act().observe(x, first);
         return x.linear(plain(lin->weight), plain(lin->bias), false);
     }
-    const Conv2d *cv = dynamic_cast<const Conv2d *>(&m);
-    if (auto *qc = dynamic_cast<const QATConv2d *>(&m)) cv = &qc->inner;
-    if (cv) {
+    if (auto *cv = dynamic_cast<const Conv2d *>(&l)) {
         auto &qcv = dynamic_cast<const QConv &>(q);
         if (qcv.is_static()) qcv.act().observe(x, first);
         return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
     }
-    return m.forward(x);
+    return l.forward(x);
 }
 
 }  // namespace
@@ -573,28 +548,29 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
     return quantize_checked(m, qt);
 }
 
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs, bool chain, bool per_channel) {
-    convs = convs || chain;
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, QuantizeOptions o) {
+    o.linears = true;
+    o.convs = o.convs || o.chain;
     // every refusal before anything is allocated
     check_quantizable(m, /*batchnorm=*/true);
     TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
     for (const Tensor &c : calib) TAPER_ASSERT(c.defined(), "quantize_static: undefined calibration tensor");
     std::vector<const Linear *> lins;
-    linears_of(m, &lins);
+    layers_of(m, &lins);
     const size_t max_k = (size_t)th_q8q8_max_k();
     const std::string above = " is above " + std::to_string(max_k) + ", where the int32 sum of the int8 product can overflow";
     for (const Linear *l : lins)
         TAPER_ASSERT(l->weight.shape()[1] <= max_k, "quantize_static: a Linear with in_features " + std::to_string(l->weight.shape()[1]) + above);
-    if (convs) {
+    if (o.convs) {
         std::vector<const Conv2d *> cvs;
-        convs_of(m, &cvs);
+        layers_of(m, &cvs);
         for (const Conv2d *c : cvs) {
             const Shape &ws = c->weight.shape();
             TAPER_ASSERT(!QConv::can_be_static(*c) || ws[1] * ws[2] * ws[3] <= max_k,
                          "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) + above);
         }
     }
-    auto q = quantize_checked(m, TH_QTYPE_INT8, true, convs, chain, per_channel);
+    auto q = quantize_checked(m, TH_QTYPE_INT8, o);
     NoGradScope no_grad;
     for (size_t i = 0; i < calib.size(); ++i) {
         Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)

@@ -529,8 +529,11 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // in that conv's epilogue (th_conv2d_q8q8_fwd_affine / _codes_affine) with its own or a following ReLU behind it, so a link of `chain` is
 // static conv, [BatchNorm2d], [ReLU], [one MaxPool2d], static conv; behind anything else it is one streaming launch
 // (th_channel_affine_fwd).  Calibration runs the float layer in eval mode; nothing of the source is modified.
-std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, bool convs = false, bool chain = false,
-                                                 bool per_channel = false);
+// (linears: set by quantize_static itself -- every Linear static; quantize() leaves all four off)
+struct QuantizeOptions {
+    bool linears = false, convs = false, chain = false, per_channel = false;
+};
+std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, QuantizeOptions o = {});
 
 // ---- quantization-aware training (src/quantization/{qat_config,qat_layers,qat_manager,fake_quantize}.rs) ----
 // A QAT layer trains its inner Linear / Conv2d against the rounding quantize() adds later: while QAT is active its forward runs on the

@@ -256,10 +256,17 @@ static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h,
     return nullptr;
 }
 
-// the kernel of a plan's NT
+// the kernel of a plan's NT and a call's form: one lookup over (nt, codes, pc, affine)
+using QcKernel = void (*)(QcArgs);
 template <bool CODES, bool PC, bool AFFINE>
-static auto qconv_kernel_of(int nt) {
+static QcKernel qconv_kernel_of(int nt) {
     return nt == 1 ? qconv_i8_kernel<1, CODES, PC, AFFINE> : nt == 2 ? qconv_i8_kernel<2, CODES, PC, AFFINE> : qconv_i8_kernel<4, CODES, PC, AFFINE>;
+}
+static QcKernel qconv_kernel(int nt, bool codes, bool pc, bool affine) {
+    static constexpr QcKernel (*of[2][2][2])(int) = {
+        {{qconv_kernel_of<false, false, false>, qconv_kernel_of<false, false, true>}, {qconv_kernel_of<false, true, false>, qconv_kernel_of<false, true, true>}},
+        {{qconv_kernel_of<true, false, false>, qconv_kernel_of<true, false, true>}, {qconv_kernel_of<true, true, false>, qconv_kernel_of<true, true, true>}}};
+    return of[codes][pc][affine](nt);
 }
 
 // ---- the max-pool on codes ----
@@ -337,33 +344,55 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
     return pack_conv_weight("th_pack_conv_weight_taper_int8", true, ctx, d_src, c_out, c_in, k_h, k_w, d_dst, cpitch);
 }
 
-// Both products: their checks (fn: the caller's name for the message), then the launch; the other form's outputs come null; pc:
-// d_wparams holds a pair per output channel; affine: d_affine holds {a, b} per output channel (null and unread otherwise)
-static int qconv_run(const char *fn, bool codes, bool pc, bool affine, const float *d_affine, th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h,
-                     int w, const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
-                     const float *d_bparams, int relu, float *d_y, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    TH_REQUIRE(ctx && d_qx && d_pixsum && d_xscale && d_qw && d_wparams && (codes ? d_yscale && d_qy : d_y != nullptr) && (!d_qb || d_bparams) && (!affine || d_affine),
-               "%s: null argument", fn);
+// One call of a product, as its entry point fills it: fn = the entry point's name for the messages; codes, pc, affine = its form (pc:
+// d_wparams holds a pair per output channel; affine: d_affine holds {a, b} per output channel); then the arguments in the prototypes'
+// order -- the 21 that every entry point takes (QC_SHARED), the f32 form's output, the codes form's four, d_affine.  What a form does not
+// take stays null / 0 and is not read.
+struct QcCall {
+    const char *fn;
+    bool codes, pc, affine;
+    th_ctx *ctx;
+    const int8_t *d_qx;
+    int cpitch;
+    const int *d_pixsum;
+    const float *d_xscale;
+    int n, c_in, h, w;
+    const int8_t *d_qw;
+    int c_out, k_h, k_w, s_h, s_w, pad_h, pad_w;
+    const float *d_wparams;
+    const int8_t *d_qb;
+    const float *d_bparams;
+    int relu;
+    float *d_y = nullptr;
+    const float *d_yscale = nullptr;
+    int8_t *d_qy = nullptr;
+    int cpitch_y = 0;
+    int *d_ypixsum = nullptr;
+    const float *d_affine = nullptr;
+};
+#define QC_SHARED ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu
+
+// both products: their checks, then the launch
+static int qconv_run(const QcCall &c) {
+    TH_REQUIRE(c.ctx && c.d_qx && c.d_pixsum && c.d_xscale && c.d_qw && c.d_wparams && (c.codes ? c.d_yscale && c.d_qy : c.d_y != nullptr) &&
+                   (!c.d_qb || c.d_bparams) && (!c.affine || c.d_affine),
+               "%s: null argument", c.fn);
     QcPlan p{};
-    const char *why = qconv_plan(n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, &p);
-    TH_REQUIRE(!why, "%s: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", fn, why, n, c_in, h, w, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w);
-    TH_REQUIRE((((uintptr_t)d_qx | (uintptr_t)d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", fn);
-    TH_REQUIRE(cpitch % 16 == 0 && cpitch >= c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", fn, cpitch, c_in);
-    if (codes) {
-        TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd%s)", fn, c_out,
-                   th_qconv_i8_chain_max_cout(), affine ? "_affine" : pc ? "_pc" : "");
-        TH_REQUIRE(((uintptr_t)d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", fn);
-        TH_REQUIRE(cpitch_y % 16 == 0 && cpitch_y >= c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", fn, cpitch_y, c_out);
+    const char *why = qconv_plan(c.n, c.c_in, c.h, c.w, c.c_out, c.k_h, c.k_w, c.s_h, c.s_w, c.pad_h, c.pad_w, &p);
+    TH_REQUIRE(!why, "%s: %s (n=%d c_in=%d %dx%d, c_out=%d k=%dx%d stride %dx%d pad %dx%d)", c.fn, why, c.n, c.c_in, c.h, c.w, c.c_out, c.k_h, c.k_w, c.s_h, c.s_w,
+               c.pad_h, c.pad_w);
+    TH_REQUIRE((((uintptr_t)c.d_qx | (uintptr_t)c.d_qw) & 15) == 0, "%s: the code pointers must be 16-byte aligned", c.fn);
+    TH_REQUIRE(c.cpitch % 16 == 0 && c.cpitch >= c.c_in, "%s: cpitch %d must be a multiple of 16 and at least c_in %d", c.fn, c.cpitch, c.c_in);
+    if (c.codes) {
+        TH_REQUIRE(p.tiles_n == 1, "%s: c_out %d is above %d, the channels one workgroup covers (a wider layer writes f32: th_conv2d_q8q8_fwd%s)", c.fn, c.c_out,
+                   th_qconv_i8_chain_max_cout(), c.affine ? "_affine" : c.pc ? "_pc" : "");
+        TH_REQUIRE(((uintptr_t)c.d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", c.fn);
+        TH_REQUIRE(c.cpitch_y % 16 == 0 && c.cpitch_y >= c.c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", c.fn, c.cpitch_y, c.c_out);
     }
-    if (n == 0) return 0;
-    const QcArgs a{d_qx, d_qw, d_pixsum, d_xscale, d_wparams, d_qb, d_bparams, d_y, d_yscale, d_qy, d_ypixsum, cpitch_y, p.win, cpitch, c_out,
-                   n * p.win.h_out * p.win.w_out, relu, p.tiles_n, affine ? d_affine : nullptr};
-    auto kernel = codes ? (pc ? qconv_kernel_of<true, true, false>(p.nt) : qconv_kernel_of<true, false, false>(p.nt))
-                        : (pc ? qconv_kernel_of<false, true, false>(p.nt) : qconv_kernel_of<false, false, false>(p.nt));
-    if (affine)
-        kernel = codes ? (pc ? qconv_kernel_of<true, true, true>(p.nt) : qconv_kernel_of<true, false, true>(p.nt))
-                       : (pc ? qconv_kernel_of<false, true, true>(p.nt) : qconv_kernel_of<false, false, true>(p.nt));
-    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, ctx->stream, a);
+    if (c.n == 0) return 0;
+    const QcArgs a{c.d_qx, c.d_qw, c.d_pixsum, c.d_xscale, c.d_wparams, c.d_qb, c.d_bparams, c.d_y, c.d_yscale, c.d_qy, c.d_ypixsum, c.cpitch_y, p.win, c.cpitch, c.c_out,
+                   c.n * p.win.h_out * p.win.w_out, c.relu, p.tiles_n, c.affine ? c.d_affine : nullptr};
+    hipLaunchKernelGGL(qconv_kernel(p.nt, c.codes, c.pc, c.affine), dim3(p.grid), dim3(256), 0, c.ctx->stream, a);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -371,8 +400,7 @@ static int qconv_run(const char *fn, bool codes, bool pc, bool affine, const flo
 int th_conv2d_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                        const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                        const float *d_bparams, int relu, float *d_y) {
-    return qconv_run("th_conv2d_q8q8_fwd", false, false, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
-                     d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
+    return qconv_run({"th_conv2d_q8q8_fwd", false, false, false, QC_SHARED, d_y});
 }
 
 int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
@@ -380,38 +408,34 @@ int th_qconv_i8_chain_max_cout(void) { return kQcChan * 4; }
 int th_conv2d_q8q8_fwd_codes(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                              const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                              const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes", true, false, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
-                     d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
+    return qconv_run({"th_conv2d_q8q8_fwd_codes", true, false, false, QC_SHARED, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum});
 }
 
 int th_conv2d_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                           const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                           const float *d_bparams, int relu, float *d_y) {
-    return qconv_run("th_conv2d_q8q8_fwd_pc", false, true, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams,
-                     d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
+    return qconv_run({"th_conv2d_q8q8_fwd_pc", false, true, false, QC_SHARED, d_y});
 }
 
 int th_conv2d_q8q8_fwd_codes_pc(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                                 const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                                 const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes_pc", true, true, false, nullptr, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w,
-                     d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
+    return qconv_run({"th_conv2d_q8q8_fwd_codes_pc", true, true, false, QC_SHARED, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum});
 }
 
 int th_conv2d_q8q8_fwd_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                               const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
                               const float *d_bparams, int relu, float *d_y, int per_channel, const float *d_affine) {
-    return qconv_run("th_conv2d_q8q8_fwd_affine", false, per_channel != 0, true, d_affine, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w,
-                     s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu, d_y, nullptr, nullptr, 0, nullptr);
+    return qconv_run({"th_conv2d_q8q8_fwd_affine", false, per_channel != 0, true, QC_SHARED, d_y, nullptr, nullptr, 0, nullptr, d_affine});
 }
 
 int th_conv2d_q8q8_fwd_codes_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
                                     const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                                     const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
                                     int per_channel, const float *d_affine) {
-    return qconv_run("th_conv2d_q8q8_fwd_codes_affine", true, per_channel != 0, true, d_affine, ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h,
-                     k_w, s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum);
+    return qconv_run({"th_conv2d_q8q8_fwd_codes_affine", true, per_channel != 0, true, QC_SHARED, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum, d_affine});
 }
+#undef QC_SHARED
 
 int th_maxpool2d_nhwc_int8(th_ctx *ctx, const int8_t *d_q, int n, int c, int h, int w, int cpitch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w,
                            int8_t *d_qy, int *d_ypixsum) {

@@ -644,3 +644,75 @@ def test_chained_twins_compute_the_float_models_function():
         err = float(np.abs(got - fl).max() / np.abs(fl).max())
         print(f"chained {name} twin vs the float model in eval mode: {err:.3e} of max |y| ({rec['err_over_scale']:.3e})")
         assert err <= 0.25, (name, err)
+
+
+# ---------------------------------------------------------------- 8: every kind of step in one Sequential
+ALL_SHAPE = (2, 2, 8, 8)
+
+
+def _all_kinds_model(rng):
+    """Every kind of step a Sequential twin resolves, the weight-only kind twice: a link through a folded BatchNorm2d, ReLU and pool; a
+    grouped conv and a 1x1 conv that stay weight-only (two slots of one dequantize workspace); a BatchNorm2d that runs alone; a nested
+    Sequential with a link inside and none across its boundary; a link across a BasicBlock's boundary; Linear + ReLU and a lone Linear."""
+    import taper_amd as T
+    pad = (1, 1)
+    bns = [T.BatchNorm2d(4), T.BatchNorm2d(8)]
+    model = T.Sequential([
+        T.Conv2d(2, 4, (3, 3), None, pad, seed=11), bns[0], T.ReLU(), T.MaxPool2d((2, 2), (2, 2)), T.Conv2dReLU(4, 8, (3, 3), None, pad, seed=12),
+        T.Conv2d(8, 8, (3, 3), None, pad, groups=2, seed=13), T.ReLU(),
+        bns[1],
+        T.Sequential([T.Conv2d(8, 4, (3, 3), None, pad, seed=14), T.Conv2d(4, 8, (3, 3), None, pad, seed=15)]),
+        T.Conv2d(8, 4, (1, 1), seed=16),
+        T.BasicBlock(4, 8, seed=17), T.Conv2d(8, 4, (3, 3), None, pad, seed=18),
+        T.Flatten(1), T.Linear(4 * 4 * 4, 8, True, seed=19), T.ReLU(), T.Linear(8, 4, True, seed=20)])
+    for bn in bns:
+        _set_bn(bn, rng)
+    _set_block_stats(model, rng, ALL_SHAPE)
+    return model
+
+
+def test_every_kind_of_step_in_one_sequential():
+    """Chained and unchained twins of the model above agree on every output bit and on everything they report.  The links: conv ->
+    BatchNorm2d -> ReLU -> pool -> Conv2dReLU, the two convs of the nested Sequential, the BasicBlock's conv -> the conv behind the block
+    (3).  Static layers: 6 convs and 2 Linear; 8 convs and 2 Linear pack 20 tensors; 3 frozen BatchNorm2d."""
+    import taper_amd as T
+    rng = np.random.default_rng(97)
+    model = _all_kinds_model(rng)
+    calib = [T.Tensor(a, ALL_SHAPE) for a in (rng.standard_normal(ALL_SHAPE).astype(f32), (1.5 * rng.standard_normal(ALL_SHAPE)).astype(f32))]
+    x = rng.standard_normal(ALL_SHAPE).astype(f32)
+    far = (3 * 1.5 * 4 * np.sign(x)).astype(f32)          # beyond the calibration range: the first codes saturate
+    far[:, :, :, ::3] = x[:, :, :, ::3]
+    T.Tape.reset()
+
+    def check(pcf):      # (a function: no twin of one pass is alive in the next, where the pool's occupancy is compared)
+        chain, plain = _static_ex(model, calib, pcf | CONVS | CHAIN), _static_ex(model, calib, pcf | CONVS)
+        assert chain.chain_links() == 3 and plain.chain_links() == 0
+        assert chain.act_scales().shape == (8,)
+        np.testing.assert_array_equal(_bits(chain.act_scales()), _bits(plain.act_scales()))
+        assert chain.storage_bytes() == plain.storage_bytes()
+        assert len(chain.affines()) == len(plain.affines()) == 3
+        for a, b in zip(chain.affines(), plain.affines()):
+            np.testing.assert_array_equal(_bits(a), _bits(b))
+        assert len(chain.tensors()) == len(plain.tensors()) == 20
+        for i, ((ka, ca, pa), (kb, cb, pb)) in enumerate(zip(chain.tensors(), plain.tensors())):
+            assert ka == kb and isinstance(pa, np.ndarray) == isinstance(pb, np.ndarray), i
+            np.testing.assert_array_equal(ca, cb, err_msg=f"tensor {i}")
+            np.testing.assert_array_equal(_bits(np.asarray(pa, f32)), _bits(np.asarray(pb, f32)), err_msg=f"tensor {i}")
+        assert any(isinstance(p, np.ndarray) for _, _, p in chain.tensors()) == bool(pcf)
+        before = _pool_in_use()
+        for data in (x, far):
+            outs = []
+            for q in (chain, plain):
+                y = q(T.Tensor(data, ALL_SHAPE))
+                outs.append(y.data())
+                del y
+                assert _pool_in_use() == before
+            assert outs[0].shape == (2, 4) and np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
+            np.testing.assert_array_equal(_bits(outs[0]), _bits(outs[1]), err_msg=f"flags {pcf}")
+            for q, full in zip((chain, plain), outs):
+                alone = q(T.Tensor(data[:1], (1,) + ALL_SHAPE[1:])).data()
+                np.testing.assert_array_equal(_bits(alone[0]), _bits(full[0]), err_msg="image 0 alone")
+                assert _pool_in_use() == before
+
+    check(0)
+    check(PER_CHANNEL)
