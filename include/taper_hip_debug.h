@@ -34,6 +34,19 @@ int th_debug_last_conv_config(th_ctx *ctx, int *out6);
  * out6[4] = images per unit) when the launch has at least one unit per two CUs, the 128-pixel kernel otherwise; 0: never;
  * 1: whenever the shape fits it. */
 int th_debug_set_conv_img(th_ctx *ctx, int mode);
+/* what a 3x3 convolution entry point would do with this shape -- pure host code, no context, the function the launch itself consumes
+ * (csrc/conv_plan.h: ConvPlan, copied out field by field).  op: 0 th_conv3x3_fwd, 1 _pool2_fwd, 2 _gap_fwd, 3 _bwd_input, 4 _bwd_weight;
+ * relu_bias = relu + 2 * (bias present) (ops 0 - 2); accumulate: ops 3 and 4; w_misalign_bytes: the weight pointer (op 4: the gradient's)
+ * off a 16-byte boundary; img_mode as th_debug_set_conv_img.  out32 = {family (0: the call is refused before any allocation or launch;
+ * 1 conv1 / conv1_pool2; 2 conv3x3_kernel; 3 conv3x3_rows_kernel; 4 conv3x3_mfma_kernel; 5 conv3x3_img_kernel; 6 conv_layer_chain_kernel;
+ * 7 conv3x3_wgrad_mfma_kernel; 8 conv_wgrad_img_kernel; 9 conv1_wgrad_kernel; 10 conv3x3_bwd_weight_kernel), CT (wgrad image form: CTW),
+ * ACC, CIT, POOL, WH, DMA, TPW, compiled WP, compiled CIS, PX, 1 if the weights go through conv3x3_prep_weights (0: read in place),
+ * images per workgroup, rows per band, bands, grid x, y, z, tile_store, gap, LDS bytes, the LDS limit of that launch, chain post, chain LIN,
+ * G, partial slabs (0: none), reduce ending (0 none; 1 slab_sum_kernel; 2 th_colsum; 3 th_colsum_accum; 4 th_colsum + wgrad_scatter_kernel),
+ * PQ (wgrad image form: PS), pixel blocks, slab channel pitch, refusal (1 plane over the LDS tile, 2 no gap plan, 3 no pool plan,
+ * 4 pad, 5 weight-gradient limits), h_out, w_out}.  Nonsense geometry is an error that names it; a shape the entry point refuses is family 0. */
+int th_debug_conv3x3_plan(int op, int n, int c_in, int h, int w, int c_out, int pad, int weight_layout, int relu_bias, int accumulate,
+                          int w_misalign_bytes, int img_mode, int *out32);
 /* what th_linear_q8_fwd (qtype TH_QTYPE_INT8) / th_linear_h16_fwd (TH_QTYPE_F16) would do with this shape and these pointers
  * (x / w: bytes off a 16-byte boundary) -- pure host code, no context, the function the launch itself consumes: out8 = {1 if the weight-
  * streaming kernel takes it (0: the dequantize workspace and th_linear_fwd; the rest is 0 then), 1 if its vector-load instance, batch tile

@@ -13,6 +13,7 @@
 // (pass of 8 channels; k-step s = tap s % 9 of channels 4 (s / 9) + lane group), bias after the sum, ReLU, strict-> pooling maxima,
 // 16-lane plane sums with the same shuffle tree -- the chain's outputs are bit-identical to the layered path's.
 #include "tail_dev.h"
+#include "conv_plan.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -1711,39 +1712,48 @@ bool rt_plan(int c_in, int h, int w, const th_conv_stage *stages, int n_stages, 
 }  // namespace
 
 namespace th {
-// th_conv3x3_fwd / _pool2_fwd / _gap_fwd (conv_mfma.hip: conv3x3_mfma_launch) ask here first.  1: launched; 0: not one of the compiled geometries
-// (or fewer images than half the CUs: one image per workgroup); -1: error
-int conv_layer_chain_launch(th_ctx *ctx, const float *x, const float *w, const float *bias, float *y, float *cnt, int n, int c_in, int hw, int c_out,
-                            int post, bool linear) {
-    if (n < kNumCU / 2) return 0;
-    LayerChainArgs a{x, w, bias, y, cnt, n};
-    const dim3 grid(n < kNumCU ? n : kNumCU);
-#define TH_LC_(S_, CI_, CO_, P_, L_)                                                                                                     \
-    do {                                                                                                                                 \
-        constexpr int fl = (CI_ * ch_cis(S_ + 2) > CO_ * ch_tile_ld(S_ * S_) ? CI_ * ch_cis(S_ + 2) : CO_ * ch_tile_ld(S_ * S_));         \
-        TH_SET_MAX_LDS(ctx, (conv_layer_chain_kernel<S_, CI_, CO_, P_, L_>), fl * 4); \
-        hipLaunchKernelGGL((conv_layer_chain_kernel<S_, CI_, CO_, P_, L_>), grid, dim3(CH_NT), fl * 4, ctx->stream, a);                   \
-        if (hipGetLastError() != hipSuccess) return -1;                                                                                  \
-        return 1;                                                                                                                        \
-    } while (0)
-#define TH_LC(S_, CI_, CO_, P_) TH_LC_(S_, CI_, CO_, P_, false)
-    if (linear) {
-        // input gradients (no bias, no ReLU, the map written) of the four batch-256 layers: 64 -> 32 @14 and 128 -> 64 @7 ran at half their
-        // forward rate in the image-resident kernel (36 us each: 23.0 / 21.5 here)
-        if (post != 0) return 0;
-        if (hw == 14 && c_in == 64 && c_out == 32) TH_LC_(14, 64, 32, 0, true);
-        if (hw == 7 && c_in == 128 && c_out == 64) TH_LC_(7, 128, 64, 0, true);
-        if (hw == 28 && c_in == 32 && c_out == 32) TH_LC_(28, 32, 32, 0, true);
-        if (hw == 14 && c_in == 64 && c_out == 64) TH_LC_(14, 64, 64, 0, true);
-        return 0;
+// The one-stage chains: (S, C_IN, C_OUT, POST, LIN).  Forward layers of the two CNNs at batch 256, and the input gradients (LIN: no bias, no
+// ReLU, the map written) of the four batch-256 layers: 64 -> 32 @14 and 128 -> 64 @7 ran at half their forward rate in the image-resident
+// kernel (36 us each: 23.0 / 21.5 here)
+#define TH_LC_SHAPES(X)                                                                                                                  \
+    X(14, 64, 32, 0, true) X(7, 128, 64, 0, true) X(28, 32, 32, 0, true) X(14, 64, 64, 0, true)                                          \
+    X(28, 32, 32, 0, false) X(28, 32, 32, 1, false) X(14, 32, 64, 0, false) X(14, 32, 64, 1, false)                                      \
+    X(14, 64, 64, 0, false) X(14, 64, 64, 1, false) X(7, 64, 128, 0, false) X(7, 64, 128, 2, false)
+constexpr int lc_lds_floats(int s, int ci, int co) {
+    return ci * ch_cis(s + 2) > co * ch_tile_ld(s * s) ? ci * ch_cis(s + 2) : co * ch_tile_ld(s * s);
+}
+
+// th_conv3x3_fwd / _pool2_fwd / _gap_fwd / _bwd_input (conv_mfma.hip: conv3x3_mfma_plan) ask here first.  true: one of the compiled geometries
+// and at least as many images as half the CUs (one image per workgroup)
+bool conv_layer_chain_plan(int n, int c_in, int hw, int c_out, int post, bool linear, ConvPlan *p) {
+    if (n < kNumCU / 2) return false;
+#define TH_LC_PLAN(S_, CI_, CO_, P_, L_)                                                                                                 \
+    if (hw == S_ && c_in == CI_ && c_out == CO_ && post == P_ && linear == L_) {                                                         \
+        p->family = CONV_F_CHAIN; p->ct = CO_ / 16; p->post = P_; p->lin = L_ ? 1 : 0;   /* (pool, gap: the caller's) */              \
+        p->img_t = 1; p->grid_x = n < kNumCU ? n : kNumCU; p->grid_y = p->grid_z = 1;                                                    \
+        p->lds = lc_lds_floats(S_, CI_, CO_) * 4; p->lds_limit = 160 << 10;                                                              \
+        return true;                                                                                                                     \
     }
-    if (hw == 28 && c_in == 32 && c_out == 32) { if (post == 0) TH_LC(28, 32, 32, 0); if (post == 1) TH_LC(28, 32, 32, 1); }
-    if (hw == 14 && c_in == 32 && c_out == 64) { if (post == 0) TH_LC(14, 32, 64, 0); if (post == 1) TH_LC(14, 32, 64, 1); }
-    if (hw == 14 && c_in == 64 && c_out == 64) { if (post == 0) TH_LC(14, 64, 64, 0); if (post == 1) TH_LC(14, 64, 64, 1); }
-    if (hw == 7 && c_in == 64 && c_out == 128) { if (post == 0) TH_LC(7, 64, 128, 0); if (post == 2) TH_LC(7, 64, 128, 2); }
-#undef TH_LC
-#undef TH_LC_
-    return 0;
+    TH_LC_SHAPES(TH_LC_PLAN)
+#undef TH_LC_PLAN
+    return false;
+}
+
+// the chain instance a plan of family CONV_F_CHAIN names.  0: launched; -1: error
+int conv_layer_chain_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *w, const float *bias, float *y, float *cnt, int n, int c_in,
+                            int hw, int c_out) {
+    LayerChainArgs a{x, w, bias, y, cnt, n};
+    const dim3 grid(p.grid_x);
+#define TH_LC_RUN(S_, CI_, CO_, P_, L_)                                                                                                  \
+    if (hw == S_ && c_in == CI_ && c_out == CO_ && p.post == P_ && (p.lin != 0) == L_) {                                                 \
+        constexpr int fl = lc_lds_floats(S_, CI_, CO_);                                                                                  \
+        TH_SET_MAX_LDS(ctx, (conv_layer_chain_kernel<S_, CI_, CO_, P_, L_>), fl * 4);                                                    \
+        hipLaunchKernelGGL((conv_layer_chain_kernel<S_, CI_, CO_, P_, L_>), grid, dim3(CH_NT), fl * 4, ctx->stream, a);                   \
+        return hipGetLastError() != hipSuccess ? -1 : 0;                                                                                 \
+    }
+    TH_LC_SHAPES(TH_LC_RUN)
+#undef TH_LC_RUN
+    return -1;
 }
 }  // namespace th
 

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "conv_plan.h"
 
 namespace th {
 
@@ -808,8 +809,8 @@ bool conv3x3_mfma_pool_supported(int c_in, int h, int w, int pad) {   // whole 2
 // -1: the image-resident kernel takes launches with >= one unit per two CUs; 0: never; 1: whenever a plan exists
 // (th_debug_set_conv_img: the parity tests force both kernels onto the same shapes)
 int g_conv_img_mode = -1;
-int conv_layer_chain_launch(th_ctx *ctx, const float *x, const float *w, const float *bias, float *y, float *cnt, int n, int c_in, int hw, int c_out,
-                            int post, bool linear);   // conv_chain.hip
+int conv_layer_chain_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *w, const float *bias, float *y, float *cnt, int n, int c_in,
+                            int hw, int c_out);   // conv_chain.hip
 
 // launch configuration of this thread's most recent matrix-core convolution (th_debug_last_conv_config)
 thread_local int t_last_conv_cfg[6] = {0, 0, 0, 0, 0, 0};
@@ -819,89 +820,43 @@ bool conv3x3_gap_supported(int n, int c_in, int h, int w_in, int c_out, int pad)
     return c_in >= MF_CI && c_out % 4 == 0 && conv_img_plan(n, c_in, h, w_in, c_out, pad, true, &pl, true);
 }
 
-int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, int w_cols, const float *bias, float *y, int n,
-                        int c_in, int h, int w_in, int c_out, int pad, int relu, bool accum, bool pool, float *gap_cnt, bool gap) {
-    TH_REQUIRE(w_ld % 4 == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_mfma: weight rows must be 16-byte aligned");
+// Which matrix-core kernel takes y (+)= conv3x3(x, w) [+ bias, relu] with weights [9*c_in][w_ld], columns [0, w_cols) readable, and every
+// template parameter, tiling and grid of its launch
+void conv3x3_mfma_plan(ConvPlan *p, int n, int c_in, int h, int w_in, int c_out, int pad, int w_ld, int w_cols, bool relu, bool has_bias,
+                       bool accum, bool pool, bool gap, int img_mode) {
+    const int h_out = h + 2 * pad - 2, w_out = w_in + 2 * pad - 2;
+    p->h_out = h_out; p->w_out = w_out;
+    p->acc = accum && !pool; p->pool = pool; p->gap = gap;
     // the batch-256 layers of the reference CNN as one-stage chains (conv_chain.hip: conv_layer_chain_kernel; same bits): the taper slab read in
     // place, ReLU on, pad 1, default kernel choice only (th_debug_set_conv_img forces the kernels below)
-    // (+ the plain sum -- no bias, no ReLU: an input gradient -- for the shapes conv_layer_chain_launch lists)
-    const bool lin = !relu && !bias && !pool && !gap;
-    if (g_conv_img_mode == -1 && !accum && (relu || lin) && pad == 1 && h == w_in && w_ld == c_out && w_cols == c_out) {
-        const int rc = conv_layer_chain_launch(ctx, x, w, bias, y, gap ? gap_cnt : nullptr, n, c_in, h, c_out, gap ? 2 : (pool ? 1 : 0), lin);
-        if (rc < 0) { th::set_error("conv_layer_chain_kernel: launch failed"); return 1; }
-        if (rc == 1) {
-            t_last_conv_cfg[0] = c_out / 16; t_last_conv_cfg[1] = 8; t_last_conv_cfg[2] = 8;   // 8: one layer through the chain's compiled mapping
-            t_last_conv_cfg[3] = n < kNumCU ? n : kNumCU; t_last_conv_cfg[4] = 1; t_last_conv_cfg[5] = pool ? 1 : 0;
-            return 0;
+    // (+ the plain sum -- no bias, no ReLU: an input gradient -- for the LIN shapes of the chain's list)
+    const bool lin = !relu && !has_bias && !pool && !gap;
+    if (img_mode == -1 && !accum && (relu || lin) && pad == 1 && h == w_in && w_ld == c_out && w_cols == c_out &&
+        conv_layer_chain_plan(n, c_in, h, c_out, gap ? 2 : (pool ? 1 : 0), lin, p))
+        return;
+    // launches with at least a unit per two CUs take the image-resident kernel (th_debug_set_conv_img 0 / 1: never / whenever it fits)
+    ConvImgPlan pl{};
+    if ((img_mode != 0 || gap) && !accum && c_in >= MF_CI && conv_img_plan(n, c_in, h, w_in, c_out, pad, pool, &pl, gap) &&
+        (gap || img_mode == 1 || (long)pl.n_groups * pl.n_co >= kNumCU / 2)) {
+        p->family = CONV_F_IMG;
+        p->ct = pl.ct; p->tpw = pl.tpw; p->img_t = pl.img_t; p->tile_store = pl.tile_store;
+        p->grid_x = 8 * ceil_div(pl.n_groups, 8) * pl.n_co; p->grid_y = p->grid_z = 1;
+        p->lds = (int)pl.lds; p->lds_limit = 150 << 10;
+        // instances with the patch geometry compiled in (the batch-256 layers of the two CNNs); everything else takes the generic ones
+        const int wp_ = w_out + 2, cis_ = pl.img_t * (h_out + 2) * wp_;
+        if ((pl.ct == 2 && pl.tpw == 13 && wp_ == 30 && cis_ == 900) ||       // 28x28, one image
+            (pl.ct == 1 && pl.tpw == 7 && wp_ == 16 && cis_ == 1024) ||       // 14x14, four images
+            (pl.ct == 1 && pl.tpw == 4 && wp_ == 9 && cis_ == 648)) {         // 7x7, eight images
+            p->wp = wp_; p->cis = cis_;
         }
+        return;
     }
-    {
-        // launches with at least a unit per two CUs take the image-resident kernel (th_debug_set_conv_img 0 / 1: never / whenever it fits)
-        const int img_env = g_conv_img_mode;
-        ConvImgPlan pl{};
-        if ((img_env != 0 || gap) && !accum && c_in >= MF_CI && conv_img_plan(n, c_in, h, w_in, c_out, pad, pool, &pl, gap) &&
-            (gap || img_env == 1 || (long)pl.n_groups * pl.n_co >= kNumCU / 2)) {
-            ConvImgArgs g{};
-            g.x = x; g.w = w; g.bias = bias; g.y = y;
-            g.n = n; g.c_in = c_in; g.h = h; g.w_in = w_in; g.c_out = c_out; g.pad = pad;
-            g.h_out = h + 2 * pad - 2; g.w_out = w_in + 2 * pad - 2; g.w_ld = w_ld; g.w_cols = w_cols;
-            g.img_t = pl.img_t; g.n_groups = pl.n_groups; g.n_co = pl.n_co; g.relu = relu;
-            g.gap = gap ? 1 : 0; g.gap_cnt = gap_cnt; g.tile_store = pl.tile_store;
-            {   // staging plans of this geometry: built on device the first time, kept with the ctx
-                const int pgs = pl.ct == 2 ? 4 : 8, n_goff = 512 * IM_PPT, n_pix = pgs * pl.tpw * 16;
-                const std::array<int, 8> key{h, w_in, pad, c_in, pl.img_t, pgs, pl.tpw, 0};
-                auto it = ctx->conv_plans.find(key);
-                if (it == ctx->conv_plans.end()) {
-                    void *tab = nullptr;
-                    TH_HIP(hipMalloc(&tab, (size_t)(n_goff + n_pix) * sizeof(int)));
-                    hipLaunchKernelGGL(conv_img_tables_kernel, dim3(ceil_div(n_goff + n_pix, 256)), dim3(256), 0, ctx->stream, (int *)tab,
-                                       (int *)tab + n_goff, n_goff, n_pix, c_in, h, w_in, pad, pl.img_t);
-                    TH_LAUNCH_CHECK();
-                    it = ctx->conv_plans.emplace(key, tab).first;
-                }
-                g.goff_tab = (const int *)it->second;
-                g.pix_tab = g.goff_tab + n_goff;
-            }
-            const dim3 grid(8 * ceil_div(pl.n_groups, 8) * pl.n_co);
-#define TH_IMG2(CTV, TPWV, PL, WPV, CISV)                                                                                   \
-            { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds); \
-              hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>), grid, dim3(512), pl.lds, ctx->stream, g); }
-            // instances with the patch geometry compiled in (the batch-256 layers of the two CNNs); everything else takes the generic ones
-#define TH_IMG_GEO(CTV, TPWV, WPV, CISV) { if (pool) TH_IMG2(CTV, TPWV, true, WPV, CISV) else TH_IMG2(CTV, TPWV, false, WPV, CISV) }
-#define TH_IMG(CTV, TPWV) TH_IMG_GEO(CTV, TPWV, 0, 0)
-            const int wp_ = g.w_out + 2, cis_ = pl.img_t * (g.h_out + 2) * wp_;
-            bool special = true;
-            if (pl.ct == 2 && pl.tpw == 13 && wp_ == 30 && cis_ == 900) TH_IMG_GEO(2, 13, 30, 900)          // 28x28, one image
-            else if (pl.ct == 1 && pl.tpw == 7 && wp_ == 16 && cis_ == 1024) TH_IMG_GEO(1, 7, 16, 1024)      // 14x14, four images
-            else if (pl.ct == 1 && pl.tpw == 4 && wp_ == 9 && cis_ == 648) TH_IMG_GEO(1, 4, 9, 648)          // 7x7, eight images
-            else {
-                special = false;
-                if (pl.ct == 2) {
-                    if (pl.tpw == 4) TH_IMG(2, 4) else if (pl.tpw == 7) TH_IMG(2, 7) else TH_IMG(2, 13)
-                } else {
-                    if (pl.tpw == 4) TH_IMG(1, 4) else if (pl.tpw == 7) TH_IMG(1, 7) else TH_IMG(1, 13)
-                }
-            }
-#undef TH_IMG_GEO
-#undef TH_IMG2
-#undef TH_IMG
-            t_last_conv_cfg[0] = pl.ct; t_last_conv_cfg[1] = special ? 4 : 2; t_last_conv_cfg[2] = pl.tpw;   // 2 / 4: the image-resident kernel, generic / compiled geometry
-            t_last_conv_cfg[3] = (int)grid.x; t_last_conv_cfg[4] = pl.img_t; t_last_conv_cfg[5] = pool ? 1 : 0;
-            TH_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    TH_REQUIRE(!gap, "conv3x3 + global average pool: no image-resident plan for this shape (th_conv3x3_gap_supported)");
-    ConvMfmaArgs a{};
-    a.x = x; a.w = w; a.bias = bias; a.y = y;
-    a.n = n; a.c_in = c_in; a.h = h; a.w_in = w_in; a.c_out = c_out; a.pad = pad;
-    a.h_out = h + 2 * pad - 2;
-    a.w_out = w_in + 2 * pad - 2;
-    a.w_ld = w_ld; a.w_cols = w_cols;
+    if (gap) { p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_GAP; return; }
+    p->family = CONV_F_MFMA;
     const int cit = c_in == 1 ? 1 : MF_CI;
-    conv_mfma_plan(a.h_out, a.w_out, n, &a.img_t, &a.rows_t, cit, pool);
-    a.bands = ceil_div(a.h_out, a.rows_t);
-    a.relu = relu;
+    p->cit = cit;
+    conv_mfma_plan(h_out, w_out, n, &p->img_t, &p->rows_t, cit, pool);
+    p->bands = ceil_div(h_out, p->rows_t);
     const int co_tiles = ceil_div(c_out, 16);
     // <= 64 output channels per workgroup: 32 accumulator + 18 prefetch VGPRs keep 3 workgroups per CU,
     // and wide layers get twice the workgroups (conv5 of the reference CNN: 232 instead of 116)
@@ -909,33 +864,115 @@ int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, i
     // fewer than 1.5 workgroups per CU (conv5 of the reference CNN: 7x7 maps, 232 workgroups): nothing overlaps a
     // workgroup's staging / barriers -- halve the channel block instead (measured 45.2 -> 40.5 us; it costs 7-9 us
     // on the 14x14 layers, which have 430 workgroups)
-    if (ct == 4 && (long)ceil_div(n, a.img_t) * a.bands * ceil_div(c_out, 64) < 384) ct = 2;
-    a.co_b = ct * 16;
-    const size_t patch_n = (size_t)cit * a.img_t * (a.rows_t + 2) * (a.w_out + 2);
-    size_t lds = (((patch_n + 4) & ~(size_t)3) + (size_t)((cit * 9 + 3) / 4 * 4) * a.co_b) * sizeof(float);
+    if (ct == 4 && (long)ceil_div(n, p->img_t) * p->bands * ceil_div(c_out, 64) < 384) ct = 2;
+    p->ct = ct;
+    const int co_b = ct * 16;
+    const size_t patch_n = (size_t)cit * p->img_t * (p->rows_t + 2) * (w_out + 2);
+    size_t lds = (((patch_n + 4) & ~(size_t)3) + (size_t)((cit * 9 + 3) / 4 * 4) * co_b) * sizeof(float);
     // whole 8-channel blocks, plain (non-accumulating) output: operands go global -> LDS directly, two LDS stages
     const bool dma = cit == MF_CI && c_in % MF_CI == 0 && !accum && ct >= 2 &&
-                     (long)a.img_t * c_in * h * w_in < (1L << 28) && (long)9 * c_in * w_ld < (1L << 28);
+                     (long)p->img_t * c_in * h * w_in < (1L << 28) && (long)9 * c_in * w_ld < (1L << 28);
     if (dma) lds *= 2;
-    if (pool) lds = std::max(lds, (size_t)a.co_b * ((size_t)(a.img_t * a.rows_t * a.w_out) | 1) * sizeof(float));   // the epilogue tile
-    dim3 grid(ceil_div(n, a.img_t) * a.bands, ceil_div(c_out, a.co_b));
+    if (pool) lds = std::max(lds, (size_t)co_b * ((size_t)(p->img_t * p->rows_t * w_out) | 1) * sizeof(float));   // the epilogue tile
+    p->dma = dma;
+    p->lds = (int)lds; p->lds_limit = 64 << 10;
+    p->grid_x = ceil_div(n, p->img_t) * p->bands; p->grid_y = ceil_div(c_out, co_b); p->grid_z = 1;
+    // launches with < 3 workgroups per CU: 8 waves per workgroup (see WH; 14x14 layers 38.3 / 62.5 -> 34.4 / 56.5 us, 7x7: 40.0 -> 36.8 us;
+    // the 28x28 layer has 1792 workgroups and gains nothing)
+    // (with LDS-DMA staging there is no per-pass staging work left for extra waves to hide: 4 waves measure 2-6 % faster on those layers)
+    p->wh = (ct >= 2 && !dma && (long)p->grid_x * p->grid_y < 768) ? 2 : 1;
+}
+
+// launches what conv3x3_mfma_plan chose (p.family CONV_F_CHAIN, CONV_F_IMG or CONV_F_MFMA)
+int conv3x3_mfma_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *w, int w_ld, int w_cols, const float *bias, float *y, int n,
+                        int c_in, int h, int w_in, int c_out, int pad, int relu, float *gap_cnt) {
+    TH_REQUIRE(w_ld % 4 == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_mfma: weight rows must be 16-byte aligned");
+    TH_REQUIRE(p.family != CONV_F_REFUSED || p.refused != CONV_REFUSED_GAP,
+               "conv3x3 + global average pool: no image-resident plan for this shape (th_conv3x3_gap_supported)");
+    const bool pool = p.pool != 0, gap = p.gap != 0;
+    if (p.family == CONV_F_CHAIN) {
+        if (conv_layer_chain_launch(ctx, p, x, w, bias, y, gap ? gap_cnt : nullptr, n, c_in, h, c_out)) {
+            th::set_error("conv_layer_chain_kernel: launch failed");
+            return 1;
+        }
+        t_last_conv_cfg[0] = c_out / 16; t_last_conv_cfg[1] = 8; t_last_conv_cfg[2] = 8;   // 8: one layer through the chain's compiled mapping
+        t_last_conv_cfg[3] = p.grid_x; t_last_conv_cfg[4] = 1; t_last_conv_cfg[5] = pool ? 1 : 0;
+        return 0;
+    }
+    if (p.family == CONV_F_IMG) {
+        ConvImgArgs g{};
+        g.x = x; g.w = w; g.bias = bias; g.y = y;
+        g.n = n; g.c_in = c_in; g.h = h; g.w_in = w_in; g.c_out = c_out; g.pad = pad;
+        g.h_out = p.h_out; g.w_out = p.w_out; g.w_ld = w_ld; g.w_cols = w_cols;
+        g.img_t = p.img_t; g.n_groups = ceil_div(n, p.img_t); g.n_co = ceil_div(c_out, 16 * p.ct); g.relu = relu;
+        g.gap = gap ? 1 : 0; g.gap_cnt = gap_cnt; g.tile_store = p.tile_store;
+        {   // staging plans of this geometry: built on device the first time, kept with the ctx
+            const int pgs = p.ct == 2 ? 4 : 8, n_goff = 512 * IM_PPT, n_pix = pgs * p.tpw * 16;
+            const std::array<int, 8> key{h, w_in, pad, c_in, p.img_t, pgs, p.tpw, 0};
+            auto it = ctx->conv_plans.find(key);
+            if (it == ctx->conv_plans.end()) {
+                void *tab = nullptr;
+                TH_HIP(hipMalloc(&tab, (size_t)(n_goff + n_pix) * sizeof(int)));
+                hipLaunchKernelGGL(conv_img_tables_kernel, dim3(ceil_div(n_goff + n_pix, 256)), dim3(256), 0, ctx->stream, (int *)tab,
+                                   (int *)tab + n_goff, n_goff, n_pix, c_in, h, w_in, pad, p.img_t);
+                TH_LAUNCH_CHECK();
+                it = ctx->conv_plans.emplace(key, tab).first;
+            }
+            g.goff_tab = (const int *)it->second;
+            g.pix_tab = g.goff_tab + n_goff;
+        }
+        const dim3 grid(p.grid_x);
+        const size_t lds = (size_t)p.lds;
+#define TH_IMG2(CTV, TPWV, PL, WPV, CISV)                                                                                   \
+        { (void)hipFuncSetAttribute((const void *)conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+          hipLaunchKernelGGL((conv3x3_img_kernel<CTV, TPWV, PL, WPV, CISV>), grid, dim3(512), lds, ctx->stream, g); }
+#define TH_IMG_GEO(CTV, TPWV, WPV, CISV) { if (pool) TH_IMG2(CTV, TPWV, true, WPV, CISV) else TH_IMG2(CTV, TPWV, false, WPV, CISV) }
+#define TH_IMG(CTV, TPWV) TH_IMG_GEO(CTV, TPWV, 0, 0)
+        const bool special = p.wp != 0;
+        if (special) {
+            if (p.wp == 30) TH_IMG_GEO(2, 13, 30, 900)          // 28x28, one image
+            else if (p.wp == 16) TH_IMG_GEO(1, 7, 16, 1024)     // 14x14, four images
+            else TH_IMG_GEO(1, 4, 9, 648)                       // 7x7, eight images
+        } else if (p.ct == 2) {
+            if (p.tpw == 4) TH_IMG(2, 4) else if (p.tpw == 7) TH_IMG(2, 7) else TH_IMG(2, 13)
+        } else {
+            if (p.tpw == 4) TH_IMG(1, 4) else if (p.tpw == 7) TH_IMG(1, 7) else TH_IMG(1, 13)
+        }
+#undef TH_IMG_GEO
+#undef TH_IMG2
+#undef TH_IMG
+        t_last_conv_cfg[0] = p.ct; t_last_conv_cfg[1] = special ? 4 : 2; t_last_conv_cfg[2] = p.tpw;   // 2 / 4: the image-resident kernel, generic / compiled geometry
+        t_last_conv_cfg[3] = (int)grid.x; t_last_conv_cfg[4] = p.img_t; t_last_conv_cfg[5] = pool ? 1 : 0;
+        TH_LAUNCH_CHECK();
+        return 0;
+    }
+    TH_REQUIRE(p.family == CONV_F_MFMA, "conv3x3_mfma: not a matrix-core plan");
+    ConvMfmaArgs a{};
+    a.x = x; a.w = w; a.bias = bias; a.y = y;
+    a.n = n; a.c_in = c_in; a.h = h; a.w_in = w_in; a.c_out = c_out; a.pad = pad;
+    a.h_out = p.h_out;
+    a.w_out = p.w_out;
+    a.w_ld = w_ld; a.w_cols = w_cols;
+    a.img_t = p.img_t; a.rows_t = p.rows_t;
+    a.bands = p.bands;
+    a.relu = relu;
+    a.co_b = p.ct * 16;
+    const size_t lds = (size_t)p.lds;
+    const dim3 grid(p.grid_x, p.grid_y);
+    const bool dma = p.dma != 0, wh2 = p.wh == 2;
 #define TH_MF(CTV, ACC, PL, WHV)                                                                                                   \
-    if (cit == 1) hipLaunchKernelGGL((conv3x3_mfma_kernel<CTV, ACC, 1, PL, WHV>), grid, dim3(256 * WHV), lds, ctx->stream, a);     \
+    if (p.cit == 1) hipLaunchKernelGGL((conv3x3_mfma_kernel<CTV, ACC, 1, PL, WHV>), grid, dim3(256 * WHV), lds, ctx->stream, a);     \
     else if (dma && !ACC && CTV >= 2) hipLaunchKernelGGL((conv3x3_mfma_kernel<(CTV >= 2 ? CTV : 2), false, MF_CI, PL, WHV, true>), grid, dim3(256 * WHV), lds, ctx->stream, a); \
     else hipLaunchKernelGGL((conv3x3_mfma_kernel<CTV, ACC, MF_CI, PL, WHV>), grid, dim3(256 * WHV), lds, ctx->stream, a);
 #define TH_MF_CT(ACC, PL)                                                       \
-    switch (ct) {                                                               \
+    switch (p.ct) {                                                             \
         case 4: if (wh2) { TH_MF(4, ACC, PL, 2) } else { TH_MF(4, ACC, PL, 1) } break;   \
         case 2: if (wh2) { TH_MF(2, ACC, PL, 2) } else { TH_MF(2, ACC, PL, 1) } break;   \
         default: TH_MF(1, ACC, PL, 1) break;                                    \
     }
-    // launches with < 3 workgroups per CU: 8 waves per workgroup (see WH; 14x14 layers 38.3 / 62.5 -> 34.4 / 56.5 us, 7x7: 40.0 -> 36.8 us;
-    // the 28x28 layer has 1792 workgroups and gains nothing)
-    // (with LDS-DMA staging there is no per-pass staging work left for extra waves to hide: 4 waves measure 2-6 % faster on those layers)
-    const bool wh2 = ct >= 2 && !dma && (long)grid.x * grid.y < 768;
-    t_last_conv_cfg[0] = ct; t_last_conv_cfg[1] = (dma && !accum && ct >= 2 && cit != 1) ? 1 : 0; t_last_conv_cfg[2] = wh2 ? 2 : 1;
+    t_last_conv_cfg[0] = p.ct; t_last_conv_cfg[1] = dma ? 1 : 0; t_last_conv_cfg[2] = wh2 ? 2 : 1;
     t_last_conv_cfg[3] = (int)grid.x; t_last_conv_cfg[4] = (int)grid.y; t_last_conv_cfg[5] = pool ? 1 : 0;
-    if (pool) TH_MF_CT(false, true) else if (accum) TH_MF_CT(true, false) else TH_MF_CT(false, false)
+    if (pool) TH_MF_CT(false, true) else if (p.acc) TH_MF_CT(true, false) else TH_MF_CT(false, false)
 #undef TH_MF_CT
 #undef TH_MF
     TH_LAUNCH_CHECK();
@@ -1152,25 +1189,34 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float *__restrict__
     }
 }
 
-// part: [G][kt][co_ld] partial slabs -> gw
-int wgrad_reduce(th_ctx *ctx, const float *part, float *gw, int G, int kt, int c_out, int co_ld, int layout, int accumulate) {
+// which ending adds G partial slabs [kt][co_ld] into gw (aligned: slabs and gw both on 16-byte boundaries)
+int wgrad_reduce_plan(int G, int kt, int c_out, int co_ld, int layout, bool accumulate, bool aligned) {
     // taper layout and unpadded channel rows: the ordered sum of the slabs IS the gradient as it lies in memory -- no scatter launch
     if (layout == 0 && co_ld == c_out) {
-        const int cols = kt * c_out;
-        if (cols % 4 == 0 && G >= 16 && ((((uintptr_t)part | (uintptr_t)gw) & 15) == 0)) {
-            hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(cols, 128)), dim3(256), 0, ctx->stream, part, gw, G, cols, accumulate);
-            TH_LAUNCH_CHECK();
-            return 0;
-        }
-        return accumulate ? th_colsum_accum(ctx, part, gw, G, cols) : th_colsum(ctx, part, gw, G, cols);
+        if ((kt * c_out) % 4 == 0 && G >= 16 && aligned) return CONV_R_SLAB_SUM;
+        return accumulate ? CONV_R_COLSUM_ACCUM : CONV_R_COLSUM;
     }
+    return CONV_R_SCATTER;
+}
+
+// part: [G][kt][co_ld] partial slabs -> gw
+int wgrad_reduce(th_ctx *ctx, const float *part, float *gw, int G, int kt, int c_out, int co_ld, int layout, int accumulate) {
+    const int ending = wgrad_reduce_plan(G, kt, c_out, co_ld, layout, accumulate != 0, ((((uintptr_t)part | (uintptr_t)gw) & 15) == 0));
+    if (ending == CONV_R_SLAB_SUM) {
+        const int cols = kt * c_out;
+        hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(cols, 128)), dim3(256), 0, ctx->stream, part, gw, G, cols, accumulate);
+        TH_LAUNCH_CHECK();
+        return 0;
+    }
+    if (ending == CONV_R_COLSUM_ACCUM) return th_colsum_accum(ctx, part, gw, G, kt * c_out);
+    if (ending == CONV_R_COLSUM) return th_colsum(ctx, part, gw, G, kt * c_out);
     void *tmp = nullptr;
     const int cols = kt * co_ld;
     if (th_malloc(ctx, (size_t)cols * sizeof(float), &tmp)) return 1;
-    if (int rc = th_colsum(ctx, part, (float *)tmp, G, cols)) return rc;
+    if (int rc = th_colsum(ctx, part, (float *)tmp, G, cols)) { th_free(ctx, tmp); return rc; }
     hipLaunchKernelGGL(wgrad_scatter_kernel, dim3(ew_grid((size_t)kt * c_out, 256)), dim3(256), 0, ctx->stream, (const float *)tmp, gw, kt,
                        c_out, co_ld, layout, accumulate);
-    TH_LAUNCH_CHECK();
+    if (hipGetLastError() != hipSuccess) { th_free(ctx, tmp); th::set_error("wgrad_scatter_kernel: launch failed"); return 1; }
     return th_free(ctx, tmp);
 }
 
@@ -1340,41 +1386,52 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_img_kernel(WgradImgArgs a) 
                 pp[(long)((g * 16 + 4 * g4 + e) * 9 + k) * C_OUT + (cb * CTW + j) * 16 + l16] = acc[k][j][e];
 }
 
-// 1: launched (slabs in *part_out, *n_slabs of them); 0: not one of the compiled shapes / batch too small
-static int conv_wgrad_img_launch(th_ctx *ctx, const float *x, const float *gy, int n, int c_in, int hw, int c_out, float **part_out, int *n_slabs) {
-    if (n < kNumCU / 2) return 0;
+// the compiled shapes of conv_wgrad_img_kernel: (S, C_IN, C_OUT, CTW, PS, IPW, BANDS)
+// (7 x 7, 64 -> 128, two images per workgroup: built and measured equal to the slab kernel -- 38.1 vs 38.5 us -- with twice the slab
+// bytes for wgrad_reduce: 49 pixels per image are too few steps for a [576][128] slab per workgroup.  Left to the slab kernel.)
+#define TH_WI_SHAPES(X)                                                                                                                  \
+    X(14, 32, 64, 2, 2, 1, 1)     /* (two pipelined bands: 24.9 vs 24.0 us) */                                                          \
+    X(14, 64, 64, 2, 1, 1, 1)     /* (two pipelined bands: 42.5 vs 39.4 us) */                                                          \
+    X(28, 32, 32, 2, 4, 1, 4)
+constexpr int wi_lds_floats(int s, int ci, int co, int ctw, int ps, int nb) {
+    const int wp = s + 2, nst = ((s / nb) * s + 3) / 4;
+    const int stage = (nb > 1 ? 2 : 1) * (ci * wi_pitch2((s / nb + 2) * wp) + co * wi_pitch2(4 * nst));
+    const int red = ps > 1 ? (8 / ps) * 9 * ctw * 256 : 0;
+    return stage > red ? stage : red;
+}
+
+// true: one of the compiled shapes on at least half a CU count of images
+static bool conv_wgrad_img_plan(int n, int c_in, int hw, int c_out, ConvPlan *p) {
+    if (n < kNumCU / 2) return false;
     const size_t xb = (size_t)n * c_in * hw * hw * 4, gb = (size_t)n * c_out * hw * hw * 4;
-    if (xb >= (1u << 31) || gb >= (1u << 31)) return 0;
-    WgradImgArgs a{x, gy, nullptr, n, 1, (unsigned)xb, (unsigned)gb};
-#define TH_WI(S_, CI_, CO_, CTW_, PS_, IPW_) TH_WIB(S_, CI_, CO_, CTW_, PS_, IPW_, 1)
-#define TH_WIB(S_, CI_, CO_, CTW_, PS_, IPW_, NB_)                                                                                        \
-    do {                                                                                                                                 \
-        a.ipw = IPW_;                                                                                                                    \
-        const int grid = ceil_div(n, IPW_);                                                                                              \
-        void *ws = nullptr;                                                                                                              \
-        if (th_malloc(ctx, (size_t)grid * 9 * CI_ * CO_ * sizeof(float), &ws)) return -1;                                                \
-        a.part = (float *)ws;                                                                                                            \
-        constexpr int wp_ = S_ + 2, nst_ = ((S_ / NB_) * S_ + 3) / 4;                                                                    \
-        constexpr int stage_ = (NB_ > 1 ? 2 : 1) * (CI_ * wi_pitch2((S_ / NB_ + 2) * wp_) + CO_ * wi_pitch2(4 * nst_)),                     \
-                      red_ = (PS_ > 1 ? (8 / PS_) * 9 * CTW_ * 256 : 0);                                                                \
-        constexpr int fl_ = stage_ > red_ ? stage_ : red_;                                                                              \
-        static_assert(fl_ * 4 <= (160 << 10), "planes fit the LDS");                                                                    \
+    if (xb >= (1u << 31) || gb >= (1u << 31)) return false;
+#define TH_WI_PLAN(S_, CI_, CO_, CTW_, PS_, IPW_, NB_)                                                                                   \
+    if (hw == S_ && c_in == CI_ && c_out == CO_) {                                                                                       \
+        static_assert(wi_lds_floats(S_, CI_, CO_, CTW_, PS_, NB_) * 4 <= (160 << 10), "planes fit the LDS");                             \
+        p->family = CONV_F_WGRAD_IMG; p->ct = CTW_; p->pq = PS_; p->img_t = IPW_; p->bands = NB_;                                         \
+        p->grid_x = ceil_div(n, IPW_); p->grid_y = p->grid_z = 1; p->slabs = p->grid_x; p->co_ld = CO_;                                  \
+        p->lds = wi_lds_floats(S_, CI_, CO_, CTW_, PS_, NB_) * 4; p->lds_limit = 160 << 10;                                              \
+        return true;                                                                                                                     \
+    }
+    TH_WI_SHAPES(TH_WI_PLAN)
+#undef TH_WI_PLAN
+    return false;
+}
+
+// launches the instance a CONV_F_WGRAD_IMG plan names into `part` (p.slabs slabs).  0: launched
+static int conv_wgrad_img_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *gy, float *part, int n, int c_in, int hw, int c_out) {
+    const size_t xb = (size_t)n * c_in * hw * hw * 4, gb = (size_t)n * c_out * hw * hw * 4;
+    WgradImgArgs a{x, gy, part, n, p.img_t, (unsigned)xb, (unsigned)gb};
+#define TH_WI_RUN(S_, CI_, CO_, CTW_, PS_, IPW_, NB_)                                                                                    \
+    if (hw == S_ && c_in == CI_ && c_out == CO_) {                                                                                       \
         auto kern = conv_wgrad_img_kernel<S_, CI_, CO_, CTW_, PS_, NB_>;                                                                 \
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, fl_ * 4);                              \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), fl_ * 4, ctx->stream, a);                                                        \
-        if (hipGetLastError() != hipSuccess) return -1;                                                                                  \
-        *part_out = a.part;                                                                                                              \
-        *n_slabs = grid;                                                                                                                 \
-        return 1;                                                                                                                        \
-    } while (0)
-    if (hw == 14 && c_in == 32 && c_out == 64) TH_WI(14, 32, 64, 2, 2, 1);     // (two pipelined bands: 24.9 vs 24.0 us)
-    if (hw == 14 && c_in == 64 && c_out == 64) TH_WI(14, 64, 64, 2, 1, 1);     // (two pipelined bands: 42.5 vs 39.4 us)
-    if (hw == 28 && c_in == 32 && c_out == 32) TH_WIB(28, 32, 32, 2, 4, 1, 4);
-    // (7 x 7, 64 -> 128, two images per workgroup: built and measured equal to the slab kernel -- 38.1 vs 38.5 us -- with twice the slab
-    // bytes for wgrad_reduce: 49 pixels per image are too few steps for a [576][128] slab per workgroup.  Left to the slab kernel.)
-#undef TH_WI
-#undef TH_WIB
-    return 0;
+        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);                                \
+        hipLaunchKernelGGL(kern, dim3(p.grid_x), dim3(512), p.lds, ctx->stream, a);                                                      \
+        return hipGetLastError() != hipSuccess ? -1 : 0;                                                                                 \
+    }
+    TH_WI_SHAPES(TH_WI_RUN)
+#undef TH_WI_RUN
+    return -1;
 }
 
 // images x rows per pixel block of the weight-gradient kernel: the tiling of <= 128 pixels by whole output rows that takes the fewest
@@ -1398,64 +1455,90 @@ static void conv_wgrad_plan(int h_out, int w_out, int n, int *img_t, int *rows_t
     }
 }
 
-int conv3x3_wgrad_mfma_launch(th_ctx *ctx, const float *x, const float *gy, float *gw, int n, int c_in, int h, int w_in, int c_out,
-                              int pad, int layout, int accumulate) {
-    if (pad == 1 && h == w_in) {
-        float *part = nullptr;
-        int n_slabs = 0;
-        const int rc = conv_wgrad_img_launch(ctx, x, gy, n, c_in, h, c_out, &part, &n_slabs);
-        if (rc < 0) { th::set_error("conv_wgrad_img_kernel: launch failed"); return 1; }
-        if (rc == 1) {
-            if (int r2 = wgrad_reduce(ctx, part, gw, n_slabs, 9 * c_in, c_out, c_out, layout, accumulate)) return r2;
-            return th_free(ctx, part);
-        }
+// the matrix-core weight gradient: which kernel, its tiling, slab count and reduce ending (gw_aligned: gw on a 16-byte boundary; the
+// slabs come from the pool, which hands out aligned blocks)
+void conv3x3_wgrad_mfma_plan(ConvPlan *p, int n, int c_in, int h, int w_in, int c_out, int pad, int layout, bool accumulate, bool gw_aligned) {
+    const int h_out = h + 2 * pad - 2, w_out = w_in + 2 * pad - 2;
+    p->h_out = h_out; p->w_out = w_out;
+    p->acc = accumulate;
+    if (pad == 1 && h == w_in && conv_wgrad_img_plan(n, c_in, h, c_out, p)) {
+        p->reduce = wgrad_reduce_plan(p->slabs, 9 * c_in, c_out, c_out, layout, accumulate, gw_aligned);
+        return;
     }
-    ConvWgradArgs a{};
-    a.x = x; a.gy = gy;
-    a.n = n; a.c_in = c_in; a.h = h; a.w_in = w_in; a.c_out = c_out; a.pad = pad;
-    a.h_out = h + 2 * pad - 2;
-    a.w_out = w_in + 2 * pad - 2;
-    conv_wgrad_plan(a.h_out, a.w_out, n, &a.img_t, &a.rows_t);
-    a.bands = ceil_div(a.h_out, a.rows_t);
-    a.n_pb = ceil_div(n, a.img_t) * a.bands;
+    p->family = CONV_F_WGRAD_MFMA;
+    conv_wgrad_plan(h_out, w_out, n, &p->img_t, &p->rows_t);
+    p->bands = ceil_div(h_out, p->rows_t);
+    p->n_pb = ceil_div(n, p->img_t) * p->bands;
     const int co_tiles = ceil_div(c_out, 16);
     const int ct = co_tiles >= 4 ? 4 : (co_tiles >= 2 ? 2 : 1);
     const int co_b = ct * 16;
     const int slabs = ceil_div(c_in, WG_CI), co_blocks = ceil_div(c_out, co_b);
-    a.co_ld = co_blocks * co_b;
+    p->ct = ct;
+    p->co_ld = co_blocks * co_b;
     // workgroups per CU in total (LDS: <= 58 KB each): two
     constexpr int kWgradWgsPerCU = 2;
     int G = ceil_div(kWgradWgsPerCU * kNumCU, slabs * co_blocks);
-    if (G > a.n_pb) G = a.n_pb;
+    if (G > p->n_pb) G = p->n_pb;
     if (G > 512) G = 512;
-    a.G = G;
+    p->G = G; p->slabs = G;
+    const size_t ci_stride = (size_t)p->img_t * (p->rows_t + 2) * (w_out + 2);
+    const size_t xb = (size_t)n * c_in * h * w_in * 4, gb = (size_t)n * c_out * h_out * w_out * 4;
+    if (ci_stride > 512 || xb >= (1u << 31) || gb >= (1u << 31)) { p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_WGRAD; return; }
+    p->pq = ci_stride <= 256 ? 1 : 2;
+    p->lds = (int)((WG_CI * (size_t)wg_cpitch((int)ci_stride) + (size_t)co_b * WG_GP) * sizeof(float) + MF_PX_MAX * sizeof(int));
+    p->lds_limit = 160 << 10;
+    p->grid_x = G; p->grid_y = slabs; p->grid_z = co_blocks;
+    p->reduce = wgrad_reduce_plan(G, 9 * c_in, c_out, p->co_ld, layout, accumulate, gw_aligned);
+}
+
+// launches what conv3x3_wgrad_mfma_plan chose
+int conv3x3_wgrad_mfma_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *gy, float *gw, int n, int c_in, int h, int w_in,
+                              int c_out, int pad, int layout, int accumulate) {
+    // (checked before the slabs are taken from the pool: an error return holds nothing)
+    TH_REQUIRE(p.family != CONV_F_REFUSED, "conv3x3_wgrad: patch chunk too large, or maps of 2 GiB and more (not supported)");
     const int kt = 9 * c_in;
     void *ws = nullptr;
-    if (th_malloc(ctx, (size_t)G * kt * a.co_ld * sizeof(float), &ws)) return 1;
+    if (th_malloc(ctx, (size_t)p.slabs * kt * p.co_ld * sizeof(float), &ws)) return 1;
+    if (p.family == CONV_F_WGRAD_IMG) {
+        if (conv_wgrad_img_launch(ctx, p, x, gy, (float *)ws, n, c_in, h, c_out)) {
+            th_free(ctx, ws);
+            th::set_error("conv_wgrad_img_kernel: launch failed");
+            return 1;
+        }
+        if (int r2 = wgrad_reduce(ctx, (const float *)ws, gw, p.slabs, kt, c_out, c_out, layout, accumulate)) { th_free(ctx, ws); return r2; }
+        return th_free(ctx, ws);
+    }
+    ConvWgradArgs a{};
+    a.x = x; a.gy = gy;
+    a.n = n; a.c_in = c_in; a.h = h; a.w_in = w_in; a.c_out = c_out; a.pad = pad;
+    a.h_out = p.h_out;
+    a.w_out = p.w_out;
+    a.img_t = p.img_t; a.rows_t = p.rows_t;
+    a.bands = p.bands;
+    a.n_pb = p.n_pb;
+    a.co_ld = p.co_ld;
+    a.G = p.G;
     a.part = (float *)ws;
-    const size_t ci_stride = (size_t)a.img_t * (a.rows_t + 2) * (a.w_out + 2);
-    TH_REQUIRE(ci_stride <= 512, "conv3x3_wgrad: patch chunk too large");
-    const size_t xb = (size_t)n * c_in * h * w_in * 4, gb = (size_t)n * c_out * a.h_out * a.w_out * 4;
-    TH_REQUIRE(xb < (1u << 31) && gb < (1u << 31), "conv3x3_wgrad: maps of 2 GiB and more are not supported");
-    a.x_bytes = (unsigned)xb;
-    a.gy_bytes = (unsigned)gb;
-    const size_t lds = (WG_CI * (size_t)wg_cpitch((int)ci_stride) + (size_t)co_b * WG_GP) * sizeof(float) + MF_PX_MAX * sizeof(int);
-    dim3 grid(G, slabs, co_blocks);
+    a.x_bytes = (unsigned)((size_t)n * c_in * h * w_in * 4);
+    a.gy_bytes = (unsigned)((size_t)n * c_out * a.h_out * a.w_out * 4);
+    const size_t lds = (size_t)p.lds;
+    dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+    hipError_t attr = hipSuccess;
 #define TH_WG(CT_, PQ_)                                                                                                                  \
     do {                                                                                                                                \
         auto kern = conv3x3_wgrad_mfma_kernel<CT_, PQ_>;                                                                                \
-        if (lds > (64u << 10)) TH_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, a);                                                                 \
+        if (lds > (64u << 10)) attr = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
+        if (attr == hipSuccess) hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, a);                                         \
     } while (0)
-    const bool one = ci_stride <= 256;
-    switch (ct) {
+    const bool one = p.pq == 1;
+    switch (p.ct) {
         case 4: if (one) TH_WG(4, 1); else TH_WG(4, 2); break;
         case 2: if (one) TH_WG(2, 1); else TH_WG(2, 2); break;
         default: if (one) TH_WG(1, 1); else TH_WG(1, 2); break;
     }
 #undef TH_WG
-    TH_LAUNCH_CHECK();
-    if (int rc = wgrad_reduce(ctx, a.part, gw, G, kt, c_out, a.co_ld, layout, accumulate)) return rc;
+    if (attr != hipSuccess || hipGetLastError() != hipSuccess) { th_free(ctx, ws); th::set_error("conv3x3_wgrad_mfma_kernel: launch failed"); return 1; }
+    if (int rc = wgrad_reduce(ctx, a.part, gw, p.G, kt, c_out, a.co_ld, layout, accumulate)) { th_free(ctx, ws); return rc; }
     return th_free(ctx, ws);
 }
 

@@ -14,6 +14,7 @@
 // LDS pipe to the input taps only.  The im2col buffer of the reference (up to
 // 231 MB at batch 256) is never materialised.
 #include "adam_dev.h"
+#include "conv_plan.h"
 
 namespace th {
 
@@ -850,21 +851,51 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float *__restric
     }
 }
 
-static int conv3x3_launch(th_ctx *ctx, const float *x, const float *w_t, const float *bias, float *y, int n, int in_ch, int h,
-                          int w, int out_ch, int co_pad, int pad, int relu, bool accum) {
+// which vector-ALU kernel takes the layer (weights prepped to [9 in_ch][co_pad]), or CONV_REFUSED_LDS
+void conv3x3_vec_plan(ConvPlan *p, int n, int in_ch, int h, int w, int out_ch, int co_pad, int pad, bool accum) {
     const int h_out = h + 2 * pad - 2, w_out = w + 2 * pad - 2;
+    p->h_out = h_out; p->w_out = w_out;
+    p->acc = accum;
+    p->lds_limit = 160 << 10;
+    int img_per_wg, plane;
     if (w_out >= 16 && w_out % TPW == 0 && h_out % TPH == 0) {
         // large planes: 2x4 pixel tiles x 8 channels, packed-FMA inner loop
+        p->family = CONV_F_TILE;
         const int tiles_h = h_out / TPH, tiles_w = w_out / TPW;
         const int tiles_per_img = tiles_h * tiles_w;
-        int img_per_wg = 256 / tiles_per_img;
-        if (img_per_wg < 1) img_per_wg = 1;
-        if (img_per_wg > n) img_per_wg = n;
-        const int plane = (tiles_h * TPH + 2 + (1 - pad)) * ((tiles_w * TPW + 2 + (1 - pad)) | 1);
-        while (img_per_wg > 1 && (size_t)img_per_wg * CI_T * plane * sizeof(float) > (64u << 10)) --img_per_wg;  // 2 workgroups per CU
-        const size_t lds = (size_t)img_per_wg * CI_T * plane * sizeof(float);
-        TH_REQUIRE(lds <= (160u << 10), "th_conv3x3: %dx%d plane does not fit the LDS tile", h, w);
-        dim3 grid(ceil_div(n, img_per_wg), co_pad / CO_T);
+        img_per_wg = 256 / tiles_per_img;
+        plane = (tiles_h * TPH + 2 + (1 - pad)) * ((tiles_w * TPW + 2 + (1 - pad)) | 1);
+        p->grid_y = co_pad / CO_T;
+    } else {
+        // small / odd planes: row tiles of PX pixels x 16 channels
+        p->family = CONV_F_ROWS;
+        p->px = (w_out % 4 == 0) ? 4 : ((w_out % 2 == 0) ? 2 : 1);
+        const int items_per_img = h_out * ((w_out + p->px - 1) / p->px);
+        img_per_wg = 256 / items_per_img;
+        plane = (h + 2) * (w + 2);
+        p->grid_y = co_pad / CO_R;
+    }
+    if (img_per_wg < 1) img_per_wg = 1;
+    if (img_per_wg > n) img_per_wg = n;
+    while (img_per_wg > 1 && (size_t)img_per_wg * CI_T * plane * sizeof(float) > (64u << 10)) --img_per_wg;  // 2 workgroups per CU
+    const size_t lds = (size_t)img_per_wg * CI_T * plane * sizeof(float);
+    p->img_t = img_per_wg;
+    p->grid_x = ceil_div(n, img_per_wg); p->grid_z = 1;
+    if (lds > (160u << 10)) {
+        p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_LDS;
+        p->lds = 0;
+        return;
+    }
+    p->lds = (int)lds;
+}
+
+static int conv3x3_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *w_t, const float *bias, float *y, int n, int in_ch, int h,
+                          int w, int out_ch, int co_pad, int pad, int relu) {
+    TH_REQUIRE(p.family == CONV_F_TILE || p.family == CONV_F_ROWS, "th_conv3x3: %dx%d plane does not fit the LDS tile", h, w);
+    const size_t lds = (size_t)p.lds;
+    const int img_per_wg = p.img_t, h_out = p.h_out, w_out = p.w_out;
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.family == CONV_F_TILE) {
 #define TH_CONV_TILE(ACC)                                                                                                       \
     {                                                                                                                           \
         auto kern = conv3x3_kernel<ACC>;                                                                                        \
@@ -872,22 +903,11 @@ static int conv3x3_launch(th_ctx *ctx, const float *x, const float *w_t, const f
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, x, w_t, bias, y, n, in_ch, h, w, out_ch, co_pad, pad, h_out, \
                            w_out, img_per_wg, relu);                                                                            \
     }
-        if (accum) TH_CONV_TILE(true) else TH_CONV_TILE(false)
+        if (p.acc) TH_CONV_TILE(true) else TH_CONV_TILE(false)
 #undef TH_CONV_TILE
         TH_LAUNCH_CHECK();
         return 0;
     }
-    // small / odd planes: row tiles of PX pixels x 16 channels
-    const int px = (w_out % 4 == 0) ? 4 : ((w_out % 2 == 0) ? 2 : 1);
-    const int items_per_img = h_out * ((w_out + px - 1) / px);
-    int img_per_wg = 256 / items_per_img;
-    if (img_per_wg < 1) img_per_wg = 1;
-    if (img_per_wg > n) img_per_wg = n;
-    const int plane = (h + 2) * (w + 2);
-    while (img_per_wg > 1 && (size_t)img_per_wg * CI_T * plane * sizeof(float) > (64u << 10)) --img_per_wg;
-    const size_t lds = (size_t)img_per_wg * CI_T * plane * sizeof(float);
-    TH_REQUIRE(lds <= (160u << 10), "th_conv3x3: %dx%d plane does not fit the LDS tile", h, w);
-    dim3 grid(ceil_div(n, img_per_wg), co_pad / CO_R);
 #define TH_CONV_ROWS(PXV, ACC)                                                                                                  \
     {                                                                                                                           \
         auto kern = conv3x3_rows_kernel<PXV, ACC>;                                                                              \
@@ -895,7 +915,8 @@ static int conv3x3_launch(th_ctx *ctx, const float *x, const float *w_t, const f
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, x, w_t, bias, y, n, in_ch, h, w, out_ch, co_pad, pad, h_out, \
                            w_out, img_per_wg, relu);                                                                            \
     }
-    if (!accum) {
+    const int px = p.px;
+    if (!p.acc) {
         if (px == 4) TH_CONV_ROWS(4, false) else if (px == 2) TH_CONV_ROWS(2, false) else TH_CONV_ROWS(1, false)
     } else {
         if (px == 4) TH_CONV_ROWS(4, true) else if (px == 2) TH_CONV_ROWS(2, true) else TH_CONV_ROWS(1, true)
@@ -909,11 +930,10 @@ static int conv3x3_launch(th_ctx *ctx, const float *x, const float *w_t, const f
 bool conv3x3_mfma_supported(int c_in, int h, int w, int pad);
 bool conv3x3_mfma_pool_supported(int c_in, int h, int w, int pad);
 bool conv3x3_gap_supported(int n, int c_in, int h, int w_in, int c_out, int pad);
-int conv3x3_mfma_launch(th_ctx *ctx, const float *x, const float *w, int w_ld, int w_cols, const float *bias, float *y, int n,
-                        int c_in, int h, int w_in, int c_out, int pad, int relu, bool accum, bool pool = false, float *gap_cnt = nullptr,
-                        bool gap = false);
-int conv3x3_wgrad_mfma_launch(th_ctx *ctx, const float *x, const float *gy, float *gw, int n, int c_in, int h, int w_in, int c_out,
-                              int pad, int layout, int accumulate);
+int conv3x3_mfma_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *w, int w_ld, int w_cols, const float *bias, float *y, int n,
+                        int c_in, int h, int w_in, int c_out, int pad, int relu, float *gap_cnt = nullptr);
+int conv3x3_wgrad_mfma_launch(th_ctx *ctx, const ConvPlan &p, const float *x, const float *gy, float *gw, int n, int c_in, int h, int w_in,
+                              int c_out, int pad, int layout, int accumulate);
 int wgrad_reduce(th_ctx *ctx, const float *part, float *gw, int G, int kt, int c_out, int co_ld, int layout, int accumulate);
 
 }  // namespace th
@@ -1199,7 +1219,111 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float *__restrict__ x,
 }
 }  // namespace th
 
+namespace th {
+static bool conv1_plane_fits(int h, int w) { return (size_t)(h + 2) * (w + 2) * sizeof(float) <= (48u << 10); }
+static bool conv3x3_pool2_ok(int c_in, int h, int w, int c_out, int pad) {
+    return (pad == 0 || pad == 1) && c_in > 0 && c_out > 0 && c_out % 4 == 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3 &&
+           conv3x3_mfma_pool_supported(c_in, h, w, pad);
+}
+static bool conv3x3_gap_ok(int n, int c_in, int h, int w, int c_out, int pad) {
+    return (pad == 0 || pad == 1) && n > 0 && c_in > 0 && c_out > 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3 &&
+           conv3x3_gap_supported(n, c_in, h, w, c_out, pad);
+}
+
+// one input channel in the taper layout on a plane of <= 48 KB: an image per workgroup on the vector ALUs
+static void conv1_plan(ConvPlan *p, int n, int h, int w, int c_out, bool pool) {
+    p->family = CONV_F_CONV1; p->pool = pool; p->cit = 1; p->img_t = 1;
+    p->grid_x = n; p->grid_y = ceil_div(c_out, C1_CO_W); p->grid_z = 1;
+    p->lds = (int)((size_t)(h + 2) * (w + 2) * sizeof(float)); p->lds_limit = 48 << 10;
+}
+
+void conv3x3_plan(ConvPlan *p, int op, int n, int c_in, int h, int w, int c_out, int pad, int weight_layout, bool relu, bool has_bias,
+                  bool accumulate, bool w_aligned, int img_mode) {
+    *p = ConvPlan{};
+    const int h_out = h + 2 * pad - 2, w_out = w + 2 * pad - 2;
+    p->h_out = h_out; p->w_out = w_out;
+    if (op == 0) {
+        // conv1: K = 9 -- one image per workgroup on the vector ALUs (17.3 -> 8 us at batch 256 against the matrix-core kernel)
+        if (c_in == 1 && weight_layout == 0 && conv1_plane_fits(h, w)) { conv1_plan(p, n, h, w, c_out, false); return; }
+        const bool mfma = conv3x3_mfma_supported(c_in, h, w, pad);
+        // the taper layout IS the [k][co] slab the matrix-core kernel stages (tensor.rs:1262): read it in place
+        if (mfma && weight_layout == 0 && c_out % 4 == 0 && w_aligned) {
+            conv3x3_mfma_plan(p, n, c_in, h, w, c_out, pad, c_out, c_out, relu, has_bias, false, false, false, img_mode);
+            return;
+        }
+        const int co_pad = (c_out + CO_R - 1) / CO_R * CO_R;   // multiple of both kernels' channel blocks
+        if (mfma) conv3x3_mfma_plan(p, n, c_in, h, w, c_out, pad, co_pad, co_pad, relu, has_bias, false, false, false, img_mode);
+        else conv3x3_vec_plan(p, n, c_in, h, w, c_out, co_pad, pad, false);
+        p->prep = 1;
+    } else if (op == 1) {
+        if (!conv3x3_pool2_ok(c_in, h, w, c_out, pad) || !w_aligned) { p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_POOL; return; }
+        if (c_in == 1 && conv1_plane_fits(h, w)) { conv1_plan(p, n, h, w, c_out, true); return; }   // conv1: one image per workgroup, VALU
+        conv3x3_mfma_plan(p, n, c_in, h, w, c_out, pad, c_out, c_out, relu, has_bias, false, true, false, img_mode);
+    } else if (op == 2) {
+        if (!conv3x3_gap_ok(n, c_in, h, w, c_out, pad) || !w_aligned) { p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_GAP; return; }
+        conv3x3_mfma_plan(p, n, c_in, h, w, c_out, pad, c_out, c_out, relu, has_bias, false, true, true, img_mode);
+    } else if (op == 3) {
+        if (pad != 1) { p->family = CONV_F_REFUSED; p->refused = CONV_REFUSED_PAD; return; }
+        // gx (+)= conv3x3(gy, mirrored filter with ci/co swapped), pad 1
+        const int ci_pad = (c_in + CO_R - 1) / CO_R * CO_R;
+        if (conv3x3_mfma_supported(c_out, h, w, 1))   // the mirrored filter [k = (co, kh, kw)][ci] feeds the matrix-core kernel as is
+            conv3x3_mfma_plan(p, n, c_out, h, w, c_in, 1, ci_pad, ci_pad, false, false, accumulate, false, false, img_mode);
+        else conv3x3_vec_plan(p, n, c_out, h, w, c_in, ci_pad, 1, accumulate);
+        p->prep = 1;
+    } else {
+        if (c_in >= 8 && conv3x3_mfma_supported(c_in, h, w, pad) && (long)n * h_out * w_out >= 2048) {   // enough channels and pixels to contract over
+            conv3x3_wgrad_mfma_plan(p, n, c_in, h, w, c_out, pad, weight_layout, accumulate, w_aligned);
+            return;
+        }
+        p->acc = accumulate;
+        // one input channel, planes that fit the LDS (conv1): one image per workgroup, partial slabs per image
+        const size_t lds1 = ((size_t)(((h + 2) * (w + 2) + 3) & ~3) + (size_t)C1W_CO * (h_out * w_out + 1) + (size_t)C1W_NS * C1W_CO * 9) * sizeof(float);
+        if (c_in == 1 && n >= 32 && h_out > 0 && w_out > 0 && lds1 <= (160u << 10)) {
+            p->family = CONV_F_WGRAD_CONV1; p->img_t = 1;
+            p->grid_x = n; p->grid_y = ceil_div(c_out, C1W_CO); p->grid_z = 1;
+            p->lds = (int)lds1; p->lds_limit = 160 << 10;
+            p->slabs = n; p->co_ld = c_out;
+            p->reduce = wgrad_reduce_plan(n, 9, c_out, c_out, weight_layout, accumulate, w_aligned);
+            return;
+        }
+        p->family = CONV_F_WGRAD_VEC;
+        int slabs = 1;
+        if ((long)c_out * c_in < 512 && (long)n * h_out * w_out >= 8192) {   // few (co, ci) pairs, many pixels (conv1): split the images
+            slabs = ceil_div(1024, c_out * c_in);
+            if (slabs > n) slabs = n;
+        }
+        p->grid_x = c_out; p->grid_y = c_in; p->grid_z = 1;
+        p->img_t = n;                                  // images per slab
+        if (slabs <= 1) return;                        // straight into gw: no slabs, no reduce
+        p->img_t = ceil_div(n, slabs);
+        p->slabs = p->grid_z = ceil_div(n, p->img_t);
+        p->co_ld = c_out;
+        p->reduce = wgrad_reduce_plan(p->slabs, c_in * 9, c_out, c_out, weight_layout, accumulate, w_aligned);
+    }
+}
+}  // namespace th
+
 extern "C" {
+
+int th_debug_conv3x3_plan(int op, int n, int c_in, int h, int w, int c_out, int pad, int weight_layout, int relu_bias, int accumulate,
+                          int w_misalign_bytes, int img_mode, int *outN) {
+    TH_REQUIRE(outN, "th_debug_conv3x3_plan: null output");
+    TH_REQUIRE(op >= 0 && op <= 4, "th_debug_conv3x3_plan: op must be 0 (fwd), 1 (pool2 fwd), 2 (gap fwd), 3 (bwd_input) or 4 (bwd_weight), got %d", op);
+    TH_REQUIRE(n > 0 && c_in > 0 && c_out > 0 && h > 0 && w > 0, "th_debug_conv3x3_plan: bad geometry n=%d c_in=%d h=%d w=%d c_out=%d", n, c_in, h, w, c_out);
+    TH_REQUIRE(pad == 0 || pad == 1, "th_debug_conv3x3_plan: pad must be 0 or 1 (got %d)", pad);
+    TH_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, "th_debug_conv3x3_plan: bad geometry: a %dx%d plane with pad %d holds no 3x3 window", h, w, pad);
+    TH_REQUIRE(weight_layout == 0 || weight_layout == 1, "th_debug_conv3x3_plan: weight_layout must be 0 (taper) or 1 (standard)");
+    TH_REQUIRE(relu_bias >= 0 && relu_bias <= 3, "th_debug_conv3x3_plan: relu_bias is relu + 2 * bias present (0 .. 3), got %d", relu_bias);
+    TH_REQUIRE(accumulate == 0 || (accumulate == 1 && op >= 3), "th_debug_conv3x3_plan: accumulate is 0, or 1 for the two backward ops");
+    TH_REQUIRE(w_misalign_bytes >= 0 && w_misalign_bytes < 16 && w_misalign_bytes % 4 == 0, "th_debug_conv3x3_plan: w_misalign_bytes must be 0, 4, 8 or 12");
+    TH_REQUIRE(img_mode >= -1 && img_mode <= 1, "th_debug_conv3x3_plan: img_mode must be -1 (auto), 0 (off) or 1 (whenever it fits)");
+    th::ConvPlan p;
+    th::conv3x3_plan(&p, op, n, c_in, h, w, c_out, pad, weight_layout, (relu_bias & 1) != 0, (relu_bias & 2) != 0, accumulate != 0,
+                     w_misalign_bytes == 0, img_mode);
+    const int *src = reinterpret_cast<const int *>(&p);
+    for (int i = 0; i < th::kConvPlanInts; ++i) outN[i] = src[i];
+    return 0;
+}
 
 int th_conv3x3_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_bias, float *d_y, int n, int c_in, int h,
                    int w, int c_out, int pad, int weight_layout, int relu) {
@@ -1207,83 +1331,79 @@ int th_conv3x3_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float 
     TH_REQUIRE(n > 0 && c_in > 0 && c_out > 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3, "th_conv3x3_fwd: bad geometry");
     TH_REQUIRE(pad == 0 || pad == 1, "th_conv3x3_fwd: pad must be 0 or 1 (got %d)", pad);
     TH_REQUIRE(weight_layout == 0 || weight_layout == 1, "th_conv3x3_fwd: weight_layout must be 0 (taper) or 1 (standard)");
-    if (c_in == 1 && weight_layout == 0 && (size_t)(h + 2) * (w + 2) * sizeof(float) <= (48u << 10)) {
-        // conv1: K = 9 -- one image per workgroup on the vector ALUs (17.3 -> 8 us at batch 256 against the matrix-core kernel)
-        const size_t lds = (size_t)(h + 2) * (w + 2) * sizeof(float);
-        hipLaunchKernelGGL(conv1_kernel, dim3(n, ceil_div(c_out, C1_CO_W)), dim3(256), lds, ctx->stream, d_x, d_w, d_bias, d_y, h, w, c_out,
-                           pad, relu);
+    ConvPlan p;
+    conv3x3_plan(&p, 0, n, c_in, h, w, c_out, pad, weight_layout, relu != 0, d_bias != nullptr, false, ((uintptr_t)d_w & 15) == 0, g_conv_img_mode);
+    // (refused before the prepped weights are taken from the pool: an error return holds nothing)
+    TH_REQUIRE(p.family != CONV_F_REFUSED, "th_conv3x3: %dx%d plane does not fit the LDS tile", h, w);
+    if (p.family == CONV_F_CONV1) {
+        hipLaunchKernelGGL(conv1_kernel, dim3(p.grid_x, p.grid_y), dim3(256), p.lds, ctx->stream, d_x, d_w, d_bias, d_y, h, w, c_out, pad, relu);
         TH_LAUNCH_CHECK();
         return 0;
     }
-    const bool mfma = conv3x3_mfma_supported(c_in, h, w, pad);
-    // the taper layout IS the [k][co] slab the matrix-core kernel stages (tensor.rs:1262): read it in place
-    if (mfma && weight_layout == 0 && c_out % 4 == 0 && ((uintptr_t)d_w & 15) == 0)
-        return conv3x3_mfma_launch(ctx, d_x, d_w, c_out, c_out, d_bias, d_y, n, c_in, h, w, c_out, pad, relu, false);
-    const int co_pad = (c_out + CO_R - 1) / CO_R * CO_R;   // multiple of both kernels' channel blocks
+    if (!p.prep) return conv3x3_mfma_launch(ctx, p, d_x, d_w, c_out, c_out, d_bias, d_y, n, c_in, h, w, c_out, pad, relu);
+    const int co_pad = (c_out + CO_R - 1) / CO_R * CO_R;
     void *wt = nullptr;
     if (th_malloc(ctx, (size_t)c_in * 9 * co_pad * sizeof(float), &wt)) return 1;
     hipLaunchKernelGGL(conv3x3_prep_weights, dim3(ew_grid((size_t)c_in * 9 * co_pad, 256)), dim3(256), 0, ctx->stream, d_w,
                        (float *)wt, c_in, c_out, weight_layout, 0, c_out, co_pad, c_in);
-    TH_LAUNCH_CHECK();
-    if (mfma) {
-        if (int rc = conv3x3_mfma_launch(ctx, d_x, (const float *)wt, co_pad, co_pad, d_bias, d_y, n, c_in, h, w, c_out, pad, relu, false)) return rc;
-    } else if (int rc = conv3x3_launch(ctx, d_x, (const float *)wt, d_bias, d_y, n, c_in, h, w, c_out, co_pad, pad, relu, false)) {
-        return rc;
-    }
+    int rc = hipGetLastError() != hipSuccess;
+    if (rc) th::set_error("conv3x3_prep_weights: launch failed");
+    else if (p.family == CONV_F_TILE || p.family == CONV_F_ROWS) rc = conv3x3_launch(ctx, p, d_x, (const float *)wt, d_bias, d_y, n, c_in, h, w, c_out, co_pad, pad, relu);
+    else rc = conv3x3_mfma_launch(ctx, p, d_x, (const float *)wt, co_pad, co_pad, d_bias, d_y, n, c_in, h, w, c_out, pad, relu);
+    if (rc) { th_free(ctx, wt); return rc; }
     return th_free(ctx, wt);
 }
 
-int th_conv3x3_pool2_supported(int c_in, int h, int w, int c_out, int pad) {
-    return (pad == 0 || pad == 1) && c_in > 0 && c_out > 0 && c_out % 4 == 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3 &&
-           conv3x3_mfma_pool_supported(c_in, h, w, pad);
-}
+int th_conv3x3_pool2_supported(int c_in, int h, int w, int c_out, int pad) { return conv3x3_pool2_ok(c_in, h, w, c_out, pad) ? 1 : 0; }
 
 int th_conv3x3_pool2_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_bias, float *d_y_pooled, int n, int c_in, int h,
                          int w, int c_out, int pad, int relu) {
     TH_REQUIRE(ctx && d_x && d_w && d_y_pooled && n > 0, "th_conv3x3_pool2_fwd: null argument");
-    TH_REQUIRE(th_conv3x3_pool2_supported(c_in, h, w, c_out, pad) && ((uintptr_t)d_w & 15) == 0,
+    ConvPlan p;
+    conv3x3_plan(&p, 1, n, c_in, h, w, c_out, pad, 0, relu != 0, d_bias != nullptr, false, ((uintptr_t)d_w & 15) == 0, g_conv_img_mode);
+    TH_REQUIRE(p.family != CONV_F_REFUSED,
                "th_conv3x3_pool2_fwd: needs the matrix-core path (c_in >= 8 or == 1), c_out %% 4 == 0, even output height / width, "
                "rows of <= 64 outputs and 16-byte aligned weights");
-    if (c_in == 1 && (size_t)(h + 2) * (w + 2) * sizeof(float) <= (48u << 10)) {   // conv1: one image per workgroup, VALU
-        const size_t lds = (size_t)(h + 2) * (w + 2) * sizeof(float);
-        hipLaunchKernelGGL(conv1_pool2_kernel, dim3(n, ceil_div(c_out, C1_CO_W)), dim3(256), lds, ctx->stream, d_x, d_w, d_bias, d_y_pooled,
+    if (p.family == CONV_F_CONV1) {
+        hipLaunchKernelGGL(conv1_pool2_kernel, dim3(p.grid_x, p.grid_y), dim3(256), p.lds, ctx->stream, d_x, d_w, d_bias, d_y_pooled,
                            h, w, c_out, pad, relu);
         TH_LAUNCH_CHECK();
         return 0;
     }
     // the taper layout IS the [k][co] slab the kernel stages (tensor.rs:1262)
-    return conv3x3_mfma_launch(ctx, d_x, d_w, c_out, c_out, d_bias, d_y_pooled, n, c_in, h, w, c_out, pad, relu, false, true);
+    return conv3x3_mfma_launch(ctx, p, d_x, d_w, c_out, c_out, d_bias, d_y_pooled, n, c_in, h, w, c_out, pad, relu);
 }
 
-int th_conv3x3_gap_supported(int n, int c_in, int h, int w, int c_out, int pad) {
-    return (pad == 0 || pad == 1) && n > 0 && c_in > 0 && c_out > 0 && h + 2 * pad >= 3 && w + 2 * pad >= 3 &&
-           conv3x3_gap_supported(n, c_in, h, w, c_out, pad) ? 1 : 0;
-}
+int th_conv3x3_gap_supported(int n, int c_in, int h, int w, int c_out, int pad) { return conv3x3_gap_ok(n, c_in, h, w, c_out, pad) ? 1 : 0; }
 
 int th_conv3x3_gap_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_bias, float *d_y_mean, float *d_cnt, int n, int c_in,
                        int h, int w, int c_out, int pad, int relu) {
     TH_REQUIRE(ctx && d_x && d_w && d_y_mean && n > 0, "th_conv3x3_gap_fwd: null argument");
-    TH_REQUIRE(th_conv3x3_gap_supported(n, c_in, h, w, c_out, pad) && ((uintptr_t)d_w & 15) == 0,
+    ConvPlan p;
+    conv3x3_plan(&p, 2, n, c_in, h, w, c_out, pad, 0, relu != 0, d_bias != nullptr, false, ((uintptr_t)d_w & 15) == 0, g_conv_img_mode);
+    TH_REQUIRE(p.family != CONV_F_REFUSED,
                "th_conv3x3_gap_fwd: needs c_in %% 8 == 0, c_out %% 4 == 0, whole images that fit a workgroup's LDS and 16-byte aligned weights");
-    return conv3x3_mfma_launch(ctx, d_x, d_w, c_out, c_out, d_bias, d_y_mean, n, c_in, h, w, c_out, pad, relu, false, true, d_cnt, true);
+    return conv3x3_mfma_launch(ctx, p, d_x, d_w, c_out, c_out, d_bias, d_y_mean, n, c_in, h, w, c_out, pad, relu, d_cnt);
 }
 
 int th_conv3x3_bwd_input(th_ctx *ctx, const float *d_gy, const float *d_w, float *d_gx, int n, int c_in, int h, int w,
                          int c_out, int pad, int weight_layout, int accumulate) {
     TH_REQUIRE(ctx && d_gy && d_w && d_gx, "th_conv3x3_bwd_input: null argument");
     TH_REQUIRE(pad == 1, "th_conv3x3_bwd_input: only pad=1 (same-size) convolutions are supported");
-    // gx (+)= conv3x3(gy, mirrored filter with ci/co swapped), pad 1
+    ConvPlan p;
+    conv3x3_plan(&p, 3, n, c_in, h, w, c_out, pad, weight_layout, false, false, accumulate != 0, true, g_conv_img_mode);
+    // (refused before the mirrored weights are taken from the pool: an error return holds nothing)
+    TH_REQUIRE(p.family != CONV_F_REFUSED, "th_conv3x3: %dx%d plane does not fit the LDS tile", h, w);
     const int ci_pad = (c_in + CO_R - 1) / CO_R * CO_R;
     void *wt = nullptr;
     if (th_malloc(ctx, (size_t)c_out * 9 * ci_pad * sizeof(float), &wt)) return 1;
     hipLaunchKernelGGL(conv3x3_prep_weights, dim3(ew_grid((size_t)c_out * 9 * ci_pad, 256)), dim3(256), 0, ctx->stream, d_w,
                        (float *)wt, c_in, c_out, weight_layout, 1, c_in, ci_pad, c_out);
-    TH_LAUNCH_CHECK();
-    if (conv3x3_mfma_supported(c_out, h, w, 1)) {   // the mirrored filter [k = (co, kh, kw)][ci] feeds the matrix-core kernel as is
-        if (int rc = conv3x3_mfma_launch(ctx, d_gy, (const float *)wt, ci_pad, ci_pad, nullptr, d_gx, n, c_out, h, w, c_in, 1, 0, accumulate != 0)) return rc;
-    } else if (int rc = conv3x3_launch(ctx, d_gy, (const float *)wt, nullptr, d_gx, n, c_out, h, w, c_in, ci_pad, 1, 0, accumulate != 0)) {
-        return rc;
-    }
+    int rc = hipGetLastError() != hipSuccess;
+    if (rc) th::set_error("conv3x3_prep_weights: launch failed");
+    else if (p.family == CONV_F_TILE || p.family == CONV_F_ROWS) rc = conv3x3_launch(ctx, p, d_gy, (const float *)wt, nullptr, d_gx, n, c_out, h, w, c_in, ci_pad, 1, 0);
+    else rc = conv3x3_mfma_launch(ctx, p, d_gy, (const float *)wt, ci_pad, ci_pad, nullptr, d_gx, n, c_out, h, w, c_in, 1, 0);
+    if (rc) { th_free(ctx, wt); return rc; }
     return th_free(ctx, wt);
 }
 
@@ -1291,42 +1411,30 @@ int th_conv3x3_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, floa
                           int c_out, int pad, int weight_layout, int accumulate) {
     TH_REQUIRE(ctx && d_x && d_gy && d_gw, "th_conv3x3_bwd_weight: null argument");
     TH_REQUIRE(pad == 0 || pad == 1, "th_conv3x3_bwd_weight: pad must be 0 or 1");
-    const int h_out = h + 2 * pad - 2, w_out = w + 2 * pad - 2;
-    if (c_in >= 8 && conv3x3_mfma_supported(c_in, h, w, pad) && (long)n * h_out * w_out >= 2048)   // enough channels and pixels to contract over
-        return conv3x3_wgrad_mfma_launch(ctx, d_x, d_gy, d_gw, n, c_in, h, w, c_out, pad, weight_layout, accumulate);
-    {
-        // one input channel, planes that fit the LDS (conv1): one image per workgroup, partial slabs per image
-        const size_t lds = ((size_t)(((h + 2) * (w + 2) + 3) & ~3) + (size_t)C1W_CO * (h_out * w_out + 1) + (size_t)C1W_NS * C1W_CO * 9) * sizeof(float);
-        if (c_in == 1 && n >= 32 && h_out > 0 && w_out > 0 && lds <= (160u << 10)) {
-            void *part = nullptr;
-            if (th_malloc(ctx, (size_t)n * 9 * c_out * sizeof(float), &part)) return 1;
-            TH_SET_MAX_LDS(ctx, conv1_wgrad_kernel, 160 << 10);
-            hipLaunchKernelGGL(conv1_wgrad_kernel, dim3(n, ceil_div(c_out, C1W_CO)), dim3(C1W_NT), lds, ctx->stream, d_x, d_gy, (float *)part, h, w,
-                               c_out, pad, h_out, w_out);
-            TH_LAUNCH_CHECK();
-            if (int rc = wgrad_reduce(ctx, (const float *)part, d_gw, n, 9, c_out, c_out, weight_layout, accumulate)) return rc;
-            return th_free(ctx, part);
-        }
-    }
-    int slabs = 1;
-    if ((long)c_out * c_in < 512 && (long)n * h_out * w_out >= 8192) {   // few (co, ci) pairs, many pixels (conv1): split the images
-        slabs = ceil_div(1024, c_out * c_in);
-        if (slabs > n) slabs = n;
-    }
-    if (slabs <= 1) {
-        hipLaunchKernelGGL(conv3x3_bwd_weight_kernel, dim3(c_out, c_in), dim3(256), 0, ctx->stream, d_x, d_gy, d_gw, (float *)nullptr, n,
+    ConvPlan p;
+    conv3x3_plan(&p, 4, n, c_in, h, w, c_out, pad, weight_layout, false, false, accumulate != 0, ((uintptr_t)d_gw & 15) == 0, g_conv_img_mode);
+    const int h_out = p.h_out, w_out = p.w_out;
+    if (p.family != CONV_F_WGRAD_CONV1 && p.family != CONV_F_WGRAD_VEC)
+        return conv3x3_wgrad_mfma_launch(ctx, p, d_x, d_gy, d_gw, n, c_in, h, w, c_out, pad, weight_layout, accumulate);
+    if (p.family == CONV_F_WGRAD_VEC && p.slabs == 0) {
+        hipLaunchKernelGGL(conv3x3_bwd_weight_kernel, dim3(p.grid_x, p.grid_y), dim3(256), 0, ctx->stream, d_x, d_gy, d_gw, (float *)nullptr, n,
                            c_in, h, w, c_out, pad, h_out, w_out, weight_layout, n, accumulate);
         TH_LAUNCH_CHECK();
         return 0;
     }
-    const int ips = ceil_div(n, slabs);
-    slabs = ceil_div(n, ips);
+    const int kt = 9 * c_in;
+    if (p.family == CONV_F_WGRAD_CONV1) TH_SET_MAX_LDS(ctx, conv1_wgrad_kernel, 160 << 10);      // (before the slabs are taken: an error return holds nothing)
     void *part = nullptr;
-    if (th_malloc(ctx, (size_t)slabs * c_in * 9 * c_out * sizeof(float), &part)) return 1;
-    hipLaunchKernelGGL(conv3x3_bwd_weight_kernel, dim3(c_out, c_in, slabs), dim3(256), 0, ctx->stream, d_x, d_gy, d_gw, (float *)part, n,
-                       c_in, h, w, c_out, pad, h_out, w_out, weight_layout, ips, 0);
-    TH_LAUNCH_CHECK();
-    if (int rc = wgrad_reduce(ctx, (const float *)part, d_gw, slabs, c_in * 9, c_out, c_out, weight_layout, accumulate)) return rc;
+    if (th_malloc(ctx, (size_t)p.slabs * kt * c_out * sizeof(float), &part)) return 1;
+    if (p.family == CONV_F_WGRAD_CONV1) {
+        hipLaunchKernelGGL(conv1_wgrad_kernel, dim3(p.grid_x, p.grid_y), dim3(C1W_NT), p.lds, ctx->stream, d_x, d_gy, (float *)part, h, w,
+                           c_out, pad, h_out, w_out);
+    } else {
+        hipLaunchKernelGGL(conv3x3_bwd_weight_kernel, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), 0, ctx->stream, d_x, d_gy, d_gw, (float *)part, n,
+                           c_in, h, w, c_out, pad, h_out, w_out, weight_layout, p.img_t, 0);
+    }
+    if (hipGetLastError() != hipSuccess) { th_free(ctx, part); th::set_error("th_conv3x3_bwd_weight: launch failed"); return 1; }
+    if (int rc = wgrad_reduce(ctx, (const float *)part, d_gw, p.slabs, kt, c_out, c_out, weight_layout, accumulate)) { th_free(ctx, part); return rc; }
     return th_free(ctx, part);
 }
 
@@ -1339,7 +1447,7 @@ int th_conv1x1_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float 
         // w viewed [C_in, C_out] (tensor.rs:1262, Q3); out2d = col . w2d -> NHWC -> NCHW (+bias)
         void *tmp = nullptr;
         if (th_malloc(ctx, (size_t)n * hw * c_out * sizeof(float), &tmp)) return 1;
-        if (int rc = th_sgemm(ctx, 0, 0, n * hw, c_out, c_in, 1.0f, d_x, d_w, 0.0f, (float *)tmp)) return rc;
+        if (int rc = th_sgemm(ctx, 0, 0, n * hw, c_out, c_in, 1.0f, d_x, d_w, 0.0f, (float *)tmp)) { th_free(ctx, tmp); return rc; }
         hipLaunchKernelGGL(nhwc_to_nchw_bias_kernel, dim3(ceil_div(c_out, 64), ceil_div(hw, 64), n), dim3(256), 0, ctx->stream,
                            (const float *)tmp, d_bias, d_y, hw, c_out, relu);
         TH_LAUNCH_CHECK();
@@ -1375,12 +1483,16 @@ int th_conv2d_general_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const
     TH_REQUIRE(windows < (1L << 31) && k < (1L << 31), "th_conv2d_general_fwd: col matrix too large");
     void *col = nullptr, *tmp = nullptr;
     if (th_malloc(ctx, (size_t)(windows * k) * sizeof(float), &col)) return 1;
-    if (th_malloc(ctx, (size_t)windows * c_out * sizeof(float), &tmp)) return 1;
+    if (th_malloc(ctx, (size_t)windows * c_out * sizeof(float), &tmp)) { th_free(ctx, col); return 1; }
     hipLaunchKernelGGL(im2col_general_kernel, dim3(ew_grid((size_t)(windows * k), 256)), dim3(256), 0, ctx->stream, d_x, (float *)col, windows * k,
                        c_in, h, w, h_out, w_out, k_h, k_w, s_h, s_w, pad_h, pad_w, dil_h, dil_w);
     TH_LAUNCH_CHECK();
     // out2d[windows, c_out] = col . w viewed [k, c_out] (tensor.rs:1262, Q3) -> NHWC -> NCHW (+bias, tensor.rs:1272-1279)
-    if (int rc = th_sgemm(ctx, 0, 0, (int)windows, c_out, (int)k, 1.0f, (const float *)col, d_w, 0.0f, (float *)tmp)) return rc;
+    if (int rc = th_sgemm(ctx, 0, 0, (int)windows, c_out, (int)k, 1.0f, (const float *)col, d_w, 0.0f, (float *)tmp)) {
+        th_free(ctx, col);
+        th_free(ctx, tmp);
+        return rc;
+    }
     hipLaunchKernelGGL(nhwc_to_nchw_bias_kernel, dim3(ceil_div(c_out, 64), ceil_div(h_out * w_out, 64), n), dim3(256), 0, ctx->stream,
                        (const float *)tmp, d_bias, d_y, h_out * w_out, c_out, relu);
     TH_LAUNCH_CHECK();
