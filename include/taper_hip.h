@@ -433,6 +433,22 @@ int th_linear_q8q8_fwd(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *
 int th_linear_q8q8_fwd_pc(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum, const float *d_xscale, int batch, int in_features,
                           const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, const int8_t *d_qb, const float *d_bparams,
                           int relu, float *d_y);
+/* Either product (per_channel != 0: th_linear_q8q8_fwd_pc's d_wparams) with a destination and optional row sums: what links two int8
+ * layers without an f32 tensor between them.  Exactly one of d_y and d_qy is set.
+ *   d_qy (codes): the epilogue's f32 value v -- th_linear_q8q8_fwd's, the same operations, bias and ReLU included -- leaves as
+ *     clamp(round(v / *d_yscale) as i32, -128, 127) (NaN -> 0) at d_qy[row * pitch_y + n]: bit for bit what th_quantize_act_int8 makes of
+ *     th_linear_q8q8_fwd's output.  d_qy 16-byte aligned, pitch_y a multiple of 16 and >= out_features; the bytes out_features ..
+ *     pitch_y - 1 of every row are written 0, and nothing outside the rows [row * pitch_y, (row + 1) * pitch_y), row < batch, is written.
+ *   d_rowsum == NULL: the kernel forms the sum of every row's codes from the x codes it reads for the product (pieces at or past
+ *     ceil(in_features / 16) count as zero; the bytes in_features .. pitch_x - 1 are 0 by the contract above).  Integer sums: the bits
+ *     are those of the call with th_quantize_act_int8's sums.
+ * th_linear_q8q8_fwd's refusals (d_rowsum aside), and: neither or both destinations, codes without d_yscale, a d_qy off a 16-byte boundary,
+ * a pitch_y that is no multiple of 16 or below out_features.  A refused call writes nothing; batch == 0 returns 0.  The same tile forms and
+ * plan (th_debug_q8q8_plan). */
+int th_linear_q8q8_fwd_link(th_ctx *ctx, const int8_t *d_qx, int pitch_x, const int *d_rowsum /* nullable */, const float *d_xscale, int batch, int in_features,
+                            const int8_t *d_qw, int pitch_w, int out_features, const float *d_wparams, int per_channel, const int8_t *d_qb,
+                            const float *d_bparams, int relu, float *d_y /* f32 dest, or null */, const float *d_yscale, int8_t *d_qy,
+                            int pitch_y /* codes dest, or null */);
 int th_qlinear_i8_kstep(void);   /* bytes of K the product stages at a time (64): the pitch a caller should round in_features up to */
 int th_q8q8_max_k(void);         /* the longest K (in_features; c_in k_h k_w of a conv) the int8 products take: 65 536 */
 /* Calibration: d_range2 = {min, max} over the FINITE elements of every tensor shown so far (first != 0: of this tensor alone) and

@@ -180,19 +180,31 @@ int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *
  * conv's effective output channels, the columns of its buffer as the float kernels read it ([c_in k_h k_w][c_out]) -- each pair from the
  * finite min / max of that channel alone (th_quantize_int8_channels), and the products read them (th_linear_q8q8_fwd_pc,
  * th_conv2d_q8q8_fwd_pc, th_conv2d_q8q8_fwd_codes_pc).  Biases and every layer that stays weight-only keep one pair; calibration, scales,
- * links and refusals are those of the per-tensor twin. */
+ * links and refusals are those of the per-tensor twin.
+ * TP_QSTATIC_LINKS keeps the activations int8 through the classifier as well: a static Linear A, optionally a ReLU, then a static Linear
+ * B directly behind in the same Sequential is a link -- A's product writes B's codes with B's scale (th_linear_q8q8_fwd_link), B skips its
+ * codec and sums its rows from the codes it reads.  With CONVS and CHAIN also set, the last stage of a static conv run of at most
+ * th_qconv_i8_chain_max_cout() output channels c, optionally ONE MaxPool2d, Flatten(1), then a static Linear with in_features = c * HW
+ * and HW * th_qconv_i8_cpitch(c) <= th_q8q8_max_k() is a link too: the Linear keeps its weight rows re-laid [HW][cpitch] and reads the
+ * channel-last codes the conv (or the pool) writes with its scale.  LINKS alone is valid (Linear links only) and combines with the three
+ * flags above.  Calibration, packing, tensors, scales and every output bit are those of the same flags without LINKS; only the launches
+ * differ, and tp_qmodule_storage_bytes counts the re-laid rows of a Linear behind a Flatten link.  The value is 16: bit 8 stays an unknown
+ * bit and is refused, like -1. */
 #define TP_QSTATIC_CONVS 1
 #define TP_QSTATIC_CHAIN 2
 #define TP_QSTATIC_PER_CHANNEL 4
+#define TP_QSTATIC_LINKS 16
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out);
-/* the layer boundaries a forward crosses in int8 (the links above); 0 for every twin but tp_module_quantize_static_chain's */
+/* the layer boundaries a forward crosses in int8 (the links above: conv -> conv, Flatten, Linear -> Linear); 0 for a twin made without
+ * TP_QSTATIC_CHAIN and TP_QSTATIC_LINKS */
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out);
 /* the calibrated activation scales in layer order: *n = their count (0 for a weight-only twin), the first min(*n, cap) into h_scales (nullable) */
 int tp_qmodule_act_scales(const tp_qmodule *q, float *h_scales, int cap, int *n);
 int tp_qmodule_free(tp_qmodule *q);
 /* QuantizedModule::forward: records no tape node; the output does not require a gradient */
 int tp_qmodule_forward(const tp_qmodule *q, const tp_tensor *x, tp_tensor **out);
-/* code bytes of every tensor (a static twin's Linear weights with their row padding), plus 8 bytes of {min_val, scale} per int8 tensor
+/* code bytes of every tensor (a static twin's Linear weights with their row padding; behind a Flatten link of TP_QSTATIC_LINKS the re-laid
+ * rows of out_features * HW * cpitch bytes the twin holds instead), plus 8 bytes of {min_val, scale} per int8 tensor
  * (per channel of a per-channel tensor), 4 bytes per activation scale and 8 bytes per channel of a frozen BatchNorm2d */
 int tp_qmodule_storage_bytes(const tp_qmodule *q, size_t *out);
 /* the packed tensors in the order of the source's parameters() without those of a BatchNorm2d (its gamma and beta are not packed: see

@@ -264,7 +264,7 @@ def accuracy(pred, targets) -> float:
     return float(out.value)
 
 
-_QSTATIC_CONVS, _QSTATIC_CHAIN, _QSTATIC_PER_CHANNEL = 1, 2, 4      # include/taper_host.h's TP_QSTATIC_* flags
+_QSTATIC_CONVS, _QSTATIC_CHAIN, _QSTATIC_PER_CHANNEL, _QSTATIC_LINKS = 1, 2, 4, 16      # include/taper_host.h's TP_QSTATIC_* flags
 
 
 # -- src/nn.rs, src/activation.rs ------------------------------------------------
@@ -347,6 +347,15 @@ class Module:
         flags = (_QSTATIC_CONVS if convs or chain else 0) | (_QSTATIC_CHAIN if chain else 0) | _QSTATIC_PER_CHANNEL
         return self._quantize_static(host.tp_module_quantize_static_ex, "quantize_static_per_channel", calib, flags)
 
+    def quantize_static_linked(self, calib, per_channel=False):
+        """quantize_static_chain whose activations stay int8 through the classifier as well: a conv run's last stage (at most 128 output
+        channels, optionally one MaxPool2d, then Flatten(1)) writes the first Linear's codes channel-last, and a Linear writes the codes of
+        the Linear directly behind it (a ReLU between the two folded in) from its epilogue; a consumer sums its own rows.  One codec
+        launch at the first static layer, no f32 tensor up to the logits.  The same scales, tensors and output bits as the twin without
+        the links (per_channel: as quantize_static_per_channel's); chain_links() counts every boundary crossed in int8."""
+        flags = _QSTATIC_CONVS | _QSTATIC_CHAIN | _QSTATIC_LINKS | (_QSTATIC_PER_CHANNEL if per_channel else 0)
+        return self._quantize_static(host.tp_module_quantize_static_ex, "quantize_static_linked", calib, flags)
+
     def _quantize_static(self, entry, name, calib, *flags):
         """one static quantize call of the host library: the calibration tensors marshalled, `flags` for the entry point that takes them"""
         tensors = [calib] if isinstance(calib, Tensor) else list(calib)
@@ -381,7 +390,8 @@ class QuantizedModule:
         return n.value
 
     def chain_links(self) -> int:
-        """the layer boundaries a forward crosses in int8: 0 for every twin but quantize_static_chain's"""
+        """the layer boundaries a forward crosses in int8 -- conv -> conv (quantize_static_chain), and with quantize_static_linked also
+        Flatten into a Linear and Linear -> Linear; 0 for every other twin"""
         n = C.c_int()
         tp_check(host.tp_qmodule_chain_links(self._h, C.byref(n)), "QuantizedModule::chain_links")
         return n.value

@@ -299,6 +299,7 @@ static void quantize_static_into(const char *fn, const tp_module *m, const tp_te
     for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
     QuantizeOptions o;
     o.convs = (flags & TP_QSTATIC_CONVS) != 0, o.chain = (flags & TP_QSTATIC_CHAIN) != 0, o.per_channel = (flags & TP_QSTATIC_PER_CHANNEL) != 0;
+    o.links = (flags & TP_QSTATIC_LINKS) != 0;
     auto h = std::make_unique<tp_qmodule>();
     h->q = quantize_static(*m->m, c, o);
     h->q->tensors(&h->tensors);
@@ -323,7 +324,7 @@ int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *
 }
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
     TP_BEGIN
-    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL)) == 0, "tp_module_quantize_static_ex: unknown flag bits");
+    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL | TP_QSTATIC_LINKS)) == 0, "tp_module_quantize_static_ex: unknown flag bits");
     TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), "tp_module_quantize_static_ex: TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
     quantize_static_into("tp_module_quantize_static_ex", m, calib, n_calib, flags, out);
     TP_END
@@ -390,7 +391,10 @@ int tp_qmodule_tensor(const tp_qmodule *q, int i, void *h_codes, float *h_params
         const size_t rows = t.shape[0], k = t.shape[1];
         std::vector<char> padded(rows * t.pitch);
         taper::th_check(th_memcpy_d2h(ctx, padded.data(), t.codes->d, padded.size()), "th_memcpy_d2h");
-        for (size_t r = 0; r < rows; ++r) std::copy_n(padded.data() + r * t.pitch, k, (char *)h_codes + r * k);
+        const size_t hw = t.relaid_c ? k / t.relaid_c : 0;   // re-laid rows: column c * hw + p lies at byte p * relaid_cpitch + c
+        for (size_t r = 0; r < rows && t.relaid_c; ++r)
+            for (size_t j = 0; j < k; ++j) ((char *)h_codes)[r * k + j] = padded[r * t.pitch + (j % hw) * t.relaid_cpitch + j / hw];
+        for (size_t r = 0; r < rows && !t.relaid_c; ++r) std::copy_n(padded.data() + r * t.pitch, k, (char *)h_codes + r * k);
     } else if (h_codes && t.n) {
         taper::th_check(th_memcpy_d2h(ctx, h_codes, t.codes->d, t.qtype == TH_QTYPE_INT8 ? t.n : 2 * t.n), "th_memcpy_d2h");
     }

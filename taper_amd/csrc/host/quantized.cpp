@@ -46,6 +46,7 @@ class QPass : public QuantizedModule {
     Tensor forward(const Tensor &x) const override { return m_->forward(x); }
     bool is_relu() const { return dynamic_cast<const ReLU *>(m_.get()) != nullptr; }
     const MaxPool2d *max_pool() const { return dynamic_cast<const MaxPool2d *>(m_.get()); }
+    const Flatten *flatten() const { return dynamic_cast<const Flatten *>(m_.get()); }
 
    private:
     std::shared_ptr<Module> m_;
@@ -75,11 +76,22 @@ struct BiasPtrs {
     const int8_t *i8() const { return static_cast<const int8_t *>(codes); }
 };
 
+// where a product goes: f32 (the default), or the codes of the next layer -- made with its `scale`, rows (a Linear's) or pixels (a
+// conv's) `pitch` bytes apart; a conv's product leaves the pixel sums out when `sums` is false (a pool that follows makes them, a Linear
+// sums its own rows).  The next layer fills it: QConv::dest, QLinear::dest.
+struct QDest {
+    const float *scale = nullptr;
+    size_t pitch = 0;
+    bool sums = true;
+    explicit operator bool() const { return scale != nullptr; }
+};
+
 class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
    public:
     // o.linears: the static int8 twin (quantize_static) -- the weight codes re-laid once with rows padded to the product's K step, and one
     // activation scale on the device that calibration fixes; o.per_channel (static only): one weight pair per row
-    QLinear(const Linear &l, int qtype, QuantizeOptions o = {})
+    // keep_packed: the packed codes stay until the enclosing Sequential has resolved its links (a Flatten link re-lays from them)
+    QLinear(const Linear &l, int qtype, QuantizeOptions o = {}, bool keep_packed = false)
         : w_(o.linears && o.per_channel ? quantize_channels(l.weight, l.weight.shape()[0], l.weight.shape()[1], 1) : quantize_tensor(l.weight, qtype)),
           k_(l.weight.shape()[1]),
           n_(l.weight.shape()[0]) {
@@ -89,13 +101,69 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         w_.pitch = (k_ + step - 1) / step * step;
         auto padded = Buffer::alloc(n_ * w_.pitch / 4);
         TH(th_pad_rows_int8(Device::ctx(), reinterpret_cast<const int8_t *>(w_.codes->d), (int)n_, (int)k_, reinterpret_cast<int8_t *>(padded->d), (int)w_.pitch));
+        if (keep_packed) packed_ = w_.codes;
         w_.codes = padded;     // (the packed copy goes back to the pool: stream order keeps it alive for the launch above)
         act_.alloc();
+    }
+    // A Flatten link ahead: the input arrives as channel-last codes [hw][cpitch] of c channels, so the rows [c][hw] are re-laid
+    // once as [hw][cpitch] (the conv weight pack with hw taps) and replace the padded copy; K becomes hw * cpitch code bytes a row.
+    void link_flatten(size_t c, size_t hw, size_t cpitch) {
+        TAPER_ASSERT(packed_ && act_ && c * hw == k_, "QuantizedLinear: a Flatten link needs the packed codes of a static layer");
+        auto relaid = Buffer::alloc(n_ * hw * cpitch / 4);
+        TH(th_pack_conv_weight_int8(Device::ctx(), reinterpret_cast<const int8_t *>(packed_->d), (int)n_, (int)c, (int)hw, 1, reinterpret_cast<int8_t *>(relaid->d),
+                                    (int)cpitch));
+        w_.codes = relaid;
+        w_.pitch = hw * cpitch;
+        w_.relaid_c = c, w_.relaid_cpitch = cpitch;
+    }
+    void drop_packed() { packed_.reset(); }
+    bool is_static() const { return (bool)act_; }
+    size_t in_features() const { return k_; }
+    size_t flat_hw() const { return w_.relaid_c ? k_ / w_.relaid_c : 0; }   // > 0: behind a Flatten link
+    // this layer as the destination of the product ahead: its scale, and the pitch of the code rows it reads (a conv ahead: of a pixel)
+    QDest dest() const { return QDest{act_.scale(), w_.relaid_c ? w_.relaid_cpitch : pitch_x(), /*sums=*/false}; }
+    // int8 codes of x and their row sums (pooled), with this layer's scale
+    struct Codes {
+        std::shared_ptr<Buffer> q, rs;   // rs empty: the product sums the rows itself
+        size_t batch = 0;
+    };
+    Codes encode(const Tensor &x) const {
+        TAPER_ASSERT(x.shape().size() == 2 && x.shape()[1] == k_, "QuantizedLinear: input must be [batch, in_features]");
+        TAPER_ASSERT(!w_.relaid_c, "QuantizedLinear: a layer behind a Flatten link takes codes");
+        const size_t batch = x.shape()[0];
+        Codes in{Buffer::alloc(std::max<size_t>(batch * pitch_x() / 4, 1)), Buffer::alloc(std::max<size_t>(batch, 1)), batch};
+        TH(th_quantize_act_int8(Device::ctx(), x.dptr(), (int)batch, (int)k_, act_.scale(), reinterpret_cast<int8_t *>(in.q->d), (int)pitch_x(),
+                                reinterpret_cast<int *>(in.rs->d)));
+        return in;
+    }
+    struct Output {   // what the QDest asked for; the other member stays empty
+        Tensor y;
+        Codes codes;
+    };
+    // the integer product on codes made with this layer's scale, rows pitch_x() apart (behind a Flatten link: the hw * cpitch bytes of an image)
+    Output product(const Codes &in, bool relu, QDest d = {}) const {
+        const BiasPtrs b(b_);
+        const size_t kk = w_.relaid_c ? w_.pitch : k_;   // code bytes of K a row (re-laid: the padded channels are zeros on both sides)
+        Output out;
+        float *y = nullptr;
+        int8_t *qy = nullptr;
+        if (d) {
+            out.codes = Codes{Buffer::alloc(std::max<size_t>(in.batch * d.pitch / 4, 1)), nullptr, in.batch};
+            qy = reinterpret_cast<int8_t *>(out.codes.q->d);
+        } else {
+            out.y = Tensor::empty({in.batch, n_});
+            y = out.y.dptr();
+        }
+        TH(th_linear_q8q8_fwd_link(Device::ctx(), reinterpret_cast<const int8_t *>(in.q->d), (int)pitch_x(), in.rs ? reinterpret_cast<const int *>(in.rs->d) : nullptr,
+                                   act_.scale(), (int)in.batch, (int)kk, reinterpret_cast<const int8_t *>(w_.codes->d), (int)w_.pitch, (int)n_, w_.params->d,
+                                   w_.per_channel() ? 1 : 0, b.i8(), b.params, relu ? 1 : 0, y, d.scale, qy, (int)d.pitch));
+        return out;
     }
     Tensor forward(const Tensor &x) const override { return forward_relu(x, false); }
     // x . deq(W)^T + deq(b), and the ReLU behind it in the same launch when the Sequential twin pairs them
     Tensor forward_relu(const Tensor &x, bool relu) const {
         TAPER_ASSERT(x.shape().size() == 2 && x.shape()[1] == k_, "QuantizedLinear: input must be [batch, in_features]");
+        TAPER_ASSERT(!w_.relaid_c, "QuantizedLinear: a layer behind a Flatten link takes codes");
         const size_t batch = x.shape()[0];
         Tensor y = Tensor::empty({batch, n_});
         th_ctx *ctx = Device::ctx();
@@ -123,10 +191,13 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
     const ActScale &act() const { return act_; }
 
    private:
+    // bytes from one row of input codes to the next: in_features rounded up to a piece; behind a Flatten link the image's hw * cpitch
+    size_t pitch_x() const { return w_.relaid_c ? w_.pitch : (k_ + 15) / 16 * 16; }
     QTensor w_;
     std::unique_ptr<QTensor> b_;
     size_t k_, n_;
-    ActScale act_;   // static only
+    ActScale act_;                     // static only
+    std::shared_ptr<Buffer> packed_;   // the packed codes, while the links are being resolved
 };
 
 // A BatchNorm2d frozen on its running pair: {a, b} per channel, made on the device when the twin is made -- a snapshot, the
@@ -172,13 +243,6 @@ struct QEpilogue {
     bool relu = false;
     const QBatchNorm *bn = nullptr;
 };
-// where the product goes: f32 NCHW (the default), or the codes of `next` (its scale, its pitch), without pixel sums when `sums` is false
-// (a pool that follows makes them)
-struct QDest {
-    const class QConv *next = nullptr;
-    bool sums = true;
-};
-
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
    public:
     // The integer product is a convolution, so it stands in for the float layer only where the float path is one: 3x3, stride 1, one
@@ -220,6 +284,7 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         Tensor y;
         QCodes codes;
     };
+    QDest dest(bool sums) const { return QDest{act_.scale(), cpitch_, sums}; }   // this layer as the destination of the product ahead
     // the integer product on codes made with this layer's scale
     Output product(const QCodes &in, QEpilogue e, QDest d = {}) const {
         const Shape &ws = w_.shape;
@@ -236,16 +301,16 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
                      reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold, tail...));
         };
         Output out;
-        if (!d.next) {
+        if (!d) {
             out.y = Tensor::empty({in.n, ws[0], ho, wo});
             if (e.bn) run(th_conv2d_q8q8_fwd_affine, out.y.dptr(), pc, e.bn->pairs());
             else run(pc ? th_conv2d_q8q8_fwd_pc : th_conv2d_q8q8_fwd, out.y.dptr());
             return out;
         }
-        QCodes &q = out.codes = QCodes::alloc(in.n, ws[0], ho, wo, d.next->cpitch_);
+        QCodes &q = out.codes = QCodes::alloc(in.n, ws[0], ho, wo, d.pitch);
         int *sums = d.sums ? q.pixsum() : nullptr;
-        if (e.bn) run(th_conv2d_q8q8_fwd_codes_affine, d.next->act_.scale(), q.codes(), (int)q.cpitch, sums, pc, e.bn->pairs());
-        else run(pc ? th_conv2d_q8q8_fwd_codes_pc : th_conv2d_q8q8_fwd_codes, d.next->act_.scale(), q.codes(), (int)q.cpitch, sums);
+        if (e.bn) run(th_conv2d_q8q8_fwd_codes_affine, d.scale, q.codes(), (int)q.cpitch, sums, pc, e.bn->pairs());
+        else run(pc ? th_conv2d_q8q8_fwd_codes_pc : th_conv2d_q8q8_fwd_codes, d.scale, q.codes(), (int)q.cpitch, sums);
         return out;
     }
     void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
@@ -320,7 +385,12 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
         const MaxPool2d *pool = nullptr;
         const QConv *next = nullptr;
     };
-    // What forward runs, in order; one of four kinds.  Every layer of `layers` belongs to exactly one step: the one that runs it or folds it.
+    // A static Linear's place in a run of them: `relu` = the ReLU layer behind it, in its epilogue
+    struct LinStage {
+        const QLinear *lin = nullptr;
+        bool relu = false;
+    };
+    // What forward runs, in order; one of five kinds.  Every layer of `layers` belongs to exactly one step: the one that runs it or folds it.
     struct Step {
         const QuantizedModule *plain = nullptr;   // any other layer (a nested Sequential's twin among them): its own forward
         const QLinear *lin = nullptr;             // a Linear, `relu`: with the ReLU behind it in the same launch
@@ -328,18 +398,37 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
         const QConv *weight_only = nullptr;       // a weight-only conv, its weights at `slot` of the call's dequantize workspace
         size_t slot = 0;
         std::vector<Stage> run;                   // static convs: one codec, codes across every link, the last stage writes f32
+        // with `links`, static Linears: the first takes f32 (one codec) or, behind `run` across a Flatten link (`flat`: the run's last stage
+        // writes this Linear's codes, through `pool` if set, and the Flatten layer is folded), codes; every inner boundary is a link; the
+        // last writes f32
+        std::vector<LinStage> lrun;
+        bool flat = false;
     };
     // The steps, once `layers` is complete: nothing they depend on changes afterwards (is_static() is fixed when a conv twin is made,
-    // calibration only fills scales).  chain = quantize_static's chain: activations stay int8 across a link.
-    void resolve(bool chain) {
+    // calibration only fills scales).  chain = quantize_static's chain: activations stay int8 across a link; links: through the Linears too.
+    void resolve(bool chain, bool links = false) {
         auto pass = [&](size_t j) { return j < layers.size() ? dynamic_cast<const QPass *>(layers[j].get()) : nullptr; };
         auto stat = [&](size_t j) {
             auto *c = j < layers.size() ? dynamic_cast<const QConv *>(layers[j].get()) : nullptr;
             return c && c->is_static() ? c : nullptr;
         };
+        auto slin = [&](size_t j) {
+            auto *l = j < layers.size() ? dynamic_cast<QLinear *>(layers[j].get()) : nullptr;
+            return l && l->is_static() ? l : nullptr;
+        };
+        // the run of static Linears that begins at layer i: [ReLU] and the next static Linear directly behind is a link
+        auto linear_run = [&](size_t &i, Step &s) {
+            for (const QLinear *l = slin(i); l; l = slin(i)) {
+                LinStage st{l, pass(i + 1) && pass(i + 1)->is_relu()};
+                i += st.relu ? 2 : 1;
+                s.lrun.push_back(st);
+            }
+        };
         for (size_t i = 0; i < layers.size();) {
             Step s;
-            if ((s.lin = dynamic_cast<const QLinear *>(layers[i].get()))) {
+            if (links && slin(i)) {
+                linear_run(i, s);
+            } else if ((s.lin = dynamic_cast<const QLinear *>(layers[i].get()))) {
                 s.relu = pass(i + 1) && pass(i + 1)->is_relu();   // Linear + ReLU: one launch, the ReLU in its epilogue
                 i += s.relu ? 2 : 1;
             } else if (stat(i)) {   // conv + ReLU: the ReLU in the product's epilogue
@@ -359,11 +448,21 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
                     if (chain && cv->out_channels() <= (size_t)th_qconv_i8_chain_max_cout()) {
                         size_t j = after;
                         if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
-                        if ((st.next = stat(j))) i = j;   // a link: the run goes on there
-                        else st.pool = nullptr;           // (a pool counts only when a static conv follows it)
+                        QLinear *fl = links && pass(j) && pass(j)->flatten() && pass(j)->flatten()->start_dim == 1 ? slin(j + 1) : nullptr;
+                        const size_t c = cv->out_channels(), cpitch = (size_t)th_qconv_i8_cpitch((int)c);
+                        if ((st.next = stat(j))) {
+                            i = j;   // a link: the run goes on there
+                        } else if (fl && fl->in_features() % c == 0 && fl->in_features() / c * cpitch <= (size_t)th_q8q8_max_k()) {
+                            fl->link_flatten(c, fl->in_features() / c, cpitch);   // a Flatten link: the Linears take over from there
+                            s.flat = true;
+                            i = j + 1;
+                        } else {
+                            st.pool = nullptr;   // (a pool counts only when a static conv or a Flatten link follows it)
+                        }
                     }
                     s.run.push_back(st);
                 }
+                if (s.flat) linear_run(i, s);
             } else if ((s.weight_only = dynamic_cast<const QConv *>(layers[i].get()))) {
                 s.slot = weight_only_.size();
                 weight_only_.push_back(s.weight_only);
@@ -373,6 +472,8 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
             }
             steps_.push_back(std::move(s));
         }
+        for (auto &l : layers)
+            if (auto *ql = dynamic_cast<QLinear *>(l.get())) ql->drop_packed();
     }
     Tensor forward(const Tensor &input) const override {
         // every weight-only conv step's weights in one dequantize launch, into one workspace that lives for this call
@@ -381,22 +482,36 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
         if (!weight_only_.empty()) ws = QConv::dequantize(weight_only_, &at);
         Tensor x = input;
         for (const Step &s : steps_) {
+            QLinear::Codes rows;   // what the Linear run reads
             if (s.lin) {
                 x = s.lin->forward_relu(x, s.relu);
             } else if (s.weight_only) {
                 x = s.weight_only->forward_with(x, at[s.slot].first, at[s.slot].second);
             } else if (s.plain) {
                 x = s.plain->forward(x);
-            } else {   // a run: one codec, then codes from product to product (pooled buffers, each returned when `cur` moves on)
+            } else if (!s.run.empty()) {   // a run: one codec, then codes from product to product (pooled buffers, each returned when `cur` moves on)
                 QCodes cur = s.run[0].conv->encode(x);
                 for (const Stage &st : s.run) {
-                    if (!st.next) {
+                    const bool last = !st.next;
+                    if (last && !s.flat) {
                         x = st.conv->product(cur, st.fold).y;
                     } else {
-                        QCodes out = st.conv->product(cur, st.fold, {st.next, /*sums=*/!st.pool}).codes;
+                        QCodes out = st.conv->product(cur, st.fold, last ? s.lrun[0].lin->dest() : st.next->dest(/*sums=*/!st.pool)).codes;
                         cur = st.pool ? max_pool_codes(out, *st.pool) : out;
                     }
                 }
+                if (s.flat) {   // the map as rows of h w cpitch code bytes: what Flatten would give the Linear, channel-last
+                    TAPER_ASSERT(cur.h * cur.w == s.lrun[0].lin->flat_hw(), "QuantizedLinear: input must be [batch, in_features]");
+                    rows = QLinear::Codes{cur.q, nullptr, cur.n};
+                }
+            } else {
+                rows = s.lrun[0].lin->encode(x);
+            }
+            for (size_t k = 0; k < s.lrun.size(); ++k) {   // codes from product to product, the last writes f32
+                const LinStage &st = s.lrun[k];
+                auto out = st.lin->product(rows, st.relu, k + 1 < s.lrun.size() ? s.lrun[k + 1].lin->dest() : QDest{});
+                rows = out.codes;
+                x = out.y;
             }
         }
         return x;
@@ -412,7 +527,10 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     }
     int chain_links() const override {
         int links = 0;
-        for (const Step &s : steps_) links += s.plain ? s.plain->chain_links() : s.run.empty() ? 0 : (int)s.run.size() - 1;
+        for (const Step &s : steps_) {
+            if (s.plain) links += s.plain->chain_links();
+            links += (s.run.empty() ? 0 : (int)s.run.size() - 1) + (s.flat ? 1 : 0) + (s.lrun.empty() ? 0 : (int)s.lrun.size() - 1);
+        }
         return links;
     }
 
@@ -460,17 +578,18 @@ std::vector<const Module *> leaves_of(const Module &m) {
     return out;
 }
 
-std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, QuantizeOptions o = {}) {
+// nested: `m` is a layer of a Sequential twin in the making (which resolves the links of its layers when they are complete)
+std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, QuantizeOptions o = {}, bool nested = false) {
     const std::vector<const Module *> leaves = leaves_of(m);
     if (dynamic_cast<const Sequential *>(&m) || leaves.size() > 1) {   // (more than one leaf of another module: a Sequential twin of them)
         auto q = std::make_unique<QSequential>();
-        for (const Module *l : leaves) q->layers.push_back(quantize_checked(*l, qtype, o));
-        q->resolve(o.chain);
+        for (const Module *l : leaves) q->layers.push_back(quantize_checked(*l, qtype, o, /*nested=*/true));
+        q->resolve(o.chain, o.links);
         return q;
     }
     const Module &l = *leaves[0];
     if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) return std::make_unique<QBatchNorm>(*bn);
-    if (auto *lin = dynamic_cast<const Linear *>(&l)) return std::make_unique<QLinear>(*lin, qtype, o);
+    if (auto *lin = dynamic_cast<const Linear *>(&l)) return std::make_unique<QLinear>(*lin, qtype, o, /*keep_packed=*/nested && o.links && o.chain);
     if (auto *c = dynamic_cast<const Conv2d *>(&l)) return std::make_unique<QConv>(*c, qtype, o);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(l)) && !(p = copy_of<Sigmoid>(l)) && !(p = copy_of<MaxPool2d>(l)) && !(p = copy_of<AvgPool2d>(l)) &&

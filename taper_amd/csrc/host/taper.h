@@ -486,7 +486,11 @@ struct QTensor {   // a QuantizedTensor (tensor.rs:2084-2108) on the device: cod
     // channels > 1: one {min_val, scale} pair per channel (params holds 2 * channels floats), element k of channel c at index
     // c * chan_stride + k * elem_stride of the packed codes (th_quantize_int8_channels); 1, 0, 1: one pair for the tensor
     size_t channels = 1, chan_stride = 0, elem_stride = 1;
+    // relaid_c > 0 (a Linear behind a Flatten link): the padded rows hold the packed row [relaid_c][hw] as [hw][relaid_cpitch]
+    // with zeros in the padded channels -- column c * hw + p of the packed row at byte p * relaid_cpitch + c; pitch = hw * relaid_cpitch
+    size_t relaid_c = 0, relaid_cpitch = 0;
     bool per_channel() const { return chan_stride != 0; }
+    // the code bytes the twin actually holds (padded or re-laid rows with their padding), and 8 bytes per {min_val, scale} pair
     size_t storage_bytes() const { return qtype == TH_QTYPE_INT8 ? (pitch ? shape[0] * pitch : n) + channels * 2 * sizeof(float) : 2 * n; }
     th_qtensor item(float *d_out) const;
 };
@@ -497,7 +501,7 @@ class QuantizedModule {
     virtual Tensor forward(const Tensor &input) const = 0;
     virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
     virtual void act_scales(std::vector<const float *> *out) const {}  // device addresses of the calibrated activation scales, in layer order
-    virtual int chain_links() const { return 0; }                      // layer boundaries a forward crosses in int8 (quantize_static's chain)
+    virtual int chain_links() const { return 0; }                      // layer boundaries a forward crosses in int8 (quantize_static's chain and links)
     // every frozen BatchNorm2d in layer order: the device address of its [channels][2] = {a, b} and its channels
     virtual void affines(std::vector<std::pair<const float *, size_t>> *out) const {}
 };
@@ -529,9 +533,19 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // in that conv's epilogue (th_conv2d_q8q8_fwd_affine / _codes_affine) with its own or a following ReLU behind it, so a link of `chain` is
 // static conv, [BatchNorm2d], [ReLU], [one MaxPool2d], static conv; behind anything else it is one streaming launch
 // (th_channel_affine_fwd).  Calibration runs the float layer in eval mode; nothing of the source is modified.
-// (linears: set by quantize_static itself -- every Linear static; quantize() leaves all four off)
+// links: the same twin once more -- scales, tensors and every output bit -- whose activations stay int8 through the classifier.
+// Linear -> Linear: a static Linear A, optionally a ReLU (in A's epilogue as before), then a static Linear B directly behind in the same
+// Sequential: A's product writes B's codes with B's scale (th_linear_q8q8_fwd_link), B skips its codec and sums its rows from the codes it
+// reads.  Flatten (with convs and chain): the last stage of a static conv run of at most th_qconv_i8_chain_max_cout() output channels c
+// (BatchNorm2d / ReLU folded in), optionally one MaxPool2d, Flatten(1), then a static Linear with in_features = c * HW and
+// HW * cpitch(c) <= th_q8q8_max_k(): the conv (or the pool) writes channel-last codes with the Linear's scale, and the Linear reads them
+// as rows of HW * cpitch bytes against its weight rows re-laid [HW][cpitch] once when the twin is made (the zero codes of the padded
+// channels add nothing; integer sums have no order).  Such a weight's storage_bytes() counts the re-laid rows, tensors() still gives the
+// packed codes.  Anything else at a boundary (a Sigmoid, a nested Sequential, another Flatten, an AvgPool, a wider conv) is no link and runs
+// as before.  chain_links() counts every int8 boundary: conv -> conv, Flatten, Linear -> Linear.
+// (linears: set by quantize_static itself -- every Linear static; quantize() leaves all five off)
 struct QuantizeOptions {
-    bool linears = false, convs = false, chain = false, per_channel = false;
+    bool linears = false, convs = false, chain = false, per_channel = false, links = false;
 };
 std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, QuantizeOptions o = {});
 
