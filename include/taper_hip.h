@@ -262,6 +262,10 @@ int th_mlp_tail(th_ctx *ctx, const float *d_x, const float *d_h, const float *d_
                 const float *d_w1, float *d_dx,
                 float *d_metrics, int64_t metrics_capacity, int64_t *d_state, int64_t advance,
                 const th_adam_fuse *w1_fuse, const th_adam_fuse *b1_fuse);
+/* th_mlp_tail's whole-tile launch for batch <= 64 and hidden <= 128 splits each 16-row block between a LOGIT wave (logits, softmax) and an
+ * OPERAND wave (everything the gradient products need, requested meanwhile): 576 threads per workgroup, same bits.  on = 0: the 320-thread
+ * launch whatever the shape -- the form tests and tools compare with.  Default 1. */
+int th_mlp_tail_set_split(th_ctx *ctx, int on);
 
 /* A three-layer classifier -- Linear + ReLU, Linear + ReLU, Linear, softmax cross-entropy (the tail of examples/train_mnist_cnn.rs:53-61
  * behind the global average pool; examples/train_mnist.rs:40-48 behind the images) -- forward AND backward in TWO launches: everything but

@@ -126,6 +126,7 @@ struct th_ctx {
     int32_t *err_word = nullptr;                      // this device's error block (host-visible; shared by the contexts of a device)
     int m2_max_ksplit = 8;                            // mlp2.hip: cap on the workgroups sharing a row block's k chunks (th_mlp2_set_max_ksplit; 1 = no split)
     bool fwd_subtiles = true;                         // gemm.hip: th_linear_fwd_ex may cut its 16 x 16 tiles into sub-tiles (th_linear_fwd_ex_set_subtiles; off = the 16 x 16 launch)
+    bool tail_split = true;                           // mlp_tail.hip: th_mlp_tail's helper-wave instances run logit and operand waves side by side (th_mlp_tail_set_split; off = the 320-thread launch)
     const uint32_t *update_guard = nullptr;           // th_ctx_set_update_guard: deferred updates / counter ticks do nothing once this device word is non-zero
     uint32_t *update_step_word = nullptr;             // ... and a tick that happens advances this word too (the in-launch exchange's step number, dp_dev.h)
     unsigned *m2_arrive = nullptr;                    // mlp2.hip: arrival counters of k-split row blocks (zero between launches); plain hipMalloc, freed with the ctx

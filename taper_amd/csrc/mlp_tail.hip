@@ -73,9 +73,26 @@ __device__ __forceinline__ void tail_prof_end(long long now) {
         }                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
+// mlp_tail_split_kernel: TAIL_STAMP is lane 0 of logit wave 0 (thread 0), TAIL_STAMP_OP lane 0 of operand wave 4 (thread 256), into a
+// table of its own; its stamp 7 is also the workgroup's end in g_tail_prof_all (the operand waves end the workgroup)
+__device__ long long g_tail_prof_op[256][8];
+#define TAIL_STAMP_OP(i)                                                                      \
+    do {                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        if (threadIdx.x == 256 && blockIdx.x < 256) {                                         \
+            const long long now_ = wall_clock64();                                            \
+            g_tail_prof_op[blockIdx.x][i] = now_;                                             \
+            if ((i) == 7) {                                                                   \
+                if (blockIdx.x == 0) tail_prof_end(now_);                                     \
+                else g_tail_prof_all[blockIdx.x][7] = now_;                                   \
+            }                                                                                 \
+        }                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+    } while (0)
 __global__ void tail_prof_mark_kernel(int i) { g_tail_prof[0][i] = g_tail_prof[1][i] = wall_clock64(); }
 #else
 #define TAIL_STAMP(i) do { } while (0)
+#define TAIL_STAMP_OP(i) do { } while (0)
 #endif
 
 // th_log_step's slot for step number state0: state0 mod capacity (capacity > 0), 32-bit when both fit -- the 64-bit remainder is a
@@ -507,10 +524,11 @@ __device__ __forceinline__ void tail_lead_log(const TailArgs &a, const float (*s
 // launch, and four ranks of the 784-64-10 model on one device (3 x 108 waiting workgroups on 256 CUs) then starve the late rank.
 constexpr int tail_helper_waves(int KS, int NW, int DPNR) { return (NW == 4 && KS <= 8 && DPNR == 0) ? 1 : 0; }
 
-template <int NW>
+template <int NW, bool SPLIT = false>
 __device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_role, bool lead, bool any_w, bool any_b, float *h_step,
                                                  const float (*sc)[36]) {
     const int lane = threadIdx.x & 63;
+    if constexpr (SPLIT) __syncthreads();   // mlp_tail_split_kernel's barrier 0 (W2's image is whole), at once: its logit waves wait for it
     // the counter / learning rate of the workgroup's fused update: plain scalar loads (nobody writes the counter in this launch)
     float step = 0.f;
     if (head_role ? any_b : any_w) {
@@ -527,6 +545,7 @@ __device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_ro
         state1_next = state1 + a.advance;
     }
     if (lane == 0) *h_step = step;
+    if constexpr (SPLIT) __syncthreads();   // mlp_tail_split_kernel: the barrier between its logit and its operand waves
     __syncthreads();                      // the working waves' final barrier
     if (lead) {
         if (a.db2 && lane < a.c) {
@@ -904,6 +923,323 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
     TAIL_STAMP(7);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The instances with a helper wave (4 working waves, hidden <= 128, no in-launch exchange), SPLIT: 576 threads.  A lone wave per SIMD is
+// issue-bound, and the longest stretch of the 320-thread form is the issue of its 43 loads, none of which depends on memory; so each 16-row
+// block j gets a PAIR of waves on one SIMD (waves j and 4 + j: the hardware deals waves to SIMDs round robin) that issue side by side:
+//   logit wave j         its 16 rows of H, targets, b2 and its SHARE of W2 as the logits' operand (k-slices j, j + 4, ..): the four logit
+//                        waves would fetch the same image (8 KB at hidden 128), so each fetches a quarter, stores it to LDS (wimg) and,
+//                        behind barrier 0, reads the whole image back; the 32 logits MFMAs, the softmax; parks dlogits in tr[j] (and, in
+//                        the lead, the rows' NLL and hit flags in rowv[j]) in the layout the lane holds; barrier 1; nothing more but
+//                        barrier 2
+//   operand wave 4 + j   everything behind the softmax needs -- W2 as dH's operand, the ReLU mask, X (dW1 role), the p / m / v it finishes --
+//                        requested before barrier 0; behind barrier 1 dlogits back from tr[j] (lane l reads what lane l of wave j wrote)
+//                        and the 320-thread form's code from its dH MFMAs on, with `wave` = j: the same MFMA chains from the same zeros,
+//                        the same wave order in every cross-wave sum
+//   wave 8               the helper (tail_helper_wave): barrier 0 at once, its work, barriers 1 and 2
+// The role is chosen once, wave-uniformly; head_role / tn_ok / any_w / any_b are workgroup-uniform and tested once per block of loads.
+// A pair whose rows are absent (batch < 64) loads nothing but the logit wave's share of W2, contributes the zeros it contributed before
+// and meets every barrier.  Every wave that gets past the workgroup-uniform returns meets EXACTLY three workgroup barriers (a miscount
+// hangs the device: count the s_barriers of each path in the listing after any change here); in the dX role (no barriers) the operand
+// waves leave where the helper leaves.  NW == 4 is launched for batch <= 64 only: ONE chunk, so there is no chunk loop here.
+// Measured in profiles/mlp_tail_split.md.
+template <int KS, int TN, bool HAS_DX>
+__global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
+    constexpr int NW = 4;
+    static_assert(tail_helper_waves(KS, NW, 0) != 0, "the split form replaces exactly the instances that have the helper wave");
+    constexpr unsigned HID = 16 * KS;
+    __shared__ float h_step;
+    __shared__ float red[NW][TN][64][4];
+    __shared__ float tr[NW][16][17];                 // dlogits of pair j: [row][class]; the padding is for the head role's transposed reads
+    __shared__ float rowv[NW][2][16];
+    __shared__ float sc[NW][36];
+    __shared__ float4 wimg[KS][64];                  // W2 as the logits' A operand, fetched once per workgroup: [k-slice][lane]
+    asm volatile("" ::"s"(a.x), "s"(a.h), "s"(a.w2), "s"(a.b2), "s"(a.targets), "s"(a.batch), "s"(a.in_f), "s"(a.c), "s"(a.dw1),
+                 "s"(a.db1), "s"(a.w1_adam.p), "s"(a.w1_adam.m), "s"(a.w1_adam.v), "s"(a.w1_adam.t), "s"(a.w1_adam.lr),
+                 "s"(a.b1_adam.p), "s"(a.b1_adam.t), "s"(a.b1_adam.lr), "s"(a.n_dw), "s"(a.n_head), "s"(a.groups), "s"(a.metrics),
+                 "s"(a.state));
+    const int t = threadIdx.x, lane = t & 63, r16 = lane & 15, g4 = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int bid = blockIdx.x;
+    TAIL_STAMP(0);
+    TAIL_STAMP_OP(0);
+    if (HAS_DX && bid >= a.n_head + a.n_dw) {
+        if (wave < NW) tail_dx_role<KS, NW>(a, bid - a.n_head - a.n_dw);   // (no barriers in this role: operand waves and helper just leave)
+        return;
+    }
+    const bool head_role = bid < a.n_head;
+    int tile_m, grp = 0;
+    if (!head_role) {   // (the block order of mlp_tail_exact_kernel)
+        const int b2 = bid - a.n_head;
+        const int tt = (b2 & 7) * (a.n_dw >> 3) + (b2 >> 3);
+        if (tt >= KS * a.groups) return;             // the whole workgroup
+        tile_m = tt % KS;
+        grp = tt / KS;
+    } else {
+        tile_m = bid;
+        if (tile_m >= KS) return;                    // the whole workgroup
+    }
+    const int C = a.c, B = a.batch;
+    const unsigned in_f = (unsigned)a.in_f;
+    const bool lead = head_role && tile_m == 0;
+    const bool any_w = a.w1_adam.p != nullptr, any_b = a.db1 && a.b1_adam.p != nullptr;
+    if (wave == 2 * NW) {
+        tail_helper_wave<NW, true>(a, head_role, lead, any_w, any_b, &h_step, sc);
+        return;
+    }
+    const int j = wave & (NW - 1);                   // the pair, its rows 16 j .. 16 j + 15: all valid or all absent
+    const int r0 = j * 16;
+    const bool rows_here = r0 < B;
+
+    if (wave < NW) {
+        // ---- logit wave j ----
+        // its share of W2 as the logits' A operand, W2[class r16][16 ks + 4 g4 ..] (rows >= C: a copy of row C-1, masked at the logits):
+        // k-slices j, j + 4, .. of the KS -- the image is fetched ONCE per workgroup and goes round through LDS
+        constexpr int NSL = (KS + NW - 1) / NW;
+        float4 wsl[NSL];
+        const unsigned w_off = ((unsigned)min(r16, C - 1) * HID + g4 * 4) * 4u;
+#pragma unroll
+        for (int q = 0; q < NSL; ++q)
+            if (q * NW + j < KS) wsl[q] = ldg4_b(a.w2, w_off + (q * NW + j) * 64);
+        auto put_slices = [&]() {
+#pragma unroll
+            for (int q = 0; q < NSL; ++q)
+                if (q * NW + j < KS) wimg[q * NW + j][lane] = wsl[q];
+        };
+        if (!rows_here) {   // (a path of its own: behind a merge, the wait for the slices is a wait for every load of the longer path)
+            put_slices();
+            __syncthreads();                         // barrier 0
+            __syncthreads();                         // barrier 1
+            __syncthreads();                         // barrier 2
+            return;
+        }
+        float4 wv[KS], hv[KS];                       // H[r0 + r16][16 ks + 4 g4 ..]
+        const unsigned h_off = ((unsigned)(r0 + r16) * HID + g4 * 4) * 4u;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) hv[ks] = ldg4_b(a.h, h_off + ks * 64);
+        const float tf = ldg_b(a.targets, (unsigned)(r0 + r16) * 4u);
+        float b2v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (a.b2) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) b2v[s] = ldg_b(a.b2, (unsigned)min(g4 * 4 + s, C - 1) * 4u);
+        }
+        TAIL_STAMP(1);
+        put_slices();
+        __syncthreads();                             // barrier 0: the image is whole
+        TAIL_STAMP(3);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) wv[ks] = wimg[ks][lane];
+        // ---- logits^T (nn.rs:54-60): four independent accumulation chains, one per float4 component ----
+        floatx4 ax = {0.f, 0.f, 0.f, 0.f}, ay = ax, az = ax, aw = ax;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            ax = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].x, hv[ks].x, ax, 0, 0, 0);
+            ay = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].y, hv[ks].y, ay, 0, 0, 0);
+            az = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].z, hv[ks].z, az, 0, 0, 0);
+            aw = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].w, hv[ks].w, aw, 0, 0, 0);
+        }
+        float lg[4], dl[4], nll_row;
+        int bi;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lg[i] = (g4 * 4 + i < C) ? ((ax[i] + ay[i]) + (az[i] + aw[i])) + b2v[i] : -INFINITY;
+        tail_row_softmax(lg, g4, C, tf, 1.0f / (float)B, dl, nll_row, bi);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) tr[j][r16][g4 * 4 + i] = dl[i];
+        if (lead && g4 == 0) {
+            rowv[j][0][r16] = nll_row;
+            rowv[j][1][r16] = (fabsf((float)bi - tf) < 1e-6f) ? 1.f : 0.f;   // loss.rs:283
+        }
+        TAIL_STAMP(4);
+        __syncthreads();                             // barrier 1: dlogits are parked
+        __syncthreads();                             // barrier 2: the operand waves' final barrier
+        return;
+    }
+
+    // ---- operand wave 4 + j ----
+    const unsigned hcol = tile_m * 16 + r16;
+    const unsigned hm_off = ((unsigned)(r0 + g4 * 4) * HID + hcol) * 4u;
+    float w2b[4], hm[4];                             // W2[class 4 g4 + s][hcol] (classes >= C meet dl == 0), H[r0 + 4 g4 + s][hcol]
+#pragma unroll
+    for (int s = 0; s < 4; ++s) w2b[s] = hm[s] = 0.f;
+    float dl[4] = {0.f, 0.f, 0.f, 0.f};
+    // dH tile (ops.rs:254-265) and the ReLU mask of the hidden layer (ops.rs:358-369, Q15), from the parked dlogits
+    auto dh_masked = [&](float (&dhm)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dl[i] = tr[j][r16][g4 * 4 + i];
+        floatx4 dh = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) dh = __builtin_amdgcn_mfma_f32_16x16x4f32(dl[s], w2b[s], dh, 0, 0, 0);
+        // (left alone the compiler forms the four hm > 0 masks where hm is loaded: a wait for H in front of barrier 1, with the p / m / v
+        // loads requested only behind it -- a second, serialised round trip)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(hm[i]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dhm[i] = hm[i] > 0.f ? dh[i] : 0.f;
+    };
+
+    if (!head_role) {
+        // ---- dW1 role: one 16-hidden x (16 TN)-input block ----
+        const unsigned col0 = grp * 16 * TN;
+        bool tn_ok[TN];                              // workgroup-uniform; tn_ok[0] always holds (col0 < in_f)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) tn_ok[tn] = col0 + tn * 16 < in_f;
+        float xv[TN][4];                             // X[r0 + 4 g4 + s][col0 + 16 tn + r16]
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) xv[tn][s] = 0.f;
+        if (rows_here) {
+            const unsigned x_off = ((unsigned)(r0 + g4 * 4) * in_f + col0 + r16) * 4u;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) w2b[s] = ldg_b(a.w2, ((unsigned)min(g4 * 4 + s, C - 1) * HID + hcol) * 4u);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) hm[s] = ldg_b(a.h, hm_off + s * HID * 4);
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+                if (tn > 0 && !tn_ok[tn]) continue;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) xv[tn][s] = ldg_b(a.x, x_off + s * in_f * 4u + tn * 64);
+            }
+        }
+        // epilogue operands: operand wave 4 + e finishes element e of every lane's C/D quad (row 4 g4 + e of the tile)
+        const unsigned e_off = ((tile_m * 16 + g4 * 4 + j) * in_f + col0 + r16) * 4u;
+        float e_p[TN], e_m[TN], e_v[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) e_p[tn] = e_m[tn] = e_v[tn] = 0.f;
+        if (any_w) {
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+                if (tn > 0 && !tn_ok[tn]) continue;
+                e_p[tn] = ldg_b(a.w1_adam.p, e_off + tn * 64);
+                e_m[tn] = ldg_b(a.w1_adam.m, e_off + tn * 64);
+                e_v[tn] = ldg_b(a.w1_adam.v, e_off + tn * 64);
+            }
+        }
+        TAIL_STAMP_OP(1);
+        __syncthreads();                             // barrier 0
+        __syncthreads();                             // barrier 1
+        TAIL_STAMP_OP(3);
+        floatx4 accdw[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) accdw[tn] = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (rows_here) {
+            float dhm[4];
+            dh_masked(dhm);
+            // ---- dW1 block (ops.rs:280-291 through the W^T node, tensor.rs:574-587) ----
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn)
+                    accdw[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(dhm[s], xv[tn][s], accdw[tn], 0, 0, 0);
+        }
+        TAIL_STAMP_OP(5);
+        // ---- deterministic cross-wave sum; operand wave 4 + e finishes element e (+ fused Adam, optim.rs:99-110) ----
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) red[j][tn][lane][i] = accdw[tn][i];
+        __syncthreads();                             // barrier 2
+        TAIL_STAMP_OP(6);
+        const float w_step = any_w ? h_step : 0.f;
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            if (!tn_ok[tn]) continue;
+            float out = red[0][tn][lane][j];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) out += red[w][tn][lane][j];
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off + tn * 64) = out;
+            if (any_w) {
+                const AdamDev &ad = a.w1_adam;
+                const AdamMV x = adam_moments(ad, e_p[tn], e_m[tn], e_v[tn], out);
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.m) + e_off + tn * 64) = x.m;
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.v) + e_off + tn * 64) = x.v;
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.p) + e_off + tn * 64) = adam_param(ad, e_p[tn], x, w_step);
+            }
+        }
+        TAIL_STAMP_OP(7);
+        return;
+    }
+
+    // ---- head role: db1[16 tile_m ..] (+ fused Adam of b1), dW2[:, 16 tile_m ..]; the lead also this pair's share of db2, loss, hits ----
+    if (rows_here) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) w2b[s] = ldg_b(a.w2, ((unsigned)min(g4 * 4 + s, C - 1) * HID + hcol) * 4u);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) hm[s] = ldg_b(a.h, hm_off + s * HID * 4);
+    }
+    const int te = t - 64 * NW;                      // thread among the operand waves: who finishes what, as thread t of the 320-thread form
+    const unsigned b1_off = (tile_m * 16 + (te & 15)) * 4u;
+    float bp_ = 0.f, bm_ = 0.f, bv_ = 0.f;
+    if (any_b) {
+        bp_ = ldg_b(a.b1_adam.p, b1_off);
+        bm_ = ldg_b(a.b1_adam.m, b1_off);
+        bv_ = ldg_b(a.b1_adam.v, b1_off);
+    }
+    TAIL_STAMP_OP(1);
+    __syncthreads();                                 // barrier 0
+    __syncthreads();                                 // barrier 1
+    TAIL_STAMP_OP(3);
+    floatx4 acc_dw2 = {0.f, 0.f, 0.f, 0.f};
+    float db1_acc = 0.f, db2_acc = 0.f, nll_acc = 0.f, hit_acc = 0.f;
+    if (rows_here) {
+        float dhm[4];
+        dh_masked(dhm);
+        // ---- db1 (tensor.rs:686-691): rows 4 g4 + i in the lane, then over g4 ----
+        db1_acc += sum_over_g4((dhm[0] + dhm[1]) + (dhm[2] + dhm[3]));
+        // ---- dW2 tile: A = dl[row 4 g4 + s][class r16] (the parked dlogits, transposed), B = H[row 4 g4 + s][hcol] ----
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            acc_dw2 = __builtin_amdgcn_mfma_f32_16x16x4f32(tr[j][g4 * 4 + s][r16], hm[s], acc_dw2, 0, 0, 0);
+        if (lead) {   // db2 (column sums of dlogits), loss, hits over this pair's 16 rows, in row order
+            float cs = 0.f, nl = 0.f, ht = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                cs += tr[j][r][r16];
+                nl += rowv[j][0][r];
+                ht += rowv[j][1][r];
+            }
+            db2_acc += cs;
+            nll_acc += nl;
+            hit_acc += ht;
+        }
+    }
+    TAIL_STAMP_OP(5);
+    // ---- cross-wave sums in wave order ----
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[j][0][lane][i] = acc_dw2[i];
+    if (g4 == 0) sc[j][r16] = db1_acc;
+    if (lead && g4 == 0) sc[j][16 + r16] = db2_acc;
+    if (lead && lane == 0) {
+        sc[j][32] = nll_acc;
+        sc[j][33] = hit_acc;
+    }
+    __syncthreads();                                 // barrier 2: behind it the helper does the lead's own stretch
+    TAIL_STAMP_OP(6);
+    const float b_step = any_b ? h_step : 0.f;
+    if (a.dw2) {   // operand wave 4 + e: class 4 g4 + e
+        const int cls = g4 * 4 + j;
+        float sum = red[0][0][lane][j];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) sum += red[w][0][lane][j];
+        if (cls < C) a.dw2[cls * HID + hcol] = sum;
+    }
+    if (a.db1 && te < 16) {
+        float out = sc[0][te];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) out += sc[w][te];
+        const int ix = tile_m * 16 + te;
+        a.db1[ix] = out;
+        if (any_b) {
+            const AdamDev &ad = a.b1_adam;
+            const AdamPMV x = adam_next(ad, bp_, bm_, bv_, out, b_step);
+            ad.m[ix] = x.m;
+            ad.v[ix] = x.v;
+            ad.p[ix] = x.p;
+        }
+    }
+    TAIL_STAMP_OP(7);
+}
+
 }  // namespace th
 
 using namespace th;
@@ -957,6 +1293,15 @@ extern "C" int th_mlp_tail_dp_supported(const th_comm *comm, th_ctx *ctx, int ba
     return 1;
 }
 
+// the split form of the instances with a helper wave (mlp_tail_split_kernel): 4 logit + 4 operand waves + the helper
+template <int KS, int TN>
+static void tail_launch_split(bool dx, int grid, hipStream_t stream, const TailArgs &a) {
+    if constexpr (tail_helper_waves(KS, 4, 0) != 0) {
+        if (dx) hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, true>), dim3(grid), dim3(576), 0, stream, a);
+        else hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, false>), dim3(grid), dim3(576), 0, stream, a);
+    }
+}
+
 static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const float *d_h, const float *d_w2, const float *d_b2,
                            const float *d_targets, int batch, int in_features, int hidden, int classes, float *d_loss,
                            float *d_ncorrect, float *d_dw1, float *d_db1, float *d_dw2, float *d_db2, const float *d_w1, float *d_dx,
@@ -1005,9 +1350,12 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
         comm_dp_count_launch(comm);
         return 0;
     }
+    // ... and of its 4-wave instances up to hidden 128, the split form unless the context asks for the 320-thread one (th_mlp_tail_set_split)
+    const bool split = exact && nw == 4 && tail_helper_waves(hidden / 16, nw, 0) != 0 && ctx->tail_split;
 #define TH_TAIL_LAUNCH(KS)                                                                                            \
     do {                                                                                                              \
-        if (exact && d_dx && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
+        if (split) tail_launch_split<KS, TN>(d_dx != nullptr, grid, ctx->stream, a);                                  \
+        else if (exact && d_dx && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
         else if (exact && d_dx) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, true, 4>), dim3(grid), dim3(tail_exact_threads(KS, 4, false)), 0, ctx->stream, a);     \
         else if (exact && nw == 8) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 8>), dim3(grid), dim3(512), 0, ctx->stream, a);     \
         else if (exact) hipLaunchKernelGGL((mlp_tail_exact_kernel<KS, TN, false, 4>), dim3(grid), dim3(tail_exact_threads(KS, 4, false)), 0, ctx->stream, a);     \
@@ -1029,6 +1377,12 @@ extern "C" int th_mlp_tail(th_ctx *ctx, const float *d_x, const float *d_h, cons
                            const th_adam_fuse *w1_fuse, const th_adam_fuse *b1_fuse) {
     return mlp_tail_launch(nullptr, ctx, d_x, d_h, d_w2, d_b2, d_targets, batch, in_features, hidden, classes, d_loss, d_ncorrect, d_dw1, d_db1,
                            d_dw2, d_db2, d_w1, d_dx, d_metrics, metrics_capacity, d_state, advance, w1_fuse, b1_fuse, nullptr);
+}
+
+extern "C" int th_mlp_tail_set_split(th_ctx *ctx, int on) {
+    TH_REQUIRE(ctx, "th_mlp_tail_set_split: null ctx");
+    ctx->tail_split = on != 0;
+    return 0;
 }
 
 extern "C" int th_mlp_tail_dp(th_comm *comm, th_ctx *ctx, const float *d_x, const float *d_h, const float *d_w2, const float *d_b2,
@@ -1054,6 +1408,11 @@ extern "C" int th_debug_tail_prof(th_ctx *ctx, long long *h_out32) {
 extern "C" int th_debug_tail_prof_all(th_ctx *ctx, long long *h_out2048) {
     TH_HIP(hipStreamSynchronize(ctx->stream));
     TH_HIP(hipMemcpyFromSymbol(h_out2048, HIP_SYMBOL(g_tail_prof_all), 256 * 8 * sizeof(long long)));
+    return 0;
+}
+extern "C" int th_debug_tail_prof_op(th_ctx *ctx, long long *h_out2048) {   // the operand waves' table (mlp_tail_split_kernel)
+    TH_HIP(hipStreamSynchronize(ctx->stream));
+    TH_HIP(hipMemcpyFromSymbol(h_out2048, HIP_SYMBOL(g_tail_prof_op), 256 * 8 * sizeof(long long)));
     return 0;
 }
 #endif

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""In-kernel stamps of the MLP step's second launch (mlp_tail_exact_kernel<8,2,false,4> at batch 64): which workgroup
-ends last.  Needs the profile build of the kernel library (`make -C taper_amd/csrc PROFILE=1`: the TAIL_STAMP points
-of mlp_tail.hip, 100 MHz wall clock, thread 0 of every workgroup).  The step's two launches run back to back on the
+"""In-kernel stamps of the MLP step's second launch (mlp_tail_split_kernel<8,2,false> at batch 64, or with `--split 0` the
+320-thread mlp_tail_exact_kernel<8,2,false,4>): which workgroup ends last.  Needs the profile build of the kernel library
+(`make -C taper_amd/csrc PROFILE=1`: the TAIL_STAMP points of mlp_tail.hip, 100 MHz wall clock, thread 0 of every workgroup).  The step's two launches run back to back on the
 stream as in the Trainer's graph; after every `--steps` steps the stamps of the LAST tail launch are read.
 
 Per role (lead head workgroup = block 0, plain head workgroups = blocks 1..7, dW1 workgroups = the rest):
@@ -14,10 +14,22 @@ Per role (lead head workgroup = block 0, plain head workgroups = blocks 1..7, dW
   sync   stamp 6 - stamp 5 (partial sums to LDS and the final barrier)
 In the instances with a helper wave the lead's stamp 7 is the later of thread 0's and the helper's.
 
+The launch's split form (mlp_tail_split_kernel, the default; `--split 0` asks the context for the 320-thread form and reports the columns
+above) stamps TWO waves per workgroup: lane 0 of logit wave 0 and lane 0 of operand wave 4 (a table of its own).  Per role then
+  lg_issue  logit wave: stamp 1 - 0 (roles, addresses, the last of its 11..15 loads requested)
+  lg_image  logit wave: stamp 3 - 1 (its two k-slices of W2 arrive and go to LDS; barrier 0: the image is whole)
+  lg_math   logit wave: stamp 4 - 3 (the image back from LDS, H's load wait, logits, softmax, dlogits parked in LDS)
+  op_issue  operand wave: stamp 1 - 0 (the last of its loads requested)
+  op_wait   operand wave: stamp 3 - 1 (barrier 0, then at barrier 1 for the logit waves)
+  op_math   operand wave: stamp 5 - 3 (dlogits back from LDS, dH, the dW1 / dW2 products)
+  op_sync   operand wave: stamp 6 - 5 (partial sums to LDS and barrier 2)
+  op_behind operand wave: stamp 7 - 6 (wave-ordered sums, stores, fused Adam)
+body / end are the operand wave's stamp 7 (the lead's: the later of it and the helper's) from the earlier stamp 0 of the two waves.
+
 The shape is fixed (784-128-10, batch 64: 8 head + 200 dW1 workgroups); the role split below and the profile build's 256-workgroup
 stamp table hold for that launch only.
 
-  python tools/prof_tail.py [--samples 200] [--json OUT] [--root TREE]
+  python tools/prof_tail.py [--samples 200] [--split 1] [--json OUT] [--root TREE]
 """
 from __future__ import annotations
 
@@ -33,6 +45,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--samples", type=int, default=200)
 ap.add_argument("--steps", type=int, default=8, help="steps enqueued per sample")
 ap.add_argument("--t0", type=int, default=1000, help="the step counter before every sample")
+ap.add_argument("--split", type=int, default=1, help="the context's split switch (0: the 320-thread form; ignored by a tree without the switch)")
 ap.add_argument("--json", default=None)
 ap.add_argument("--root", default=str(Path(__file__).resolve().parent.parent), help="the checkout whose taper_amd package (and built libraries) to load")
 args = ap.parse_args()
@@ -50,6 +63,12 @@ IN, HID, OUT, B = 784, 128, 10, 64
 N_HEAD, N_BLOCKS = 8, 208     # mlp_tail_launch: n_head = 8, n_dw = 8 * ceil(784 / 32) = 200
 assert N_HEAD == (HID // 16 + 7) // 8 * 8 and N_BLOCKS - N_HEAD == (HID // 16 * -(-IN // 32) + 7) // 8 * 8 and N_BLOCKS <= 256
 ctx = hip.Ctx(0)
+SPLIT = bool(args.split) and hasattr(lib, "th_mlp_tail_set_split")
+if hasattr(lib, "th_mlp_tail_set_split"):
+    ctx.call("th_mlp_tail_set_split", int(SPLIT))
+if SPLIT:
+    lib.th_debug_tail_prof_op.argtypes = [C.c_void_p, C.c_void_p]
+    lib.th_debug_tail_prof_op.restype = C.c_int
 rng = np.random.default_rng(0)
 f = lambda *shape: ctx.upload(rng.uniform(-0.05, 0.05, shape).astype(np.float32))
 x, y = ctx.upload(rng.uniform(0, 1, (B, IN)).astype(np.float32)), ctx.upload(rng.integers(0, OUT, B).astype(np.float32))
@@ -73,14 +92,37 @@ def step():
 
 
 rows = []
-buf = np.zeros((256, 8), np.int64)
+buf, buf_op = np.zeros((256, 8), np.int64), np.zeros((256, 8), np.int64)
+
+
+def split_row(s, o):
+    """one sample of the split form: s = logit wave 0's stamps, o = operand wave 4's (us); s[:, 7] is the workgroup's end"""
+    first = np.minimum(s[:, 0], o[:, 0])
+    start = first.min()
+    body, end = s[:, 7] - first, s[:, 7] - start
+    dw = slice(N_HEAD, N_BLOCKS)
+    row = {}
+    for name, tab, hi, lo in (("lg_issue", s, 1, 0), ("lg_image", s, 3, 1), ("lg_math", s, 4, 3), ("op_issue", o, 1, 0), ("op_wait", o, 3, 1), ("op_math", o, 5, 3),
+                              ("op_sync", o, 6, 5), ("op_behind", o, 7, 6)):
+        d = tab[:, hi] - tab[:, lo]
+        row.update({f"lead_{name}": d[0], f"head_{name}": np.median(d[1:N_HEAD]), f"dw_{name}": np.median(d[dw])})
+    return dict(row, lead_body=body[0], lead_end=end[0], head_body=np.median(body[1:N_HEAD]), head_end=np.median(end[1:N_HEAD]),
+                dw_body=np.median(body[dw]), dw_end=np.median(end[dw]), dw_end_max=end[dw].max(), launch=end.max(),
+                last_is_lead=float(end.argmax() == 0))
+
+
 for it in range(args.samples + 10):
     lib.th_memcpy_h2d(ctx.h, int(tick), tick0.ctypes.data, tick0.nbytes)
     for _ in range(args.steps):
         step()
     if lib.th_debug_tail_prof_all(ctx.h, buf.ctypes.data) != 0:
         sys.exit("th_debug_tail_prof_all failed")
+    if SPLIT and lib.th_debug_tail_prof_op(ctx.h, buf_op.ctypes.data) != 0:
+        sys.exit("th_debug_tail_prof_op failed")
     if it < 10:
+        continue
+    if SPLIT:
+        rows.append(split_row(buf[:N_BLOCKS].astype(np.float64) * 0.01, buf_op[:N_BLOCKS].astype(np.float64) * 0.01))
         continue
     s = buf[:N_BLOCKS].astype(np.float64) * 0.01          # us
     start = s[:, 0].min()
@@ -101,7 +143,7 @@ out["lead_end_minus_dw_end_max"] = round(float(np.median([r["lead_end"] - r["dw_
 # run-to-run spread of the figure the decision rests on: the medians of five equal parts of the samples
 parts = np.array_split(np.array([r["lead_end"] - r["dw_end"] for r in rows]), 5)
 out["lead_minus_dw_spread_of_5"] = round(float(max(np.median(p) for p in parts) - min(np.median(p) for p in parts)), 3)
-out["samples"], out["t0"] = len(rows), args.t0
+out["samples"], out["t0"], out["split"] = len(rows), args.t0, int(SPLIT)
 for k, v in out.items():
     print(f"{k:32s} {v}")
 if args.json:
