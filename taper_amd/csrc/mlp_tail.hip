@@ -55,18 +55,21 @@ struct TailArgs {
 #ifdef TH_PROFILE
 __device__ long long g_tail_prof[2][16];   // [0] lead head workgroup, [1] first dW1 workgroup
 __device__ long long g_tail_prof_all[256][8];   // stamps 0..7 of every workgroup (blocks 0..255): who ends last (tools/prof_tail.py)
-// stamp 7 of the lead: the later of thread 0's and the helper wave's (the clock only rises, so no reset between launches)
-__device__ __forceinline__ void tail_prof_end(long long now) {
-    atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof[0][7]), (unsigned long long)now);
-    atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof_all[0][7]), (unsigned long long)now);
+// stamp 7 of a workgroup: the latest of its stamping waves' (thread 0's; in mlp_tail_split_kernel also operand wave 4's; in the lead also the
+// helper wave's) -- the clock only rises, so no reset between launches
+__device__ __forceinline__ void tail_prof_end(long long now, int bid = 0) {
+    if (bid == 0) atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof[0][7]), (unsigned long long)now);
+    if (bid < 256) atomicMax(reinterpret_cast<unsigned long long *>(&g_tail_prof_all[bid][7]), (unsigned long long)now);
 }
 #define TAIL_STAMP(i)                                                                         \
     do {                                                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                    \
         if (threadIdx.x == 0) {                                                               \
             const long long now_ = wall_clock64();                                            \
-            if ((i) == 7 && blockIdx.x == 0) tail_prof_end(now_);                             \
-            else {                                                                            \
+            if ((i) == 7) {                                                                   \
+                tail_prof_end(now_, blockIdx.x);                                              \
+                if (blockIdx.x == a.n_head) g_tail_prof[1][7] = now_;                         \
+            } else {                                                                          \
                 if (blockIdx.x == 0 || blockIdx.x == a.n_head) g_tail_prof[blockIdx.x == 0 ? 0 : 1][i] = now_; \
                 if (blockIdx.x < 256 && (i) < 8) g_tail_prof_all[blockIdx.x][i] = now_;       \
             }                                                                                 \
@@ -74,7 +77,8 @@ __device__ __forceinline__ void tail_prof_end(long long now) {
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
 // mlp_tail_split_kernel: TAIL_STAMP is lane 0 of logit wave 0 (thread 0), TAIL_STAMP_OP lane 0 of operand wave 4 (thread 256), into a
-// table of its own; its stamp 7 is also the workgroup's end in g_tail_prof_all (the operand waves end the workgroup)
+// table of its own.  The logit wave's stamps 6 / 2: behind barrier 2, and its own end (in a dW1 workgroup it finishes tile 1); stamp 7 of
+// either wave goes into the workgroup's end in g_tail_prof_all
 __device__ long long g_tail_prof_op[256][8];
 #define TAIL_STAMP_OP(i)                                                                      \
     do {                                                                                      \
@@ -82,10 +86,7 @@ __device__ long long g_tail_prof_op[256][8];
         if (threadIdx.x == 256 && blockIdx.x < 256) {                                         \
             const long long now_ = wall_clock64();                                            \
             g_tail_prof_op[blockIdx.x][i] = now_;                                             \
-            if ((i) == 7) {                                                                   \
-                if (blockIdx.x == 0) tail_prof_end(now_);                                     \
-                else g_tail_prof_all[blockIdx.x][7] = now_;                                   \
-            }                                                                                 \
+            if ((i) == 7) tail_prof_end(now_, blockIdx.x);                                    \
         }                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
@@ -930,8 +931,8 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
 //   logit wave j         its 16 rows of H, targets, b2 and its SHARE of W2 as the logits' operand (k-slices j, j + 4, ..): the four logit
 //                        waves would fetch the same image (8 KB at hidden 128), so each fetches a quarter, stores it to LDS (wimg) and,
 //                        behind barrier 0, reads the whole image back; the 32 logits MFMAs, the softmax; parks dlogits in tr[j] (and, in
-//                        the lead, the rows' NLL and hit flags in rowv[j]) in the layout the lane holds; barrier 1; nothing more but
-//                        barrier 2
+//                        the lead, the rows' NLL and hit flags in rowv[j]) in the layout the lane holds; barrier 1; barrier 2; in the
+//                        dW1 role it then FINISHES its element of the block's second 16-column tile (below)
 //   operand wave 4 + j   everything behind the softmax needs -- W2 as dH's operand, the ReLU mask, X (dW1 role), the p / m / v it finishes --
 //                        requested before barrier 0; behind barrier 1 dlogits back from tr[j] (lane l reads what lane l of wave j wrote)
 //                        and the 320-thread form's code from its dH MFMAs on, with `wave` = j: the same MFMA chains from the same zeros,
@@ -942,7 +943,11 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
 // and meets every barrier.  Every wave that gets past the workgroup-uniform returns meets EXACTLY three workgroup barriers (a miscount
 // hangs the device: count the s_barriers of each path in the listing after any change here); in the dX role (no barriers) the operand
 // waves leave where the helper leaves.  NW == 4 is launched for batch <= 64 only: ONE chunk, so there is no chunk loop here.
-// Measured in profiles/mlp_tail_split.md.
+// Behind barrier 2 a dW1 workgroup's block is finished by the PAIR, one 16-column tile per wave: operand wave 4 + j element j of every
+// lane's C/D quad in tile 0, logit wave j (the older wave of the SIMD, idle since barrier 1) the same element in tile 1 -- the cross-wave
+// sum in wave order, the dW1 store, the fused Adam element from p / m / v words the wave requested itself (the logit wave right behind
+// the image's read-back, so they are in flight under its MFMAs and softmax).  The head role's finish stays on the operand waves.
+// Measured in profiles/mlp_tail_split.md and profiles/mlp_tail_pairs.md.
 template <int KS, int TN, bool HAS_DX>
 __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     constexpr int NW = 4;
@@ -990,9 +995,30 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     const int j = wave & (NW - 1);                   // the pair, its rows 16 j .. 16 j + 15: all valid or all absent
     const int r0 = j * 16;
     const bool rows_here = r0 < B;
+    // dW1 role: the PAIR finishes the block, one 16-column tile per wave -- operand wave 4 + e element e of every lane's C/D quad (row
+    // 4 g4 + e of the tile) in tile 0, logit wave e the same element in tile 1; each requests the p / m / v word it finishes itself.
+    // (Three inlined copies -- operand wave, logit wave, logit wave without rows: paths that join again share their waits, see below)
+    static_assert(TN == 2, "one tile per wave of a pair");
+    auto pair_offset = [&](int tn) { return ((tile_m * 16 + g4 * 4 + j) * in_f + grp * 16 * TN + r16) * 4u + tn * 64; };
+    // behind barrier 2: the deterministic cross-wave sum of tile tn, element j (+ fused Adam, optim.rs:99-110)
+    auto finish_tile = [&](int tn, unsigned e_off, float e_p, float e_m, float e_v) __attribute__((always_inline)) {
+        const float w_step = any_w ? h_step : 0.f;
+        float out = red[0][tn][lane][j];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) out += red[w][tn][lane][j];
+        *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off) = out;
+        if (any_w) {
+            const AdamDev &ad = a.w1_adam;
+            const AdamMV x = adam_moments(ad, e_p, e_m, e_v, out);
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.m) + e_off) = x.m;
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.v) + e_off) = x.v;
+            *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.p) + e_off) = adam_param(ad, e_p, x, w_step);
+        }
+    };
 
     if (wave < NW) {
         // ---- logit wave j ----
+        const bool finishes = !head_role && (unsigned)grp * 16 * TN + 16 < in_f;   // (the last column group of 784 inputs has no second tile)
         // its share of W2 as the logits' A operand, W2[class r16][16 ks + 4 g4 ..] (rows >= C: a copy of row C-1, masked at the logits):
         // k-slices j, j + 4, .. of the KS -- the image is fetched ONCE per workgroup and goes round through LDS
         constexpr int NSL = (KS + NW - 1) / NW;
@@ -1006,53 +1032,78 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
             for (int q = 0; q < NSL; ++q)
                 if (q * NW + j < KS) wimg[q * NW + j][lane] = wsl[q];
         };
-        if (!rows_here) {   // (a path of its own: behind a merge, the wait for the slices is a wait for every load of the longer path)
+        if (!rows_here) {   // (a path of its own to its end: behind a merge, the wait for the slices is a wait for every load of the longer path)
             put_slices();
             __syncthreads();                         // barrier 0
             __syncthreads();                         // barrier 1
             __syncthreads();                         // barrier 2
+            if (finishes) {   // its pair parked zeros.  (The requests only here: a request still in flight where this path joins the exit
+                              // makes the other path wait for it in front of its own loads of H)
+                const unsigned e_off = pair_offset(1);
+                if (any_w) finish_tile(1, e_off, ldg_b(a.w1_adam.p, e_off), ldg_b(a.w1_adam.m, e_off), ldg_b(a.w1_adam.v, e_off));
+                else finish_tile(1, e_off, 0.f, 0.f, 0.f);
+            }
             return;
         }
-        float4 wv[KS], hv[KS];                       // H[r0 + r16][16 ks + 4 g4 ..]
-        const unsigned h_off = ((unsigned)(r0 + r16) * HID + g4 * 4) * 4u;
+        {
+            float4 wv[KS], hv[KS];                   // H[r0 + r16][16 ks + 4 g4 ..]
+            const unsigned h_off = ((unsigned)(r0 + r16) * HID + g4 * 4) * 4u;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) hv[ks] = ldg4_b(a.h, h_off + ks * 64);
-        const float tf = ldg_b(a.targets, (unsigned)(r0 + r16) * 4u);
-        float b2v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (a.b2) {
+            for (int ks = 0; ks < KS; ++ks) hv[ks] = ldg4_b(a.h, h_off + ks * 64);
+            const float tf = ldg_b(a.targets, (unsigned)(r0 + r16) * 4u);
+            float b2v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (a.b2) {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) b2v[s] = ldg_b(a.b2, (unsigned)min(g4 * 4 + s, C - 1) * 4u);
+                for (int s = 0; s < 4; ++s) b2v[s] = ldg_b(a.b2, (unsigned)min(g4 * 4 + s, C - 1) * 4u);
+            }
+            TAIL_STAMP(1);
+            const unsigned e_off = pair_offset(1);
+            put_slices();
+            __syncthreads();                         // barrier 0: the image is whole
+            TAIL_STAMP(3);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) wv[ks] = wimg[ks][lane];
+            // the p / m / v words behind the last load the logits need: in flight under the MFMAs and the softmax, used behind barrier 2.
+            // No branch: behind a merge the waits in front of the MFMAs and of the softmax become waits for these three as well -- a
+            // logit wave that finishes nothing (head role, no second tile, no fused update) asks for its rows' target word again
+            float e_p, e_m, e_v;
+            {
+                const bool req = finishes && any_w;
+                const unsigned q_off = req ? e_off : (unsigned)(r0 + r16) * 4u;
+                e_p = ldg_b(req ? a.w1_adam.p : a.targets, q_off);
+                e_m = ldg_b(req ? a.w1_adam.m : a.targets, q_off);
+                e_v = ldg_b(req ? a.w1_adam.v : a.targets, q_off);
+                __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler sinks the three requests behind the MFMAs)
+            }
+            // ---- logits^T (nn.rs:54-60): four independent accumulation chains, one per float4 component ----
+            floatx4 ax = {0.f, 0.f, 0.f, 0.f}, ay = ax, az = ax, aw = ax;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                ax = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].x, hv[ks].x, ax, 0, 0, 0);
+                ay = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].y, hv[ks].y, ay, 0, 0, 0);
+                az = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].z, hv[ks].z, az, 0, 0, 0);
+                aw = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].w, hv[ks].w, aw, 0, 0, 0);
+            }
+            float lg[4], dl[4], nll_row;
+            int bi;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lg[i] = (g4 * 4 + i < C) ? ((ax[i] + ay[i]) + (az[i] + aw[i])) + b2v[i] : -INFINITY;
+            tail_row_softmax(lg, g4, C, tf, 1.0f / (float)B, dl, nll_row, bi);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tr[j][r16][g4 * 4 + i] = dl[i];
+            if (lead && g4 == 0) {
+                rowv[j][0][r16] = nll_row;
+                rowv[j][1][r16] = (fabsf((float)bi - tf) < 1e-6f) ? 1.f : 0.f;   // loss.rs:283
+            }
+            TAIL_STAMP(4);
+            __syncthreads();                         // barrier 1: dlogits are parked
+            __syncthreads();                         // barrier 2: the operand waves' final barrier
+            TAIL_STAMP(6);
+            if (finishes) finish_tile(1, e_off, e_p, e_m, e_v);
+            TAIL_STAMP(2);
+            TAIL_STAMP(7);
+            return;
         }
-        TAIL_STAMP(1);
-        put_slices();
-        __syncthreads();                             // barrier 0: the image is whole
-        TAIL_STAMP(3);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) wv[ks] = wimg[ks][lane];
-        // ---- logits^T (nn.rs:54-60): four independent accumulation chains, one per float4 component ----
-        floatx4 ax = {0.f, 0.f, 0.f, 0.f}, ay = ax, az = ax, aw = ax;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            ax = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].x, hv[ks].x, ax, 0, 0, 0);
-            ay = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].y, hv[ks].y, ay, 0, 0, 0);
-            az = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].z, hv[ks].z, az, 0, 0, 0);
-            aw = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[ks].w, hv[ks].w, aw, 0, 0, 0);
-        }
-        float lg[4], dl[4], nll_row;
-        int bi;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) lg[i] = (g4 * 4 + i < C) ? ((ax[i] + ay[i]) + (az[i] + aw[i])) + b2v[i] : -INFINITY;
-        tail_row_softmax(lg, g4, C, tf, 1.0f / (float)B, dl, nll_row, bi);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tr[j][r16][g4 * 4 + i] = dl[i];
-        if (lead && g4 == 0) {
-            rowv[j][0][r16] = nll_row;
-            rowv[j][1][r16] = (fabsf((float)bi - tf) < 1e-6f) ? 1.f : 0.f;   // loss.rs:283
-        }
-        TAIL_STAMP(4);
-        __syncthreads();                             // barrier 1: dlogits are parked
-        __syncthreads();                             // barrier 2: the operand waves' final barrier
-        return;
     }
 
     // ---- operand wave 4 + j ----
@@ -1080,9 +1131,7 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     if (!head_role) {
         // ---- dW1 role: one 16-hidden x (16 TN)-input block ----
         const unsigned col0 = grp * 16 * TN;
-        bool tn_ok[TN];                              // workgroup-uniform; tn_ok[0] always holds (col0 < in_f)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) tn_ok[tn] = col0 + tn * 16 < in_f;
+        const bool tn1_ok = col0 + 16 < in_f;        // workgroup-uniform; tile 0 is always there (col0 < in_f)
         float xv[TN][4];                             // X[r0 + 4 g4 + s][col0 + 16 tn + r16]
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
@@ -1096,24 +1145,18 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
             for (int s = 0; s < 4; ++s) hm[s] = ldg_b(a.h, hm_off + s * HID * 4);
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) {
-                if (tn > 0 && !tn_ok[tn]) continue;
+                if (tn > 0 && !tn1_ok) continue;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) xv[tn][s] = ldg_b(a.x, x_off + s * in_f * 4u + tn * 64);
             }
         }
-        // epilogue operands: operand wave 4 + e finishes element e of every lane's C/D quad (row 4 g4 + e of the tile)
-        const unsigned e_off = ((tile_m * 16 + g4 * 4 + j) * in_f + col0 + r16) * 4u;
-        float e_p[TN], e_m[TN], e_v[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) e_p[tn] = e_m[tn] = e_v[tn] = 0.f;
+        // epilogue operands of tile 0 (tile 1's are its logit wave's)
+        const unsigned e_off = pair_offset(0);
+        float e_p = 0.f, e_m = 0.f, e_v = 0.f;
         if (any_w) {
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                if (tn > 0 && !tn_ok[tn]) continue;
-                e_p[tn] = ldg_b(a.w1_adam.p, e_off + tn * 64);
-                e_m[tn] = ldg_b(a.w1_adam.m, e_off + tn * 64);
-                e_v[tn] = ldg_b(a.w1_adam.v, e_off + tn * 64);
-            }
+            e_p = ldg_b(a.w1_adam.p, e_off);
+            e_m = ldg_b(a.w1_adam.m, e_off);
+            e_v = ldg_b(a.w1_adam.v, e_off);
         }
         TAIL_STAMP_OP(1);
         __syncthreads();                             // barrier 0
@@ -1133,29 +1176,13 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
                     accdw[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(dhm[s], xv[tn][s], accdw[tn], 0, 0, 0);
         }
         TAIL_STAMP_OP(5);
-        // ---- deterministic cross-wave sum; operand wave 4 + e finishes element e (+ fused Adam, optim.rs:99-110) ----
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
             for (int i = 0; i < 4; ++i) red[j][tn][lane][i] = accdw[tn][i];
         __syncthreads();                             // barrier 2
         TAIL_STAMP_OP(6);
-        const float w_step = any_w ? h_step : 0.f;
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            if (!tn_ok[tn]) continue;
-            float out = red[0][tn][lane][j];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) out += red[w][tn][lane][j];
-            *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off + tn * 64) = out;
-            if (any_w) {
-                const AdamDev &ad = a.w1_adam;
-                const AdamMV x = adam_moments(ad, e_p[tn], e_m[tn], e_v[tn], out);
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.m) + e_off + tn * 64) = x.m;
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.v) + e_off + tn * 64) = x.v;
-                *reinterpret_cast<float *>(reinterpret_cast<char *>(ad.p) + e_off + tn * 64) = adam_param(ad, e_p[tn], x, w_step);
-            }
-        }
+        finish_tile(0, e_off, e_p, e_m, e_v);
         TAIL_STAMP_OP(7);
         return;
     }

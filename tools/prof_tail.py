@@ -23,8 +23,13 @@ above) stamps TWO waves per workgroup: lane 0 of logit wave 0 and lane 0 of oper
   op_wait   operand wave: stamp 3 - 1 (barrier 0, then at barrier 1 for the logit waves)
   op_math   operand wave: stamp 5 - 3 (dlogits back from LDS, dH, the dW1 / dW2 products)
   op_sync   operand wave: stamp 6 - 5 (partial sums to LDS and barrier 2)
-  op_behind operand wave: stamp 7 - 6 (wave-ordered sums, stores, fused Adam)
-body / end are the operand wave's stamp 7 (the lead's: the later of it and the helper's) from the earlier stamp 0 of the two waves.
+  op_behind operand wave: stamp 7 - 6 (wave-ordered sums, stores, fused Adam of tile 0; head role: dW2, db1)
+  lg_sync   logit wave: stamp 6 - 4 (barrier 1, then at barrier 2 for the operand waves)
+  lg_behind logit wave: stamp 2 - 6 (dW1 workgroups: wave-ordered sums, stores, fused Adam of tile 1; 0 where it finishes nothing)
+  parked    logit wave's stamp 4 from the earlier stamp 0 of the two waves (entry -> dlogits parked)
+(lg_sync / lg_behind only from a build that stamps them.)
+body / end are the workgroup's stamp 7 -- the latest of its logit wave's, its operand wave's and, in the lead, the helper's -- from the
+earlier stamp 0 of the two waves.
 
 The shape is fixed (784-128-10, batch 64: 8 head + 200 dW1 workgroups); the role split below and the profile build's 256-workgroup
 stamp table hold for that launch only.
@@ -102,10 +107,18 @@ def split_row(s, o):
     body, end = s[:, 7] - first, s[:, 7] - start
     dw = slice(N_HEAD, N_BLOCKS)
     row = {}
-    for name, tab, hi, lo in (("lg_issue", s, 1, 0), ("lg_image", s, 3, 1), ("lg_math", s, 4, 3), ("op_issue", o, 1, 0), ("op_wait", o, 3, 1), ("op_math", o, 5, 3),
-                              ("op_sync", o, 6, 5), ("op_behind", o, 7, 6)):
+    cols = [("lg_issue", s, 1, 0), ("lg_image", s, 3, 1), ("lg_math", s, 4, 3), ("op_issue", o, 1, 0), ("op_wait", o, 3, 1), ("op_math", o, 5, 3),
+            ("op_sync", o, 6, 5), ("op_behind", o, 7, 6)]
+    if s[:, 6].any():   # a build whose logit waves work behind barrier 2
+        own_end = np.maximum(s[:, 2], s[:, 6])   # (a logit wave that finishes nothing leaves no stamp 2 of this launch)
+        s = s.copy()
+        s[:, 2] = own_end
+        cols += [("lg_sync", s, 6, 4), ("lg_behind", s, 2, 6)]
+    for name, tab, hi, lo in cols:
         d = tab[:, hi] - tab[:, lo]
         row.update({f"lead_{name}": d[0], f"head_{name}": np.median(d[1:N_HEAD]), f"dw_{name}": np.median(d[dw])})
+    parked = s[:, 4] - first
+    row.update(lead_parked=parked[0], head_parked=np.median(parked[1:N_HEAD]), dw_parked=np.median(parked[dw]), last_block=float(end.argmax()))
     return dict(row, lead_body=body[0], lead_end=end[0], head_body=np.median(body[1:N_HEAD]), head_end=np.median(end[1:N_HEAD]),
                 dw_body=np.median(body[dw]), dw_end=np.median(end[dw]), dw_end_max=end[dw].max(), launch=end.max(),
                 last_is_lead=float(end.argmax() == 0))
@@ -136,7 +149,9 @@ for it in range(args.samples + 10):
                      head_body=np.median(body[1:N_HEAD]), head_end=np.median(end[1:N_HEAD]), head_behind_barrier=np.median(s[1:N_HEAD, 7] - s[1:N_HEAD, 6]),
                      dw_body=np.median(body[dw]), dw_end=np.median(end[dw]), dw_end_max=end[dw].max(), dw_step=np.median(stepsz[dw]),
                      launch=end.max(), last_is_lead=float(end.argmax() == 0)))
-out = {k: round(float(np.median([r[k] for r in rows])), 3) for k in rows[0] if k != "last_is_lead"}
+out = {k: round(float(np.median([r[k] for r in rows])), 3) for k in rows[0] if k not in ("last_is_lead", "last_block")}
+if SPLIT:
+    out["last_is_head_frac"] = round(float(np.mean([0 < r["last_block"] < N_HEAD for r in rows])), 3)
 out["last_is_lead_frac"] = round(float(np.mean([r["last_is_lead"] for r in rows])), 3)
 out["lead_end_minus_dw_end_median"] = round(float(np.median([r["lead_end"] - r["dw_end"] for r in rows])), 3)
 out["lead_end_minus_dw_end_max"] = round(float(np.median([r["lead_end"] - r["dw_end_max"] for r in rows])), 3)
