@@ -11,25 +11,11 @@
 //    For the latency-bound MNIST-MLP shapes (64x128x784, 128x784x64, ...).
 // Operands are described by (row stride, col stride) so NN / NT / TN / TT all
 // run the same code: "KC" = k-contiguous in memory, "MC" = m/n-contiguous.
-#include "adam_dev.h"
+#include "small16_dev.h"
 
 namespace th {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-struct Epilogue {
-    float alpha, beta;
-    const float *bias;  // per output column (n), nullable
-    int relu;
-    AdamDev adam;       // adam.p != nullptr: C is a complete gradient and the Adam update of the
-                        // parameter at the same index runs right here (th_linear_bwd_adam)
-    // sgemm_tile, unsplit launches only (th_linear_bwd_adam_ex2): the backward of the fused Linear + ReLU IN FRONT of a layer, folded into that
-    // layer's dX product -- C <- C * [mask > 0] (mask: the layer's input, [m][n] like C; ops.rs:358-369) and colpart [tiles_m][n] (nullable):
-    // column sums of the stored tile rows, which th_colsum over the tile rows turns into the bias gradient of the layer in front (tensor.rs:686-691)
-    const float *mask;
-    float *colpart;
-};
 
 static inline Epilogue make_ep(float alpha, float beta, const float *bias = nullptr, int relu = 0) {
     return Epilogue{alpha, beta, bias, relu, AdamDev{nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f}, nullptr, nullptr};
@@ -43,224 +29,12 @@ __device__ __forceinline__ float epilogue_apply(float acc, float c_old, const Ep
     return v;
 }
 
-// ------------------------------------------------------------------------
-// small / latency-bound kernel
-// ------------------------------------------------------------------------
-// One workgroup (NW waves) per 16x16 output tile; wave w covers its share of
-// [kbeg_slice, kend_slice).  Lane l: r = l & 15 (row of A / col of B),
-// g = l >> 4 (which 4-wide k group).  In MFMA step s the lane supplies
-// k = kk + 4*g + s for BOTH operands, so every k is used exactly once.
-// MASKED: A values are multiplied by (Amask[same index] > 0) on the fly -- the
-// ReLU backward (ops.rs:358-369) folded into the operand load of the two
-// backward GEMMs of a Linear layer.
-struct SmallArgs {
-    const float *A, *Amask, *B;
-    float *C, *partial;
-    int m, n, k;
-    long a_rs, a_cs, b_rs, b_cs;
-    int kslice, a_vec, b_vec;
-    Epilogue ep;
-    int xcd_blocks = 0;   // sgemm_small16_tick only: 8 x 4 tiles handed out as one 2 x 2 block per XCD
-};
-
-#ifdef TH_PROFILE
-// stamps 0..5 of th_linear_fwd_ex's launch (tools/prof_fwd.py): per workgroup, lane 0 of wave 0 ([0]) and of the last wave that owns a whole
-// chunk ([1]); 100 MHz wall clock.  Nothing else reads the buffer.
-constexpr int kFwdProfBlocks = 320;
-__device__ long long g_fwd_prof[kFwdProfBlocks][2][6];
-#define FWD_STAMP(i)                                                                          \
-    do {                                                                                      \
-        if constexpr (STAMPED) {                                                              \
-            __builtin_amdgcn_sched_barrier(0);                                                \
-            if (stamp_slot >= 0) g_fwd_prof[stamp_blk][stamp_slot][i] = wall_clock64();       \
-            __builtin_amdgcn_sched_barrier(0);                                                \
-        }                                                                                     \
-    } while (0)
-// the value must be in its register: the compiler waits for the load (or the MFMA) that writes it in front of this point
-#define FWD_LANDED(v) do { if constexpr (STAMPED) asm volatile("" ::"v"(v)); } while (0)
-#else
-#define FWD_STAMP(i) do { } while (0)
-#define FWD_LANDED(v) do { } while (0)
-#endif
-
-// RM x RN (powers of two up to 16): the workgroup owns that SUB-TILE of a 16 x 16 MFMA tile (th_linear_fwd_ex).  Every output element of
-// v_mfma_f32_16x16x4_f32 is its own FMA chain over k (experiments/mfma_fma_chain.hip), so feeding RM rows of A and RN of B into the same
-// MFMAs over the same chunks, and dropping the C/D elements outside, gives the bits of the 16 x 16 form.  Lanes past the sub-tile alias one of
-// its rows (no further cache line) and supply zeros; the C/D elements outside the sub-tile are neither summed nor stored.
-template <bool A_KC, bool B_KC, int NW, bool MASKED, int RM = 16, int RN = 16, bool STAMPED = false>
-__device__ __forceinline__ void small16_body(const SmallArgs &p, int tile_row, int tile_col, int zslice, float (*red)[64][4]) {
-    constexpr bool SUB = RM < 16 || RN < 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    const int row0 = tile_row * RM, col0 = tile_col * RN;
-    const int kbeg_slice = zslice * p.kslice;
-    const int kend_slice = min(p.k, kbeg_slice + p.kslice);
-    // split the slice between the NW waves in multiples of 16
-    const int kwave = ((kend_slice - kbeg_slice + 16 * NW - 1) / (16 * NW)) * 16;
-    const int kbeg = kbeg_slice + wave * kwave;
-    const int kend = min(kend_slice, kbeg + kwave);
-#ifdef TH_PROFILE
-    const int stamp_blk = blockIdx.x + gridDim.x * blockIdx.y;
-    const int stamp_last = max((kend_slice - kbeg_slice) / kwave - 1, 0) % NW;
-    const int stamp_slot = (lane != 0 || stamp_blk >= kFwdProfBlocks) ? -1 : wave == 0 ? 0 : wave == stamp_last ? 1 : -1;
-#endif
-    FWD_STAMP(0);
-
-    const int arow = row0 + (SUB ? r & (RM - 1) : r), bcol = col0 + (SUB ? r & (RN - 1) : r);
-    const bool a_ok = (!SUB || r < RM) && arow < p.m, b_ok = (!SUB || r < RN) && bcol < p.n;
-    const long a_off = (long)(a_ok ? arow : SUB ? row0 : 0) * p.a_rs;
-    const float *ap = p.A + a_off;
-    const float *mp = MASKED ? p.Amask + a_off : nullptr;
-    const float *bp = p.B + (long)(b_ok ? bcol : SUB ? col0 : 0) * p.b_cs;
-
-    // These shapes are latency-bound: after a kernel boundary every dependent
-    // global round trip costs ~0.5-1 us.  So (a) everything the epilogue will
-    // need from memory -- bias, the old C for beta != 0, the Adam state of a fused
-    // update -- is requested by wave 0 NOW, under the operand loads; (b) the
-    // operand loads of CH k-steps (64 k per wave) are all issued before the
-    // first MFMA consumes any.
-    // Epilogue work is spread over waves 0..3: wave e finishes output element e of every lane (row
-    // 4*(lane>>4) + e of the tile), so the p / m / v traffic of a fused Adam update and the final adds
-    // run on four SIMDs instead of one.
-    const int ecol = col0 + (lane & 15);
-    const bool fuse_adam = p.ep.adam.p != nullptr && p.partial == nullptr;
-    const int erow = row0 + (lane >> 4) * 4 + wave;     // meaningful for wave < 4
-    const bool e_sub = !SUB || ((lane >> 4) * 4 + wave < RM && (lane & 15) < RN);   // the C/D elements of the sub-tile
-    const bool e_ok = wave < 4 && erow < p.m && ecol < p.n && e_sub;
-    const long e_ix = e_ok ? (long)erow * p.n + ecol : 0;
-    float e_bias = 0.f, e_cold = 0.f, e_p = 0.f, e_m = 0.f, e_v = 0.f, e_step = 0.f;
-    if (e_ok) {
-        if (p.ep.beta != 0.0f && !p.partial) e_cold = p.C[e_ix];
-        if (fuse_adam) {
-            e_p = p.ep.adam.p[e_ix];
-            e_m = p.ep.adam.m[e_ix];
-            e_v = p.ep.adam.v[e_ix];
-            e_step = adam_dev_step(p.ep.adam);
-        }
-        if (p.ep.bias) e_bias = p.ep.bias[ecol];
-    }
-    constexpr int CH = 4;
-    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int kk0 = kbeg; kk0 < kend; kk0 += 16 * CH) {
-        float av[CH][4], bv[CH][4];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const int kb = kk0 + 16 * c + g * 4;
-            if (A_KC && p.a_vec && kb + 4 <= kend) {
-                float4 t = *reinterpret_cast<const float4 *>(ap + kb);
-                av[c][0] = t.x; av[c][1] = t.y; av[c][2] = t.z; av[c][3] = t.w;
-                if (MASKED) {
-                    float4 q = *reinterpret_cast<const float4 *>(mp + kb);
-                    av[c][0] = q.x > 0.f ? av[c][0] : 0.f; av[c][1] = q.y > 0.f ? av[c][1] : 0.f;
-                    av[c][2] = q.z > 0.f ? av[c][2] : 0.f; av[c][3] = q.w > 0.f ? av[c][3] : 0.f;
-                }
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const bool in = kb + s < kend;
-                    float v = in ? ap[(long)(kb + s) * p.a_cs] : 0.f;
-                    if (MASKED) v = (in && mp[(long)(kb + s) * p.a_cs] > 0.f) ? v : 0.f;
-                    av[c][s] = v;
-                }
-            }
-            if (B_KC && p.b_vec && kb + 4 <= kend) {
-                float4 t = *reinterpret_cast<const float4 *>(bp + kb);
-                bv[c][0] = t.x; bv[c][1] = t.y; bv[c][2] = t.z; bv[c][3] = t.w;
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) bv[c][s] = (kb + s < kend) ? bp[(long)(kb + s) * p.b_rs] : 0.f;
-            }
-        }
-        if (kk0 == kbeg) {
-            FWD_STAMP(1);
-            FWD_LANDED(av[0][0]);
-            FWD_LANDED(bv[0][0]);
-            FWD_STAMP(2);
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            if (kk0 + 16 * c >= kend) break;  // wave-uniform
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const float a = a_ok ? av[c][s] : 0.f;
-                const float b = b_ok ? bv[c][s] : 0.f;
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-            }
-        }
-    }
-    FWD_LANDED(acc[0]);
-    FWD_STAMP(3);
-
-    // deterministic in-workgroup reduction: every wave parks its 4 partial sums; wave e adds element e
-    // of waves 0..NW-1 in wave order
-    if (!SUB || (g * 4 < RM && r < RN)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
-    }
-    __syncthreads();
-    FWD_STAMP(4);
-    if (wave < 4 && e_sub) {
-        float sum = red[0][lane][wave];
-        for (int w = 1; w < NW; ++w) sum += red[w][lane][wave];
-        // C/D map of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + i  (here i = wave)
-        if (e_ok) {
-            if (p.partial) {
-                p.partial[(long)zslice * p.m * p.n + e_ix] = sum;
-            } else {
-                float out = p.ep.alpha * sum;
-                if (p.ep.beta != 0.0f) out += p.ep.beta * e_cold;
-                if (p.ep.bias) out += e_bias;
-                if (p.ep.relu) out = out > 0.0f ? out : 0.0f;
-                p.C[e_ix] = out;
-                if (fuse_adam) {  // th_linear_bwd_adam: C is a complete gradient (optim.rs:99-110)
-                    const AdamDev &ad = p.ep.adam;
-                    const AdamMV x = adam_moments(ad, e_p, e_m, e_v, out);
-                    ad.m[e_ix] = x.m;
-                    ad.v[e_ix] = x.v;
-                    ad.p[e_ix] = adam_param(ad, e_p, x, e_step);
-                }
-            }
-        }
-    }
-#ifdef TH_PROFILE
-    if constexpr (STAMPED) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): stamp 5 is the store's return, not its issue
-#endif
-    FWD_STAMP(5);
-}
-
+// the small / latency-bound kernel's body: small16_dev.h
 // grid = (tiles_n, tiles_m, kz); block = 64 * NW
 template <bool A_KC, bool B_KC, int NW>
 __global__ __launch_bounds__(64 * NW) void sgemm_small16(SmallArgs p) {
     __shared__ float red[NW][64][4];
     small16_body<A_KC, B_KC, NW, false>(p, blockIdx.y, blockIdx.x, blockIdx.z, red);
-}
-
-// th_linear_fwd_ex: the same tiles on rows [0, gridDim.y - 1) of the grid; block (0, gridDim.y - 1) applies the
-// carried Adam slices with the step counter as it stands and then opens the next step (t += 1).
-// The tiles are this launch's tail, not that spare workgroup: measured in situ it adds 0.08-0.11 us to the step over plain tiles
-// (tools/step_tails_probe.py, profiles/mlp_step_tails.md), and a one-round-trip rewrite of it gained nothing that probe can tell from noise -- not kept.
-template <bool A_KC, bool B_KC, int NW, int RM = 16, int RN = 16>
-__global__ __launch_bounds__(64 * NW) void sgemm_small16_tick(SmallArgs p, AdamSlices x, int32_t *tick) {
-    __shared__ float red[NW][64][4];
-    if (blockIdx.y + 1 < gridDim.y) {
-        int tm = blockIdx.y, tn = blockIdx.x;
-        if (p.xcd_blocks) {
-            // 64 x 128 outputs (the MNIST MLP's layer 1 at batch 64): block b runs on XCD b % 8; give every XCD the (sub-)tiles of one 32 x 32
-            // block of H instead of a column of them, so its L2 fetches 32 rows of X and 32 of W (200 KB) instead of all of X and 16 of W (250 KB)
-            constexpr int SBM = 32 / RM, SBN = 32 / RN;
-            static_assert(SBN == 2 || SBN == 4, "sub-tiles of 16 or 8 columns");
-            const int b = blockIdx.x + gridDim.x * blockIdx.y, q = b & 7, j = b >> 3;
-            tm = SBM * (q >> 2) + (j >> (SBN == 4 ? 2 : 1));
-            tn = SBN * (q & 3) + (j & (SBN - 1));
-        }
-#ifdef TH_PROFILE
-        small16_body<A_KC, B_KC, NW, false, RM, RN, true>(p, tm, tn, 0, red);
-#else
-        small16_body<A_KC, B_KC, NW, false, RM, RN>(p, tm, tn, 0, red);
-#endif
-        return;
-    }
-    if (blockIdx.x == 0) adam_slices_then_tick(x, tick);
 }
 
 // second pass of grid-level split-K: fixed slice order -> deterministic.  With ep.adam set, C is a
@@ -1360,17 +1134,8 @@ int th_linear_fwd_ex(th_ctx *ctx, const float *d_x, const float *d_w, const floa
     const FwdExPlan pl = fwd_ex_plan(m, n, k, ctx->fwd_subtiles != 0);
     // the latency-bound case this entry exists for: 16x16 MFMA tiles, no grid-level K split -> ONE launch
     if (pl.one_launch) {
-        SmallArgs p{d_x, nullptr, d_w, d_y, nullptr, m, n, k, k, 1, 1, k, (k + 15) / 16 * 16, 0, 0, make_ep(1.0f, 0.0f, d_b, relu)};
-        p.a_vec = aligned16(d_x) && (k % 4 == 0);
-        p.b_vec = aligned16(d_w) && (k % 4 == 0);
-        const AdamSlices x = make_adam_slices(extra, n_extra, ctx);
-        const dim3 grid(pl.grid_x, pl.grid_y, 1);
-        p.xcd_blocks = pl.xcd_blocks;
-        if (pl.rm == 8) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16, 8, 8>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
-        else if (pl.waves == 16) hipLaunchKernelGGL((sgemm_small16_tick<true, true, 16>), grid, dim3(1024), 0, ctx->stream, p, x, d_tick);
-        else hipLaunchKernelGGL((sgemm_small16_tick<true, true, 4>), grid, dim3(256), 0, ctx->stream, p, x, d_tick);
-        TH_LAUNCH_CHECK();
-        return 0;
+        const FwdTickLaunch q{pl.rm, pl.waves, pl.grid_x, pl.grid_y, pl.xcd_blocks, aligned16(d_x) && (k % 4 == 0), aligned16(d_w) && (k % 4 == 0)};
+        return fwd_tick_launch(ctx, q, d_x, d_w, d_b, d_y, m, n, k, relu, make_adam_slices(extra, n_extra, ctx), d_tick);
     }
     // other shapes: the slices (old counter), the tick, then the product
     if (int rc = th_adam_slices(ctx, extra, n_extra)) return rc;
@@ -1394,15 +1159,6 @@ int th_debug_linear_fwd_ex_plan(int batch, int in_features, int out_features, in
     std::copy(out, out + 8, out8);
     return 0;
 }
-
-#ifdef TH_PROFILE
-int th_debug_fwd_prof(th_ctx *ctx, long long *h_out, int n_blocks) {
-    TH_REQUIRE(ctx && h_out && n_blocks >= 1 && n_blocks <= th::kFwdProfBlocks, "th_debug_fwd_prof: bad argument");
-    TH_HIP(hipStreamSynchronize(ctx->stream));
-    TH_HIP(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(th::g_fwd_prof), (size_t)n_blocks * 12 * sizeof(long long)));
-    return 0;
-}
-#endif
 
 }  // extern "C" (reopened below)
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """In-kernel stamps of the MLP step's first launch (th_linear_fwd_ex: sgemm_small16_tick at 784 -> 128): where a tile workgroup
 spends its time.  Needs the profile build of the kernel library (`make -C taper_amd/csrc PROFILE=1`: the FWD_STAMP points of
-small16_body in gemm.hip, 100 MHz wall clock, lane 0 of wave 0 and of the last wave that owns a whole K chunk, every workgroup).
+small16_body in small16_dev.h and the entry reading of fwd_tick.hip, 100 MHz wall clock, lane 0 of wave 0 and of the last wave that owns a whole K chunk, every workgroup).
 The step's two launches run back to back on the stream as in the Trainer's graph (tools/step_tails_probe.py's chain), so the
 launch finds X unread and W1 just rewritten by the gradient launch's Adam epilogue; after every `--steps` steps the stamps of the
 LAST forward launch are read.
@@ -9,10 +9,14 @@ LAST forward launch are read.
   stamp 0  entry                              3  last MFMA retired
         1  all operand loads issued           4  behind the barrier
         2  operands of the first MFMA landed  5  the store has returned
+        6  the kernel's true entry, read in front of any argument use (stamp 0, "entry" of the body, lies behind the kernel's
+           choice of role and its tile numbers, in front of the operand addresses)
 
 Per wave (w0 = wave 0, wl = the last whole-chunk wave), medians over the tile workgroups, then over the samples, us:
   issue  1 - 0      land  2 - 1      mfma  3 - 2      wait  3 - 1 (loads issued -> all of them consumed)
   sync   4 - 3      store 5 - 4      body  5 - 0      end   5 - the launch's earliest stamp 0
+  args   0 - 6 (true entry -> the body starts forming operand addresses)      entry_issue  1 - 6 (true entry -> all operand loads requested:
+  what the kernel-argument fetches cost shows here)
 and the workgroup that ends last (block id, its end).  A beyond-L2 round trip is about 0.4 us (an HBM miss: 900 cycles).
 
   python tools/prof_fwd.py [--batch 64] [--subtiles 1] [--samples 200] [--json OUT] [--root TREE]
@@ -76,9 +80,10 @@ def step():
              int(g2) + 4 * OUT * HID, None, None, metrics, 4096, state, 1, C.byref(w1f), C.byref(b1f))
 
 
-SEGS = (("issue", 1, 0), ("land", 2, 1), ("mfma", 3, 2), ("wait", 3, 1), ("sync", 4, 3), ("store", 5, 4), ("body", 5, 0))
+SEGS = (("issue", 1, 0), ("land", 2, 1), ("mfma", 3, 2), ("wait", 3, 1), ("sync", 4, 3), ("store", 5, 4), ("body", 5, 0), ("args", 0, 6),
+        ("entry_issue", 1, 6))
 rows = []
-buf = np.zeros((n_tiles, 2, 6), np.int64)
+buf = np.zeros((n_tiles, 2, 8), np.int64)   # (slots 0..6 are stamps, 7 is unused)
 for it in range(args.samples + 10):
     lib.th_memcpy_h2d(ctx.h, int(tick), tick0.ctypes.data, tick0.nbytes)
     for _ in range(args.steps):
