@@ -459,6 +459,29 @@ int th_q8q8_max_k(void);         /* the longest K (in_features; c_in k_h k_w of 
  * d_scale = the scale th_fake_quant_act gives that range: max(|min|, |max|) / 127, all zero -> (0, 1), all equal to m -> (0.9 m, 1.1 m).
  * Two launches on th_quantize_int8's min / max partials. */
 int th_act_range_update(th_ctx *ctx, const float *d_x, int64_t n, int first, float *d_range2, float *d_scale);
+/* Percentile calibration (csrc/qcalib.hip): a histogram of |x| over the range th_act_range_update found, then the scale of the smallest
+ * clip that keeps keep_ppm millionths of the elements.  Both calls only enqueue work (no synchronisation, nothing read back, nothing
+ * allocated: they can be captured) and use integer atomics only, so the counters are bit-identical from run to run.
+ * th_act_hist_update adds every FINITE element of d_x[0, n) (NaN and +-inf are skipped, as the range skips them) to d_bins, num_bins
+ * 64-bit counters that the caller zeroes before the first call; later calls accumulate.  With amax = max(|d_range2[0]|, |d_range2[1]|)
+ * read on the device and inv = (float)num_bins / amax, the bin of v is min((int)(|v| * inv), num_bins - 1), each f32 operation rounded
+ * once.  The cast never sees a product that is not finite: +inf (an element above a tiny range; every non-zero element when amax is 0)
+ * and NaN (0 * inf when amax is 0; a NaN amax) take the last bin.  So an element above amax -- a tensor the range pass never saw -- and
+ * every element equal to amax count in the last bin, and with an infinite amax (a range over nothing finite) every finite element counts
+ * in bin 0.  Per-workgroup 32-bit counters in LDS, merged once per workgroup; 16-byte loads when d_x is 16-byte aligned, scalar loads
+ * otherwise -- the same counters either way.  Refused before a launch: a null ctx, d_range2 or d_bins, a null d_x with n > 0, n < 0 or
+ * n >= 2^40, num_bins outside [16, th_act_hist_max_bins()].  n == 0 returns 0 and launches nothing.
+ * th_act_scale_from_hist (one workgroup): total = the sum of the bins, k = the first bin with cum[k] * 1 000 000 >= total * keep_ppm
+ * (64-bit integers: exact for total < 2^43), threshold T = (float)(k + 1) * (amax / (float)num_bins) -- exactly amax when
+ * k == num_bins - 1 -- and d_scale[0] = T / 127.0f; d_stats4 = {k, total, cum[k], bins[k]}.  Fallback: min == max, an amax that is not a
+ * normal number (zero, subnormal, infinite, NaN) or total == 0 leaves d_scale[0] as th_act_range_update wrote it and writes
+ * d_stats4 = {num_bins - 1, total, total, bins[num_bins - 1]}: the rules of such a range stay in one place.  The element that set amax
+ * counts in the last bin, so keep_ppm = 1 000 000 on the histogram of the tensors the range came from gives th_act_range_update's scale
+ * bit for bit.  Refused before the launch: a null argument, num_bins outside [16, th_act_hist_max_bins()], keep_ppm outside
+ * [1, 1 000 000]. */
+int th_act_hist_update(th_ctx *ctx, const float *d_x, int64_t n, const float *d_range2, int num_bins, uint64_t *d_bins);
+int th_act_scale_from_hist(th_ctx *ctx, const uint64_t *d_bins, int num_bins, const float *d_range2, int keep_ppm, float *d_scale, uint64_t *d_stats4);
+int th_act_hist_max_bins(void);   /* the most bins a workgroup's LDS counters hold: 8 192 */
 
 /* ---- calibrated int8 convolution: the same arithmetic over a window, an implicit GEMM on the integer matrix cores (csrc/qconv_i8.hip) ----
  * Codes are channel-last: qx[n][h][w][cpitch] and qw[c_out][k_h k_w][cpitch], cpitch a multiple of 16 and >= c_in, the bytes

@@ -195,6 +195,24 @@ int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *
 #define TP_QSTATIC_PER_CHANNEL 4
 #define TP_QSTATIC_LINKS 16
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out);
+/* tp_module_quantize_static_ex with the rule that turns the calibration tensors into each static layer's activation scale.  `flags`: the
+ * TP_QSTATIC_* flags above, their rules unchanged; every twin form, the BatchNorm folds and the QAT inner layers combine with either
+ * method -- only the value of each layer's scale differs.  method = TP_CALIB_MINMAX: tp_module_quantize_static_ex itself (keep_ppm and
+ * num_bins are not read; nothing more runs or is allocated).  method = TP_CALIB_PERCENTILE: the calibration set is shown twice -- the
+ * range pass, then every static layer adds its float inputs to its own histogram of |x| with num_bins bins over [0, max(|min|, |max|)]
+ * (th_act_hist_update) -- and each scale becomes T / 127, T the upper edge of the first bin at which keep_ppm millionths of the layer's
+ * finite input elements are kept (th_act_scale_from_hist; its fallbacks leave the min / max scale).  keep_ppm = 1 000 000 gives the
+ * min / max scales bit for bit.  The histograms are released before the call returns.  Refused by name before the model or the device is
+ * touched: flags as above, a method that is neither, and with TP_CALIB_PERCENTILE keep_ppm outside [1, 1 000 000] or num_bins outside
+ * [16, th_act_hist_max_bins()]; then tp_module_quantize_static's refusals.
+ * tp_qmodule_calibration: static layer i in tp_qmodule_act_scales order, of any static twin -- out4 = {finite min, finite max, threshold,
+ * scale}, stats4 = {bin, total, kept, bin_count}: the bin the threshold ends, the finite elements counted, those at or below the
+ * threshold's bin, and that bin's own count (all 0 for a min / max twin, whose threshold is max(|min|, |max|)). */
+#define TP_CALIB_MINMAX 0
+#define TP_CALIB_PERCENTILE 1
+int tp_module_quantize_static_cal(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, int method, int keep_ppm, int num_bins,
+                                  tp_qmodule **out);
+int tp_qmodule_calibration(const tp_qmodule *q, int i, float *out4, uint64_t *stats4);
 /* the layer boundaries a forward crosses in int8 (the links above: conv -> conv, Flatten, Linear -> Linear); 0 for a twin made without
  * TP_QSTATIC_CHAIN and TP_QSTATIC_LINKS */
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out);

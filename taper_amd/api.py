@@ -265,6 +265,7 @@ def accuracy(pred, targets) -> float:
 
 
 _QSTATIC_CONVS, _QSTATIC_CHAIN, _QSTATIC_PER_CHANNEL, _QSTATIC_LINKS = 1, 2, 4, 16      # include/taper_host.h's TP_QSTATIC_* flags
+_CALIB_MINMAX, _CALIB_PERCENTILE = 0, 1                                                 # ... and its TP_CALIB_* methods
 
 
 # -- src/nn.rs, src/activation.rs ------------------------------------------------
@@ -356,6 +357,18 @@ class Module:
         flags = _QSTATIC_CONVS | _QSTATIC_CHAIN | _QSTATIC_LINKS | (_QSTATIC_PER_CHANNEL if per_channel else 0)
         return self._quantize_static(host.tp_module_quantize_static_ex, "quantize_static_linked", calib, flags)
 
+    def quantize_static_calibrated(self, calib, percentile=99.99, bins=2048, convs=True, chain=True, per_channel=False, links=False):
+        """Any static twin (by `convs`, `chain`, `per_channel` and `links`, as the calls above) whose activation scales come from a
+        percentile of each static layer's |input| over `calib` instead of its min / max: the calibration set runs twice, the second
+        time into a histogram of `bins` bins per layer on the device, and each scale is the upper edge of the first bin that keeps
+        `percentile` per cent of the layer's finite input elements, over 127 -- one outlier no longer sets the scale of a layer.
+        keep_ppm = round(percentile * 1e4) must lie in [1, 1 000 000]; percentile=100 gives the min / max scales bit for bit.  Packing,
+        tensors, links and refusals are those of the same flags; calibration() reports what each layer kept."""
+        flags = ((_QSTATIC_CONVS if convs or chain else 0) | (_QSTATIC_CHAIN if chain else 0) | (_QSTATIC_PER_CHANNEL if per_channel else 0)
+                 | (_QSTATIC_LINKS if links else 0))
+        return self._quantize_static(host.tp_module_quantize_static_cal, "quantize_static_calibrated", calib, flags, _CALIB_PERCENTILE,
+                                     int(round(float(percentile) * 1e4)), int(bins))
+
     def _quantize_static(self, entry, name, calib, *flags):
         """one static quantize call of the host library: the calibration tensors marshalled, `flags` for the entry point that takes them"""
         tensors = [calib] if isinstance(calib, Tensor) else list(calib)
@@ -404,6 +417,20 @@ class QuantizedModule:
         out = np.zeros(n.value, np.float32)
         if n.value:
             tp_check(host.tp_qmodule_act_scales(self._h, out.ctypes.data, n.value, C.byref(n)), "QuantizedModule::act_scales")
+        return out
+
+    def calibration(self):
+        """one dict per static layer, in act_scales() order: the finite `min` and `max` of the layer's float inputs over the calibration
+        set, the clip `threshold` and `scale` = threshold / 127, and of a quantize_static_calibrated twin the histogram's `bin` the
+        threshold ends, `total` finite elements counted, `kept` of them at or below that bin and `bin_count` in the bin itself (0 for a
+        min / max twin, whose threshold is max(|min|, |max|))"""
+        n = C.c_int()
+        tp_check(host.tp_qmodule_act_scales(self._h, None, 0, C.byref(n)), "QuantizedModule::calibration")
+        out = []
+        for i in range(n.value):
+            f, u = np.zeros(4, np.float32), np.zeros(4, np.uint64)
+            tp_check(host.tp_qmodule_calibration(self._h, i, f.ctypes.data, u.ctypes.data), "QuantizedModule::calibration")
+            out.append(dict(min=f[0], max=f[1], threshold=f[2], scale=f[3], bin=int(u[0]), total=int(u[1]), kept=int(u[2]), bin_count=int(u[3])))
         return out
 
     def affines(self):

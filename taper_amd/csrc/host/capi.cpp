@@ -1,5 +1,6 @@
 // capi.cpp -- include/taper_host.h: opaque-handle C ABI over the C++ host.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "../../../include/taper_host.h"
@@ -19,6 +20,7 @@ struct tp_qmodule {
     std::unique_ptr<QuantizedModule> q;
     std::vector<const QTensor *> tensors;
     std::vector<const float *> act_scales;
+    std::vector<ActCalibration> calibrations;
     std::vector<std::pair<const float *, size_t>> affines;
 };
 struct tp_observer { std::unique_ptr<MinMaxObserver> minmax; std::unique_ptr<HistogramObserver> hist; };   // one of the two, by kind
@@ -293,19 +295,27 @@ int tp_module_quantize(const tp_module *m, int qtype, int enabled, tp_qmodule **
     TP_END
 }
 // every static twin, by TP_QSTATIC_* flags: `fn` is the caller's name for the message
-static void quantize_static_into(const char *fn, const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
+static void quantize_static_into(const char *fn, const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out,
+                                 Calibration cal = {}) {
     TAPER_ASSERT(m && out, std::string(fn) + ": null argument");
     std::vector<Tensor> c;   // (a null list or a null entry is an undefined tensor: refused with the other checks, after the module's own)
     for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
     QuantizeOptions o;
     o.convs = (flags & TP_QSTATIC_CONVS) != 0, o.chain = (flags & TP_QSTATIC_CHAIN) != 0, o.per_channel = (flags & TP_QSTATIC_PER_CHANNEL) != 0;
     o.links = (flags & TP_QSTATIC_LINKS) != 0;
+    o.calibration = cal;
     auto h = std::make_unique<tp_qmodule>();
     h->q = quantize_static(*m->m, c, o);
     h->q->tensors(&h->tensors);
     h->q->act_scales(&h->act_scales);
+    h->q->calibrations(&h->calibrations);
     h->q->affines(&h->affines);
     *out = h.release();
+}
+// the flag rules of every call that takes TP_QSTATIC_* flags
+static void check_qstatic_flags(const std::string &fn, int flags) {
+    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL | TP_QSTATIC_LINKS)) == 0, fn + ": unknown flag bits");
+    TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), fn + ": TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
 }
 int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN
@@ -324,9 +334,43 @@ int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *
 }
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out) {
     TP_BEGIN
-    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL | TP_QSTATIC_LINKS)) == 0, "tp_module_quantize_static_ex: unknown flag bits");
-    TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), "tp_module_quantize_static_ex: TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
+    check_qstatic_flags("tp_module_quantize_static_ex", flags);
     quantize_static_into("tp_module_quantize_static_ex", m, calib, n_calib, flags, out);
+    TP_END
+}
+int tp_module_quantize_static_cal(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, int method, int keep_ppm, int num_bins,
+                                  tp_qmodule **out) {
+    TP_BEGIN
+    const std::string fn = "tp_module_quantize_static_cal";
+    // the arguments that need nothing but themselves first: a refused call has touched neither the model nor the device
+    check_qstatic_flags(fn, flags);
+    TAPER_ASSERT(method == TP_CALIB_MINMAX || method == TP_CALIB_PERCENTILE, fn + ": unknown method " + std::to_string(method) + " (TP_CALIB_MINMAX or TP_CALIB_PERCENTILE)");
+    if (method == TP_CALIB_PERCENTILE) {
+        TAPER_ASSERT(keep_ppm >= 1 && keep_ppm <= 1000000, fn + ": keep_ppm must be in [1, 1000000] (got " + std::to_string(keep_ppm) + ")");
+        TAPER_ASSERT(num_bins >= 16 && num_bins <= th_act_hist_max_bins(),
+                     fn + ": num_bins must be in [16, " + std::to_string(th_act_hist_max_bins()) + "] (got " + std::to_string(num_bins) + ")");
+    }
+    Calibration cal;
+    cal.method = method == TP_CALIB_PERCENTILE ? CalibMethod::Percentile : CalibMethod::MinMax;
+    if (method == TP_CALIB_PERCENTILE) cal.keep_ppm = keep_ppm, cal.num_bins = num_bins;
+    quantize_static_into(fn.c_str(), m, calib, n_calib, flags, out, cal);
+    TP_END
+}
+int tp_qmodule_calibration(const tp_qmodule *q, int i, float *out4, uint64_t *stats4) {
+    TP_BEGIN
+    TAPER_ASSERT(q && out4 && stats4, "tp_qmodule_calibration: null argument");
+    TAPER_ASSERT(i >= 0 && (size_t)i < q->calibrations.size(), "tp_qmodule_calibration: index out of range");
+    const ActCalibration &c = q->calibrations[(size_t)i];
+    float r[3];
+    uint64_t s[4] = {0, 0, 0, 0};
+    taper::th_check(th_memcpy_d2h(Device::ctx(), r, c.range, sizeof(r)), "th_memcpy_d2h");
+    if (c.stats) taper::th_check(th_memcpy_d2h(Device::ctx(), s, c.stats, sizeof(s)), "th_memcpy_d2h");
+    // th_act_scale_from_hist's threshold from its own bin, the same f32 operations; the whole range where the range rule stands
+    const float amax = std::max(std::fabs(r[0]), std::fabs(r[1]));
+    const bool clipped = c.stats && s[0] + 1 < (uint64_t)c.num_bins;
+    out4[0] = r[0], out4[1] = r[1], out4[3] = r[2];
+    out4[2] = clipped ? (float)(s[0] + 1) * (amax / (float)c.num_bins) : amax;
+    std::copy(s, s + 4, stats4);
     TP_END
 }
 int tp_qmodule_chain_links(const tp_qmodule *q, int *out) {

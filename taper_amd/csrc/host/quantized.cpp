@@ -54,15 +54,41 @@ class QPass : public QuantizedModule {
 
 // The calibrated activation of a static twin, on the device: {finite min, finite max} of the calibration inputs, then the scale they
 // give.  Empty in a weight-only twin.
+// Percentile calibration adds, while quantize_static runs, `hist`: the layer's own counters over the final range, made and
+// zeroed at its first input of pass two and given back once the scale is written; `stats`, the four integers of the report, stays.
 struct ActScale {
     std::shared_ptr<Buffer> buf;
+    mutable std::shared_ptr<Buffer> hist, stats;   // (calibration fills a twin it only reads otherwise)
+    mutable int bins = 0;
     explicit operator bool() const { return buf != nullptr; }
     void alloc() { buf = Buffer::alloc(3); }
     const float *scale() const { return buf->d + 2; }
+    uint64_t *counters() const { return reinterpret_cast<uint64_t *>(hist->d); }
+    uint64_t *report() const { return reinterpret_cast<uint64_t *>(stats->d); }
     // calibration: the finite min / max of one more float input of the layer, and the scale of the range so far
     void observe(const Tensor &x, bool first) const { TH(th_act_range_update(Device::ctx(), x.dptr(), (int64_t)x.len(), first ? 1 : 0, buf->d, buf->d + 2)); }
+    // pass two: one more float input of the layer into its histogram of |x| against the final range
+    void observe_hist(const Tensor &x, int num_bins) const {
+        th_ctx *ctx = Device::ctx();
+        if (!hist) {
+            hist = Buffer::alloc(2 * (size_t)num_bins);
+            stats = Buffer::alloc(8);
+            bins = num_bins;
+            TH(th_fill_f32(ctx, hist->d, 0.0f, 2 * (size_t)num_bins));   // (the bits of 0.0f are those of a zero counter)
+        }
+        TH(th_act_hist_update(ctx, x.dptr(), (int64_t)x.len(), buf->d, bins, counters()));
+    }
+    // after pass two: the scale of the clip that keeps keep_ppm millionths, the report, and the counters back to the pool
+    void scale_from_hist(int keep_ppm) const {
+        if (!hist) return;
+        TH(th_act_scale_from_hist(Device::ctx(), counters(), bins, buf->d, keep_ppm, buf->d + 2, report()));
+        hist.reset();   // (stream order keeps it alive for the launch above)
+    }
     void list(std::vector<const float *> *out) const {
         if (buf) out->push_back(scale());
+    }
+    void list(std::vector<ActCalibration> *out) const {
+        if (buf) out->push_back(ActCalibration{buf->d, stats ? report() : nullptr, bins});
     }
 };
 
@@ -188,6 +214,7 @@ class QLinear : public QuantizedModule {   // nn.rs:62-69, 88-120
         if (b_) out->push_back(b_.get());
     }
     void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
+    void calibrations(std::vector<ActCalibration> *out) const override { act_.list(out); }
     const ActScale &act() const { return act_; }
 
    private:
@@ -314,6 +341,7 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         return out;
     }
     void act_scales(std::vector<const float *> *out) const override { act_.list(out); }
+    void calibrations(std::vector<ActCalibration> *out) const override { act_.list(out); }
     const ActScale &act() const { return act_; }
     Tensor forward(const Tensor &x) const override {   // alone: dequantize its own two tensors
         if (is_static()) return product(encode(x), {}).y;   // two launches: the codec (its buffers pooled, returned with this expression), then the product
@@ -522,6 +550,9 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     void act_scales(std::vector<const float *> *out) const override {
         for (const auto &l : layers) l->act_scales(out);
     }
+    void calibrations(std::vector<ActCalibration> *out) const override {
+        for (const auto &l : layers) l->calibrations(out);
+    }
     void affines(std::vector<std::pair<const float *, size_t>> *out) const override {
         for (const auto &l : layers) l->affines(out);
     }
@@ -611,14 +642,15 @@ void layers_of(const Module &m, std::vector<const L *> *out) {
 // Linear twin and every static conv twin in `q` shown its float input.  The parameters go in as views that require no gradient: no tape node is recorded.
 // A Sequential twin's layers are the twins of leaves_of(m), one each and in that order (quantize_checked made them so).
 // A BatchNorm2d runs in eval mode on its running pair whatever its flag says, by the kernel itself: the layer is only read.
-Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first) {
+// hist_bins > 0: pass two of the percentile calibration -- the same walk, every static layer adds its input to its histogram instead.
+Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, bool first, int hist_bins = 0) {
     auto plain = [](const Tensor &t) { return t.defined() ? Tensor::from_device(t.dptr(), t.shape()) : Tensor(); };
     const std::vector<const Module *> leaves = leaves_of(m);
     if (auto *qs = dynamic_cast<const QSequential *>(&q)) {
         TAPER_ASSERT(leaves.size() == qs->layers.size(), "calibrate: the twin is not this model's");
         Tensor h = x;
         auto twin = qs->layers.begin();
-        for (const Module *l : leaves) h = calibrate(*l, **twin++, h, first);
+        for (const Module *l : leaves) h = calibrate(*l, **twin++, h, first, hist_bins);
         return h;
     }
     const Module &l = *leaves[0];
@@ -634,15 +666,27 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
         return y;
     }
     if (auto *lin = dynamic_cast<const Linear *>(&l)) {
-        dynamic_cast<const QLinear &>(q).act().observe(x, first);
+        const ActScale &act = dynamic_cast<const QLinear &>(q).act();
+        hist_bins ? act.observe_hist(x, hist_bins) : act.observe(x, first);
         return x.linear(plain(lin->weight), plain(lin->bias), false);
     }
     if (auto *cv = dynamic_cast<const Conv2d *>(&l)) {
         auto &qcv = dynamic_cast<const QConv &>(q);
-        if (qcv.is_static()) qcv.act().observe(x, first);
+        if (qcv.is_static()) hist_bins ? qcv.act().observe_hist(x, hist_bins) : qcv.act().observe(x, first);
         return cv->forward_with(x, plain(cv->weight), plain(cv->bias));
     }
     return l.forward(x);
+}
+
+// every static layer's ActScale of a twin, nested Sequential twins included
+void each_act_scale(const QuantizedModule &q, const std::function<void(const ActScale &)> &f) {
+    if (auto *qs = dynamic_cast<const QSequential *>(&q)) {
+        for (const auto &l : qs->layers) each_act_scale(*l, f);
+    } else if (auto *l = dynamic_cast<const QLinear *>(&q)) {
+        if (l->is_static()) f(l->act());
+    } else if (auto *c = dynamic_cast<const QConv *>(&q)) {
+        if (c->is_static()) f(c->act());
+    }
 }
 
 }  // namespace
@@ -672,6 +716,14 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
     o.convs = o.convs || o.chain;
     // every refusal before anything is allocated
     check_quantizable(m, /*batchnorm=*/true);
+    const Calibration &cal = o.calibration;
+    const bool percentile = cal.method == CalibMethod::Percentile;
+    TAPER_ASSERT(percentile || cal.method == CalibMethod::MinMax, "quantize_static: unknown calibration method " + std::to_string((int)cal.method));
+    if (percentile) {
+        TAPER_ASSERT(cal.keep_ppm >= 1 && cal.keep_ppm <= 1000000, "quantize_static: keep_ppm must be in [1, 1000000] (got " + std::to_string(cal.keep_ppm) + ")");
+        TAPER_ASSERT(cal.num_bins >= 16 && cal.num_bins <= th_act_hist_max_bins(),
+                     "quantize_static: num_bins must be in [16, " + std::to_string(th_act_hist_max_bins()) + "] (got " + std::to_string(cal.num_bins) + ")");
+    }
     TAPER_ASSERT(!calib.empty(), "quantize_static: at least one calibration tensor is needed");
     for (const Tensor &c : calib) TAPER_ASSERT(c.defined(), "quantize_static: undefined calibration tensor");
     std::vector<const Linear *> lins;
@@ -694,6 +746,10 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
     for (size_t i = 0; i < calib.size(); ++i) {
         Tensor x = Tensor::from_device(calib[i].dptr(), calib[i].shape());   // (a view that requires no gradient)
         calibrate(m, *q, x, i == 0);
+    }
+    if (percentile) {   // pass two against the final ranges, then one scale launch per static layer
+        for (const Tensor &c : calib) calibrate(m, *q, Tensor::from_device(c.dptr(), c.shape()), false, cal.num_bins);
+        each_act_scale(*q, [&](const ActScale &a) { a.scale_from_hist(cal.keep_ppm); });
     }
     return q;
 }

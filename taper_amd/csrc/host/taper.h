@@ -495,6 +495,26 @@ struct QTensor {   // a QuantizedTensor (tensor.rs:2084-2108) on the device: cod
     th_qtensor item(float *d_out) const;
 };
 
+// How quantize_static turns the calibration tensors into each static layer's activation scale.  MinMax: the finite min / max
+// of the layer's float inputs (th_act_range_update), nothing else runs or is allocated.  Percentile: the calibration set is shown twice --
+// pass one is the range pass; in pass two every static layer adds its float inputs to its own histogram of |x| with num_bins bins over
+// the final range (th_act_hist_update); then one th_act_scale_from_hist per layer writes the scale of the smallest clip that keeps
+// keep_ppm millionths of the elements, and the histogram goes back to the pool.  keep_ppm = 1 000 000 gives the MinMax scales bit for
+// bit.  keep_ppm outside [1, 1 000 000] and num_bins outside [16, th_act_hist_max_bins()] are refused with quantize_static's other
+// refusals, before anything is allocated (both are read only with Percentile).
+enum class CalibMethod { MinMax = 0, Percentile = 1 };
+struct Calibration {
+    CalibMethod method = CalibMethod::MinMax;
+    int keep_ppm = 999900, num_bins = 2048;
+};
+// One static layer's calibration record, on the device: range = {finite min, finite max, scale}; stats = {bin, total, kept, bin_count}
+// as 64-bit integers (th_act_scale_from_hist's d_stats4) of a Percentile twin, null otherwise
+struct ActCalibration {
+    const float *range = nullptr;
+    const uint64_t *stats = nullptr;
+    int num_bins = 0;
+};
+
 class QuantizedModule {
    public:
     virtual ~QuantizedModule() = default;
@@ -502,6 +522,7 @@ class QuantizedModule {
     virtual void tensors(std::vector<const QTensor *> *out) const {}   // in the order of the source module's parameters()
     virtual void act_scales(std::vector<const float *> *out) const {}  // device addresses of the calibrated activation scales, in layer order
     virtual int chain_links() const { return 0; }                      // layer boundaries a forward crosses in int8 (quantize_static's chain and links)
+    virtual void calibrations(std::vector<ActCalibration> *out) const {}   // one record per static layer, in act_scales() order
     // every frozen BatchNorm2d in layer order: the device address of its [channels][2] = {a, b} and its channels
     virtual void affines(std::vector<std::pair<const float *, size_t>> *out) const {}
 };
@@ -546,6 +567,7 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // (linears: set by quantize_static itself -- every Linear static; quantize() leaves all five off)
 struct QuantizeOptions {
     bool linears = false, convs = false, chain = false, per_channel = false, links = false;
+    Calibration calibration;   // combines with every member above: only the value of each layer's scale differs
 };
 std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, QuantizeOptions o = {});
 

@@ -19,6 +19,7 @@
 // from run to run.  More bins than that, or edges that are not finite (an infinity or only NaNs in the first observation: the literal scan
 // is the definition there): a second form with a search per element over the edges in global memory and atomics on the global bins.
 #include "common.h"
+#include "hist_dev.h"
 #include "stream_dev.h"
 
 namespace th {
@@ -28,11 +29,7 @@ constexpr int kObsParts = 512;                     // workgroups of a fold's fir
 constexpr int64_t kObsPartMin = 4 * 256 * 8;       // elements per fold workgroup at least
 constexpr int kObsMapGrid = 2048;                  // workgroups of the element-wise passes at most (8 per CU)
 
-constexpr int kObsLdsMaxBins = 8192;               // (8193 table entries + 8192 counters) * 4 B = 64 KiB + 4: two such workgroups fit a CU's 160 KiB
-constexpr int kHistThreads = 1024;                 // 16 waves share a table and a set of counters: half the merges of two 8-wave workgroups
-constexpr int kHistGrid = 256;                     // one workgroup per CU
-constexpr int64_t kHistWgMin = 4 * 1024 * 4;       // elements per counting workgroup at least: a small tensor pays few table loads and merges
-constexpr int kHistGlobalGrid = 1024;
+constexpr int kHistGlobalGrid = 1024;              // (the LDS form's sizes: hist_dev.h)
 
 // ---- MinMaxObserver::observe ----
 __global__ __launch_bounds__(kObsThreads) void obs_minmax_first_kernel(const float *__restrict__ x, float *__restrict__ mn, float *__restrict__ mx, int64_t n) {
@@ -146,18 +143,10 @@ __global__ __launch_bounds__(kHistThreads) void obs_hist_lds_kernel(const float 
     const float e0 = edges[0], span = edges[nb] - e0;
     const float inv = span > 0.0f ? (float)nb / span : INFINITY;
 
-    // The wave's hot bin: elements that fall into it are counted by ballot into hot_n (wave-uniform) and skip the LDS add.  After each
-    // round of loads a wave that caught few elements that way looks for a better candidate among the lanes of the round's last element.
-    int hot = 0;
-    unsigned hot_n = 0, hot_seen = 0;   // hot_seen: hot_n at the last retarget
-    auto tally = [&](int k) {
-        hot_n += __popcll(__ballot(k == hot));
-        if (k != hot) atomicAdd(&cnt[k], 1u);
-    };
+    // the wave's hot bin, the walk by whole waves and the merge are hist_dev.h's; the bin of a value is this pass's own
+    HotBin hb{cnt};
     auto count = [&](float v, bool valid) {   // the loops of the ends: lanes past the end count nothing
-        const int k = valid ? obs_bin_guess(e, nb, v, e0, inv) : -1;
-        hot_n += __popcll(__ballot(k == hot));
-        if (k >= 0 && k != hot) atomicAdd(&cnt[k], 1u);
+        hb.count(valid ? obs_bin_guess(e, nb, v, e0, inv) : -1);
     };
     int last = 0;
     auto count4 = [&](float4 a) {   // the four bins first (their table reads overlap), then the counters
@@ -170,69 +159,13 @@ __global__ __launch_bounds__(kHistThreads) void obs_hist_lds_kernel(const float 
             if (!ok2) k2 = obs_bin_table_search(e, nb, a.z);
             if (!ok3) k3 = obs_bin_table_search(e, nb, a.w);
         }
-        tally(k0); tally(k1); tally(k2); tally(k3);
+        hb.tally(k0); hb.tally(k1); hb.tally(k2); hb.tally(k3);
         last = k3;
     };
-    auto retarget = [&](unsigned seen) {   // seen: elements the wave counted since the last call
-        if ((hot_n - hot_seen) * 8 < seen) {
-            unsigned long long rest = __ballot(last != hot);
-            for (int tries = 0; tries < 3 && rest; ++tries) {
-                const int cand = __builtin_amdgcn_readfirstlane(__shfl(last, __ffsll((long long)rest) - 1, 64));
-                const unsigned long long same = __ballot(last == cand);
-                if (__popcll(same) >= 8) {
-                    if (hot_n && (threadIdx.x & 63) == 0) atomicAdd(&cnt[hot], hot_n);
-                    hot_n = 0;
-                    hot = cand;
-                    break;
-                }
-                rest &= ~same;
-            }
-        }
-        hot_seen = hot_n;
-    };
-
-    const int64_t t0 = (int64_t)blockIdx.x * kHistThreads + threadIdx.x, stride = (int64_t)gridDim.x * kHistThreads;
-    int64_t head = 0;
-    if (((uintptr_t)x & 15) == 0) {
-        const float4 *x4 = (const float4 *)x;
-        const int64_t n4 = n >> 2;
-        // whole waves only (jw is the wave's first index: the trip count is wave-uniform, so hot / hot_n stay uniform and every ballot
-        // sees 64 lanes) -- which is why this walk is written out here and is not stream_dev.h's span_walk, whose lanes stop one by one;
-        // four 16-byte loads in flight per lane
-        int64_t jw = t0 - (threadIdx.x & 63);
-        for (; jw + 3 * stride + 63 < n4; jw += 4 * stride) {
-            const int64_t j = jw + (threadIdx.x & 63);
-            const float4 a = x4[j], b = x4[j + stride], c = x4[j + 2 * stride], d = x4[j + 3 * stride];
-            count4(a); count4(b); count4(c); count4(d);
-            retarget(16 * 64);
-        }
-        // the rest the same way, one load at a time: lanes past the end count nothing
-        for (int64_t jj = jw; jj < n4; jj += stride) {
-            const int64_t mine = jj + (threadIdx.x & 63);
-            const bool valid = mine < n4;
-            const float4 a = valid ? x4[mine] : make_float4(0.f, 0.f, 0.f, 0.f);
-            count(a.x, valid); count(a.y, valid); count(a.z, valid); count(a.w, valid);
-        }
-        head = n4 << 2;
-    }
-    {
-        const int64_t iw = head + t0 - (threadIdx.x & 63);
-        for (int64_t ii = iw; ii < n; ii += stride) {
-            const int64_t mine = ii + (threadIdx.x & 63);
-            const bool valid = mine < n;
-            count(valid ? x[mine] : 0.0f, valid);
-        }
-    }
-    if (hot_n && (threadIdx.x & 63) == 0) atomicAdd(&cnt[hot], hot_n);
+    hist_wave_walk(x, n, count4, [&] { hb.retarget(last, 16 * 64); }, count);
+    hb.flush();
     __syncthreads();
-    // merge: non-zero counters only, each workgroup from a bin of its own
-    const int start = (int)(((long long)blockIdx.x * nb) / gridDim.x);
-    for (int i = threadIdx.x; i < nb; i += kHistThreads) {
-        int k = i + start;
-        if (k >= nb) k -= nb;
-        const unsigned c = cnt[k];
-        if (c) atomicAdd(&bins[k], (unsigned long long)c);
-    }
+    hist_merge(cnt, nb, bins);
 }
 
 // ---- the counting pass, global form: any number of bins ----
