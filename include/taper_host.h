@@ -418,6 +418,10 @@ int tp_trainer_train_step(tp_trainer *t, const tp_tensor *images, const tp_tenso
 int tp_trainer_run_epoch(tp_trainer *t, tp_loader *l, int mode, size_t max_steps, float *avg_loss, float *accuracy,
                          size_t *total_correct, size_t *total_samples, size_t *num_batches, float *per_step,
                          size_t per_step_cap);
+/* What the last mode-1 call did, in order, as (kind, steps) pairs: 0 the state reset launched on its own, 1 steps enqueued eagerly (the
+ * last, partial batch: a trailing (1, 1)), 2 / 3 a step graph captured / replayed, 4 / 5 a whole-call graph (reset + steps) captured /
+ * replayed.  A read-only query, as the plan queries: n_out (nullable) receives the number of pairs, pairs (nullable) at most cap_pairs. */
+int tp_trainer_last_replays(const tp_trainer *t, int64_t *pairs, size_t cap_pairs, size_t *n_out);
 
 /* train.rs:175-261: fit = epochs of train + evaluate + scheduler.step(Some(val_loss)) + metrics + early
  * stop at val_acc > 0.99; graph != 0 trains through the captured step */

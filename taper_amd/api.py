@@ -1233,6 +1233,15 @@ class Trainer:
     def train_epoch_graph(self, loader, max_steps=0): return self.run_epoch(loader, self.GRAPH, max_steps)
     def evaluate(self, loader): return self.run_epoch(loader, self.EVAL)
 
+    def last_replays(self):
+        """what the last train_epoch_graph call did, in order: [(kind, steps)] with kind 0 the state reset on its own, 1 steps enqueued
+        eagerly, 2 / 3 a step graph captured / replayed, 4 / 5 a whole-call graph captured / replayed (read-only)"""
+        n = C.c_size_t()
+        tp_check(host.tp_trainer_last_replays(self._h, None, 0, C.byref(n)), "last_replays")
+        buf = np.zeros(2 * n.value, np.int64)
+        tp_check(host.tp_trainer_last_replays(self._h, buf.ctypes.data, n.value, None), "last_replays")
+        return [(int(k), int(s)) for k, s in buf.reshape(-1, 2)]
+
     # -- train.rs:175-292 ---------------------------------------------------------
     def fit(self, train_loader: DataLoader, val_loader: DataLoader, epochs: int, verbose: bool = False, graph: bool = True):
         tp_check(host.tp_trainer_fit(self._h, train_loader._h, val_loader._h, int(epochs), 1 if verbose else 0, 1 if graph else 0), "fit")

@@ -863,6 +863,16 @@ static int copy_text(const std::string &s, char *buf, size_t cap) {
     buf[n] = 0;
     return 0;
 }
+int tp_trainer_last_replays(const tp_trainer *t, int64_t *pairs, size_t cap_pairs, size_t *n_out) {
+    TP_BEGIN
+    const auto &ev = t->t->last_replays();
+    if (n_out) *n_out = ev.size();
+    for (size_t i = 0; pairs && i < ev.size() && i < cap_pairs; ++i) {
+        pairs[2 * i] = ev[i].first;
+        pairs[2 * i + 1] = ev[i].second;
+    }
+    TP_END
+}
 int tp_trainer_set_scheduler(tp_trainer *t, tp_sched *s) { TP_BEGIN t->t->scheduler = s ? s->s : nullptr; TP_END }
 int tp_trainer_fit(tp_trainer *t, tp_loader *train, tp_loader *val, size_t epochs, int verbose, int graph) {
     TP_BEGIN t->t->fit(*train->l, *val->l, epochs, verbose != 0, graph != 0); TP_END

@@ -1072,6 +1072,86 @@ struct StepPlan {
     void key(std::vector<uintptr_t> *out) const;   // appends what a captured step bakes in of it (the layers follow from the model)
 };
 
+// The Trainer's cache of captured steps: which graphs a call of Trainer::train_epoch_graph records, which it replays, and the
+// record of what the last call did.  The policy is the small functions of sizes below; each rule stands once.  (trainer.cpp)
+class StepGraphs {
+   public:
+    // What a call did, in order (Trainer::last_replays, tp_trainer_last_replays): a read-only record, cleared by begin_call.
+    enum Event : int64_t {
+        kReset = 0,         // the state reset launched on its own
+        kEager = 1,         // enqueue_steps outside any capture (the last, partial batch: a trailing (1, 1))
+        kCapture = 2,       // a step graph captured
+        kReplay = 3,        // a step graph replayed
+        kCaptureWhole = 4,  // a whole-call graph (state reset + steps) captured
+        kReplayWhole = 5,   // a whole-call graph replayed
+    };
+    enum class Kind { Ladder, Remainder, Whole };   // the three capture sites; they differ in message and latch only (capture)
+
+    StepGraphs() { events_.reserve(16); }   // (allocated once: a steady call appends one event)
+    StepGraphs(const StepGraphs &) = delete;
+    StepGraphs &operator=(const StepGraphs &) = delete;
+    ~StepGraphs() { drop(); }
+
+    // Destroys every graph and forgets the whole-call lengths that failed (another key: another launch sequence may capture).  The capture
+    // latch stays: it holds for the lifetime of the Trainer.
+    void drop();
+    // Starts a call: clears the record and takes the key of everything this call's captured steps would bake in.  A mismatch with the key
+    // the cached step graphs were recorded under (the key of the call whose ladder recorded) drops everything.
+    void begin_call(std::vector<uintptr_t> key);
+    // TAPER_NO_GRAPH=1 / TAPER_DP_EAGER=1, or a ladder capture that failed: from here on nothing is recorded and no whole-call graph replays
+    // (step graphs cached before still do).
+    void latch_off() { off_ = true; }
+    void note(Event kind, size_t steps) { events_.emplace_back((int64_t)kind, (int64_t)steps); }
+    const std::vector<std::pair<int64_t, int64_t>> &events() const { return events_; }
+
+    // ---- the policy: functions of sizes and of what is cached ----
+    // A whole-call graph serves a call of n_full full steps and no partial batch.
+    bool serves_whole(size_t n_full) const { return !off_ && find(whole_, n_full) != nullptr; }
+    // A binary ladder of sizes (chunk, chunk/2, chunk/4, ..., 1 by integer halving): whatever an epoch (or a short run: 20 steps = 16 + 4)
+    // leaves over after its whole chunks replays as at most log2(chunk) graphs instead of dozens of single-step launches (~10 us of host
+    // time each).  A size is recorded by the first call long enough to use it behind the one eager step in front of the recording (a short
+    // first call -- e.g. a 2-step warm-up -- only records the 1-step graph); size 1 whenever it is missing.  (r01's ladder divided by 4)
+    std::vector<size_t> ladder_to_record(size_t chunk, size_t n_full) const;
+    // What an epoch leaves over after its whole chunks (937 steps = 7 x 128 + 41), or a short run as a whole (20 steps), would replay as one
+    // ladder graph per set bit (41 = 32 + 8 + 1; 20 = 16 + 4), ~10 us of host time and a stream gap each: the first call that meets such a
+    // remainder records ONE graph of exactly that many steps (the ladder graphs are complete by then; at most four cached sizes that are
+    // no power of two -- a chunk that is none brings its ladder's own sizes into that count).
+    bool wants_remainder(size_t tail) const;
+    // A call that is ONE graph of full batches (the contract's 20 steps; any short run repeated) replays a graph that also holds the state
+    // reset in front of its steps: one host launch instead of two and no stream gap between them (3.5 us of host time in front of the
+    // replay + the reset's own launch: ~5 of such a call's 250 us, r05).  Recorded by the first call of that length that finds its plain
+    // step graph in place, with nothing of the call run yet and no partial batch (the caller's part); at most four lengths.
+    bool wants_whole(size_t n_full) const;
+
+    // ---- the actions ----
+    // Records `body` (enqueue_steps, behind the state reset for Kind::Whole) as a graph of `steps` steps and caches it.  When the body
+    // throws, enqueue_steps had already changed host state (deferred / fused Adam bookkeeping, grad slot flags, the tape): the partial graph
+    // is ended and destroyed, the host is put back to "between steps" before anything replays, the kind's message is printed and its latch
+    // set -- Ladder: capture off for this Trainer (the same op list is enqueued eagerly from here on: identical results, one host launch
+    // per kernel); Whole: that length (a later call of it does not try, print and fail again; reset + replay stay two launches);
+    // Remainder: none (the ladder keeps serving it).  Then `rethrow` decides: a collective that cannot be captured must not take the run
+    // down, but without a communicator nothing here is expected to fail.  -> whether the graph is cached.
+    bool capture(Kind kind, size_t steps, Adam &optimizer, bool rethrow, const std::function<void()> &body);
+    void replay_whole(size_t n_full);                        // (serves_whole(n_full), or a capture of it just succeeded)
+    size_t replay_largest(size_t left);                      // the largest cached size that still fits; 0: none does (or none is cached)
+
+   private:
+    using Graphs = std::vector<std::pair<size_t, th_graph *>>;
+    static th_graph *find(const Graphs &v, size_t steps) {
+        for (auto &g : v)
+            if (g.first == steps) return g.second;
+        return nullptr;
+    }
+    bool have(size_t steps) const { return find(steps_, steps) != nullptr; }
+    Graphs steps_;                         // (steps per replay, graph), largest first
+    Graphs whole_;                         // (steps, graph): state reset + that many full steps -- a whole call in one replay
+    std::vector<size_t> whole_failed_;     // call lengths whose whole-call capture failed once: not tried again
+    std::vector<uintptr_t> key_, call_key_;   // what the cached step graphs bake in (Trainer::graph_key); this call's
+    bool current() const { return key_ == call_key_; }
+    bool off_ = false;
+    std::vector<std::pair<int64_t, int64_t>> events_;
+};
+
 class Trainer {  // train.rs:74-172
    public:
     std::shared_ptr<Module> model;
@@ -1092,7 +1172,8 @@ class Trainer {  // train.rs:74-172
     EpochResult train_epoch(DataLoader &loader);              // train.rs:98-144 (eager, synchronising)
     EpochResult evaluate(DataLoader &loader);                 // train.rs:147-172
     // same arithmetic, but the step's op list is captured once into a hipGraph
-    // and replayed; loss / n_correct stay on device until the epoch ends.
+    // and replayed; loss / n_correct stay on device until the epoch ends.  Which graphs a call records
+    // and replays is StepGraphs' policy (StepGraphs above); last_replays() below reports what it did.
     EpochResult train_epoch_graph(DataLoader &loader, size_t max_steps = 0);
     // train.rs:175-261: epochs of train + evaluate, scheduler.step(Some(val_loss)) -> optimizer.set_lr,
     // metrics, early stop at val_acc > 0.99.  graph = true trains through the captured step.
@@ -1106,7 +1187,9 @@ class Trainer {  // train.rs:74-172
     void load_checkpoint(const std::string &path);
     void save_optimizer_state(const std::string &path) const;
     void load_optimizer_state(const std::string &path);
-    ~Trainer();
+    // What the last train_epoch_graph call did, in order: (StepGraphs::Event, steps) -- which graphs it recorded and replayed.  A read-only
+    // query in the tradition of the plan queries (tp_trainer_last_replays); it changes nothing it reports.
+    const std::vector<std::pair<int64_t, int64_t>> &last_replays() const { return graphs_.events(); }
 
    private:
     // gathers `steps` batches with one launch, then enqueues the compute of each step
@@ -1114,16 +1197,17 @@ class Trainer {  // train.rs:74-172
                        size_t batch, size_t steps);
     void enqueue_compute(const StepPlan &plan, float *d_xb, float *d_yb, size_t batch, const th_row_source *rows = nullptr);
     StepPlan plan_step(size_t batch, int64_t n_rows) const;   // n_rows: the rows the in-place form (Mlp2Rows) may read
-    void drop_graphs();
-    std::vector<std::pair<size_t, th_graph *>> graphs_;  // (steps per replay, graph), largest first
-    std::vector<std::pair<size_t, th_graph *>> whole_graphs_;  // (steps, graph): state reset + that many full steps -- a whole call in one replay
-    bool graph_capture_failed_ = false;
-    std::vector<size_t> whole_capture_failed_;                 // call lengths whose whole-call capture failed once: not tried again
-    std::vector<uintptr_t> graph_key_;   // what the captured steps bake in (train_epoch_graph); a mismatch drops the graphs
-    std::shared_ptr<Buffer> xb_, yb_, state_, metrics_, step_loss_, step_ncorrect_;
+    void drop_graphs() { graphs_.drop(); }   // (a buffer the captured steps hold was replaced, or a by-value kernel argument changed)
+    // what the captured steps bake in; a mismatch drops the graphs (StepGraphs::begin_call)
+    std::vector<uintptr_t> graph_key(const StepPlan &plan, const float *d_img, const float *d_lab, const int32_t *d_idx, size_t n, size_t bs) const;
+    void sync_qat_descriptors();         // in front of any step of a train_epoch_graph call, and of graph_key, which reads the generation
+    std::shared_ptr<Buffer> xb_, yb_, state_, metrics_;
     QATWeightPass qat_pass_;             // QAT models: every active layer's weights fake-quantized by one launch pair per step
     bool has_qat() const;                // (throws for a model that holds one QAT layer twice)
     size_t metrics_cap_ = 0;
+    // The captured steps: which sizes a call records and replays, the one capture path, the record of the last call (StepGraphs above).
+    // (the last member: its graphs go before the buffers they point into)
+    StepGraphs graphs_;
 };
 
 }  // namespace taper

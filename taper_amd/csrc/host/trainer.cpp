@@ -201,14 +201,32 @@ EpochResult Trainer::train_epoch(DataLoader &loader) {  // train.rs:98-144
     return r;
 }
 
+// A log of {loss, n_correct} per batch -> the epoch's figures (evaluate, train_epoch_graph): the first n_full batches have bs rows, the one
+// behind them last_rows.
+static EpochResult epoch_result(const float *log, size_t nb, size_t n_full, size_t bs, size_t last_rows) {
+    EpochResult r;
+    r.num_batches = nb;
+    float total_loss = 0.f;
+    for (size_t s = 0; s < nb; ++s) {
+        const size_t b = s < n_full ? bs : last_rows;
+        const float acc = log[2 * s + 1] / (float)b;      // loss.rs:289
+        r.total_correct += (size_t)(acc * (float)b);      // train.rs:117, :160 (truncating cast, Q13)
+        r.total_samples += b;
+        total_loss += log[2 * s];
+        r.losses.push_back(log[2 * s]);
+        r.ncorrect.push_back(log[2 * s + 1]);
+    }
+    r.avg_loss = total_loss / (float)nb;
+    r.accuracy = (float)r.total_correct / (float)r.total_samples;
+    return r;
+}
+
 EpochResult Trainer::evaluate(DataLoader &loader) {  // train.rs:147-172
     // Same formulas, no per-batch read-back: the loss kernel appends {loss, n_correct} of every batch to a device
     // log (as in the graph-replayed training epoch) and the host reads the log once at the end.
-    EpochResult r;
     loader.reset();
     const size_t nb = loader.num_batches();
-    r.num_batches = nb;
-    if (nb == 0) return r;
+    if (nb == 0) return EpochResult{};
     // BatchNorm2d layers run on their running statistics for the duration; each gets its own flag back (Dropout is left as it is)
     struct EvalMode {
         std::vector<std::pair<BatchNorm2d *, bool>> was;
@@ -227,7 +245,6 @@ EpochResult Trainer::evaluate(DataLoader &loader) {  // train.rs:147-172
     th_ctx *ctx = Device::ctx();
     auto log = Buffer::alloc(2 * nb), st = Buffer::alloc(4);
     TH(th_fill_f32(ctx, st->d, 0.f, 4));
-    std::vector<size_t> sizes;
     Tensor images, labels;
     // nothing is differentiated here: a Sequential's conv front may take the launches that never write the full-resolution maps
     // (conv + pool pairs, the one-launch conv chain from batch 96 up) exactly as inside a training step
@@ -241,24 +258,12 @@ EpochResult Trainer::evaluate(DataLoader &loader) {  // train.rs:147-172
         Tensor logits = model->forward(shape_input(images, sample_shape));
         Tensor ncorrect;
         cross_entropy_loss(logits, labels, &ncorrect, &sink);   // loss.rs:136-195 + the count of loss.rs:271-290
-        sizes.push_back(b);
     }
     Tape::reset();
     std::vector<float> mt(2 * nb);
     TH(th_memcpy_d2h(ctx, mt.data(), log->d, mt.size() * sizeof(float)));
-    float total_loss = 0.f;
-    for (size_t s = 0; s < nb && s < sizes.size(); ++s) {
-        const size_t b = sizes[s];
-        const float acc = mt[2 * s + 1] / (float)b;       // loss.rs:289
-        r.total_correct += (size_t)(acc * (float)b);      // train.rs:160 (truncating cast, Q13)
-        r.total_samples += b;
-        total_loss += mt[2 * s];
-        r.losses.push_back(mt[2 * s]);
-        r.ncorrect.push_back(mt[2 * s + 1]);
-    }
-    r.avg_loss = total_loss / (float)nb;
-    r.accuracy = (float)r.total_correct / (float)r.total_samples;
-    return r;
+    const size_t bs = loader.batch_size(), n_full = loader.dataset().len() / bs;   // (DataLoader::next: full batches, then what is left)
+    return epoch_result(mt.data(), nb, n_full, bs, loader.dataset().len() - n_full * bs);
 }
 
 // The captured form of a step: identical arithmetic, but nothing is read back.  The batches
@@ -504,57 +509,117 @@ bool Trainer::has_qat() const {
     return !mods.empty();
 }
 
-void Trainer::drop_graphs() {
-    for (auto &g : graphs_) th_graph_destroy(g.second);
-    graphs_.clear();
-    for (auto &g : whole_graphs_) th_graph_destroy(g.second);
-    whole_graphs_.clear();
-    whole_capture_failed_.clear();   // (another key: another launch sequence may capture)
+// ---- StepGraphs: policy, the one capture path, replay (taper.h)
+void StepGraphs::drop() {
+    for (auto &g : steps_) th_graph_destroy(g.second);
+    steps_.clear();
+    for (auto &g : whole_) th_graph_destroy(g.second);
+    whole_.clear();
+    whole_failed_.clear();
 }
 
-EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
+void StepGraphs::begin_call(std::vector<uintptr_t> key) {
+    events_.clear();
+    call_key_ = std::move(key);
+    if (!steps_.empty() && !current()) drop();
+}
+
+static bool power_of_two(size_t v) { return (v & (v - 1)) == 0; }
+
+std::vector<size_t> StepGraphs::ladder_to_record(size_t chunk, size_t n_full) const {
+    std::vector<size_t> want;
+    if (n_full == 0 || off_) return want;
+    for (size_t s = chunk; s >= 1; s /= 2)
+        if ((s == 1 || n_full >= s + 1) && !have(s)) want.push_back(s);
+    return want;
+}
+
+bool StepGraphs::wants_remainder(size_t tail) const {
+    size_t exact = 0;
+    for (auto &g : steps_) exact += power_of_two(g.first) ? 0 : 1;
+    return tail > 2 && !power_of_two(tail) && !have(tail) && have(1) && exact < 4 && !off_ && current();
+}
+
+bool StepGraphs::wants_whole(size_t n_full) const {
+    return n_full >= 2 && have(n_full) && whole_.size() < 4 && !off_ &&
+           std::find(whole_failed_.begin(), whole_failed_.end(), n_full) == whole_failed_.end() && current();
+}
+
+bool StepGraphs::capture(Kind kind, size_t steps, Adam &optimizer, bool rethrow, const std::function<void()> &body) {
     th_ctx *ctx = Device::ctx();
-    static const bool trace = std::getenv("TAPER_TRACE_EPOCH") != nullptr;   // host-side timeline of one call (stderr), a measurement probe
-    const auto t_enter = std::chrono::steady_clock::now();
-    auto us_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    loader.reset();
-    const MNISTDataset &ds = loader.dataset();
-    const size_t n = ds.len(), bs = loader.batch_size();
-    size_t nb = loader.num_batches();
-    if (max_steps && max_steps < nb) nb = max_steps;
-    const size_t n_full = std::min(nb, n / bs);
-    // the forms of the full and the last, partial batch; steps per replay: graph_chunk, capped so that the gathered batches of one chunk stay
-    // within 256 MB (steps that read their rows in place gather nothing)
-    const size_t rem_rows = nb > n_full ? n - n_full * bs : 0;
-    const StepPlan plan = plan_step(bs, (int64_t)n), rem_plan = rem_rows ? plan_step(rem_rows, (int64_t)n) : StepPlan{};
-    const bool full_in_place = plan.form == StepForm::Mlp2Rows;
-    const size_t chunk = full_in_place ? std::max<size_t>(graph_chunk, 1) : std::max<size_t>(std::min<size_t>(graph_chunk, ((size_t)1 << 26) / (bs * 784)), 1);
-    const float *d_img = ds.images.dptr(), *d_lab = ds.labels.dptr();
-    // full batch, index order (mnist.rs:355-363 without shuffle): the gather would be an identity copy of 188 MB
-    const int32_t *d_idx = (!loader.shuffled() && bs >= n && nb == 1) ? nullptr : loader.d_indices();
-    // staging rows for the gathered forms: a chunk of full batches, and / or the last partial batch when it is too small for the in-place form
-    const size_t stage_rows = std::max(full_in_place ? (size_t)0 : chunk * bs, (rem_rows && rem_plan.form != StepForm::Mlp2Rows) ? rem_rows : (size_t)0);
-    if (d_idx && stage_rows && (!xb_ || xb_->n < stage_rows * 784)) {   // (the zero-copy forms read the dataset in place: no staging buffers)
-        drop_graphs();
-        xb_ = Buffer::alloc(stage_rows * 784);
-        yb_ = Buffer::alloc(stage_rows);
+    TH(th_graph_begin(ctx));
+    th_graph *g = nullptr;
+    try {
+        body();
+        TH(th_graph_end(ctx, &g));
+    } catch (const std::exception &e) {
+        if (!g) th_graph_end(ctx, &g);
+        if (g) th_graph_destroy(g);
+        optimizer.set_carry_deferred(false);
+        optimizer.drop_step_bookkeeping();
+        optimizer.zero_grad();
+        Tape::reset();
+        switch (kind) {
+            case Kind::Ladder:
+                fprintf(stderr, "taper: step capture with the communicator failed (%s); running data-parallel steps eagerly\n", e.what());
+                off_ = true;
+                break;
+            case Kind::Remainder:
+                fprintf(stderr, "taper: capturing a %zu-step remainder graph failed (%s); the ladder graphs serve it\n", steps, e.what());
+                break;
+            case Kind::Whole:
+                fprintf(stderr, "taper: capturing a whole-call graph of %zu steps failed (%s); reset + replay stay two launches\n", steps, e.what());
+                whole_failed_.push_back(steps);
+                break;
+        }
+        if (rethrow) throw;
+        return false;
     }
-    if (!state_) state_ = Buffer::alloc(4);
-    // the step log is sized for the loader's whole epoch even when this call stops early (max_steps): the captured graphs
-    // hold its address, and a short first call followed by a full epoch would otherwise drop and re-record every graph
-    if (metrics_cap_ < loader.num_batches() + 1) {
-        drop_graphs();
-        metrics_cap_ = loader.num_batches() + 1;
-        // pinned host memory: the loss kernels write {loss, n_correct} of every step straight into it (8 B per step, posted writes), and the
-        // host reads it after ONE stream synchronisation -- a staged device-to-host copy costs a short run (the contract's 20 steps) ~20 us
-        metrics_ = Buffer::alloc_host(2 * metrics_cap_);
+    if (kind == Kind::Whole) {
+        whole_.emplace_back(steps, g);
+    } else {
+        steps_.insert(std::find_if(steps_.begin(), steps_.end(), [&](const auto &x) { return x.first < steps; }), {steps, g});   // largest first
+        if (kind == Kind::Ladder) key_ = call_key_;
     }
-    // Everything a captured step bakes in: the full batch's plan (the choice of launch sequence, and every switch it read -- a communicator's
-    // inkernel / fuse_adam included), then the kernel arguments and what the layered path reads: the dataset and index buffers (two loaders
-    // over one dataset share the images but own their index vectors), the epoch length the gather wraps at, the label buffer, the input
-    // reshape, the communicator, the optimizer's arenas.  (nullptr indices = the zero-copy full-batch form, a different graph.)  Any
-    // mismatch re-records.  (The last, partial batch is never captured -- enqueue_steps plans it afresh every call -- and a call cut short
-    // by max_steps has none: keying on its plan would re-record the graphs whenever such calls alternate with whole epochs.)
+    note(kind == Kind::Whole ? kCaptureWhole : kCapture, steps);
+    return true;
+}
+
+void StepGraphs::replay_whole(size_t n_full) {
+    TH(th_graph_launch(Device::ctx(), find(whole_, n_full)));
+    note(kReplayWhole, n_full);
+}
+
+size_t StepGraphs::replay_largest(size_t left) {
+    for (auto &g : steps_)
+        if (g.first <= left) {
+            TH(th_graph_launch(Device::ctx(), g.second));
+            note(kReplay, g.first);
+            return g.first;
+        }
+    return 0;
+}
+
+static bool env_is_1(const char *name) {   // read on every call: a process may set and unset the operator overrides between calls
+    const char *e = std::getenv(name);
+    return e && e[0] == '1';
+}
+
+// QAT: the descriptor buffer the steps read is uploaded in front of any step of a call, and graph_key then keys on its generation -- a
+// buffer replaced since (an eager train_step after a layer switched) has gone back to the pool, and the graphs that read it must not replay
+void Trainer::sync_qat_descriptors() {
+    std::vector<const QATModule *> active;
+    qat_modules(*model, &active, true);
+    qat_pass_.sync(active);
+}
+
+// Everything a captured step bakes in: the kernel arguments and what the layered path reads -- the dataset and index buffers (two loaders
+// over one dataset share the images but own their index vectors), the epoch length the gather wraps at, the label buffer, the input
+// reshape, the communicator, the optimizer's arenas -- then the full batch's plan (the choice of launch sequence, and every switch it read:
+// a communicator's inkernel / fuse_adam included).  (nullptr indices = the zero-copy full-batch form, a different graph.)  Any
+// mismatch re-records.  (The last, partial batch is never captured -- enqueue_steps plans it afresh every call -- and a call cut short
+// by max_steps has none: keying on its plan would re-record the graphs whenever such calls alternate with whole epochs.)
+std::vector<uintptr_t> Trainer::graph_key(const StepPlan &plan, const float *d_img, const float *d_lab, const int32_t *d_idx, size_t n, size_t bs) const {
     std::vector<uintptr_t> key{(uintptr_t)d_img, (uintptr_t)d_lab, (uintptr_t)d_idx, (uintptr_t)n, (uintptr_t)bs, (uintptr_t)comm.get(),
                                (uintptr_t)model.get(), (uintptr_t)optimizer.get(), (uintptr_t)optimizer->flat().p_arena->d,
                                (uintptr_t)optimizer->flat().g_arena->d, (uintptr_t)(xb_ ? xb_->d : nullptr), (uintptr_t)metrics_->d};
@@ -574,14 +639,11 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         key.push_back(h);
     }
     // QAT: whether each layer fake-quantizes (the global switch, training mode, every layer's own flag) and its codec and activation switch,
-    // and the descriptor buffer the steps read: uploaded here, before any step of this call, and keyed by its generation -- a buffer
-    // replaced since (an eager train_step after a layer switched) has gone back to the pool, and the graphs that read it must not replay
+    // and the generation of the descriptor buffer (sync_qat_descriptors)
     {
-        std::vector<const QATModule *> mods, active;
+        std::vector<const QATModule *> mods;
         qat_modules(*model, &mods, false);
-        qat_modules(*model, &active, true);
         if (!mods.empty()) {
-            qat_pass_.sync(active);
             key.push_back((uintptr_t)qat::enabled() | (uintptr_t)qat::is_training() << 1);
             key.push_back((uintptr_t)qat_pass_.generation());
         }
@@ -594,179 +656,122 @@ EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
         batchnorm_modules(*model, &bns);
         for (const BatchNorm2d *b : bns) key.push_back((uintptr_t)0xb0 | (uintptr_t)b->is_training());
     }
-    if (!graphs_.empty() && graph_key_ != key) drop_graphs();
+    return key;
+}
 
-    size_t done = 0;
-    // A call that is ONE graph of full batches (the contract's 20 steps; any short run repeated) replays a graph that also holds the state
-    // reset in front of its steps: one host launch instead of two and no stream gap between them (3.5 us of host time in front of the
-    // replay + the reset's own launch: ~5 of such a call's 250 us, r05).  Recorded below, by the first call of that length that finds its
-    // plain graph in place.
-    th_graph *whole = nullptr;
-    if (nb == n_full && !graph_capture_failed_ && !(std::getenv("TAPER_NO_GRAPH") && std::getenv("TAPER_NO_GRAPH")[0] == '1'))
-        for (auto &g : whole_graphs_)
-            if (g.first == n_full) whole = g.second;
-    const double us_prep = us_since(t_enter);
-    if (!whole) TH(th_fill_f32(ctx, state_->d, 0.f, 4));  // step = 0, cursor = 0
-    const double us_fill = us_since(t_enter);
-    if (whole) {
-        TH(th_graph_launch(ctx, whole));
-        done = n_full;
+static bool trace_epoch() {   // TAPER_TRACE_EPOCH: host-side timeline of one call (stderr), a measurement probe
+    static const bool on = std::getenv("TAPER_TRACE_EPOCH") != nullptr;
+    return on;
+}
+
+EpochResult Trainer::train_epoch_graph(DataLoader &loader, size_t max_steps) {
+    th_ctx *ctx = Device::ctx();
+    const auto t_enter = std::chrono::steady_clock::now();
+    auto us_since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+    // ---- sizes and plans
+    loader.reset();
+    const MNISTDataset &ds = loader.dataset();
+    const size_t n = ds.len(), bs = loader.batch_size();
+    size_t nb = loader.num_batches();
+    if (max_steps && max_steps < nb) nb = max_steps;
+    const size_t n_full = std::min(nb, n / bs);
+    // the forms of the full and the last, partial batch; steps per replay: graph_chunk, capped so that the gathered batches of one chunk stay
+    // within 256 MB (steps that read their rows in place gather nothing)
+    const size_t rem_rows = nb > n_full ? n - n_full * bs : 0;   // the last, partial batch (mnist.rs:373-385 keeps it)
+    const StepPlan plan = plan_step(bs, (int64_t)n), rem_plan = rem_rows ? plan_step(rem_rows, (int64_t)n) : StepPlan{};
+    const bool full_in_place = plan.form == StepForm::Mlp2Rows;
+    const size_t chunk = full_in_place ? std::max<size_t>(graph_chunk, 1) : std::max<size_t>(std::min<size_t>(graph_chunk, ((size_t)1 << 26) / (bs * 784)), 1);
+    const float *d_img = ds.images.dptr(), *d_lab = ds.labels.dptr();
+    // full batch, index order (mnist.rs:355-363 without shuffle): the gather would be an identity copy of 188 MB
+    const int32_t *d_idx = (!loader.shuffled() && bs >= n && nb == 1) ? nullptr : loader.d_indices();
+    // ---- staging and log buffers (the captured graphs hold their addresses: a new buffer drops the graphs)
+    // staging rows for the gathered forms: a chunk of full batches, and / or the last partial batch when it is too small for the in-place form
+    const size_t stage_rows = std::max(full_in_place ? (size_t)0 : chunk * bs, (rem_rows && rem_plan.form != StepForm::Mlp2Rows) ? rem_rows : (size_t)0);
+    if (d_idx && stage_rows && (!xb_ || xb_->n < stage_rows * 784)) {   // (the zero-copy forms read the dataset in place: no staging buffers)
+        drop_graphs();
+        xb_ = Buffer::alloc(stage_rows * 784);
+        yb_ = Buffer::alloc(stage_rows);
     }
-    // Graph sizes still missing for this epoch length (a short first call -- e.g. a 2-step warm-up -- only
-    // records the 1-step graph; the chunk graph is added by the first call long enough to use it).
-    auto have = [&](size_t steps) {
-        for (auto &g : graphs_)
-            if (g.first == steps) return true;
-        return false;
+    if (!state_) state_ = Buffer::alloc(4);
+    // the step log is sized for the loader's whole epoch even when this call stops early (max_steps): the captured graphs
+    // hold its address, and a short first call followed by a full epoch would otherwise drop and re-record every graph
+    if (metrics_cap_ < loader.num_batches() + 1) {
+        drop_graphs();
+        metrics_cap_ = loader.num_batches() + 1;
+        // pinned host memory: the loss kernels write {loss, n_correct} of every step straight into it (8 B per step, posted writes), and the
+        // host reads it after ONE stream synchronisation -- a staged device-to-host copy costs a short run (the contract's 20 steps) ~20 us
+        metrics_ = Buffer::alloc_host(2 * metrics_cap_);
+    }
+    // ---- key
+    sync_qat_descriptors();
+    graphs_.begin_call(graph_key(plan, d_img, d_lab, d_idx, n, bs));
+
+    // ---- schedule: what is recorded and what replays is StepGraphs' policy (taper.h); here is the order of a call
+    auto reset_state = [&] { TH(th_fill_f32(ctx, state_->d, 0.f, 4)); };   // step = 0, cursor = 0
+    auto steps_of = [&](size_t batch, size_t steps) { enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, batch, steps); };
+    auto eager = [&](size_t batch, size_t steps) {
+        steps_of(batch, steps);
+        graphs_.note(StepGraphs::kEager, steps);
+    };
+    auto capture = [&](StepGraphs::Kind kind, size_t steps, const std::function<void()> &body) {
+        return graphs_.capture(kind, steps, *optimizer, !comm, body);
     };
     // operator override: TAPER_NO_GRAPH=1 enqueues every step's op list eagerly instead of replaying captured graphs -- same kernels, same
     // results, one host launch per kernel (rocprofv3 on ROCm 7.2 crashes inside hipGraphLaunch once several instantiated graphs are replayed
     // back to back: profiling runs use this)
-    if (!graph_capture_failed_ && std::getenv("TAPER_NO_GRAPH") && std::getenv("TAPER_NO_GRAPH")[0] == '1') graph_capture_failed_ = true;
-    // operator override: TAPER_DP_EAGER=1 keeps data-parallel steps out of hipGraphs (collectives launched eagerly)
-    if (comm && !graph_capture_failed_ && std::getenv("TAPER_DP_EAGER") && std::getenv("TAPER_DP_EAGER")[0] == '1')
-        graph_capture_failed_ = true;
-    // a binary ladder of sizes (chunk, chunk/2, chunk/4, ..., 1): whatever an epoch (or a short run: 20 steps = 16 + 4)
-    // leaves over after its whole chunks replays as at most log2(chunk) graphs instead of dozens of single-step
-    // launches (~10 us of host time each).  A size is recorded by the first call long enough to use it.
-    // (r01's ladder divided by 4)
-    std::vector<size_t> want;
-    for (size_t steps = chunk;; steps /= 2) {
-        if (steps < 1) steps = 1;
-        if (!((steps > 1 && n_full < steps + 1) || have(steps)) && std::find(want.begin(), want.end(), steps) == want.end())
-            want.push_back(steps);
-        if (steps == 1) break;
-    }
-    if (!whole && !want.empty() && n_full > 0 && !graph_capture_failed_) {
-        // step 0 runs eagerly (pool warm-up, has_grad mask upload); then the SAME host code
-        // is run under stream capture to record the op list of 1 step and of a chunk of
-        // steps (one hipGraphLaunch per chunk amortises the ~10 us host cost of a replay)
-        enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, bs, 1);
-        done = 1;
-        for (size_t steps : want) {
-            TH(th_graph_begin(ctx));
-            th_graph *g = nullptr;
-            try {
-                enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, bs, steps);
-                TH(th_graph_end(ctx, &g));
-            } catch (const std::exception &e) {
-                if (!g) th_graph_end(ctx, &g);
-                if (g) th_graph_destroy(g);
-                if (!comm) throw;
-                // a collective that cannot be captured must not take the run down: the same op list
-                // is enqueued eagerly from here on (identical results, one host launch per kernel)
-                fprintf(stderr, "taper: step capture with the communicator failed (%s); running data-parallel steps eagerly\n", e.what());
-                graph_capture_failed_ = true;
-                break;
-            }
-            graphs_.emplace_back(steps, g);
-        }
-        std::sort(graphs_.begin(), graphs_.end(), [](const auto &x, const auto &y) { return x.first > y.first; });   // largest first
-        graph_key_ = key;
-    }
-    // What an epoch leaves over after its whole chunks (937 steps = 7 x 128 + 41), or a short run as a whole (20 steps), would replay as one
-    // ladder graph per set bit (41 = 32 + 8 + 1; 20 = 16 + 4), ~10 us of host time and a stream gap each: the first call that meets such a
-    // remainder records ONE graph of exactly that many steps (the ladder graphs are complete by then; at most four distinct remainders).
+    if (env_is_1("TAPER_NO_GRAPH")) graphs_.latch_off();
+    size_t done = 0;
+    const bool whole = !rem_rows && graphs_.serves_whole(n_full);
+    const double us_prep = us_since(t_enter);
     if (!whole) {
-        const size_t tail = n_full - done > 0 ? (n_full - done) % chunk : 0;
-        size_t exact = 0;
-        for (auto &g : graphs_) exact += (g.first & (g.first - 1)) != 0 ? 1 : 0;
-        if (tail > 2 && (tail & (tail - 1)) != 0 && !have(tail) && have(1) && exact < 4 && !graph_capture_failed_ &&
-            graph_key_ == key) {
-            TH(th_graph_begin(ctx));
-            th_graph *g = nullptr;
-            try {
-                enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, bs, tail);
-                TH(th_graph_end(ctx, &g));
-                graphs_.emplace_back(tail, g);
-                std::sort(graphs_.begin(), graphs_.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
-            } catch (const std::exception &e) {
-                // enqueue_steps had already changed host state when it failed (deferred / fused Adam bookkeeping, grad slot flags, the
-                // tape): put it back to "between steps" before anything replays.  The ladder keeps serving the remainder.
-                fprintf(stderr, "taper: capturing a %zu-step remainder graph failed (%s); the ladder graphs serve it\n", tail, e.what());
-                if (!g) th_graph_end(ctx, &g);
-                if (g) th_graph_destroy(g);
-                if (auto *adam = dynamic_cast<Adam *>(optimizer.get())) {
-                    adam->set_carry_deferred(false);
-                    adam->drop_step_bookkeeping();
-                }
-                optimizer->zero_grad();
-                Tape::reset();
-                if (!comm) throw;   // (as the ladder capture: without a communicator nothing here is expected to fail)
-            }
-        }
+        reset_state();
+        graphs_.note(StepGraphs::kReset, 0);
     }
-    if (!whole && done == 0 && nb == n_full && n_full >= 2 && have(n_full) && whole_graphs_.size() < 4 && !graph_capture_failed_ && graph_key_ == key &&
-        std::find(whole_capture_failed_.begin(), whole_capture_failed_.end(), n_full) == whole_capture_failed_.end()) {
-        TH(th_graph_begin(ctx));
-        th_graph *g = nullptr;
-        try {
-            TH(th_fill_f32(ctx, state_->d, 0.f, 4));
-            enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, bs, n_full);
-            TH(th_graph_end(ctx, &g));
-            whole_graphs_.emplace_back(n_full, g);
-            // ... and serves this very call (a second reset in front of the steps changes nothing): a graph's FIRST replay pays its
-            // upload, which must not fall into a later, timed call
-            TH(th_graph_launch(ctx, g));
+    const double us_fill = us_since(t_enter);
+    if (whole) {
+        graphs_.replay_whole(n_full);
+        done = n_full;
+    }
+    // operator override: TAPER_DP_EAGER=1 keeps data-parallel steps out of hipGraphs (collectives launched eagerly)
+    // (read behind a whole-call replay, as it always was: the call that first sees it may still be served by one)
+    if (comm && env_is_1("TAPER_DP_EAGER")) graphs_.latch_off();
+    if (!whole) {
+        const std::vector<size_t> ladder = graphs_.ladder_to_record(chunk, n_full);
+        if (!ladder.empty()) {
+            // step 0 runs eagerly (pool warm-up, has_grad mask upload); then the SAME host code
+            // is run under stream capture to record the op list of 1 step and of a chunk of
+            // steps (one hipGraphLaunch per chunk amortises the ~10 us host cost of a replay)
+            eager(bs, 1);
+            done = 1;
+            for (size_t steps : ladder)
+                if (!capture(StepGraphs::Kind::Ladder, steps, [&] { steps_of(bs, steps); })) break;
+        }
+        const size_t tail = (n_full - done) % chunk;
+        if (graphs_.wants_remainder(tail)) capture(StepGraphs::Kind::Remainder, tail, [&] { steps_of(bs, tail); });
+        // ... a whole-call graph serves the very call that records it (a second reset in front of the steps changes nothing): a graph's
+        // FIRST replay pays its upload, which must not fall into a later, timed call
+        if (done == 0 && !rem_rows && graphs_.wants_whole(n_full) &&
+            capture(StepGraphs::Kind::Whole, n_full, [&] { reset_state(); steps_of(bs, n_full); })) {
+            graphs_.replay_whole(n_full);
             done = n_full;
-        } catch (const std::exception &e) {
-            fprintf(stderr, "taper: capturing a whole-call graph of %zu steps failed (%s); reset + replay stay two launches\n", n_full, e.what());
-            whole_capture_failed_.push_back(n_full);   // (latched: a later call of this length does not try, print and fail again)
-            if (!g) th_graph_end(ctx, &g);
-            if (g) th_graph_destroy(g);
-            if (auto *adam = dynamic_cast<Adam *>(optimizer.get())) {
-                adam->set_carry_deferred(false);
-                adam->drop_step_bookkeeping();
-            }
-            optimizer->zero_grad();
-            Tape::reset();
-            if (!comm) throw;
         }
     }
     while (done < n_full) {
-        bool launched = false;
-        for (auto &g : graphs_) {
-            if (done + g.first <= n_full) {
-                TH(th_graph_launch(ctx, g.second));
-                done += g.first;
-                launched = true;
-                break;
-            }
-        }
-        if (!launched) {  // no graph fits (e.g. n_full == 1 on a later call): run the step eagerly
-            enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, bs, 1);
-            ++done;
-        }
+        const size_t steps = graphs_.replay_largest(n_full - done);
+        if (!steps) eager(bs, 1);   // no graph fits (e.g. n_full == 1 on a later call): run the step eagerly
+        done += steps ? steps : 1;
     }
-    if (nb > n_full) {  // the last, partial batch (mnist.rs:373-385 keeps it)
-        const size_t rem = n - n_full * bs;
-        enqueue_steps(d_img, d_lab, d_idx, (int64_t)n, rem, 1);
-    }
+    if (rem_rows) eager(rem_rows, 1);
     loader.advance(std::min(n, nb * bs));
 
+    // ---- synchronise
     const double us_enqueued = us_since(t_enter);
     Device::sync();
     check_comm();
-    if (trace) fprintf(stderr, "taper trace: train_epoch_graph %zu steps (%s%s%s): state reset enqueued at %.1f - %.1f us, all enqueued after %.1f us, stream idle after %.1f us\n", nb,
-                       step_form_names[(int)plan.form], rem_rows ? ", last batch " : "", rem_rows ? step_form_names[(int)rem_plan.form] : "", us_prep, us_fill, us_enqueued, us_since(t_enter));
-    const float *mt = metrics_->d;   // host-visible (th_host_malloc); every step's entry has landed once the stream is idle
-    EpochResult r;
-    r.num_batches = nb;
-    float total_loss = 0.f;
-    for (size_t s = 0; s < nb; ++s) {
-        const size_t b = (s < n_full) ? bs : n - n_full * bs;
-        const float acc = mt[2 * s + 1] / (float)b;       // loss.rs:289
-        r.total_correct += (size_t)(acc * (float)b);      // train.rs:117 (Q13)
-        r.total_samples += b;
-        total_loss += mt[2 * s];
-        r.losses.push_back(mt[2 * s]);
-        r.ncorrect.push_back(mt[2 * s + 1]);
-    }
-    r.avg_loss = total_loss / (float)nb;
-    r.accuracy = (float)r.total_correct / (float)r.total_samples;
-    return r;
+    if (trace_epoch()) fprintf(stderr, "taper trace: train_epoch_graph %zu steps (%s%s%s): state reset enqueued at %.1f - %.1f us, all enqueued after %.1f us, stream idle after %.1f us\n", nb,
+                               step_form_names[(int)plan.form], rem_rows ? ", last batch " : "", rem_rows ? step_form_names[(int)rem_plan.form] : "", us_prep, us_fill, us_enqueued, us_since(t_enter));
+    // ---- result: the log is host-visible (th_host_malloc); every step's entry has landed once the stream is idle
+    return epoch_result(metrics_->d, nb, n_full, bs, rem_rows);
 }
-
-Trainer::~Trainer() { drop_graphs(); }
 
 }  // namespace taper

@@ -208,12 +208,19 @@ def test_remainder_graph_equals_the_ladder_graphs():
         opt = T.Adam(model.parameters(), 1e-3, None, None, 1e-4)
         tr = T.Trainer(model, opt, graph_chunk=chunk)
         loader = T.DataLoader(T.MNISTDataset.from_host(x, y), batch, True, seed=5)
-        losses = []
+        losses, records = [], []
         for _ in range(2):
             ep = tr.run_epoch(loader, T.Trainer.GRAPH)
             assert ep["num_batches"] == 20
             losses += list(ep["losses"])
+            records.append(tr.last_replays())
         assert opt.t() == 40
+        # (kind, steps): 0 the state reset, 1 eager, 2 / 3 a step graph captured / replayed, 4 / 5 a whole-call graph captured / replayed
+        if chunk == 128:   # the second epoch records the 20-step graph, the whole-call graph around it, and replays that one
+            assert records[1] == [(0, 0), (2, 20), (4, 20), (5, 20)]
+        else:              # the ladder and the 3-step remainder behind the eager step; then five chunk graphs
+            assert records[0] == [(0, 0), (1, 1), (2, 4), (2, 2), (2, 1), (2, 3)] + [(3, 4)] * 4 + [(3, 3)]
+            assert records[1] == [(0, 0)] + [(3, 4)] * 5
         out.append((np.asarray(losses), [p.data() for p in model.parameters()]))
     np.testing.assert_array_equal(out[0][0], out[1][0])
     for a, b in zip(out[0][1], out[1][1]):
