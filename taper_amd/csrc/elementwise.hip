@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void ew2w_kernel(const float *__restrict__ a, 
 
 // three inputs, two optional accumulate outputs (Div backward)
 __global__ __launch_bounds__(256) void div_bwd_kernel(const float *__restrict__ g, const float *__restrict__ a,
-                                                      const float *__restrict__ b, float *__restrict__ ga,
-                                                      float *__restrict__ gb, size_t n) {
+                                                      const float *__restrict__ b, float *ga, float *gb, size_t n) {
+    // (ga and gb are the same slot for x / x: no __restrict__ on them, the store to ga[i] must stay in front of the load of gb[i])
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = tid; i < n; i += stride) {

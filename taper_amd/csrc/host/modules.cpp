@@ -64,11 +64,15 @@ Tensor cross_entropy_loss(const Tensor &logits, const Tensor &targets, Tensor *n
     if (need_grad) {
         loss.set_requires_grad(true);
         Tensor lg = logits, lp = logp, t = targets, out = loss;
-        Tape::push(loss, true, [lg, lp, t, out, dunit, b, c]() {
+        // (adopted at most once: the slot's later writers accumulate INTO dunit, which then no longer holds the forward kernel's gradient --
+        // a backward() behind a zero_grad() on the same tape forms it again from logp)
+        auto adopted = std::make_shared<bool>(false);
+        Tape::push(loss, true, [lg, lp, t, out, dunit, b, c, adopted]() {
             if (!out.has_grad()) return;
-            if (out.grad_->shared_const && !lg.has_grad() && !lg.grad_->buf_is_arena) {
+            if (out.grad_->shared_const && !lg.has_grad() && !lg.grad_->buf_is_arena && !*adopted) {
                 // loss.backward() on the root: upstream grad is the constant 1 and logits.grad is
                 // None -> (softmax - onehot)/B from the forward kernel IS the gradient: adopt it
+                *adopted = true;
                 lg.grad_->buf = dunit;
                 lg.grad_->has = true;
                 lg.grad_->known_zero = false;

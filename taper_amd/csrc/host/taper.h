@@ -1204,6 +1204,7 @@ class Trainer {  // train.rs:74-172
     std::shared_ptr<Buffer> xb_, yb_, state_, metrics_;
     QATWeightPass qat_pass_;             // QAT models: every active layer's weights fake-quantized by one launch pair per step
     bool has_qat() const;                // (throws for a model that holds one QAT layer twice)
+    bool has_shared_parameter() const;   // a parameter that two layers use (a tied layer): its gradient is complete only after both backwards
     size_t metrics_cap_ = 0;
     // The captured steps: which sizes a call records and replays, the one capture path, the record of the last call (StepGraphs above).
     // (the last member: its graphs go before the buffers they point into)

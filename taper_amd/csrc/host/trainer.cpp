@@ -323,6 +323,14 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
         TAPER_ASSERT(!comm, "QAT: data-parallel training of a QAT model is not supported");
         return take(StepForm::Layered, nl, {});
     }
+    // a tied layer trains layer by layer too, and Adam runs behind the whole backward: the node of the layer's LATER use finds the gradient
+    // slot empty and would apply (or defer) the update on that use's share alone, the earlier use would then read the updated weight for its
+    // dX and add a dW that Adam::step skips as already applied -- and no fused form is written for one weight in two places
+    if (has_shared_parameter()) {
+        take(StepForm::Layered, nl, {});
+        p.fused_adam = false;
+        return p;
+    }
     Linear *last = (fuse_head && nl) ? linear(nl - 1) : nullptr;
     Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && relu(nl - 2)) ? linear(nl - 3) : nullptr;
     Linear *hidden0 = (hidden && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;   // a three-layer classifier: th_mlp3_xent, two launches
@@ -507,6 +515,14 @@ bool Trainer::has_qat() const {
         for (size_t j = i + 1; j < mods.size(); ++j)
             TAPER_ASSERT(mods[i] != mods[j], "QAT: the model holds the same QAT layer twice; the Trainer does not train a shared QAT layer");
     return !mods.empty();
+}
+
+bool Trainer::has_shared_parameter() const {
+    const std::vector<Tensor> ps = model->parameters();
+    for (size_t i = 0; i < ps.size(); ++i)
+        for (size_t j = i + 1; j < ps.size(); ++j)
+            if (ps[i].dptr() == ps[j].dptr()) return true;
+    return false;
 }
 
 // ---- StepGraphs: policy, the one capture path, replay (taper.h)
