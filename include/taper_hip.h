@@ -618,6 +618,22 @@ int th_batchnorm2d_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const f
                        int hw, int batch_stats, int accumulate_mask);
 /* the workgroups a channel's n * hw elements are shared among (1: every call above is a single launch); 0 for a shape that is refused */
 int th_batchnorm2d_split(int n, int c, int hw);
+/* The tail of a residual block, the skip connection added inside the normalisation's map: th_batchnorm2d_fwd with
+ *     y = max(((x - mean) * a + b) + r, floor),   a = invstd * gamma, b = beta, floor = 0 with relu and -inf without
+ * every operation rounded once, in this order: the plain call's value with relu = 0, then the add, then the ReLU (which comes after the
+ * add).  Statistics, the saved pair, the running update and the launch counts are th_batchnorm2d_fwd's.  d_residual [n, c, hw] is only
+ * read; it may be d_x and may not be d_y.  16-byte accesses need d_residual aligned like d_x and d_y.  Refused before anything is
+ * enqueued: what th_batchnorm2d_fwd refuses, a null d_residual, d_residual == d_y. */
+int th_bn_residual_fwd(th_ctx *ctx, const float *d_x, const float *d_residual, const float *d_gamma, const float *d_beta, float *d_y,
+                       float *d_running_mean, float *d_running_var, float *d_save_mean, float *d_save_invstd, int n, int c, int hw, float eps,
+                       float momentum, int training, int relu);
+/* th_batchnorm2d_bwd, whose map pass also writes the residual's gradient d_gr [n, c, hw] = gy, masked by y > 0 when d_y_or_null (the
+ * y of th_bn_residual_fwd) is given.  accumulate_mask: bits 0-2 as there, bit 3 (value 8) set: += into d_gr, clear: overwrite.  With
+ * d_gx_or_null null the map still runs, for d_gr alone.  The same launch counts.  Refused before anything is enqueued: what
+ * th_batchnorm2d_bwd refuses, a null d_gr, d_gr == d_gx_or_null. */
+int th_bn_residual_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const float *d_y_or_null, const float *d_gamma,
+                       const float *d_save_mean, const float *d_save_invstd, float *d_gx_or_null, float *d_gr, float *d_ggamma, float *d_gbeta,
+                       int n, int c, int hw, int batch_stats, int accumulate_mask);
 /* A BatchNorm2d frozen on its running pair for the quantized twins (csrc/quant.hip): d_affine[c][2] = {a, b} with
  *     invstd = 1 / sqrt(running_var + eps),   a = gamma * invstd,   b = beta - running_mean * a
  * every operation rounded once (the square root too: sqrtf, where the eval path's intrinsic is good to one ulp), in this order.  One launch, nothing read back: capturable.  Refused before the launch: a null pointer,

@@ -139,7 +139,17 @@ int tp_batchnorm2d_running_stats(const tp_module *m, float *h_mean, float *h_var
 int tp_batchnorm2d_set_running_stats(tp_module *m, const float *h_mean, const float *h_var);
 /* Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) with the ReLU fused; parameters(): the conv's, then gamma, beta */
 int tp_basic_block_new(int in_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
-/* saved-but-not-trained state (the running statistics), concatenated over a Sequential's / BasicBlock's children; shares storage */
+/* y = bn(x) + residual, then the layer's ReLU (fuse_relu: after the add), inside the normalisation's own launches: one tape
+ * node whose backward also leaves the residual's gradient.  Statistics and the running update are tp_module_forward's.  Fails with
+ * "BatchNorm2d::forward_add: ..." for a residual of another shape and for one that shares x's storage. */
+int tp_batchnorm2d_forward_add(const tp_module *m, const tp_tensor *x, const tp_tensor *residual, tp_tensor **out);
+/* conv3x3(in, out, stride, pad 1) -> BatchNorm2d + ReLU -> conv3x3(out, out, 1, pad 1) -> BatchNorm2d with the shortcut added and the ReLU
+ * behind the add.  Shortcut: the input when in == out and stride == 1, else conv3x3(in, out, stride, pad 1) -> BatchNorm2d (a 3x3
+ * projection: the float 1x1 path is not a usable one).  No conv has a bias; seeds: seed, seed + 1, seed + 2 (the projection).
+ * parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w, gamma beta]; buffers: the running pairs in that order.
+ * Non-positive arguments fail before the device is touched.  No quantized twin: tp_module_quantize* refuse the block. */
+int tp_residual_block_new(int in_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
+/* saved-but-not-trained state (the running statistics), concatenated over a Sequential's / BasicBlock's / ResidualBlock's children; shares storage */
 int tp_module_num_buffers(const tp_module *m, int *out);
 int tp_module_buffer(const tp_module *m, int i, tp_tensor **out);
 /* train() / eval() of every BatchNorm2d and every Dropout inside m */

@@ -598,6 +598,13 @@ class BatchNorm2d(Module):
             raise TaperError("BatchNorm2d::set_running_stats: num_features values each expected")
         tp_check(host.tp_batchnorm2d_set_running_stats(self._h, m.ctypes.data, v.ctypes.data), "BatchNorm2d::set_running_stats")
 
+    def forward_add(self, x: Tensor, residual: Tensor) -> Tensor:
+        """bn(x) + residual, then the layer's ReLU (fuse_relu: after the add), inside the normalisation's own launches: a residual block's
+        tail as one tape node.  The residual has x's shape and its own storage."""
+        h = _p()
+        tp_check(host.tp_batchnorm2d_forward_add(self._h, x._h, residual._h, C.byref(h)), "BatchNorm2d::forward_add")
+        return Tensor(_h=h.value)
+
     @property
     def gamma(self): return self.parameters()[0]
 
@@ -610,6 +617,16 @@ class BasicBlock(Module):
 
     def __init__(self, in_channels, out_channels, stride=1, seed=1):
         super().__init__(_mk(host.tp_basic_block_new, "BasicBlock::new", int(in_channels), int(out_channels), int(stride), int(seed)))
+
+
+class ResidualBlock(Module):
+    """conv3x3(in, out, stride) -> BatchNorm2d + ReLU -> conv3x3(out, out) -> BatchNorm2d + shortcut -> ReLU, the add and the last ReLU inside
+    the second normalisation's kernels.  Shortcut: the input when in == out and stride == 1, else conv3x3(in, out, stride) -> BatchNorm2d
+    (a 3x3 projection, not a 1x1).  No conv has a bias.  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w,
+    gamma beta]; buffers(): the running pairs in that order."""
+
+    def __init__(self, in_channels, out_channels, stride=1, seed=1):
+        super().__init__(_mk(host.tp_residual_block_new, "ResidualBlock::new", int(in_channels), int(out_channels), int(stride), int(seed)))
 
 
 class Sequential(Module):

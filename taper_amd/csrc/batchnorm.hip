@@ -4,6 +4,8 @@
 //   th_batchnorm2d_fwd   training: per-channel mean / biased variance over the M = n * hw elements of a channel, the running update
 //                        (unbiased variance) and y = (x - mean) * (invstd * gamma) + beta [+ ReLU]; eval: the same map on the running pair
 //   th_batchnorm2d_bwd   gbeta = sum gy, ggamma = sum gy * xh, gx = gamma * invstd * (gy - gbeta / M - xh * ggamma / M)
+//   th_bn_residual_fwd   the same forward with a skip connection added in the map: y = ((x - mean) * a + b) + r [+ ReLU, after the add]
+//   th_bn_residual_bwd   the same backward, whose map pass also writes the residual's gradient gr = gy (masked by y > 0 with the ReLU)
 //
 // One set of kernels over two geometries.  The five kernel templates (fwd_parts, fwd_train, fwd_eval, bwd_parts, bwd_final) hold the
 // passes and every per-channel formula once; a GEOMETRY says which elements a workgroup's lanes own and how their sums meet:
@@ -24,6 +26,10 @@
 // partials itself (the same fixed order in every workgroup: no hand-off between workgroups, no atomics) and maps its share; item s = 0
 // also writes the per-channel outputs (saved statistics and the running update; ggamma / gbeta).  S == 1: ONE launch, the workgroup sums
 // its share and reads it a second time for the map, out of L2.  Eval: one launch.  bn_run is that ladder, once.
+//
+// The residual (kRes) is a template parameter of the three kernels that hold a map (fwd_train, fwd_eval, bwd_final); every statement it
+// adds stands under `if constexpr`, so the plain instances are the kernels they were.  The sums do not involve the residual: fwd_parts
+// and bwd_parts serve both.
 //
 // Numerics.  The sums of the forward are taken of x - K, K = the channel's first element, the same in every workgroup:
 // mean = K + s1 / M, var = (s2 - s1 * s1 / M) / M -- the cancellation is that of a channel centred within its own spread, whatever
@@ -260,6 +266,8 @@ struct BnAffine {
     float mean, a, b, floor_;
     __device__ __forceinline__ BnAffine(float mean_, float a_, float b_, int relu) : mean(mean_), a(a_), b(b_), floor_(relu ? 0.0f : -INFINITY) {}
     __device__ __forceinline__ float operator()(float v) const { return fmaxf((v - mean) * a + b, floor_); }
+    // with a residual: the plain map's value (before its floor), then the add, then the floor -- each rounded once, in this order
+    __device__ __forceinline__ float operator()(float v, float r) const { return fmaxf(((v - mean) * a + b) + r, floor_); }
 };
 
 // the batch statistics of a channel from its shifted sums; the lead lane saves them and updates the running pair
@@ -352,12 +360,20 @@ __global__ __launch_bounds__(kBnThreads) void fwd_parts(const float *__restrict_
     }
 }
 
-// the training forward's statistics, running update and map.  kSingle: S == 1, the sums are taken here (part unused)
-template <class G, bool kSingle>
+// y of a unit: f(x), or f(x, r) with the residual
+template <class V, bool kRes>
+__device__ __forceinline__ V bn_y(const BnAffine &f, const V &v, const V &r) {
+    if constexpr (kRes) return vmap(f, v, r);
+    else return vmap(f, v);
+}
+
+// the training forward's statistics, running update and map.  kSingle: S == 1, the sums are taken here (part unused).  kRes: res is added
+// in the map (null otherwise)
+template <class G, bool kSingle, bool kRes>
 __global__ __launch_bounds__(kBnThreads) void fwd_train(const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,
                                                         float *__restrict__ y, float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ save_mean, float *__restrict__ save_invstd, const float *__restrict__ part,
-                                                        BnDims d, float eps, float momentum, int relu) {
+                                                        BnDims d, float eps, float momentum, int relu, const float *__restrict__ res) {
     using V = typename G::Unit;
     __shared__ float lds[G::kLds];
     const G g(d);
@@ -373,26 +389,33 @@ __global__ __launch_bounds__(kBnThreads) void fwd_train(const float *__restrict_
         const auto t = g.trip(cur, it, !kSingle);
         V v0 = V(), v1 = V(), v2 = V(), v3 = V();
         if constexpr (!kSingle && G::kPrefetch) v0 = at<V>(x, t.i0), v1 = at<V>(x, t.i1), v2 = at<V>(x, t.i2), v3 = at<V>(x, t.i3);
+        // (the residual's trip the same way, unbranched and younger than the partials: the wait in front of the fold counts eight loads out)
+        V r0 = V(), r1 = V(), r2 = V(), r3 = V();
+        if constexpr (kRes && !kSingle && G::kPrefetch) r0 = at<V>(res, t.i0), r1 = at<V>(res, t.i1), r2 = at<V>(res, t.i2), r3 = at<V>(res, t.i3);
         if constexpr (kSingle) fwd_sums(g, x, cur, k, &s1, &s2);
         g.sum2(&s1, &s2, lds);
         float mean, invstd;
         bn_batch_stats(g.lead(it), it.ch, k, s1, s2, fm, eps, momentum, running_mean, running_var, save_mean, save_invstd, &mean, &invstd);
         const BnAffine f(mean, g.on(it) ? invstd * gamma[it.ch] : 0.0f, g.on(it) ? beta[it.ch] : 0.0f, relu);
         if (t.pre) {
-            put(y, t.i0, vmap(f, v0));
-            put(y, t.i1, vmap(f, v1));
-            put(y, t.i2, vmap(f, v2));
-            put(y, t.i3, vmap(f, v3));
+            put(y, t.i0, bn_y<V, kRes>(f, v0, r0));
+            put(y, t.i1, bn_y<V, kRes>(f, v1, r1));
+            put(y, t.i2, bn_y<V, kRes>(f, v2, r2));
+            put(y, t.i3, bn_y<V, kRes>(f, v3, r3));
         }
-        g.walk(cur, [&](int64_t i) { put(y, i, vmap(f, at<V>(x, i))); });
+        g.walk(cur, [&](int64_t i) {
+            if constexpr (kRes) put(y, i, vmap(f, at<V>(x, i), at<V>(res, i)));
+            else put(y, i, vmap(f, at<V>(x, i)));
+        });
     }
 }
 
-template <class G>
+template <class G, bool kRes>
 __global__ __launch_bounds__(kBnThreads) void fwd_eval(const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,
                                                        float *__restrict__ y, const float *__restrict__ running_mean,
                                                        const float *__restrict__ running_var, float *__restrict__ save_mean,
-                                                       float *__restrict__ save_invstd, BnDims d, float eps, int relu) {
+                                                       float *__restrict__ save_invstd, BnDims d, float eps, int relu,
+                                                       const float *__restrict__ res) {
     using V = typename G::Unit;
     const G g(d);
     for (int w = blockIdx.x; w < g.items(); w += gridDim.x) {
@@ -401,7 +424,10 @@ __global__ __launch_bounds__(kBnThreads) void fwd_eval(const float *__restrict__
         float mean, invstd;
         bn_running_stats(g.lead(it), it.ch, eps, running_mean, running_var, save_mean, save_invstd, &mean, &invstd);
         const BnAffine f(mean, invstd * gamma[it.ch], beta[it.ch], relu);
-        g.walk(g.cursor(it), [&](int64_t i) { put(y, i, vmap(f, at<V>(x, i))); });
+        g.walk(g.cursor(it), [&](int64_t i) {
+            if constexpr (kRes) put(y, i, vmap(f, at<V>(x, i), at<V>(res, i)));
+            else put(y, i, vmap(f, at<V>(x, i)));
+        });
     }
 }
 
@@ -423,12 +449,14 @@ __global__ __launch_bounds__(kBnThreads) void bwd_parts(const float *__restrict_
     }
 }
 
-// the channel sums (kSingle: taken here), ggamma / gbeta by item s = 0, and the map unless gx is null.  acc: bit 0 gx, 1 ggamma, 2 gbeta
-template <class G, bool kSingle, bool kMask>
+// the channel sums (kSingle: taken here), ggamma / gbeta by item s = 0, and the map unless gx is null.  acc: bit 0 gx, 1 ggamma, 2 gbeta.
+// kRes: the map also writes gr = the masked gy (acc bit 3: += into gr), and runs for gr alone when gx is null
+template <class G, bool kSingle, bool kMask, bool kRes>
 __global__ __launch_bounds__(kBnThreads) void bwd_final(const float *__restrict__ gy, const float *__restrict__ x, const float *__restrict__ y,
                                                         const float *__restrict__ gamma, const float *__restrict__ save_mean,
                                                         const float *__restrict__ save_invstd, float *__restrict__ gx, float *__restrict__ ggamma,
-                                                        float *__restrict__ gbeta, const float *__restrict__ part, BnDims d, int batch_stats, int acc) {
+                                                        float *__restrict__ gbeta, const float *__restrict__ part, BnDims d, int batch_stats, int acc,
+                                                        float *__restrict__ gr) {
     using V = typename G::Unit;
     __shared__ float lds[G::kLds];
     const G g(d);
@@ -440,7 +468,7 @@ __global__ __launch_bounds__(kBnThreads) void bwd_final(const float *__restrict_
         float s1 = 0.0f, s2 = 0.0f;
         if constexpr (!kSingle) g.load_parts(part, it, &s1, &s2);
         auto cur = g.cursor(it);
-        const auto t = g.trip(cur, it, !kSingle && gx);
+        const auto t = g.trip(cur, it, !kSingle && (kRes || gx));
         V g0 = V(), g1 = V(), g2 = V(), g3 = V(), x0 = V(), x1 = V(), x2 = V(), x3 = V();
         if constexpr (!kSingle && G::kPrefetch) {
             g0 = bn_gy<V, kMask>(gy, y, t.i0), g1 = bn_gy<V, kMask>(gy, y, t.i1), g2 = bn_gy<V, kMask>(gy, y, t.i2), g3 = bn_gy<V, kMask>(gy, y, t.i3);
@@ -449,12 +477,18 @@ __global__ __launch_bounds__(kBnThreads) void bwd_final(const float *__restrict_
         if constexpr (kSingle) bwd_sums<G, kMask>(g, gy, x, y, cur, mean, invstd, &s1, &s2);
         g.sum2(&s1, &s2, lds);
         if (g.lead(it)) bn_put_grads(it.ch, acc, s1, s2, ggamma, gbeta);
-        if (!gx) continue;
+        if constexpr (!kRes) {
+            if (!gx) continue;
+        }
         // gx of gy and x: a * (g - c1 - xh * c2) with the batch's statistics, a * g with the running pair; added to what is there on bit 0
         const float a = g.on(it) ? gamma[it.ch] * invstd : 0.0f;
         const float c1 = batch_stats ? s1 / fm : 0.0f, c2 = batch_stats ? s2 / fm : 0.0f;
         const bool add = (acc & 1) != 0;
         auto emit = [&](int64_t i, const V &gv, const V &xv) {
+            if constexpr (kRes) {   // the residual's gradient is the masked gy, which sits in a register here
+                put(gr, i, (acc & 8) ? vmap([](float gs, float old) { return old + gs; }, gv, at<V>(gr, i)) : gv);
+                if (!gx) return;
+            }
             V r = batch_stats ? vmap([=](float gs, float xe) { return a * (gs - c1 - ((xe - mean) * invstd) * c2); }, gv, xv)
                               : vmap([=](float gs) { return a * gs; }, gv);
             if (add) r = vmap([](float rv, float old) { return old + rv; }, r, at<V>(gx, i));
@@ -524,6 +558,52 @@ static int bn_run(th_ctx *ctx, const BnPlan &p, bool split, Parts parts, Second 
     return th_free(ctx, part);
 }
 
+// The launches of a forward whose arguments the entry point has checked.  kRes: d_residual is added in the map (null otherwise); it
+// counts for the plan, so that an unaligned residual takes the scalar instance
+template <bool kRes>
+static int bn_forward(th_ctx *ctx, const float *d_x, const float *d_residual, const float *d_gamma, const float *d_beta, float *d_y,
+                      float *d_running_mean, float *d_running_var, float *d_save_mean, float *d_save_invstd, int n, int c, int hw, float eps,
+                      float momentum, int training, int relu) {
+    const BnPlan p = bn_plan(n, c, hw, {d_x, d_y, d_residual});
+    const dim3 g(p.grid), b(kBnThreads);
+    return bn_dispatch(p, false, [&](auto geo, auto) {
+        using G = typename decltype(geo)::type;
+        return bn_run(
+            ctx, p, training && p.S > 1, [&](float *part) { hipLaunchKernelGGL(fwd_parts<G>, g, b, 0, ctx->stream, d_x, part, p.dims); },
+            [&](auto single, const float *part) {
+                if (training)
+                    hipLaunchKernelGGL((fwd_train<G, decltype(single)::value, kRes>), g, b, 0, ctx->stream, d_x, d_gamma, d_beta, d_y,
+                                       d_running_mean, d_running_var, d_save_mean, d_save_invstd, part, p.dims, eps, momentum, relu, d_residual);
+                else
+                    hipLaunchKernelGGL((fwd_eval<G, kRes>), g, b, 0, ctx->stream, d_x, d_gamma, d_beta, d_y, d_running_mean, d_running_var,
+                                       d_save_mean, d_save_invstd, p.dims, eps, relu, d_residual);
+            });
+    });
+}
+
+// The launches of a checked backward.  kRes: d_gr gets the residual's gradient in the map pass (null otherwise)
+template <bool kRes>
+static int bn_backward(th_ctx *ctx, const float *d_gy, const float *d_x, const float *d_y_or_null, const float *d_gamma, const float *d_save_mean,
+                       const float *d_save_invstd, float *d_gx_or_null, float *d_gr, float *d_ggamma, float *d_gbeta, int n, int c, int hw,
+                       int batch_stats, int accumulate_mask) {
+    const BnPlan p = bn_plan(n, c, hw, {d_gy, d_x, d_y_or_null, d_gx_or_null, d_gr});
+    const dim3 g(p.grid), b(kBnThreads);
+    return bn_dispatch(p, d_y_or_null != nullptr, [&](auto geo, auto mask) {
+        using G = typename decltype(geo)::type;
+        constexpr bool kMask = decltype(mask)::value;
+        // (without a map the second launch only folds: one workgroup per channel would do, the items s > 0 leave at once)
+        return bn_run(
+            ctx, p, p.S > 1,
+            [&](float *part) {
+                hipLaunchKernelGGL((bwd_parts<G, kMask>), g, b, 0, ctx->stream, d_gy, d_x, d_y_or_null, d_save_mean, d_save_invstd, part, p.dims);
+            },
+            [&](auto single, const float *part) {
+                hipLaunchKernelGGL((bwd_final<G, decltype(single)::value, kMask, kRes>), g, b, 0, ctx->stream, d_gy, d_x, d_y_or_null, d_gamma,
+                                   d_save_mean, d_save_invstd, d_gx_or_null, d_ggamma, d_gbeta, part, p.dims, batch_stats, accumulate_mask, d_gr);
+            });
+    });
+}
+
 }  // namespace th
 
 using namespace th;
@@ -545,21 +625,23 @@ int th_batchnorm2d_fwd(th_ctx *ctx, const float *d_x, const float *d_gamma, cons
     TH_REQUIRE(std::isfinite(eps) && eps > 0.0f, "th_batchnorm2d_fwd: eps must be finite and positive (got %g)", (double)eps);
     TH_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "th_batchnorm2d_fwd: momentum must be in [0, 1] (got %g)", (double)momentum);
     TH_REQUIRE(!(training && (int64_t)n * hw == 1), "th_batchnorm2d_fwd: Expected more than 1 value per channel when training");
-    const BnPlan p = bn_plan(n, c, hw, {d_x, d_y});
-    const dim3 g(p.grid), b(kBnThreads);
-    return bn_dispatch(p, false, [&](auto geo, auto) {
-        using G = typename decltype(geo)::type;
-        return bn_run(
-            ctx, p, training && p.S > 1, [&](float *part) { hipLaunchKernelGGL(fwd_parts<G>, g, b, 0, ctx->stream, d_x, part, p.dims); },
-            [&](auto single, const float *part) {
-                if (training)
-                    hipLaunchKernelGGL((fwd_train<G, decltype(single)::value>), g, b, 0, ctx->stream, d_x, d_gamma, d_beta, d_y, d_running_mean,
-                                       d_running_var, d_save_mean, d_save_invstd, part, p.dims, eps, momentum, relu);
-                else
-                    hipLaunchKernelGGL(fwd_eval<G>, g, b, 0, ctx->stream, d_x, d_gamma, d_beta, d_y, d_running_mean, d_running_var, d_save_mean,
-                                       d_save_invstd, p.dims, eps, relu);
-            });
-    });
+    return bn_forward<false>(ctx, d_x, nullptr, d_gamma, d_beta, d_y, d_running_mean, d_running_var, d_save_mean, d_save_invstd, n, c, hw, eps,
+                             momentum, training, relu);
+}
+
+int th_bn_residual_fwd(th_ctx *ctx, const float *d_x, const float *d_residual, const float *d_gamma, const float *d_beta, float *d_y,
+                       float *d_running_mean, float *d_running_var, float *d_save_mean, float *d_save_invstd, int n, int c, int hw, float eps,
+                       float momentum, int training, int relu) {
+    TH_REQUIRE(ctx && d_x && d_residual && d_gamma && d_beta && d_y && d_running_mean && d_running_var && d_save_mean && d_save_invstd,
+               "th_bn_residual_fwd: null argument");
+    TH_REQUIRE(d_residual != d_y, "th_bn_residual_fwd: d_residual may not be d_y (it is only read; it may be d_x)");
+    TH_REQUIRE(n > 0 && c > 0 && hw > 0, "th_bn_residual_fwd: n, c and hw must be positive (got %d, %d, %d)", n, c, hw);
+    TH_REQUIRE((int64_t)n * hw < ((int64_t)1 << 31), "th_bn_residual_fwd: %lld elements per channel: fewer than 2^31 are supported", (long long)n * hw);
+    TH_REQUIRE(std::isfinite(eps) && eps > 0.0f, "th_bn_residual_fwd: eps must be finite and positive (got %g)", (double)eps);
+    TH_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "th_bn_residual_fwd: momentum must be in [0, 1] (got %g)", (double)momentum);
+    TH_REQUIRE(!(training && (int64_t)n * hw == 1), "th_bn_residual_fwd: Expected more than 1 value per channel when training");
+    return bn_forward<true>(ctx, d_x, d_residual, d_gamma, d_beta, d_y, d_running_mean, d_running_var, d_save_mean, d_save_invstd, n, c, hw, eps,
+                            momentum, training, relu);
 }
 
 int th_batchnorm2d_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const float *d_y_or_null, const float *d_gamma, const float *d_save_mean,
@@ -569,22 +651,21 @@ int th_batchnorm2d_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const f
     TH_REQUIRE(n > 0 && c > 0 && hw > 0, "th_batchnorm2d_bwd: n, c and hw must be positive (got %d, %d, %d)", n, c, hw);
     TH_REQUIRE((int64_t)n * hw < ((int64_t)1 << 31), "th_batchnorm2d_bwd: %lld elements per channel: fewer than 2^31 are supported", (long long)n * hw);
     TH_REQUIRE((accumulate_mask & ~7) == 0, "th_batchnorm2d_bwd: accumulate_mask has bits 0 (gx), 1 (ggamma) and 2 (gbeta) (got %d)", accumulate_mask);
-    const BnPlan p = bn_plan(n, c, hw, {d_gy, d_x, d_y_or_null, d_gx_or_null});
-    const dim3 g(p.grid), b(kBnThreads);
-    return bn_dispatch(p, d_y_or_null != nullptr, [&](auto geo, auto mask) {
-        using G = typename decltype(geo)::type;
-        constexpr bool kMask = decltype(mask)::value;
-        // (without a map the second launch only folds: one workgroup per channel would do, the items s > 0 leave at once)
-        return bn_run(
-            ctx, p, p.S > 1,
-            [&](float *part) {
-                hipLaunchKernelGGL((bwd_parts<G, kMask>), g, b, 0, ctx->stream, d_gy, d_x, d_y_or_null, d_save_mean, d_save_invstd, part, p.dims);
-            },
-            [&](auto single, const float *part) {
-                hipLaunchKernelGGL((bwd_final<G, decltype(single)::value, kMask>), g, b, 0, ctx->stream, d_gy, d_x, d_y_or_null, d_gamma, d_save_mean,
-                                   d_save_invstd, d_gx_or_null, d_ggamma, d_gbeta, part, p.dims, batch_stats, accumulate_mask);
-            });
-    });
+    return bn_backward<false>(ctx, d_gy, d_x, d_y_or_null, d_gamma, d_save_mean, d_save_invstd, d_gx_or_null, nullptr, d_ggamma, d_gbeta, n, c, hw,
+                              batch_stats, accumulate_mask);
+}
+
+int th_bn_residual_bwd(th_ctx *ctx, const float *d_gy, const float *d_x, const float *d_y_or_null, const float *d_gamma, const float *d_save_mean,
+                       const float *d_save_invstd, float *d_gx_or_null, float *d_gr, float *d_ggamma, float *d_gbeta, int n, int c, int hw,
+                       int batch_stats, int accumulate_mask) {
+    TH_REQUIRE(ctx && d_gy && d_x && d_gamma && d_save_mean && d_save_invstd && d_gr && d_ggamma && d_gbeta, "th_bn_residual_bwd: null argument");
+    TH_REQUIRE(d_gr != d_gx_or_null, "th_bn_residual_bwd: d_gr may not be d_gx (two gradients, two buffers)");
+    TH_REQUIRE(n > 0 && c > 0 && hw > 0, "th_bn_residual_bwd: n, c and hw must be positive (got %d, %d, %d)", n, c, hw);
+    TH_REQUIRE((int64_t)n * hw < ((int64_t)1 << 31), "th_bn_residual_bwd: %lld elements per channel: fewer than 2^31 are supported", (long long)n * hw);
+    TH_REQUIRE((accumulate_mask & ~15) == 0, "th_bn_residual_bwd: accumulate_mask has bits 0 (gx), 1 (ggamma), 2 (gbeta) and 3 (gr) (got %d)",
+               accumulate_mask);
+    return bn_backward<true>(ctx, d_gy, d_x, d_y_or_null, d_gamma, d_save_mean, d_save_invstd, d_gx_or_null, d_gr, d_ggamma, d_gbeta, n, c, hw,
+                             batch_stats, accumulate_mask);
 }
 
 }  // extern "C"

@@ -221,6 +221,19 @@ int tp_basic_block_new(int in_ch, int out_ch, int stride, uint64_t seed, tp_modu
     *out = new tp_module{std::make_shared<BasicBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed)};
     TP_END
 }
+int tp_batchnorm2d_forward_add(const tp_module *m, const tp_tensor *x, const tp_tensor *residual, tp_tensor **out) {
+    TP_BEGIN
+    TAPER_ASSERT(x && residual && out, "tp_batchnorm2d_forward_add: null argument");
+    *out = wrap(as_batchnorm(m)->forward_add(x->t, residual->t));
+    TP_END
+}
+int tp_residual_block_new(int in_ch, int out_ch, int stride, uint64_t seed, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_residual_block_new: null argument");
+    TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "ResidualBlock: in_channels, out_channels and stride must be positive");
+    *out = new tp_module{std::make_shared<ResidualBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed)};
+    TP_END
+}
 int tp_module_num_buffers(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->buffers().size(); TP_END }
 int tp_module_buffer(const tp_module *m, int i, tp_tensor **out) {
     TP_BEGIN

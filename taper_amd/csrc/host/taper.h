@@ -431,6 +431,10 @@ class BatchNorm2d : public Module {
     bool is_training() const { return training_; }
     void set_running_stats(const std::vector<float> &mean, const std::vector<float> &var);
     Tensor forward(const Tensor &x) const override;   // x: [N, num_features, H, W]
+    // y = bn(x) + residual, then the layer's ReLU (after the add), in the normalisation's own map (th_bn_residual_fwd): a residual block's
+    // tail as one launch set and one tape node whose backward also leaves the residual's gradient.  Throws "BatchNorm2d::forward_add: ..."
+    // for a residual of another shape and for one that shares x's storage
+    Tensor forward_add(const Tensor &x, const Tensor &residual) const;
     std::vector<Tensor> parameters() const override { return {gamma, beta}; }
     std::vector<Tensor> buffers() const override { return {running_mean, running_var}; }
     const char *name() const override { return fuse_relu ? "BatchNorm2dReLU" : "BatchNorm2d"; }
@@ -451,6 +455,29 @@ class BasicBlock : public Module {
     const char *name() const override { return "BasicBlock"; }
 };
 
+// A ResNet-style block (no upstream counterpart): conv3x3(in, out, stride, pad 1) -> BatchNorm2d + ReLU -> conv3x3(out, out, 1, pad 1) ->
+// BatchNorm2d.forward_add(., shortcut) with the ReLU after the add.  The shortcut is the block's input when in == out and stride == 1,
+// else conv3x3(in, out, stride, pad 1) -> BatchNorm2d (no ReLU).  The projection is a 3x3 convolution, not torchvision's 1x1: the float
+// 1x1 path keeps the reference's row-scrambling reinterpretation and is not a usable projection.  No conv carries a bias:
+// in front of a normalisation its gradient is zero analytically, and Adam turns the rounding noise into steps.
+// Seeds: conv1 seed, conv2 seed + 1, the projection seed + 2.
+class ResidualBlock : public Module {
+   public:
+    Conv2d conv1;
+    BatchNorm2d bn1;
+    Conv2d conv2;
+    BatchNorm2d bn2;
+    std::unique_ptr<Conv2d> shortcut_conv;       // null: the identity shortcut
+    std::unique_ptr<BatchNorm2d> shortcut_bn;
+    // zero arguments throw before the device is touched
+    ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed);
+    Tensor forward(const Tensor &x) const override;
+    std::vector<BatchNorm2d *> batchnorms();            // bn1, bn2, [the shortcut's]
+    std::vector<Tensor> parameters() const override;   // conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w, gamma beta]
+    std::vector<Tensor> buffers() const override;      // the running pairs in the same order
+    const char *name() const override { return "ResidualBlock"; }
+};
+
 class Sequential : public Module {  // nn.rs:130-162
    public:
     std::vector<std::shared_ptr<Module>> layers;
@@ -466,7 +493,7 @@ class Sequential : public Module {  // nn.rs:130-162
     const char *name() const override { return "Sequential"; }
 };
 
-// The BatchNorm2d layers of a model (a Sequential's and a BasicBlock's, or the module itself), in order
+// The BatchNorm2d layers of a model (a Sequential's, a BasicBlock's and a ResidualBlock's, or the module itself), in order
 void batchnorm_modules(Module &m, std::vector<BatchNorm2d *> *out);
 // train() / eval() of every BatchNorm2d and every Dropout inside `m`
 void set_training(Module &m, bool on);
