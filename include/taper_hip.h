@@ -915,7 +915,15 @@ int th_u8_to_unit_f32(th_ctx *ctx, const uint8_t *d_in, float *d_out, size_t n);
  * (examples/train_mnist.rs:110-111,121 read loss / accuracy on the host every
  * step): metrics[2*s] = loss[0], metrics[2*s+1] = ncorrect[0] with
  * s = d_state[0] % capacity; then d_state[0] += 1 (step) and
- * d_state[1] += advance (sample cursor used by th_gather_batch). */
+ * d_state[1] += advance (sample cursor used by th_gather_batch).
+ *
+ * THE STEP LOG.  Every fused step form takes the same four arguments --
+ * d_metrics, metrics_capacity, d_state, advance -- and one thread of its last
+ * launch does exactly the above with the loss and hit count of that launch
+ * ("the step log (th_log_step)" in the descriptions above and below; device
+ * side: csrc/step_log_dev.h).  d_metrics is nullable (no log); with d_metrics,
+ * d_state must be given and metrics_capacity > 0, else the entry returns an
+ * error.  d_state[0] >= 0: it starts at 0 and only the log advances it. */
 int th_log_step(th_ctx *ctx, const float *d_loss, const float *d_ncorrect, float *d_metrics, int64_t capacity,
                 int64_t *d_state, int64_t advance);
 

@@ -13,6 +13,7 @@
 // (pass of 8 channels; k-step s = tap s % 9 of channels 4 (s / 9) + lane group), bias after the sum, ReLU, strict-> pooling maxima,
 // 16-lane plane sums with the same shuffle tree -- the chain's outputs are bit-identical to the layered path's.
 #include "tail_dev.h"
+#include "step_log_dev.h"
 #include "conv_plan.h"
 
 TH_USES_DEVICE_ERRORS()
@@ -1882,7 +1883,7 @@ int th_conv_chain_mlp3_xent(th_ctx *ctx, const float *d_x, const th_conv_stage *
         TH_REQUIRE(!(layers[l].w_fuse && layers[l].w_fuse->d_p) || layers[l].d_dw, "th_conv_chain_mlp3_xent: a fused weight update needs d_dw");
         TH_REQUIRE(!(layers[l].b_fuse && layers[l].b_fuse->d_p) || layers[l].d_db, "th_conv_chain_mlp3_xent: a fused bias update needs d_db");
     }
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_conv_chain_mlp3_xent: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_conv_chain_mlp3_xent");
     TH_REQUIRE(!(gap && gap->d_cnt) || (d_dx && gap->d_gb && gap->hw > 0 && gap->d_cnt == d_cnt),
                "th_conv_chain_mlp3_xent: the gap bias finish needs d_dx, d_gb, hw > 0 and the counts this launch writes");
     // workspace: A1, A2, dZ1, dZ2, dZ3, the rows' {NLL, hit}

@@ -12,6 +12,7 @@
 // Operands are described by (row stride, col stride) so NN / NT / TN / TT all
 // run the same code: "KC" = k-contiguous in memory, "MC" = m/n-contiguous.
 #include "small16_dev.h"
+#include "step_log_dev.h"
 
 namespace th {
 
@@ -278,14 +279,7 @@ __global__ __launch_bounds__(256) void mlp3_grads_kernel(Mlp3GradArgs a) {
             const float l = n / (float)a.batch;   // loss.rs:164
             a.loss[0] = l;
             if (a.ncorrect) a.ncorrect[0] = h;
-            if (a.metrics) {                      // the step log of th_log_step
-                const int64_t s0 = a.state[0], s1 = a.state[1];
-                const int64_t slot = s0 < a.capacity ? s0 : s0 % a.capacity;
-                a.metrics[2 * slot] = l;
-                a.metrics[2 * slot + 1] = h;
-                a.state[0] = s0 + 1;
-                a.state[1] = s1 + a.advance;
-            }
+            if (a.metrics) step_log_write(a.metrics, a.capacity, a.state, a.advance, l, h);
         }
         return;
     }

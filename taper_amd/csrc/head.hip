@@ -25,6 +25,7 @@
 // softmax, dlogits and dH are row-local); dW / db / {nll, hits} go to per-workgroup slots and
 // head_finish_kernel (+ th_colsum for many slots) adds them in slot order: deterministic, no atomics.
 #include "adam_dev.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(HEAD_T) void linear_xent_head_kernel(HeadArgs a) {
     // ---- everything this launch needs from global memory is requested up front: after a kernel
     //      boundary each dependent round trip costs ~1 us, so none may hide behind a barrier ----
     const float bias_v = (a.bias && r16 < C) ? a.bias[r16] : 0.f;               // logits epilogue
-    const int64_t log_slot = (t == 0 && a.metrics && !multi) ? a.state[0] % a.capacity : 0;  // step log
+    const int64_t log_slot = (t == 0 && a.metrics && !multi) ? step_log_slot(a.state[0], a.capacity) : 0;  // step log
     const bool own_dw = a.dw && wave < (KP / 16);
     const bool fuse_w = own_dw && a.w_adam.p, fuse_b = a.db && t < C && a.b_adam.p;
     float wp_[4], wm_[4], wv_[4], w_step = 0.f, bp_ = 0.f, bm_ = 0.f, bv_ = 0.f, b_step = 0.f;
@@ -362,12 +363,7 @@ __global__ __launch_bounds__(HEAD_T) void linear_xent_head_kernel(HeadArgs a) {
         if (!multi) a.loss[0] = l;
         if (!multi && a.ncorrect) a.ncorrect[0] = hsum;
         if (!multi && a.adam_tick) a.adam_tick[0] = tick_old + 1;  // optim.rs:84
-        if (!multi && a.metrics) {  // the step log of th_log_step
-            a.metrics[2 * log_slot] = l;
-            a.metrics[2 * log_slot + 1] = hsum;
-            a.state[0] += 1;
-            a.state[1] += a.advance;
-        }
+        if (!multi && a.metrics) step_log_write(a.metrics, log_slot, l, hsum, a.state, a.state[0] + 1, a.state[1] + a.advance);
     }
 
     HEAD_STAMP(7);
@@ -459,13 +455,7 @@ __global__ __launch_bounds__(256) void head_finish_kernel(HeadArgs a, const floa
         a.loss[0] = l;
         if (a.ncorrect) a.ncorrect[0] = hsum;
         if (a.adam_tick) a.adam_tick[0] += 1;  // optim.rs:84
-        if (a.metrics) {
-            const int64_t slot = a.state[0] % a.capacity;
-            a.metrics[2 * slot] = l;
-            a.metrics[2 * slot + 1] = hsum;
-            a.state[0] += 1;
-            a.state[1] += a.advance;
-        }
+        if (a.metrics) step_log_write(a.metrics, a.capacity, a.state, a.advance, l, hsum);
     }
 }
 
@@ -500,7 +490,7 @@ extern "C" int th_linear_xent_head_masked(th_ctx *ctx, const float *d_h, const f
     TH_REQUIRE(batch > 0 && batch <= (1 << 22) && classes > 0 && classes <= HEAD_CMAX && in_features > 0 && in_features <= HEAD_KMAX,
                "th_linear_xent_head: needs batch <= 4194304, classes <= 16, in_features <= 256 (got %d, %d, %d)", batch, classes,
                in_features);
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_linear_xent_head: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_linear_xent_head");
     TH_REQUIRE(!(w_fuse && w_fuse->d_p) || d_dw, "th_linear_xent_head: fused W update needs d_dw");
     TH_REQUIRE(!(b_fuse && b_fuse->d_p) || d_db, "th_linear_xent_head: fused b update needs d_db");
     HeadArgs a{d_h, d_w, d_bias, d_targets, batch, in_features, classes, d_logits, d_loss, d_ncorrect, d_dh, d_dw, d_db,

@@ -25,6 +25,61 @@ static float *grad_slot(const Tensor &p) {
     return p.grad_->buf->d;
 }
 
+// ---- the contract the fused loss forms share, stated once: parameter gradients are written, never accumulated (every slot empty); dX is
+// adopted, never added; the tape node supports only loss.backward() from the root; the step's last launch writes the step log.
+static const StepLogSink kNoLog;   // no step log: the launches receive nullptr / 0
+
+static bool fresh_param(const Tensor &p) { return p.get_requires_grad() && !p.has_grad(); }   // trains, and its slot is empty
+// absent, or trains with an empty slot and one element per output feature
+static bool fresh_bias(const Tensor &b, size_t out_features) { return !b.defined() || (fresh_param(b) && b.shape() == Shape{out_features}); }
+// no gradient wanted, or none present and no arena behind the slot: dX is written, never accumulated
+static bool writable_input(const Tensor &x) { return !(x.get_requires_grad() && (x.has_grad() || x.grad_->buf_is_arena)); }
+static bool aligned16(const Tensor &t) { return ((uintptr_t)t.dptr() & 15) == 0; }
+
+// the three Linear layers of a classifier behind `in_features` inputs: shapes chain, every weight and bias trains with an empty slot
+static bool classifier3_ok(size_t in_features, const Tensor (&w)[3], const Tensor (&b)[3]) {
+    for (int l = 0; l < 3; ++l) {
+        if (w[l].shape().size() != 2 || w[l].shape()[1] != in_features) return false;
+        if (!fresh_param(w[l]) || !aligned16(w[l])) return false;
+        if (!b[l].defined() || !fresh_bias(b[l], w[l].shape()[0])) return false;   // (these launches demand a bias)
+        in_features = w[l].shape()[0];
+    }
+    return true;
+}
+
+// th_mlp3_layer records of `nl` Linear layers, first to last: gradient slots, and the fused updates where an optimizer step is open
+static void build_mlp3_layers(const Tensor *w, const Tensor *b, size_t nl, Adam *fa, th_mlp3_layer *layers, th_adam_fuse *wf, th_adam_fuse *bf) {
+    for (size_t l = 0; l < nl; ++l) {
+        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].defined() ? b[l].dptr() : nullptr, grad_slot(w[l]), grad_slot(b[l]), nullptr, nullptr,
+                                  (int)w[l].shape()[0]};
+        if (fa && fa->fuse_for(w[l], &wf[l])) layers[l].w_fuse = &wf[l];
+        if (fa && b[l].defined() && fa->fuse_for(b[l], &bf[l])) layers[l].b_fuse = &bf[l];
+    }
+}
+
+// dX from the forward launch IS x's gradient (upstream gradient 1, slot empty): adopted, never added
+static void adopt_grad(const Tensor &x, const std::shared_ptr<Buffer> &buf, const char *who) {
+    TAPER_ASSERT(!x.has_grad() && !x.grad_->buf_is_arena, std::string(who) + ": input already has a gradient");
+    x.grad_->buf = buf;
+    x.grad_->has = true;
+    x.grad_->shared_const = false;
+}
+
+// The tape node of a fused form.  The launches produced every gradient for an upstream gradient of exactly 1, so only loss.backward()
+// from the root is supported: the node runs the form's own `extra` (dX adoption, column sums, the gap bias), then marks the slot of every
+// defined parameter in `params` (grad_slot() handed them to the launches).
+static void push_root_only(Tensor &loss, const char *who, std::vector<Tensor> params, std::function<void()> extra = nullptr) {
+    loss.set_requires_grad(true);
+    Tensor out = loss;
+    Tape::push(loss, true, [out, who, params, extra]() {
+        if (!out.has_grad()) return;
+        TAPER_ASSERT(out.grad_->shared_const, std::string(who) + ": only loss.backward() from the root is supported");
+        if (extra) extra();
+        for (const Tensor &p : params)
+            if (p.defined()) p.grad_->has = true;
+    });
+}
+
 // ---------------------------------------------------------------- loss
 Tensor log_softmax(const Tensor &x, int dim) {  // loss.rs:101-126
     const int nd = (int)x.shape().size();
@@ -58,9 +113,9 @@ Tensor cross_entropy_loss(const Tensor &logits, const Tensor &targets, Tensor *n
     // the gradient for an upstream grad of exactly 1 comes out of the forward kernel
     std::shared_ptr<Buffer> dunit = need_grad ? Buffer::alloc(logits.len()) : nullptr;
     float *nc = n_correct_slot(n_correct_out);
+    const StepLogSink &sink = log ? *log : kNoLog;
     TH(th_softmax_xent_fwd(ctx, logits.dptr(), targets.dptr(), b, c, logp.dptr(), loss.dptr(), nullptr, nc,
-                           dunit ? dunit->d : nullptr, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                           log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr));
+                           dunit ? dunit->d : nullptr, sink.d_metrics, sink.capacity, sink.d_state, sink.advance, sink.d_adam_tick));
     if (need_grad) {
         loss.set_requires_grad(true);
         Tensor lg = logits, lp = logp, t = targets, out = loss;
@@ -102,23 +157,13 @@ Tensor linear_cross_entropy(const Tensor &h, const Tensor &w, const Tensor &bias
     Tensor loss = Tensor::empty({1});
     float *nc = n_correct_slot(n_correct_out);
     const bool h_grad = h.get_requires_grad();
-    const bool w_grad = w.get_requires_grad() && !w.has_grad();
-    const bool b_grad = bias.defined() && bias.get_requires_grad() && !bias.has_grad();
+    const bool w_grad = fresh_param(w);
+    const bool b_grad = bias.defined() && fresh_param(bias);
     TAPER_ASSERT(!w.get_requires_grad() || w_grad, "linear_cross_entropy: weight already has a gradient (accumulation unsupported)");
     TAPER_ASSERT(!(bias.defined() && bias.get_requires_grad()) || b_grad, "linear_cross_entropy: bias already has a gradient");
     // gradient destinations: parameter grads go straight into their (currently None) slots
     std::shared_ptr<Buffer> dh = h_grad ? Buffer::alloc(h.len()) : nullptr;
-    float *dw = nullptr, *db = nullptr;
-    if (w_grad) {
-        if (!w.grad_->buf) w.grad_->buf = Buffer::alloc(w.len());
-        dw = w.grad_->buf->d;
-        w.grad_->known_zero = false;
-    }
-    if (b_grad) {
-        if (!bias.grad_->buf) bias.grad_->buf = Buffer::alloc(bias.len());
-        db = bias.grad_->buf->d;
-        bias.grad_->known_zero = false;
-    }
+    float *dw = w_grad ? grad_slot(w) : nullptr, *db = b_grad ? grad_slot(bias) : nullptr;
     // The head's own W / b updates ride in the next backward launch (Adam::defer_for): applied in
     // this single-workgroup kernel they cost 2.4 us of extra round trips, there they are free.
     const th_adam_fuse *pw = nullptr, *pb = nullptr;
@@ -129,26 +174,16 @@ Tensor linear_cross_entropy(const Tensor &h, const Tensor &w, const Tensor &bias
     // h straight out of a fused Linear+ReLU: dH leaves the kernel already masked (the large-batch backward of that
     // layer would otherwise spend a pass over [B, hidden] on it)
     const bool mask_dh = dh && h.grad_->relu_output;
+    const StepLogSink &sink = log ? *log : kNoLog;
     TH(th_linear_xent_head_masked(ctx, h.dptr(), w.dptr(), bias.defined() ? bias.dptr() : nullptr, targets.dptr(), b, k, c, nullptr,
-                                  loss.dptr(), nc, dh ? dh->d : nullptr, dw, db, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                                  log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr, pw, pb,
-                                  mask_dh ? 1 : 0));
+                                  loss.dptr(), nc, dh ? dh->d : nullptr, dw, db, sink.d_metrics, sink.capacity, sink.d_state, sink.advance,
+                                  sink.d_adam_tick, pw, pb, mask_dh ? 1 : 0));
     if (h_grad || w_grad || b_grad) {
-        loss.set_requires_grad(true);
-        Tensor hh = h, ww = w, bb = bias, out = loss;
-        Tape::push(loss, true, [hh, ww, bb, out, dh, w_grad, b_grad, mask_dh]() {
-            if (!out.has_grad()) return;
-            // the gradients were produced by the forward launch for an upstream grad of exactly 1
-            TAPER_ASSERT(out.grad_->shared_const, "linear_cross_entropy: only loss.backward() from the root is supported");
-            if (dh) {
-                TAPER_ASSERT(!hh.has_grad() && !hh.grad_->buf_is_arena, "linear_cross_entropy: input already has a gradient");
-                hh.grad_->buf = dh;
-                hh.grad_->has = true;
-                hh.grad_->shared_const = false;
-                hh.grad_->premasked = mask_dh;
-            }
-            if (w_grad) ww.grad_->has = true;
-            if (b_grad) bb.grad_->has = true;
+        Tensor hh = h;
+        push_root_only(loss, "linear_cross_entropy", {w_grad ? w : Tensor(), b_grad ? bias : Tensor()}, [hh, dh, mask_dh]() {
+            if (!dh) return;
+            adopt_grad(hh, dh, "linear_cross_entropy");
+            hh.grad_->premasked = mask_dh;
         });
     }
     return loss;
@@ -157,9 +192,8 @@ Tensor linear_cross_entropy(const Tensor &h, const Tensor &w, const Tensor &bias
 bool linear_cross_entropy_wide_supported(const Tensor &h, const Tensor &w, const Tensor &bias) {
     if (h.shape().size() != 2 || w.shape().size() != 2 || h.shape()[1] != w.shape()[1]) return false;
     if (w.shape()[1] <= 256 || w.shape()[0] > 16 || h.shape()[0] < 1 || h.shape()[0] > 4096) return false;
-    if (!w.get_requires_grad() || w.has_grad()) return false;
-    if (bias.defined() && (!bias.get_requires_grad() || bias.has_grad())) return false;
-    return !(h.get_requires_grad() && (h.has_grad() || h.grad_->buf_is_arena));   // dX is written, never accumulated
+    if (!fresh_param(w) || (bias.defined() && !fresh_param(bias))) return false;   // (fresh_bias() without its shape demand)
+    return writable_input(h);
 }
 
 Tensor linear_cross_entropy_wide(const Tensor &h, const Tensor &w, const Tensor &bias, const Tensor &targets, Tensor *n_correct_out,
@@ -178,35 +212,25 @@ Tensor linear_cross_entropy_wide(const Tensor &h, const Tensor &w, const Tensor 
     // CNN at batch 256 (r05 / r06, with a knob since retired; HISTORY.md): the head grew from 11.9 to 22.5 us -- Adam's p / m / v round trip
     // behind the dW reduction in every workgroup, an agent-scope fence per workgroup, the last arriver's serial finish -- against the 5.0 us
     // finishing launch it replaces: step 57.2 -> 64.1 us.  The Trainer does not use it.)
+    const StepLogSink &sink = log ? *log : kNoLog;
     TH(th_linear_xent_wide_ex(Device::ctx(), h.dptr(), w.dptr(), bias.defined() ? bias.dptr() : nullptr, targets.dptr(), b, k, c, loss.dptr(),
-                              nc, dh ? dh->d : nullptr, dw, db, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                              log ? log->d_state : nullptr, log ? log->advance : 0, log ? log->d_adam_tick : nullptr, cs ? cs->d : nullptr));
+                              nc, dh ? dh->d : nullptr, dw, db, sink.d_metrics, sink.capacity, sink.d_state, sink.advance, sink.d_adam_tick,
+                              cs ? cs->d : nullptr));
     if (Adam *fa = FusedAdamScope::active()) {   // complete gradients; every workgroup of the launch read W
         fa->defer_for(w);
         if (bias.defined()) fa->defer_for(bias);
     }
-    loss.set_requires_grad(true);
-    Tensor hh = h, ww = w, bb = bias, out = loss;
-    Tape::push(loss, true, [hh, ww, bb, out, dh, cs]() {
-        if (!out.has_grad()) return;
-        TAPER_ASSERT(out.grad_->shared_const, "linear_cross_entropy_wide: only loss.backward() from the root is supported");
+    Tensor hh = h;
+    push_root_only(loss, "linear_cross_entropy_wide", {w, bias}, [hh, dh, cs]() {
         if (cs) hh.grad_->colsum = cs;
-        if (dh) {
-            TAPER_ASSERT(!hh.has_grad() && !hh.grad_->buf_is_arena, "linear_cross_entropy_wide: input already has a gradient");
-            hh.grad_->buf = dh;
-            hh.grad_->has = true;
-            hh.grad_->shared_const = false;
-        }
-        ww.grad_->has = true;
-        if (bb.defined()) bb.grad_->has = true;
+        if (dh) adopt_grad(hh, dh, "linear_cross_entropy_wide");
     });
     return loss;
 }
 
 bool conv_chain_head_supported(const Tensor &x, const std::vector<ConvStage> &stages, const Tensor &w, const Tensor &bias) {
     if (stages.empty() || stages.back().post != TH_CHAIN_MAXPOOL2 || x.shape().size() != 4 || w.shape().size() != 2) return false;
-    if (!w.get_requires_grad() || w.has_grad()) return false;
-    if (bias.defined() && (!bias.get_requires_grad() || bias.has_grad() || bias.shape() != Shape{w.shape()[0]})) return false;
+    if (!fresh_param(w) || !fresh_bias(bias, w.shape()[0])) return false;
     const Tensor &cb = stages.back().bias;
     if (cb.defined() && cb.get_requires_grad() && cb.has_grad()) return false;   // gradients are written, never accumulated
     size_t h = x.shape()[2], wd = x.shape()[3];
@@ -241,37 +265,27 @@ Tensor conv_chain_head_cross_entropy(const Tensor &x, const std::vector<ConvStag
     float *dw = grad_slot(w), *db = grad_slot(bias), *gcb = cb_grad ? grad_slot(cbias) : nullptr;
     th_adam_fuse wf{}, bf{}, cf{};
     const bool fw = fa && fa->fuse_for(w, &wf), fb = fa && bias.defined() && fa->fuse_for(bias, &bf), fc = fa && cb_grad && fa->fuse_for(cbias, &cf);
-    const Communicator *xc = log ? log->exchange : nullptr;
+    const StepLogSink &sink = log ? *log : kNoLog;
+    const Communicator *xc = sink.exchange;
     if (xc && xc->n_ranks > 1) {
         // data parallel: the launch exchanges every finished sum with the peers; its epilogues apply the mean
         TAPER_ASSERT(fa && xc->wide_exchange_ok(n, k, classes, c_last), "conv_chain_head_cross_entropy: the in-launch exchange does not cover this step");
         TH(th_wide_head_grads_dp(xc->handle(), ctx, map.dptr(), dl->d, rowstat->d, cbpart ? cbpart->d : nullptr, n, k, classes, c_last, dw, db, gcb,
-                                 loss.dptr(), nc, log ? log->d_metrics : nullptr, log ? log->capacity : 0, log ? log->d_state : nullptr,
-                                 log ? log->advance : 0, fw ? &wf : nullptr, fb ? &bf : nullptr, fc ? &cf : nullptr, fa->d_tick()));
+                                 loss.dptr(), nc, sink.d_metrics, sink.capacity, sink.d_state, sink.advance, fw ? &wf : nullptr,
+                                 fb ? &bf : nullptr, fc ? &cf : nullptr, fa->d_tick()));
     } else
     TH(th_wide_head_grads(ctx, map.dptr(), dl->d, rowstat->d, cbpart ? cbpart->d : nullptr, n, k, classes, c_last, dw, db, gcb, loss.dptr(), nc,
-                          log ? log->d_metrics : nullptr, log ? log->capacity : 0, log ? log->d_state : nullptr, log ? log->advance : 0,
-                          fw ? &wf : nullptr, fb ? &bf : nullptr, fc ? &cf : nullptr));
-    loss.set_requires_grad(true);
-    Tensor ww = w, bb = bias, cc = cb_grad ? cbias : Tensor(), out = loss;
-    Tape::push(loss, true, [ww, bb, cc, out]() {
-        if (!out.has_grad()) return;
-        // the gradients were produced by the forward launches for an upstream grad of exactly 1
-        TAPER_ASSERT(out.grad_->shared_const, "conv_chain_head_cross_entropy: only loss.backward() from the root is supported");
-        ww.grad_->has = true;
-        if (bb.defined()) bb.grad_->has = true;
-        if (cc.defined()) cc.grad_->has = true;
-    });
+                          sink.d_metrics, sink.capacity, sink.d_state, sink.advance, fw ? &wf : nullptr, fb ? &bf : nullptr, fc ? &cf : nullptr));
+    push_root_only(loss, "conv_chain_head_cross_entropy", {w, bias, cb_grad ? cbias : Tensor()});
     return loss;
 }
 
 bool mlp_tail_supported(const Tensor &x, const Tensor &w1, const Tensor &b1, const Tensor &w2, const Tensor &b2) {
     if (x.shape().size() != 2 || w1.shape().size() != 2 || w2.shape().size() != 2) return false;
     if (x.shape()[1] != w1.shape()[1] || w2.shape()[1] != w1.shape()[0]) return false;
-    if (x.get_requires_grad() && (x.has_grad() || x.grad_->buf_is_arena)) return false;   // dX is written, never accumulated
-    if (!w1.get_requires_grad() || !w2.get_requires_grad() || w1.has_grad() || w2.has_grad()) return false;
+    if (!writable_input(x) || !fresh_param(w1) || !fresh_param(w2)) return false;
     for (const Tensor *b : {&b1, &b2})
-        if (b->defined() && (!b->get_requires_grad() || b->has_grad())) return false;
+        if (b->defined() && !fresh_param(*b)) return false;   // (fresh_bias() without its shape demand)
     return th_mlp_tail_supported((int)x.shape()[0], (int)x.shape()[1], (int)w1.shape()[0], (int)w2.shape()[0],
                                  x.get_requires_grad() ? 1 : 0) != 0;
 }
@@ -305,36 +319,25 @@ Tensor mlp_tail_cross_entropy(const Tensor &x, const Tensor &w1, const Tensor &b
         if (!need_dx && fa->fuse_for(w1, &wf)) pw = &wf;
         if (b1.defined() && fa->fuse_for(b1, &bf)) pb = &bf;
     }
-    const Communicator *xc = log ? log->exchange : nullptr;
+    const StepLogSink &sink = log ? *log : kNoLog;
+    const Communicator *xc = sink.exchange;
     if (xc && xc->n_ranks > 1) {
         // data parallel: the launch exchanges every finished slice with the peers; its epilogues apply the mean
         TAPER_ASSERT(fa && !need_dx && xc->tail_exchange_ok(b, in_f, hid, c), "mlp_tail_cross_entropy: the in-launch exchange does not cover this step");
         TH(th_mlp_tail_dp(xc->handle(), ctx, x.dptr(), h.dptr(), w2.dptr(), b2.defined() ? b2.dptr() : nullptr, targets.dptr(), b, in_f, hid, c,
-                          loss.dptr(), nc, dw1, db1, dw2, db2, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                          log ? log->d_state : nullptr, log ? log->advance : 0, pw, pb, fa->d_tick()));
+                          loss.dptr(), nc, dw1, db1, dw2, db2, sink.d_metrics, sink.capacity, sink.d_state, sink.advance, pw, pb, fa->d_tick()));
     } else
     TH(th_mlp_tail(ctx, x.dptr(), h.dptr(), w2.dptr(), b2.defined() ? b2.dptr() : nullptr, targets.dptr(), b, in_f, hid, c, loss.dptr(),
-                   nc, dw1, db1, dw2, db2, need_dx ? w1.dptr() : nullptr, dx ? dx->d : nullptr, log ? log->d_metrics : nullptr,
-                   log ? log->capacity : 0, log ? log->d_state : nullptr, log ? log->advance : 0, pw, pb));
+                   nc, dw1, db1, dw2, db2, need_dx ? w1.dptr() : nullptr, dx ? dx->d : nullptr, sink.d_metrics, sink.capacity, sink.d_state,
+                   sink.advance, pw, pb));
     if (fa) {   // complete gradients of parameters this launch read: updated by the next launch that does not read them
         if (need_dx) fa->defer_for(w1);
         fa->defer_for(w2);
         if (b2.defined()) fa->defer_for(b2);
     }
-    loss.set_requires_grad(true);
-    Tensor p1 = w1, p2 = b1, p3 = w2, p4 = b2, out = loss, keep = h, xin = x;
-    Tape::push(loss, true, [p1, p2, p3, p4, out, keep, xin, dx]() {
-        if (!out.has_grad()) return;
-        // the gradients were produced by the forward launches for an upstream grad of exactly 1
-        TAPER_ASSERT(out.grad_->shared_const, "mlp_tail_cross_entropy: only loss.backward() from the root is supported");
-        if (dx) {
-            TAPER_ASSERT(!xin.has_grad() && !xin.grad_->buf_is_arena, "mlp_tail_cross_entropy: input already has a gradient");
-            xin.grad_->buf = dx;
-            xin.grad_->has = true;
-            xin.grad_->shared_const = false;
-        }
-        for (const Tensor *p : {&p1, &p2, &p3, &p4})
-            if (p->defined()) p->grad_->has = true;
+    Tensor keep = h, xin = x;
+    push_root_only(loss, "mlp_tail_cross_entropy", {w1, b1, w2, b2}, [keep, xin, dx]() {
+        if (dx) adopt_grad(xin, dx, "mlp_tail_cross_entropy");
     });
     return loss;
 }
@@ -345,8 +348,7 @@ bool mlp2_params_ok(const std::vector<Tensor> &w, const std::vector<Tensor> &b) 
     if ((w.size() != 2 && w.size() != 3) || b.size() != w.size()) return false;
     for (size_t l = 0; l < w.size(); ++l) {
         if (w[l].shape().size() != 2 || (l > 0 && w[l].shape()[1] != w[l - 1].shape()[0])) return false;
-        if (!w[l].get_requires_grad() || w[l].has_grad() || ((uintptr_t)w[l].dptr() & 15) != 0) return false;
-        if (b[l].defined() && (!b[l].get_requires_grad() || b[l].has_grad() || b[l].shape() != Shape{w[l].shape()[0]})) return false;
+        if (!fresh_param(w[l]) || !aligned16(w[l]) || !fresh_bias(b[l], w[l].shape()[0])) return false;
     }
     return true;
 }
@@ -378,36 +380,18 @@ Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vec
     const size_t nl = w.size();
     th_adam_fuse fw[3], fb[3];
     th_mlp3_layer L[3];
-    for (size_t l = 0; l < nl; ++l) {
-        L[l].d_w = w[l].dptr();
-        L[l].d_b = b[l].defined() ? b[l].dptr() : nullptr;
-        L[l].d_dw = grad_slot(w[l]);
-        L[l].d_db = grad_slot(b[l]);
-        L[l].w_fuse = (fa && fa->fuse_for(w[l], &fw[l])) ? &fw[l] : nullptr;
-        L[l].b_fuse = (fa && b[l].defined() && fa->fuse_for(b[l], &fb[l])) ? &fb[l] : nullptr;
-        L[l].out_features = (int)w[l].shape()[0];
-    }
+    build_mlp3_layers(w.data(), b.data(), nl, fa, L, fw, fb);
+    const StepLogSink &sink = log ? *log : kNoLog;
     if (nl == 2)
         TH(th_mlp2_xent(ctx, &src, (int)batch, (int)w[0].shape()[1], L[0].out_features, L[1].out_features, L[0].d_w, L[0].d_b, L[1].d_w, L[1].d_b,
-                        L[0].d_dw, L[0].d_db, L[1].d_dw, L[1].d_db, loss.dptr(), nc, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                        log ? log->d_state : nullptr, log ? log->advance : 0, fa ? fa->d_tick() : nullptr, L[0].w_fuse, L[0].b_fuse, L[1].w_fuse,
-                        L[1].b_fuse));
+                        L[0].d_dw, L[0].d_db, L[1].d_dw, L[1].d_db, loss.dptr(), nc, sink.d_metrics, sink.capacity, sink.d_state, sink.advance,
+                        fa ? fa->d_tick() : nullptr, L[0].w_fuse, L[0].b_fuse, L[1].w_fuse, L[1].b_fuse));
     else
-        TH(th_mlp2_xent_deep(ctx, &src, (int)batch, (int)w[0].shape()[1], L, loss.dptr(), nc, log ? log->d_metrics : nullptr, log ? log->capacity : 0,
-                             log ? log->d_state : nullptr, log ? log->advance : 0, fa ? fa->d_tick() : nullptr));
-    loss.set_requires_grad(true);
-    std::vector<Tensor> ps;
-    for (size_t l = 0; l < nl; ++l) {
-        ps.push_back(w[l]);
-        if (b[l].defined()) ps.push_back(b[l]);
-    }
-    Tensor out = loss;
-    Tape::push(loss, true, [ps, out]() {
-        if (!out.has_grad()) return;
-        // the gradients were produced by the forward launches for an upstream grad of exactly 1
-        TAPER_ASSERT(out.grad_->shared_const, "mlp2_cross_entropy: only loss.backward() from the root is supported");
-        for (const Tensor &p : ps) p.grad_->has = true;
-    });
+        TH(th_mlp2_xent_deep(ctx, &src, (int)batch, (int)w[0].shape()[1], L, loss.dptr(), nc, sink.d_metrics, sink.capacity, sink.d_state,
+                             sink.advance, fa ? fa->d_tick() : nullptr));
+    std::vector<Tensor> ps(w);
+    ps.insert(ps.end(), b.begin(), b.end());
+    push_root_only(loss, "mlp2_cross_entropy", ps);
     return loss;
 }
 
@@ -416,17 +400,8 @@ Tensor mlp2_cross_entropy(const th_row_source &src, size_t batch, const std::vec
 // gradients of the activations down to dX) and one for every parameter gradient with Adam in the epilogues.  No launch reads a
 // parameter another one of the step updates, so nothing is deferred; the first launch opens the optimizer step.
 bool mlp3_supported(const Tensor &x, const Tensor (&w)[3], const Tensor (&b)[3]) {
-    if (x.shape().size() != 2) return false;
-    size_t in_f = x.shape()[1];
-    for (int l = 0; l < 3; ++l) {
-        if (w[l].shape().size() != 2 || w[l].shape()[1] != in_f) return false;
-        if (!w[l].get_requires_grad() || w[l].has_grad()) return false;
-        if (!b[l].defined() || b[l].shape() != Shape{w[l].shape()[0]} || !b[l].get_requires_grad() || b[l].has_grad()) return false;
-        if (((uintptr_t)w[l].dptr() & 15) != 0) return false;
-        in_f = w[l].shape()[0];
-    }
-    if (x.get_requires_grad() && (x.has_grad() || x.grad_->buf_is_arena)) return false;   // dX is written, never accumulated
-    if (((uintptr_t)x.dptr() & 15) != 0) return false;
+    if (x.shape().size() != 2 || !classifier3_ok(x.shape()[1], w, b)) return false;
+    if (!writable_input(x) || !aligned16(x)) return false;
     return th_mlp3_supported((int)x.shape()[0], (int)x.shape()[1], (int)w[0].shape()[0], (int)w[1].shape()[0], (int)w[2].shape()[0]) != 0;
 }
 
@@ -441,13 +416,7 @@ Tensor mlp3_cross_entropy(const Tensor &x, const Tensor (&w)[3], const Tensor (&
     float *nc = n_correct_slot(n_correct_out);
     th_mlp3_layer layers[3];
     th_adam_fuse wf[3], bf[3];
-    for (int l = 0; l < 3; ++l) {
-        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), grad_slot(w[l]), grad_slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
-        if (fa) {
-            if (fa->fuse_for(w[l], &wf[l])) layers[l].w_fuse = &wf[l];
-            if (fa->fuse_for(b[l], &bf[l])) layers[l].b_fuse = &bf[l];
-        }
-    }
+    build_mlp3_layers(w, b, 3, fa, layers, wf, bf);
     const bool need_dx = x.get_requires_grad();
     std::shared_ptr<Buffer> dx = need_dx ? Buffer::alloc(x.len()) : nullptr;
     // x = the plane means of a bias-only Conv2dReLU + global average pool (GradSlot::gapfin_*): that conv's bias gradient and update
@@ -465,23 +434,12 @@ Tensor mlp3_cross_entropy(const Tensor &x, const Tensor (&w)[3], const Tensor (&
         gap.hw = x.grad_->gapfin_hw;
         if (fa && fa->fuse_for_slot(gap_slot, &gf)) gap.b_fuse = &gf;
     }
+    const StepLogSink &sink = log ? *log : kNoLog;
     TH(th_mlp3_xent(ctx, x.dptr(), targets.dptr(), (int)x.shape()[0], (int)x.shape()[1], layers, dx ? dx->d : nullptr, loss.dptr(), nc,
-                    log ? log->d_metrics : nullptr, log ? log->capacity : 0, log ? log->d_state : nullptr, log ? log->advance : 0,
-                    fa ? fa->d_tick() : nullptr, gap_slot ? &gap : nullptr));
-    loss.set_requires_grad(true);
-    std::vector<Tensor> params{w[0], b[0], w[1], b[1], w[2], b[2]};
-    Tensor out = loss, xin = x;
-    Tape::push(loss, true, [params, out, xin, dx, gap_slot]() {
-        if (!out.has_grad()) return;
-        // the gradients were produced by the forward launches for an upstream grad of exactly 1
-        TAPER_ASSERT(out.grad_->shared_const, "mlp3_cross_entropy: only loss.backward() from the root is supported");
-        if (dx) {
-            TAPER_ASSERT(!xin.has_grad() && !xin.grad_->buf_is_arena, "mlp3_cross_entropy: input already has a gradient");
-            xin.grad_->buf = dx;
-            xin.grad_->has = true;
-            xin.grad_->shared_const = false;
-        }
-        for (const Tensor &p : params) p.grad_->has = true;
+                    sink.d_metrics, sink.capacity, sink.d_state, sink.advance, fa ? fa->d_tick() : nullptr, gap_slot ? &gap : nullptr));
+    Tensor xin = x;
+    push_root_only(loss, "mlp3_cross_entropy", {w[0], b[0], w[1], b[1], w[2], b[2]}, [xin, dx, gap_slot]() {
+        if (dx) adopt_grad(xin, dx, "mlp3_cross_entropy");
         if (gap_slot) {
             gap_slot->has = true;
             xin.grad_->gapfin_done = true;
@@ -494,14 +452,7 @@ bool conv_chain_mlp3_supported(const Tensor &x, const std::vector<ConvStage> &st
     if (stages.empty() || stages.back().post != TH_CHAIN_GLOBAL_AVG || x.shape().size() != 4) return false;
     constexpr size_t kMaxBatch = 384;   // (one image per workgroup: at 1 024 images the classifier's own row launch is the faster form, 393 against 403 us)
     if (x.shape()[0] > kMaxBatch) return false;
-    size_t in_f = stages.back().weight.shape()[0];
-    for (int l = 0; l < 3; ++l) {
-        if (w[l].shape().size() != 2 || w[l].shape()[1] != in_f) return false;
-        if (!w[l].get_requires_grad() || w[l].has_grad()) return false;
-        if (!b[l].defined() || b[l].shape() != Shape{w[l].shape()[0]} || !b[l].get_requires_grad() || b[l].has_grad()) return false;
-        if (((uintptr_t)w[l].dptr() & 15) != 0) return false;
-        in_f = w[l].shape()[0];
-    }
+    if (!classifier3_ok(stages.back().weight.shape()[0], w, b)) return false;
     const Tensor &cb = stages.back().bias;
     if (cb.defined() && cb.get_requires_grad() && cb.has_grad()) return false;   // gradients are written, never accumulated
     return x.conv_chain_mlp3_supported(stages, (int)w[0].shape()[0], (int)w[1].shape()[0], (int)w[2].shape()[0]) != 0;
@@ -521,13 +472,7 @@ Tensor conv_chain_mlp3_cross_entropy(const Tensor &x, const std::vector<ConvStag
     float *nc = n_correct_slot(n_correct_out);
     th_mlp3_layer layers[3];
     th_adam_fuse wf[3], bf[3];
-    for (int l = 0; l < 3; ++l) {
-        layers[l] = th_mlp3_layer{w[l].dptr(), b[l].dptr(), grad_slot(w[l]), grad_slot(b[l]), nullptr, nullptr, (int)w[l].shape()[0]};
-        if (fa) {
-            if (fa->fuse_for(w[l], &wf[l])) layers[l].w_fuse = &wf[l];
-            if (fa->fuse_for(b[l], &bf[l])) layers[l].b_fuse = &bf[l];
-        }
-    }
+    build_mlp3_layers(w, b, 3, fa, layers, wf, bf);
     // the last conv's bias (the only conv parameter the reference's tape reaches, quirk Q2): its gradient is formed by the gradient launch
     // from the plane means' gradient and the positive counts the chain launch leaves
     const Tensor &cbias = stages.back().bias;
@@ -544,19 +489,11 @@ Tensor conv_chain_mlp3_cross_entropy(const Tensor &x, const std::vector<ConvStag
         gap.hw = (int)hw;
         if (fa && fa->fuse_for(cbias, &gf)) gap.b_fuse = &gf;
     }
+    const StepLogSink &sink = log ? *log : kNoLog;
     Tensor means = x.conv_chain_mlp3(stages, cnt ? cnt->d : nullptr, targets.dptr(), layers, dx ? dx->d : nullptr, loss.dptr(), nc,
-                                     log ? log->d_metrics : nullptr, log ? log->capacity : 0, log ? log->d_state : nullptr, log ? log->advance : 0,
-                                     fa ? fa->d_tick() : nullptr, cb_grad ? &gap : nullptr);
-    loss.set_requires_grad(true);
-    std::vector<Tensor> params{w[0], b[0], w[1], b[1], w[2], b[2]};
-    if (cb_grad) params.push_back(cbias);
-    Tensor out = loss, keep = means;
-    Tape::push(loss, true, [params, out, keep]() {
-        if (!out.has_grad()) return;
-        // the gradients were produced by the forward launches for an upstream grad of exactly 1
-        TAPER_ASSERT(out.grad_->shared_const, "conv_chain_mlp3_cross_entropy: only loss.backward() from the root is supported");
-        for (const Tensor &p : params) p.grad_->has = true;
-    });
+                                     sink.d_metrics, sink.capacity, sink.d_state, sink.advance, fa ? fa->d_tick() : nullptr,
+                                     cb_grad ? &gap : nullptr);
+    push_root_only(loss, "conv_chain_mlp3_cross_entropy", {w[0], b[0], w[1], b[1], w[2], b[2], cb_grad ? cbias : Tensor()}, [means]() {});   // (the node holds the plane means)
     return loss;
 }
 

@@ -19,6 +19,7 @@
 // fp32 sums are reordered with respect to the reference's k-ordered chains (k quads permuted inside a 32-chunk, K slices, row blocks):
 // within the 1e-4 relative bar, like every GEMM here; index work (argmax, hits) is exact.
 #include "tail_dev.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -946,7 +947,7 @@ __global__ __launch_bounds__(256) void mlp2_finish_kernel(Mlp2FinishArgs a) {
         const float l = q0 / (float)a.batch;          // loss.rs:164
         a.loss[0] = l;
         if (a.ncorrect) a.ncorrect[0] = q1;
-        if (a.metrics) {                              // th_log_step
+        if (a.metrics) {   // the step log of step_log_dev.h, written out: its slot function moves this kernel's SGPR count
             const int64_t s0 = a.state[0], s1 = a.state[1];
             const int64_t slot = s0 < a.capacity ? s0 : s0 % a.capacity;
             a.metrics[2 * slot] = l;
@@ -1123,7 +1124,7 @@ int th_mlp2_xent_deep_supported(int batch, int in_features, int h1, int h2, int 
 #define M2_COMMON_CHECKS(NAME)                                                                                                                                  \
     TH_REQUIRE(!src->d_indices || (src->n_indices >= batch && src->n_indices < (1LL << 30)), NAME ": the index vector must hold at least one batch (and fewer than 2^30 entries)"); \
     TH_REQUIRE(src->d_indices || src->n_rows >= batch, NAME ": a dense row block must hold the batch");                                                        \
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), NAME ": metrics need d_state and a capacity")
+    TH_REQUIRE_STEP_LOG(NAME)
 
 int th_mlp2_xent(th_ctx *ctx, const th_row_source *src, int batch, int in_features, int hidden, int classes, const float *d_w1,
                  const float *d_b1, const float *d_w2, const float *d_b2, float *d_dw1, float *d_db1, float *d_dw2, float *d_db2,

@@ -16,6 +16,7 @@
 // MFMA operand order: k-step s of a 16-deep block uses, for lane group g, element k = 4 g + s (one float4 per lane and block, as in
 // sgemm_small16): every k once, sums within fp32 rounding of the k-ordered reference chain (tolerance 1e-4, like every GEMM here).
 #include "tail_dev.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -338,7 +339,7 @@ int th_mlp3_xent(th_ctx *ctx, const float *d_x, const float *d_targets, int batc
         TH_REQUIRE(!(layers[l].b_fuse && layers[l].b_fuse->d_p) || layers[l].d_db, "th_mlp3_xent: a fused bias update needs d_db");
     }
     TH_REQUIRE(((uintptr_t)d_x & 15) == 0, "th_mlp3_xent: d_x must be 16-byte aligned");
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_mlp3_xent: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_mlp3_xent");
     TH_REQUIRE(!(gap && gap->d_cnt) || (d_dx && gap->d_gb && gap->hw > 0), "th_mlp3_xent: the gap bias finish needs d_dx, d_gb and hw > 0");
     // workspace: A1, A2, dZ1, dZ2, dZ3, the blocks' partial sums
     const int n_blk = batch / 16;

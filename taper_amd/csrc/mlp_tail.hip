@@ -30,6 +30,7 @@
 // (th_adam_slice) to the next launch that does not read them (th_linear_fwd_ex of the next step).
 #include "tail_dev.h"
 #include "dp_dev.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -96,13 +97,7 @@ __global__ void tail_prof_mark_kernel(int i) { g_tail_prof[0][i] = g_tail_prof[1
 #define TAIL_STAMP_OP(i) do { } while (0)
 #endif
 
-// th_log_step's slot for step number state0: state0 mod capacity (capacity > 0), 32-bit when both fit -- the 64-bit remainder is a
-// 140-instruction routine.  Uniform; the lead head workgroup forms it in its prologue, under the operand loads.
-__device__ __forceinline__ int64_t tail_log_slot(int64_t state0, int64_t capacity) {
-    if (state0 < capacity) return state0;
-    if ((((uint64_t)state0 | (uint64_t)capacity) >> 32) == 0) return (int64_t)((uint32_t)state0 % (uint32_t)capacity);
-    return state0 % capacity;
-}
+// (the step-log slot, step_log_slot() of step_log_dev.h: the lead head workgroup forms it in its prologue, under the operand loads)
 
 template <int KS, int TN>
 __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(256) void mlp_tail_kernel(TailArgs a) {
             if (fuse_b1) b_step = adam_step_size(b_lr, a.b1_adam.beta1, a.b1_adam.beta2, b_t);
             // ... and the lead's step-log slot and next state words: nothing of them depends on this launch's results
             if (lead && a.metrics) {
-                log_slot = tail_log_slot(state0, a.capacity);
+                log_slot = step_log_slot(state0, a.capacity);
                 state0_next = state0 + 1;
                 state1_next = state1 + a.advance;
             }
@@ -541,7 +536,7 @@ __device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_ro
     int64_t log_slot = 0, state0_next = 0, state1_next = 0;
     if (log) {
         const int64_t state0 = sload(a.state), state1 = sload(a.state + 1);
-        log_slot = tail_log_slot(state0, a.capacity);
+        log_slot = step_log_slot(state0, a.capacity);
         state0_next = state0 + 1;
         state1_next = state1 + a.advance;
     }
@@ -702,7 +697,7 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
     // n / B and the stores are left.
     int64_t log_slot = 0, state0_next = 0, state1_next = 0;
     if (log_here) {
-        log_slot = tail_log_slot(state0, a.capacity);
+        log_slot = step_log_slot(state0, a.capacity);
         state0_next = state0 + 1;
         state1_next = state1 + a.advance;
     }
@@ -1341,7 +1336,7 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
                "th_mlp_tail: d_dx needs d_w1 and whole tiles (hidden 32 / 64 / 128 / 256, batch and in_features multiples of 16)");
     TH_REQUIRE(!d_dx || !(w1_fuse && w1_fuse->d_p), "th_mlp_tail: with d_dx the launch reads W1, its update must be deferred (th_adam_slice)");
     TH_REQUIRE((((uintptr_t)d_h | (uintptr_t)d_w2) & 15) == 0, "th_mlp_tail: d_h and d_w2 must be 16-byte aligned");
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_mlp_tail: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_mlp_tail");
     TH_REQUIRE(!(b1_fuse && b1_fuse->d_p) || d_db1, "th_mlp_tail: fused b1 update needs d_db1");
     constexpr int TN = 2;   // input tiles per dW1 workgroup
     TailArgs a{};

@@ -125,6 +125,7 @@ __global__ __launch_bounds__(256) void u8_to_unit_kernel(const uint8_t *__restri
 __global__ void log_step_kernel(const float *__restrict__ loss, const float *__restrict__ ncorrect, float *__restrict__ metrics,
                                 int64_t capacity, int64_t *__restrict__ state, int64_t advance) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
+        // the step log of step_log_dev.h, written out: its slot function moves this kernel's SGPR count
         const int64_t s = state[0] % capacity;
         metrics[2 * s] = loss ? loss[0] : 0.f;
         metrics[2 * s + 1] = ncorrect ? ncorrect[0] : 0.f;

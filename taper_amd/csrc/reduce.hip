@@ -3,6 +3,7 @@
 // 271-290).  All HBM-bound; reductions use wave64 shuffles + a fixed-order LDS
 // combine (no atomics -> deterministic).
 #include "common.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -424,22 +425,10 @@ __device__ __forceinline__ void xent_row(const XentArgs &a, int row, int sub, fl
     if (sub == 0 && a.argmax_out) a.argmax_out[row] = (float)bi;
 }
 
-struct StepLog {  // th_log_step folded into the loss kernel (nullable metrics)
-    float *metrics;
-    int64_t capacity;
-    int64_t *state;
-    int64_t advance;
-    int32_t *adam_tick;  // nullable: Adam's t += 1 (optim.rs:84) for a step whose updates run fused
-};
-
 __device__ __forceinline__ void step_log(const StepLog &lg, float loss, float ncorrect) {
     if (lg.adam_tick) lg.adam_tick[0] += 1;
     if (!lg.metrics) return;
-    const int64_t s = lg.state[0] % lg.capacity;
-    lg.metrics[2 * s] = loss;
-    lg.metrics[2 * s + 1] = ncorrect;
-    lg.state[0] += 1;
-    lg.state[1] += lg.advance;
+    step_log_write(lg.metrics, step_log_slot(lg.state[0], lg.capacity), loss, ncorrect, lg.state, lg.state[0] + 1, lg.state[1] + lg.advance);
 }
 
 // whole batch in ONE workgroup (batch <= 1024): rows -> block reduce -> loss, count, log
@@ -832,7 +821,7 @@ int th_softmax_xent_fwd(th_ctx *ctx, const float *d_logits, const float *d_targe
                         float *d_loss, float *d_argmax, float *d_ncorrect, float *d_dlogits_unit, float *d_metrics,
                         int64_t metrics_capacity, int64_t *d_state, int64_t advance, int32_t *d_adam_tick) {
     TH_REQUIRE(ctx && d_logits && d_targets && d_loss && batch > 0 && classes > 0, "th_softmax_xent_fwd: bad argument");
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_softmax_xent_fwd: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_softmax_xent_fwd");
     XentArgs a{d_logits, d_targets, batch, classes, d_logp, d_argmax, d_dlogits_unit};
     StepLog lg{d_metrics, metrics_capacity, d_state, advance, d_adam_tick};
     const bool narrow = classes <= 16;

@@ -12,6 +12,7 @@
 #include "tail_dev.h"
 #include "dp_dev.h"
 #include "adam_dev.h"
+#include "step_log_dev.h"
 
 TH_USES_DEVICE_ERRORS()
 
@@ -254,13 +255,7 @@ __global__ __launch_bounds__(64 * WH_NW) void wide_head_kernel(WideArgs a) {
                 const float l = n / (float)B;   // loss.rs:164
                 a.loss[0] = l;
                 if (a.ncorrect) a.ncorrect[0] = hsum;
-                if (a.metrics) {
-                    const int64_t slot = state0 < a.capacity ? state0 : state0 % a.capacity;
-                    a.metrics[2 * slot] = l;
-                    a.metrics[2 * slot + 1] = hsum;
-                    a.state[0] = state0 + 1;
-                    a.state[1] = state1 + a.advance;
-                }
+                if (a.metrics) step_log_write(a.metrics, step_log_slot(state0, a.capacity), l, hsum, a.state, state0 + 1, state1 + a.advance);
             }
         }
         __syncthreads();
@@ -332,13 +327,7 @@ __global__ __launch_bounds__(64 * WH_NW) void wide_head_kernel(WideArgs a) {
         a.loss[0] = l;
         if (a.ncorrect) a.ncorrect[0] = hsum;
         if (a.adam_tick) a.adam_tick[0] = tick_old + 1;   // optim.rs:84 (nobody else touches the counter in this launch)
-        if (a.metrics) {
-            const int64_t slot = state0 < a.capacity ? state0 : state0 % a.capacity;
-            a.metrics[2 * slot] = l;
-            a.metrics[2 * slot + 1] = hsum;
-            a.state[0] = state0 + 1;
-            a.state[1] = state1 + a.advance;
-        }
+        if (a.metrics) step_log_write(a.metrics, step_log_slot(state0, a.capacity), l, hsum, a.state, state0 + 1, state1 + a.advance);
     }
 }
 
@@ -522,13 +511,7 @@ __global__ __launch_bounds__(64 * WH_NW) void wide_grads_kernel(WideGradArgs a) 
             const float l = st2[0] / (float)B;   // loss.rs:164
             a.loss[0] = l;
             if (a.ncorrect) a.ncorrect[0] = st2[1];
-            if (a.metrics) {
-                const int64_t slot = state0 < a.capacity ? state0 : state0 % a.capacity;
-                a.metrics[2 * slot] = l;
-                a.metrics[2 * slot + 1] = st2[1];
-                a.state[0] = state0 + 1;
-                a.state[1] = state1 + a.advance;
-            }
+            if (a.metrics) step_log_write(a.metrics, step_log_slot(state0, a.capacity), l, st2[1], a.state, state0 + 1, state1 + a.advance);
         }
         return;
     }
@@ -556,7 +539,7 @@ static int wide_launch(th_ctx *ctx, const float *d_x, const float *d_w, const fl
     TH_REQUIRE(ctx && d_x && d_w && d_targets && d_loss && d_dw, "th_linear_xent_wide: null argument");
     TH_REQUIRE(batch > 0 && batch <= 4096 && in_features > 0 && classes > 0 && classes <= 16,
                "th_linear_xent_wide: needs batch <= 4096, classes <= 16 (got %d, %d)", batch, classes);
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_linear_xent_wide: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_linear_xent_wide");
     float *partial = nullptr;
     int kz = 0;
     if (int rc = linear_fwd_partials(ctx, d_x, d_w, batch, classes, in_features, &partial, &kz)) return rc;
@@ -610,7 +593,7 @@ static int wide_grads_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const
                              const th_adam_fuse *w_fuse, const th_adam_fuse *b_fuse, const th_adam_fuse *cb_fuse, int32_t *d_tick) {
     TH_REQUIRE(ctx && d_x && d_dl && d_rowstat && d_dw && d_loss, "th_wide_head_grads: null argument");
     TH_REQUIRE(batch > 0 && in_features > 0 && classes > 0 && classes <= 16, "th_wide_head_grads: needs classes <= 16 (got %d)", classes);
-    TH_REQUIRE(!d_metrics || (d_state && metrics_capacity > 0), "th_wide_head_grads: metrics need d_state and a capacity");
+    TH_REQUIRE_STEP_LOG("th_wide_head_grads");
     TH_REQUIRE((d_cbpart != nullptr) == (d_conv_gb != nullptr) && (!d_cbpart || conv_c > 0),
                "th_wide_head_grads: the conv bias needs d_cbpart, d_conv_gb and conv_c together");
     TH_REQUIRE(!(b_fuse && b_fuse->d_p) || d_db, "th_wide_head_grads: a fused bias update needs d_db");
