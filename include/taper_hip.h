@@ -840,6 +840,18 @@ int th_conv3x3_bwd_input(th_ctx *ctx, const float *d_gy, const float *d_w, float
                          int n, int c_in, int h, int w, int c_out, int pad, int weight_layout, int accumulate);
 int th_conv3x3_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, float *d_gw,
                           int n, int c_in, int h, int w, int c_out, int pad, int weight_layout, int accumulate);
+/* The exact 3x3 convolution with stride (2, 2), padding (1, 1), dilation 1, one group, and both of its gradients, direct on the fp32
+ * matrix cores (csrc/conv_s2.hip; not in the reference, whose strided path is th_conv2d_general_fwd's Q9 gather and has no gradient).
+ * h and w are the INPUT's in all three; h_out = (h - 1) / 2 + 1, w_out likewise; output pixel (oh, ow) has its window's top-left corner
+ * at (2 oh - 1, 2 ow - 1).  Any n, c_in, c_out, h, w >= 1.  weight_layout as in th_conv3x3_fwd (0: the buffer read as [9 c_in][c_out],
+ * Q3; 1: [co][ci][kh][kw]).  accumulate as in the stride-1 calls: 0 overwrites every element of the output with no zero fill in front.
+ * No atomics: the same bits from run to run. */
+int th_conv3x3_s2_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_bias /*nullable*/, float *d_y,
+                      int n, int c_in, int h, int w, int c_out, int weight_layout, int relu);
+int th_conv3x3_s2_bwd_input(th_ctx *ctx, const float *d_gy, const float *d_w, float *d_gx,
+                            int n, int c_in, int h, int w, int c_out, int weight_layout, int accumulate);
+int th_conv3x3_s2_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, float *d_gw,
+                             int n, int c_in, int h, int w, int c_out, int weight_layout, int accumulate);
 
 /* max-pool: tensor.rs:1391-1521.  s_h == 0 -> stride = kernel (1403).
  * d_argmax: int64 absolute flat input index per output (1449-1461). */

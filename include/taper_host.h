@@ -88,6 +88,16 @@ int tp_unsqueeze(const tp_tensor *x, int dim, tp_tensor **out);
 int tp_linear(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b /* nullable */, int relu, tp_tensor **out);
 int tp_conv2d(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b /* nullable */, int stride_h, int stride_w,
               int pad_h, int pad_w, int dil_h, int dil_w, int relu, tp_tensor **out);
+/* tp_conv2d with a trailing flags word (0: exactly tp_conv2d).  Bit 0, TP_CONV_EXACT_STRIDE (not in the reference): the call must be 3x3,
+ * stride (2, 2), padding (1, 1), dilation (1, 1); it runs the exact strided convolution (th_conv3x3_s2_fwd) instead of the reference's
+ * general gather (Q9), and under tp_set_full_backward(1) its weight and input take gradients by the stride-1 rules.  Any other geometry
+ * with the bit, and any unknown bit, is refused by name.  The same word is the last argument of tp_conv2d_new_ex (one group),
+ * tp_basic_block_new_ex and tp_residual_block_new_ex; the blocks hand the bit to every conv of theirs whose stride is 2, change nothing
+ * at stride 1 and refuse any other stride with it.  The flag is constructor state, not checkpoint content; tp_module_quantize* refuse a
+ * model that holds such a conv. */
+#define TP_CONV_EXACT_STRIDE 1
+int tp_conv2d_ex(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b /* nullable */, int stride_h, int stride_w,
+                 int pad_h, int pad_w, int dil_h, int dil_w, int relu, int flags, tp_tensor **out);
 int tp_max_pool2d(const tp_tensor *x, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, tp_tensor **out);
 int tp_avg_pool2d(const tp_tensor *x, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, tp_tensor **out);
 
@@ -107,6 +117,8 @@ int tp_relu_new(tp_module **out);
 int tp_sigmoid_new(tp_module **out);
 int tp_conv2d_new(int in_ch, int out_ch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, int with_bias,
                   int fuse_relu, uint64_t seed, tp_module **out);
+int tp_conv2d_new_ex(int in_ch, int out_ch, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, int with_bias,
+                     int fuse_relu, uint64_t seed, int flags, tp_module **out);   /* flags: see tp_conv2d_ex */
 /* nn.rs:180-354 with groups > 1: weight [out, in/groups, k, k]; forward = slice_channels / slice_output_channels /
  * slice_1d, one conv2d per group, cat(dim 1) (nn.rs:289-332, 859-1014).  Like the reference's, the slices carry no tape
  * nodes: a grouped convolution is forward-only (nothing behind it, nor its own parameters, receives a gradient). */
@@ -139,6 +151,7 @@ int tp_batchnorm2d_running_stats(const tp_module *m, float *h_mean, float *h_var
 int tp_batchnorm2d_set_running_stats(tp_module *m, const float *h_mean, const float *h_var);
 /* Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) with the ReLU fused; parameters(): the conv's, then gamma, beta */
 int tp_basic_block_new(int in_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
+int tp_basic_block_new_ex(int in_channels, int out_channels, int stride, uint64_t seed, int flags, tp_module **out);   /* flags: see tp_conv2d_ex */
 /* y = bn(x) + residual, then the layer's ReLU (fuse_relu: after the add), inside the normalisation's own launches: one tape
  * node whose backward also leaves the residual's gradient.  Statistics and the running update are tp_module_forward's.  Fails with
  * "BatchNorm2d::forward_add: ..." for a residual of another shape and for one that shares x's storage. */
@@ -149,6 +162,10 @@ int tp_batchnorm2d_forward_add(const tp_module *m, const tp_tensor *x, const tp_
  * parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w, gamma beta]; buffers: the running pairs in that order.
  * Non-positive arguments fail before the device is touched.  No quantized twin: tp_module_quantize* refuse the block. */
 int tp_residual_block_new(int in_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
+/* flags: see tp_conv2d_ex.  With TP_CONV_EXACT_STRIDE and stride 2, conv1 and the projection are true convolutions that train under
+ * tp_set_full_backward(1): the downsampling block to train with (the default block's strided convs keep the reference's gather and take
+ * no gradient). */
+int tp_residual_block_new_ex(int in_channels, int out_channels, int stride, uint64_t seed, int flags, tp_module **out);
 /* saved-but-not-trained state (the running statistics), concatenated over a Sequential's / BasicBlock's / ResidualBlock's children; shares storage */
 int tp_module_num_buffers(const tp_module *m, int *out);
 int tp_module_buffer(const tp_module *m, int i, tp_tensor **out);

@@ -13,6 +13,7 @@ import numpy as np
 from ._lib import TaperError, host, tp_check
 
 _p = C.c_void_p
+EXACT_STRIDE = 1   # TP_CONV_EXACT_STRIDE: bit 0 of the flags word of tp_conv2d_ex and the *_new_ex constructors
 
 
 def _shape_arr(shape):
@@ -226,12 +227,19 @@ class Tensor:
     def linear(self, weight, bias=None, relu=False):
         return self._un(host.tp_linear, "linear", weight._h, bias._h if bias is not None else None, 1 if relu else 0)
 
-    def conv2d(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), relu=False):
-        return self._un(host.tp_conv2d, "conv2d", weight._h, bias._h if bias is not None else None, stride[0], stride[1],
-                        padding[0], padding[1], dilation[0], dilation[1], 1 if relu else 0)
+    def conv2d(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), relu=False, exact_stride=False):
+        """exact_stride: the exact 3x3 / stride (2, 2) / padding (1, 1) convolution, which takes weight and input gradients under
+        set_full_backward(True); any other geometry with the flag is refused by name.  Without it a strided call keeps the reference's
+        general gather, which is no convolution and has no gradient."""
+        b = bias._h if bias is not None else None
+        if exact_stride:
+            return self._un(host.tp_conv2d_ex, "conv2d", weight._h, b, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+                            1 if relu else 0, EXACT_STRIDE)
+        return self._un(host.tp_conv2d, "conv2d", weight._h, b, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+                        1 if relu else 0)
 
-    def conv2d_relu(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
-        return self.conv2d(weight, bias, stride, padding, dilation, relu=True)
+    def conv2d_relu(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), exact_stride=False):
+        return self.conv2d(weight, bias, stride, padding, dilation, relu=True, exact_stride=exact_stride)
 
     def max_pool2d(self, kernel_size, stride=None, padding=(0, 0)):
         s = stride or (0, 0)
@@ -508,19 +516,30 @@ class Sigmoid(Module):
 
 
 class Conv2d(Module):
+    """exact_stride: the layer is the exact 3x3 convolution with stride (2, 2) and padding (1, 1) (one group), and under
+    set_full_backward(True) its weight and its input take gradients like a stride-1 layer's; the constructor refuses any other geometry
+    with the flag by name.  Without it a strided Conv2d keeps the reference's general gather: not a convolution, no gradient.
+    The flag is constructor state (a checkpoint holds the parameters alone); quantize* refuse such a layer."""
+
     def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True,
-                 seed=1, _relu=False):
+                 seed=1, _relu=False, exact_stride=False):
         if dilation not in (None, (1, 1)):
             raise TaperError("Conv2d: dilation is out of scope (SURVEY.md section 2 row 8)")
         s, p = stride or (1, 1), padding or (0, 0)
+        if exact_stride:
+            if int(groups or 1) != 1:
+                raise TaperError(f"Conv2d exact_stride: groups must be 1 (got {int(groups)})")
+            super().__init__(_mk(host.tp_conv2d_new_ex, "Conv2d::new", int(in_ch), int(out_ch), kernel_size[0], kernel_size[1],
+                                 s[0], s[1], p[0], p[1], 1 if bias else 0, 1 if _relu else 0, int(seed), EXACT_STRIDE))
+            return
         # groups > 1 (nn.rs:289-332): slice / conv per group / cat, forward only like the reference
         super().__init__(_mk(host.tp_conv2d_grouped_new, "Conv2d::new", int(in_ch), int(out_ch), kernel_size[0], kernel_size[1],
                              s[0], s[1], p[0], p[1], int(groups or 1), 1 if bias else 0, 1 if _relu else 0, int(seed)))
 
 
 class Conv2dReLU(Conv2d):
-    def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True, seed=1):
-        super().__init__(in_ch, out_ch, kernel_size, stride, padding, dilation, groups, bias, seed, _relu=True)
+    def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True, seed=1, exact_stride=False):
+        super().__init__(in_ch, out_ch, kernel_size, stride, padding, dilation, groups, bias, seed, _relu=True, exact_stride=exact_stride)
 
 
 class MaxPool2d(Module):
@@ -613,20 +632,44 @@ class BatchNorm2d(Module):
 
 
 class BasicBlock(Module):
-    """nn.rs:829-857 as announced: Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) -> ReLU; parameters(): the conv's, then gamma, beta"""
+    """nn.rs:829-857 as announced: Conv2d::conv3x3(in, out, stride, 1) -> BatchNorm2d(out) -> ReLU; parameters(): the conv's, then gamma, beta.
+    BasicBlock.exact_stride(...) builds the block whose conv, at stride 2, is Conv2d(exact_stride=True); nothing changes at stride 1; any
+    other stride is refused by name."""
 
     def __init__(self, in_channels, out_channels, stride=1, seed=1):
         super().__init__(_mk(host.tp_basic_block_new, "BasicBlock::new", int(in_channels), int(out_channels), int(stride), int(seed)))
+
+    @classmethod
+    def exact_stride(cls, in_channels, out_channels, stride=1, seed=1):
+        """the block with the exact strided convolution (tp_basic_block_new_ex, TP_CONV_EXACT_STRIDE); the constructor's arguments"""
+        blk = cls.__new__(cls)
+        Module.__init__(blk, _mk(host.tp_basic_block_new_ex, "BasicBlock::new", int(in_channels), int(out_channels), int(stride), int(seed),
+                                 EXACT_STRIDE))
+        return blk
 
 
 class ResidualBlock(Module):
     """conv3x3(in, out, stride) -> BatchNorm2d + ReLU -> conv3x3(out, out) -> BatchNorm2d + shortcut -> ReLU, the add and the last ReLU inside
     the second normalisation's kernels.  Shortcut: the input when in == out and stride == 1, else conv3x3(in, out, stride) -> BatchNorm2d
     (a 3x3 projection, not a 1x1).  No conv has a bias.  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w,
-    gamma beta]; buffers(): the running pairs in that order."""
+    gamma beta]; buffers(): the running pairs in that order.
+
+    A downsampling block (stride 2) by default keeps the reference's strided path in conv1 and in the projection: the general gather of
+    SURVEY Q9, which is no convolution and records no weight or input gradient, so those two convs stay at their initial values.
+    ResidualBlock.exact_stride(in, out, 2) is the block to train with: both strided convs are Conv2d(exact_stride=True) -- true 3x3 /
+    stride 2 / pad 1 convolutions on the matrix cores whose weights and inputs take gradients under set_full_backward(True).  With
+    stride 1 it builds the same block as the constructor; any other stride is refused by name."""
 
     def __init__(self, in_channels, out_channels, stride=1, seed=1):
         super().__init__(_mk(host.tp_residual_block_new, "ResidualBlock::new", int(in_channels), int(out_channels), int(stride), int(seed)))
+
+    @classmethod
+    def exact_stride(cls, in_channels, out_channels, stride=1, seed=1):
+        """the block with the exact strided convolutions (tp_residual_block_new_ex, TP_CONV_EXACT_STRIDE); the constructor's arguments"""
+        blk = cls.__new__(cls)
+        Module.__init__(blk, _mk(host.tp_residual_block_new_ex, "ResidualBlock::new", int(in_channels), int(out_channels), int(stride),
+                                 int(seed), EXACT_STRIDE))
+        return blk
 
 
 class Sequential(Module):

@@ -136,8 +136,16 @@ Tensor BatchNorm2d::forward_add(const Tensor &x, const Tensor &residual) const {
     return out;
 }
 
-BasicBlock::BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed)
-    : conv(in_ch, out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, true, seed), bn(out_ch, 1e-5f, 0.1f, true) {}
+// the flag a block hands to its convs of this stride: the exact strided convolution exists for stride 2 alone
+static bool exact_for(const char *block, size_t stride, bool exact_stride) {
+    TAPER_ASSERT(!exact_stride || stride == 1 || stride == 2,
+                 std::string(block) + " exact_stride: the stride must be 1 or 2 (got " + std::to_string(stride) + ")");
+    return exact_stride && stride == 2;
+}
+
+BasicBlock::BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride)
+    : conv(in_ch, out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, true, seed, 1, exact_for("BasicBlock", stride, exact_stride)),
+      bn(out_ch, 1e-5f, 0.1f, true) {}
 
 static size_t checked_block(size_t in_ch, size_t out_ch, size_t stride) {
     TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0 && in_ch <= 0x7fffffffu && out_ch <= 0x7fffffffu && stride <= 0x7fffffffu,
@@ -145,14 +153,15 @@ static size_t checked_block(size_t in_ch, size_t out_ch, size_t stride) {
     return in_ch;
 }
 
-ResidualBlock::ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed)
-    : conv1(checked_block(in_ch, out_ch, stride), out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, false, seed),
+ResidualBlock::ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride)
+    : conv1(checked_block(in_ch, out_ch, stride), out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, false, seed, 1,
+            exact_for("ResidualBlock", stride, exact_stride)),
       bn1(out_ch, 1e-5f, 0.1f, true),
       conv2(out_ch, out_ch, {3, 3}, {1, 1}, {1, 1}, false, seed + 1),
       bn2(out_ch, 1e-5f, 0.1f, true) {
     if (in_ch != out_ch || stride != 1) {
         shortcut_conv = std::make_unique<Conv2d>(in_ch, out_ch, std::make_pair(3, 3), std::make_pair((int)stride, (int)stride), std::make_pair(1, 1),
-                                                 false, seed + 2);
+                                                 false, seed + 2, 1, exact_for("ResidualBlock", stride, exact_stride));
         shortcut_bn = std::make_unique<BatchNorm2d>(out_ch, 1e-5f, 0.1f, false);
     }
 }

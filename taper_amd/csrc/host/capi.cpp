@@ -148,6 +148,20 @@ int tp_conv2d(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b, int sh
               tp_tensor **out) {
     TP_BEGIN *out = wrap(x->t.conv2d(w->t, opt_t(b), {sh, sw}, {ph, pw}, {dh, dw}, relu != 0)); TP_END
 }
+// the `flags` word of the *_ex constructors and of tp_conv2d_ex: bit 0 = the exact strided convolution; any other bit is refused by name
+static bool exact_stride_flag(const char *fn, int flags) {
+    TAPER_ASSERT((flags & ~TP_CONV_EXACT_STRIDE) == 0, std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~TP_CONV_EXACT_STRIDE) +
+                                                          " (bit 0, the exact stride, is the only flag)");
+    return (flags & TP_CONV_EXACT_STRIDE) != 0;
+}
+int tp_conv2d_ex(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b, int sh, int sw, int ph, int pw, int dh, int dw, int relu, int flags,
+                 tp_tensor **out) {
+    TP_BEGIN
+    TAPER_ASSERT(x && w && out, "tp_conv2d_ex: null argument");
+    const bool exact = exact_stride_flag("tp_conv2d_ex", flags);
+    *out = wrap(x->t.conv2d(w->t, opt_t(b), {sh, sw}, {ph, pw}, {dh, dw}, relu != 0, exact));
+    TP_END
+}
 int tp_max_pool2d(const tp_tensor *x, int kh, int kw, int sh, int sw, int ph, int pw, tp_tensor **out) {
     TP_BEGIN *out = wrap(x->t.max_pool2d({kh, kw}, {sh, sw}, {ph, pw})); TP_END
 }
@@ -221,6 +235,14 @@ int tp_basic_block_new(int in_ch, int out_ch, int stride, uint64_t seed, tp_modu
     *out = new tp_module{std::make_shared<BasicBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed)};
     TP_END
 }
+int tp_basic_block_new_ex(int in_ch, int out_ch, int stride, uint64_t seed, int flags, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_basic_block_new_ex: null argument");
+    TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "BasicBlock: in_channels, out_channels and stride must be positive");
+    const bool exact = exact_stride_flag("tp_basic_block_new_ex", flags);
+    *out = new tp_module{std::make_shared<BasicBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed, exact)};
+    TP_END
+}
 int tp_batchnorm2d_forward_add(const tp_module *m, const tp_tensor *x, const tp_tensor *residual, tp_tensor **out) {
     TP_BEGIN
     TAPER_ASSERT(x && residual && out, "tp_batchnorm2d_forward_add: null argument");
@@ -232,6 +254,14 @@ int tp_residual_block_new(int in_ch, int out_ch, int stride, uint64_t seed, tp_m
     TAPER_ASSERT(out, "tp_residual_block_new: null argument");
     TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "ResidualBlock: in_channels, out_channels and stride must be positive");
     *out = new tp_module{std::make_shared<ResidualBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed)};
+    TP_END
+}
+int tp_residual_block_new_ex(int in_ch, int out_ch, int stride, uint64_t seed, int flags, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_residual_block_new_ex: null argument");
+    TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "ResidualBlock: in_channels, out_channels and stride must be positive");
+    const bool exact = exact_stride_flag("tp_residual_block_new_ex", flags);
+    *out = new tp_module{std::make_shared<ResidualBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed, exact)};
     TP_END
 }
 int tp_module_num_buffers(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->buffers().size(); TP_END }
@@ -253,6 +283,17 @@ int tp_conv2d_new(int ic, int oc, int kh, int kw, int sh, int sw, int ph, int pw
     TP_BEGIN
     auto c = std::make_shared<Conv2d>((size_t)ic, (size_t)oc, std::make_pair(kh, kw), std::make_pair(sh, sw), std::make_pair(ph, pw),
                                       bias != 0, seed);
+    c->fuse_relu = relu != 0;
+    *out = new tp_module{c};
+    TP_END
+}
+int tp_conv2d_new_ex(int ic, int oc, int kh, int kw, int sh, int sw, int ph, int pw, int bias, int relu, uint64_t seed, int flags,
+                     tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_conv2d_new_ex: null argument");
+    const bool exact = exact_stride_flag("tp_conv2d_new_ex", flags);
+    auto c = std::make_shared<Conv2d>((size_t)ic, (size_t)oc, std::make_pair(kh, kw), std::make_pair(sh, sw), std::make_pair(ph, pw),
+                                      bias != 0, seed, 1, exact);
     c->fuse_relu = relu != 0;
     *out = new tp_module{c};
     TP_END

@@ -160,10 +160,13 @@ class Tensor {
     Tensor slice_1d(size_t start, size_t end) const;               // nn.rs:917-925
     static Tensor cat(const std::vector<Tensor> &tensors, size_t dim);  // nn.rs:928-1014 (2-D dim 0/1, 4-D dim 1)
     // conv / pool (tensor.rs:1221-1660).  bias may be undefined (None).
+    // exact_stride (not in the reference): the call must be 3x3, stride (2, 2), padding (1, 1), dilation (1, 1) and runs the exact strided
+    // convolution (th_conv3x3_s2_fwd) instead of the reference's general gather (Q9); under full_backward its weight and input take
+    // gradients by the stride-1 rules (th_conv3x3_s2_bwd_weight / _bwd_input).  Any other geometry with the flag is refused by name.
     Tensor conv2d(const Tensor &weight, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                  std::pair<int, int> dilation, bool relu = false) const;
+                  std::pair<int, int> dilation, bool relu = false, bool exact_stride = false) const;
     Tensor conv2d_relu(const Tensor &weight, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                       std::pair<int, int> dilation) const;
+                       std::pair<int, int> dilation, bool exact_stride = false) const;
     // Conv2dReLU (3x3, stride 1) + MaxPool2d(2, 2) as ONE launch that writes only the pooled tensor (th_conv3x3_pool2_fwd).
     // Trainer-internal: valid in faithful mode (Q2: the conv's only gradient is its bias, taken from the pooled tensors)
     // when nobody else reads the conv output.  conv2d_relu_maxpool2_supported tells whether the pair qualifies.
@@ -341,8 +344,11 @@ class Conv2d : public Module {  // nn.rs:180-354
     std::pair<int, int> stride{1, 1}, padding{0, 0}, dilation{1, 1};
     size_t groups = 1;     // > 1: slice, convolve per group, cat (nn.rs:289-332) -- forward only, like the reference
     bool fuse_relu = false;
+    // the exact strided convolution with both gradients (Tensor::conv2d's flag): 3x3, stride (2, 2), padding (1, 1), one group -- anything
+    // else with the flag throws in the constructor.  Constructor state, not checkpoint content.
+    bool exact_stride = false;
     Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride, std::pair<int, int> padding,
-           bool with_bias, uint64_t seed, size_t groups = 1);
+           bool with_bias, uint64_t seed, size_t groups = 1, bool exact_stride = false);
     Tensor forward(const Tensor &x) const override;
     // nn.rs:280-332 with the given weight / bias (the quantized twin passes its dequantized tensors)
     Tensor forward_with(const Tensor &x, const Tensor &w, const Tensor &b) const;
@@ -353,8 +359,8 @@ class Conv2d : public Module {  // nn.rs:180-354
 class Conv2dReLU : public Conv2d {  // nn.rs:433-490
    public:
     Conv2dReLU(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride,
-               std::pair<int, int> padding, bool with_bias, uint64_t seed)
-        : Conv2d(in_ch, out_ch, kernel, stride, padding, with_bias, seed) {
+               std::pair<int, int> padding, bool with_bias, uint64_t seed, bool exact_stride = false)
+        : Conv2d(in_ch, out_ch, kernel, stride, padding, with_bias, seed, 1, exact_stride) {
         fuse_relu = true;
     }
 };
@@ -448,7 +454,8 @@ class BasicBlock : public Module {
    public:
     Conv2d conv;
     BatchNorm2d bn;
-    BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed);
+    // exact_stride: handed to the conv when stride == 2 (Conv2d::exact_stride); nothing changes at stride 1; any other stride is refused
+    BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride = false);
     Tensor forward(const Tensor &x) const override { return bn.forward(conv.forward(x)); }
     std::vector<Tensor> parameters() const override;   // the conv's, then gamma, beta (nn.rs:852-856)
     std::vector<Tensor> buffers() const override { return bn.buffers(); }
@@ -470,7 +477,9 @@ class ResidualBlock : public Module {
     std::unique_ptr<Conv2d> shortcut_conv;       // null: the identity shortcut
     std::unique_ptr<BatchNorm2d> shortcut_bn;
     // zero arguments throw before the device is touched
-    ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed);
+    // exact_stride: handed to every conv of the block whose stride is 2 (conv1 and the projection: Conv2d::exact_stride) -- the block to
+    // train with; nothing changes at stride 1; any other stride with the flag is refused by name
+    ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride = false);
     Tensor forward(const Tensor &x) const override;
     std::vector<BatchNorm2d *> batchnorms();            // bn1, bn2, [the shortcut's]
     std::vector<Tensor> parameters() const override;   // conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w, gamma beta]
