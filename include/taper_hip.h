@@ -852,6 +852,19 @@ int th_conv3x3_s2_bwd_input(th_ctx *ctx, const float *d_gy, const float *d_w, fl
                             int n, int c_in, int h, int w, int c_out, int weight_layout, int accumulate);
 int th_conv3x3_s2_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, float *d_gw,
                              int n, int c_in, int h, int w, int c_out, int weight_layout, int accumulate);
+/* The exact pointwise convolution: kernel 1x1, stride (s, s) with s in {1, 2}, padding 0, dilation 1, one group, and both of its gradients,
+ * direct on the fp32 matrix cores (csrc/conv_pw.hip; not in the reference, whose 1x1 path is th_conv1x1_fwd's Q4 reinterpretation: no
+ * convolution for c_in > 1, no stride, no gradient).  h and w are the INPUT's in all three; h_out = (h - 1) / s + 1, w_out likewise; output
+ * pixel (oh, ow) reads input pixel (s oh, s ow).  Any n, c_in, c_out, h, w >= 1.  weight_layout 0: the buffer read as [c_in][c_out] (Q3, as
+ * the 3x3 calls read it); 1: [c_out][c_in].  accumulate as in the 3x3 gradient calls: 0 overwrites every element of the output with no zero
+ * fill in front -- at stride 2 the input pixels no output reads get +0.0 from the same launch; 1 leaves those pixels untouched.
+ * No atomics: the same bits from run to run. */
+int th_conv1x1_exact_fwd(th_ctx *ctx, const float *d_x, const float *d_w, const float *d_bias /*nullable*/, float *d_y,
+                         int n, int c_in, int h, int w, int c_out, int stride, int weight_layout, int relu);
+int th_conv1x1_exact_bwd_input(th_ctx *ctx, const float *d_gy, const float *d_w, float *d_gx,
+                               int n, int c_in, int h, int w, int c_out, int stride, int weight_layout, int accumulate);
+int th_conv1x1_exact_bwd_weight(th_ctx *ctx, const float *d_x, const float *d_gy, float *d_gw,
+                                int n, int c_in, int h, int w, int c_out, int stride, int weight_layout, int accumulate);
 
 /* max-pool: tensor.rs:1391-1521.  s_h == 0 -> stride = kernel (1403).
  * d_argmax: int64 absolute flat input index per output (1449-1461). */

@@ -59,6 +59,18 @@ int th_debug_conv3x3_s2_plan(int op, int n, int c_in, int h, int w, int c_out, i
 /* what this thread's most recent th_conv3x3_s2_* call launched: out8 = {op, CT, accumulate, grid x, y, z, LDS bytes, reduce ending}
  * (op -1: none yet) */
 int th_debug_last_conv_s2_config(th_ctx *ctx, int *out8);
+/* what an exact pointwise convolution entry point would do with this shape -- pure host code, no context, the function the launch itself
+ * consumes (csrc/conv_pw_plan.h: ConvPwPlan, copied out field by field).  op: 0 th_conv1x1_exact_fwd, 1 _bwd_input, 2 _bwd_weight; h, w: the
+ * input's; relu_bias = relu + 2 * (bias present) (op 0); accumulate: ops 1 and 2; w_misalign_bytes: the gradient pointer of op 2 off a
+ * 16-byte boundary.  out20 = {op, CT (16-channel tiles per workgroup), accumulate, stride, pixels of the flat (image, oh, ow) axis per
+ * workgroup tile, the most images one tile touches (ops 0, 1), tiles, grid x, y, z, LDS bytes, the LDS limit of that launch, G, partial
+ * slabs, reduce ending (as th_debug_conv3x3_plan), input channels per slab (op 2), slab channel pitch, refusal (0: the call launches; 1 grid
+ * over the device limit or 2^31 output pixels and more, 2 operand of 2 GiB and more behind one descriptor), h_out, w_out}. */
+int th_debug_conv1x1_exact_plan(int op, int n, int c_in, int h, int w, int c_out, int stride, int weight_layout, int relu_bias, int accumulate,
+                                int w_misalign_bytes, int *out20);
+/* what this thread's most recent th_conv1x1_exact_* call launched: out9 = {op, CT, accumulate, stride, grid x, y, z, LDS bytes, reduce
+ * ending} (op -1: none yet) */
+int th_debug_last_conv_pw_config(th_ctx *ctx, int *out9);
 /* what th_linear_q8_fwd (qtype TH_QTYPE_INT8) / th_linear_h16_fwd (TH_QTYPE_F16) would do with this shape and these pointers
  * (x / w: bytes off a 16-byte boundary) -- pure host code, no context, the function the launch itself consumes: out8 = {1 if the weight-
  * streaming kernel takes it (0: the dequantize workspace and th_linear_fwd; the rest is 0 then), 1 if its vector-load instance, batch tile

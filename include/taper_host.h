@@ -96,6 +96,13 @@ int tp_conv2d(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b /* null
  * at stride 1 and refuse any other stride with it.  The flag is constructor state, not checkpoint content; tp_module_quantize* refuse a
  * model that holds such a conv. */
 #define TP_CONV_EXACT_STRIDE 1
+/* Value 16, TP_CONV_EXACT_POINTWISE (not in the reference; bits 2, 4 and 8 stay unknown): the call must be 1x1, stride (1, 1) or (2, 2),
+ * padding (0, 0), dilation (1, 1); it runs the exact pointwise convolution (th_conv1x1_exact_fwd) instead of the reference's 1x1
+ * reinterpretation (Q4: no convolution for c_in > 1, no stride, no gradient), and under tp_set_full_backward(1) its weight and input take
+ * gradients.  Known to tp_conv2d_ex and tp_conv2d_new_ex (one group; with bit 0 as well -- 17 -- refused by name: a kernel is 3x3 or 1x1)
+ * and to tp_residual_block_new_ex, where it means "pointwise shortcut" and combines with bit 0; tp_basic_block_new_ex refuses it as
+ * unknown.  Constructor state, not checkpoint content; tp_module_quantize* refuse a model that holds such a conv. */
+#define TP_CONV_EXACT_POINTWISE 16
 int tp_conv2d_ex(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b /* nullable */, int stride_h, int stride_w,
                  int pad_h, int pad_w, int dil_h, int dil_w, int relu, int flags, tp_tensor **out);
 int tp_max_pool2d(const tp_tensor *x, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, tp_tensor **out);
@@ -166,6 +173,15 @@ int tp_residual_block_new(int in_channels, int out_channels, int stride, uint64_
  * tp_set_full_backward(1): the downsampling block to train with (the default block's strided convs keep the reference's gather and take
  * no gradient). */
 int tp_residual_block_new_ex(int in_channels, int out_channels, int stride, uint64_t seed, int flags, tp_module **out);
+/* With TP_CONV_EXACT_POINTWISE the projection is a 1x1 exact pointwise convolution(in, out, stride) -> BatchNorm2d in place of the 3x3 (same
+ * seed + 2, no bias; strides 1 and 2 alone); with an identity shortcut the flag changes nothing.
+ *
+ * The bottleneck block: pointwise(in, mid) -> BatchNorm2d + ReLU -> conv3x3(mid, mid, stride, pad 1; the exact strided convolution at
+ * stride 2) -> BatchNorm2d + ReLU -> pointwise(mid, out) -> BatchNorm2d + shortcut -> ReLU.  Shortcut: the input when in == out and stride
+ * == 1, else pointwise(in, out, stride) -> BatchNorm2d.  Every 1x1 is the exact pointwise convolution, no conv has a bias, seeds seed ..
+ * seed + 3 in that order; stride 1 or 2 (others refused by name).  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, conv3 w,
+ * bn3 gamma beta, [shortcut conv w, gamma beta]; buffers: the running pairs in that order.  No quantized twin. */
+int tp_bottleneck_block_new(int in_channels, int mid_channels, int out_channels, int stride, uint64_t seed, tp_module **out);
 /* saved-but-not-trained state (the running statistics), concatenated over a Sequential's / BasicBlock's / ResidualBlock's children; shares storage */
 int tp_module_num_buffers(const tp_module *m, int *out);
 int tp_module_buffer(const tp_module *m, int i, tp_tensor **out);

@@ -12,7 +12,7 @@ from . import hip  # noqa: F401
 from ._lib import TaperError, build_native  # noqa: F401
 from . import dist  # noqa: F401
 from .api import (  # noqa: F401
-    SGD, Adam, AdamW, AdaptiveAvgPool2d, AvgPool2d, BasicBlock, BatchNorm2d, Communicator, Conv2d, Conv2dReLU, CosineAnnealingLR, DataLoader, Device,
+    SGD, Adam, AdamW, AdaptiveAvgPool2d, AvgPool2d, BasicBlock, BatchNorm2d, BottleneckBlock, Communicator, Conv2d, Conv2dReLU, CosineAnnealingLR, DataLoader, Device,
     Dropout, ExponentialLR, Flatten, HistogramObserver, Linear, MaxPool2d, MinMaxObserver, MNISTDataset, Module, ObserverManager, QATConfig, QATConv2d, QATLinear, QuantizedModule, ReduceLROnPlateau, ReLU, ResidualBlock, Sequential, Sigmoid,
     StepLR, Tape, Tensor, Trainer, accuracy, bce_loss, cross_entropy_loss, cross_entropy_loss_onehot, format_f32, log_softmax,
     mse_loss, one_hot, qat, set_conv_chain, set_conv_chain_head, set_full_backward, softmax,

@@ -14,6 +14,7 @@ from ._lib import TaperError, host, tp_check
 
 _p = C.c_void_p
 EXACT_STRIDE = 1   # TP_CONV_EXACT_STRIDE: bit 0 of the flags word of tp_conv2d_ex and the *_new_ex constructors
+EXACT_POINTWISE = 16   # TP_CONV_EXACT_POINTWISE: the exact 1x1 convolution (tp_residual_block_new_ex: the pointwise shortcut)
 
 
 def _shape_arr(shape):
@@ -227,19 +228,22 @@ class Tensor:
     def linear(self, weight, bias=None, relu=False):
         return self._un(host.tp_linear, "linear", weight._h, bias._h if bias is not None else None, 1 if relu else 0)
 
-    def conv2d(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), relu=False, exact_stride=False):
+    def conv2d(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), relu=False, exact_stride=False, exact_pointwise=False):
         """exact_stride: the exact 3x3 / stride (2, 2) / padding (1, 1) convolution, which takes weight and input gradients under
         set_full_backward(True); any other geometry with the flag is refused by name.  Without it a strided call keeps the reference's
-        general gather, which is no convolution and has no gradient."""
+        general gather, which is no convolution and has no gradient.
+        exact_pointwise: the exact 1x1 convolution with stride (1, 1) or (2, 2) and no padding, with the same gradients; any other geometry
+        with the flag, and both flags together, are refused by name.  Without it a 1x1 call keeps the reference's reinterpretation (SURVEY
+        Q4), which is no convolution for more than one input channel, takes no stride and has no gradient."""
         b = bias._h if bias is not None else None
-        if exact_stride:
+        if exact_stride or exact_pointwise:
             return self._un(host.tp_conv2d_ex, "conv2d", weight._h, b, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                            1 if relu else 0, EXACT_STRIDE)
+                            1 if relu else 0, (EXACT_STRIDE if exact_stride else 0) | (EXACT_POINTWISE if exact_pointwise else 0))
         return self._un(host.tp_conv2d, "conv2d", weight._h, b, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
                         1 if relu else 0)
 
-    def conv2d_relu(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), exact_stride=False):
-        return self.conv2d(weight, bias, stride, padding, dilation, relu=True, exact_stride=exact_stride)
+    def conv2d_relu(self, weight, bias, stride=(1, 1), padding=(0, 0), dilation=(1, 1), exact_stride=False, exact_pointwise=False):
+        return self.conv2d(weight, bias, stride, padding, dilation, relu=True, exact_stride=exact_stride, exact_pointwise=exact_pointwise)
 
     def max_pool2d(self, kernel_size, stride=None, padding=(0, 0)):
         s = stride or (0, 0)
@@ -519,18 +523,21 @@ class Conv2d(Module):
     """exact_stride: the layer is the exact 3x3 convolution with stride (2, 2) and padding (1, 1) (one group), and under
     set_full_backward(True) its weight and its input take gradients like a stride-1 layer's; the constructor refuses any other geometry
     with the flag by name.  Without it a strided Conv2d keeps the reference's general gather: not a convolution, no gradient.
-    The flag is constructor state (a checkpoint holds the parameters alone); quantize* refuse such a layer."""
+    The flag is constructor state (a checkpoint holds the parameters alone); quantize* refuse such a layer.
+    exact_pointwise: the layer is the exact 1x1 convolution with stride (1, 1) or (2, 2) and no padding (one group), with the same
+    gradients, constructor state and quantize* refusal.  Without it a 1x1 Conv2d keeps the reference's reinterpretation."""
 
     def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True,
-                 seed=1, _relu=False, exact_stride=False):
+                 seed=1, _relu=False, exact_stride=False, exact_pointwise=False):
         if dilation not in (None, (1, 1)):
             raise TaperError("Conv2d: dilation is out of scope (SURVEY.md section 2 row 8)")
         s, p = stride or (1, 1), padding or (0, 0)
-        if exact_stride:
+        if exact_stride or exact_pointwise:
             if int(groups or 1) != 1:
-                raise TaperError(f"Conv2d exact_stride: groups must be 1 (got {int(groups)})")
+                raise TaperError(f"Conv2d {'exact_stride' if exact_stride else 'exact_pointwise'}: groups must be 1 (got {int(groups)})")
             super().__init__(_mk(host.tp_conv2d_new_ex, "Conv2d::new", int(in_ch), int(out_ch), kernel_size[0], kernel_size[1],
-                                 s[0], s[1], p[0], p[1], 1 if bias else 0, 1 if _relu else 0, int(seed), EXACT_STRIDE))
+                                 s[0], s[1], p[0], p[1], 1 if bias else 0, 1 if _relu else 0, int(seed),
+                                 (EXACT_STRIDE if exact_stride else 0) | (EXACT_POINTWISE if exact_pointwise else 0)))
             return
         # groups > 1 (nn.rs:289-332): slice / conv per group / cat, forward only like the reference
         super().__init__(_mk(host.tp_conv2d_grouped_new, "Conv2d::new", int(in_ch), int(out_ch), kernel_size[0], kernel_size[1],
@@ -538,8 +545,10 @@ class Conv2d(Module):
 
 
 class Conv2dReLU(Conv2d):
-    def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True, seed=1, exact_stride=False):
-        super().__init__(in_ch, out_ch, kernel_size, stride, padding, dilation, groups, bias, seed, _relu=True, exact_stride=exact_stride)
+    def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True, seed=1, exact_stride=False,
+                 exact_pointwise=False):
+        super().__init__(in_ch, out_ch, kernel_size, stride, padding, dilation, groups, bias, seed, _relu=True, exact_stride=exact_stride,
+                         exact_pointwise=exact_pointwise)
 
 
 class MaxPool2d(Module):
@@ -651,7 +660,8 @@ class BasicBlock(Module):
 class ResidualBlock(Module):
     """conv3x3(in, out, stride) -> BatchNorm2d + ReLU -> conv3x3(out, out) -> BatchNorm2d + shortcut -> ReLU, the add and the last ReLU inside
     the second normalisation's kernels.  Shortcut: the input when in == out and stride == 1, else conv3x3(in, out, stride) -> BatchNorm2d
-    (a 3x3 projection, not a 1x1).  No conv has a bias.  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w,
+    (a 3x3 projection by default; ResidualBlock.pointwise_shortcut(...) builds the block with the 1x1 projection every ResNet uses).  No conv
+    has a bias.  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w,
     gamma beta]; buffers(): the running pairs in that order.
 
     A downsampling block (stride 2) by default keeps the reference's strided path in conv1 and in the projection: the general gather of
@@ -670,6 +680,28 @@ class ResidualBlock(Module):
         Module.__init__(blk, _mk(host.tp_residual_block_new_ex, "ResidualBlock::new", int(in_channels), int(out_channels), int(stride),
                                  int(seed), EXACT_STRIDE))
         return blk
+
+    @classmethod
+    def pointwise_shortcut(cls, in_channels, out_channels, stride=1, seed=1, exact_stride=True):
+        """the block whose projection is Conv2d(in, out, (1, 1), stride, exact_pointwise=True, bias=False) -> BatchNorm2d in place of the 3x3
+        (tp_residual_block_new_ex, TP_CONV_EXACT_POINTWISE): a ninth of the projection's arithmetic and weights, same seed + 2; exact_stride
+        as in ResidualBlock.exact_stride (conv1 at stride 2).  Strides 1 and 2; with an identity shortcut it is the constructor's block."""
+        blk = cls.__new__(cls)
+        Module.__init__(blk, _mk(host.tp_residual_block_new_ex, "ResidualBlock::new", int(in_channels), int(out_channels), int(stride),
+                                 int(seed), EXACT_POINTWISE | (EXACT_STRIDE if exact_stride else 0)))
+        return blk
+
+
+class BottleneckBlock(Module):
+    """pointwise(in, mid) -> BatchNorm2d + ReLU -> conv3x3(mid, mid, stride; the exact strided convolution at stride 2) -> BatchNorm2d + ReLU ->
+    pointwise(mid, out) -> BatchNorm2d + shortcut -> ReLU, the add and the last ReLU inside the third normalisation's kernels.  Shortcut: the
+    input when in == out and stride == 1, else pointwise(in, out, stride) -> BatchNorm2d.  Every 1x1 is Conv2d(exact_pointwise=True); no conv has
+    a bias; seeds seed .. seed + 3 in that order; stride 1 or 2.  parameters(): conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, conv3 w, bn3
+    gamma beta, [shortcut conv w, gamma beta]; buffers(): the running pairs in that order.  Trains under set_full_backward(True)."""
+
+    def __init__(self, in_channels, mid_channels, out_channels, stride=1, seed=1):
+        super().__init__(_mk(host.tp_bottleneck_block_new, "BottleneckBlock::new", int(in_channels), int(mid_channels), int(out_channels),
+                             int(stride), int(seed)))
 
 
 class Sequential(Module):

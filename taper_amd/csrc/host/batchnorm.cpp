@@ -147,21 +147,27 @@ BasicBlock::BasicBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed
     : conv(in_ch, out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, true, seed, 1, exact_for("BasicBlock", stride, exact_stride)),
       bn(out_ch, 1e-5f, 0.1f, true) {}
 
-static size_t checked_block(size_t in_ch, size_t out_ch, size_t stride) {
+static size_t checked_block(size_t in_ch, size_t out_ch, size_t stride, bool pointwise_shortcut = false) {
     TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0 && in_ch <= 0x7fffffffu && out_ch <= 0x7fffffffu && stride <= 0x7fffffffu,
                  "ResidualBlock: in_channels, out_channels and stride must be positive");
+    // the pointwise convolution exists for strides 1 and 2 alone
+    TAPER_ASSERT(!pointwise_shortcut || stride == 1 || stride == 2,
+                 "ResidualBlock pointwise_shortcut: the stride must be 1 or 2 (got " + std::to_string(stride) + ")");
     return in_ch;
 }
 
-ResidualBlock::ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride)
-    : conv1(checked_block(in_ch, out_ch, stride), out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, false, seed, 1,
+ResidualBlock::ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride, bool pointwise_shortcut)
+    : conv1(checked_block(in_ch, out_ch, stride, pointwise_shortcut), out_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, false, seed, 1,
             exact_for("ResidualBlock", stride, exact_stride)),
       bn1(out_ch, 1e-5f, 0.1f, true),
       conv2(out_ch, out_ch, {3, 3}, {1, 1}, {1, 1}, false, seed + 1),
       bn2(out_ch, 1e-5f, 0.1f, true) {
     if (in_ch != out_ch || stride != 1) {
-        shortcut_conv = std::make_unique<Conv2d>(in_ch, out_ch, std::make_pair(3, 3), std::make_pair((int)stride, (int)stride), std::make_pair(1, 1),
-                                                 false, seed + 2, 1, exact_for("ResidualBlock", stride, exact_stride));
+        if (pointwise_shortcut)
+            shortcut_conv = std::make_unique<Conv2d>(Conv2d::pointwise(in_ch, out_ch, stride, seed + 2));
+        else
+            shortcut_conv = std::make_unique<Conv2d>(in_ch, out_ch, std::make_pair(3, 3), std::make_pair((int)stride, (int)stride),
+                                                     std::make_pair(1, 1), false, seed + 2, 1, exact_for("ResidualBlock", stride, exact_stride));
         shortcut_bn = std::make_unique<BatchNorm2d>(out_ch, 1e-5f, 0.1f, false);
     }
 }
@@ -196,6 +202,69 @@ std::vector<Tensor> ResidualBlock::buffers() const {
     return b;
 }
 
+static size_t checked_bottleneck(size_t in_ch, size_t mid_ch, size_t out_ch, size_t stride) {
+    TAPER_ASSERT(in_ch > 0 && mid_ch > 0 && out_ch > 0 && stride > 0 && in_ch <= 0x7fffffffu && mid_ch <= 0x7fffffffu && out_ch <= 0x7fffffffu &&
+                     stride <= 0x7fffffffu,
+                 "BottleneckBlock: in_channels, mid_channels, out_channels and stride must be positive");
+    TAPER_ASSERT(stride == 1 || stride == 2, "BottleneckBlock: the stride must be 1 or 2 (got " + std::to_string(stride) + ")");
+    return in_ch;
+}
+
+BottleneckBlock::BottleneckBlock(size_t in_ch, size_t mid_ch, size_t out_ch, size_t stride, uint64_t seed)
+    : conv1(Conv2d::pointwise(checked_bottleneck(in_ch, mid_ch, out_ch, stride), mid_ch, 1, seed)),
+      bn1(mid_ch, 1e-5f, 0.1f, true),
+      conv2(mid_ch, mid_ch, {3, 3}, {(int)stride, (int)stride}, {1, 1}, false, seed + 1, 1, stride == 2),
+      bn2(mid_ch, 1e-5f, 0.1f, true),
+      conv3(Conv2d::pointwise(mid_ch, out_ch, 1, seed + 2)),
+      bn3(out_ch, 1e-5f, 0.1f, true) {
+    if (in_ch != out_ch || stride != 1) {
+        shortcut_conv = std::make_unique<Conv2d>(Conv2d::pointwise(in_ch, out_ch, stride, seed + 3));
+        shortcut_bn = std::make_unique<BatchNorm2d>(out_ch, 1e-5f, 0.1f, false);
+    }
+}
+
+Tensor BottleneckBlock::forward(const Tensor &x) const {
+    const Tensor h = conv3.forward(bn2.forward(conv2.forward(bn1.forward(conv1.forward(x)))));
+    return bn3.forward_add(h, shortcut_conv ? shortcut_bn->forward(shortcut_conv->forward(x)) : x);
+}
+
+std::vector<BatchNorm2d *> BottleneckBlock::batchnorms() {
+    std::vector<BatchNorm2d *> b{&bn1, &bn2, &bn3};
+    if (shortcut_bn) b.push_back(shortcut_bn.get());
+    return b;
+}
+
+std::vector<Tensor> BottleneckBlock::parameters() const {
+    std::vector<Tensor> p{conv1.weight, bn1.gamma, bn1.beta, conv2.weight, bn2.gamma, bn2.beta, conv3.weight, bn3.gamma, bn3.beta};
+    if (shortcut_conv) {
+        p.push_back(shortcut_conv->weight);
+        p.push_back(shortcut_bn->gamma);
+        p.push_back(shortcut_bn->beta);
+    }
+    return p;
+}
+
+std::vector<Tensor> BottleneckBlock::buffers() const {
+    std::vector<Tensor> b{bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var, bn3.running_mean, bn3.running_var};
+    if (shortcut_bn) {
+        b.push_back(shortcut_bn->running_mean);
+        b.push_back(shortcut_bn->running_var);
+    }
+    return b;
+}
+
+bool holds_exact_pointwise(const Module &m) {
+    if (auto *s = dynamic_cast<const Sequential *>(&m)) {
+        for (const auto &l : s->layers)
+            if (holds_exact_pointwise(*l)) return true;
+        return false;
+    }
+    if (auto *cv = dynamic_cast<const Conv2d *>(&m)) return cv->exact_pointwise;
+    if (auto *bb = dynamic_cast<const BasicBlock *>(&m)) return bb->conv.exact_pointwise;
+    if (auto *rb = dynamic_cast<const ResidualBlock *>(&m)) return rb->shortcut_conv && rb->shortcut_conv->exact_pointwise;
+    return dynamic_cast<const BottleneckBlock *>(&m) != nullptr;
+}
+
 std::vector<Tensor> BasicBlock::parameters() const {
     std::vector<Tensor> p = conv.parameters();
     for (const Tensor &t : bn.parameters()) p.push_back(t);
@@ -216,6 +285,8 @@ void batchnorm_modules(Module &m, std::vector<BatchNorm2d *> *out) {
         out->push_back(&bb->bn);
     } else if (auto *rb = dynamic_cast<ResidualBlock *>(&m)) {
         for (BatchNorm2d *b : rb->batchnorms()) out->push_back(b);
+    } else if (auto *nb = dynamic_cast<BottleneckBlock *>(&m)) {
+        for (BatchNorm2d *b : nb->batchnorms()) out->push_back(b);
     } else if (auto *bn = dynamic_cast<BatchNorm2d *>(&m)) {
         out->push_back(bn);
     }
@@ -228,6 +299,8 @@ void set_training(Module &m, bool on) {
         bb->bn.set_training(on);
     } else if (auto *rb = dynamic_cast<ResidualBlock *>(&m)) {
         for (BatchNorm2d *b : rb->batchnorms()) b->set_training(on);
+    } else if (auto *nb = dynamic_cast<BottleneckBlock *>(&m)) {
+        for (BatchNorm2d *b : nb->batchnorms()) b->set_training(on);
     } else if (auto *bn = dynamic_cast<BatchNorm2d *>(&m)) {
         bn->set_training(on);
     } else if (auto *d = dynamic_cast<Dropout *>(&m)) {

@@ -154,12 +154,19 @@ static bool exact_stride_flag(const char *fn, int flags) {
                                                           " (bit 0, the exact stride, is the only flag)");
     return (flags & TP_CONV_EXACT_STRIDE) != 0;
 }
+// ... of the functions that also know TP_CONV_EXACT_POINTWISE (value 16): the message prints the bits that are unknown, and those alone
+static void known_flags(const char *fn, int flags) {
+    constexpr int known = TP_CONV_EXACT_STRIDE | TP_CONV_EXACT_POINTWISE;
+    TAPER_ASSERT((flags & ~known) == 0, std::string(fn) + ": unknown flag bits " + std::to_string(flags & ~known) +
+                                            " (1, the exact stride, and 16, the exact pointwise convolution, are the flags)");
+}
 int tp_conv2d_ex(const tp_tensor *x, const tp_tensor *w, const tp_tensor *b, int sh, int sw, int ph, int pw, int dh, int dw, int relu, int flags,
                  tp_tensor **out) {
     TP_BEGIN
     TAPER_ASSERT(x && w && out, "tp_conv2d_ex: null argument");
-    const bool exact = exact_stride_flag("tp_conv2d_ex", flags);
-    *out = wrap(x->t.conv2d(w->t, opt_t(b), {sh, sw}, {ph, pw}, {dh, dw}, relu != 0, exact));
+    known_flags("tp_conv2d_ex", flags);
+    *out = wrap(x->t.conv2d(w->t, opt_t(b), {sh, sw}, {ph, pw}, {dh, dw}, relu != 0, (flags & TP_CONV_EXACT_STRIDE) != 0,
+                            (flags & TP_CONV_EXACT_POINTWISE) != 0));
     TP_END
 }
 int tp_max_pool2d(const tp_tensor *x, int kh, int kw, int sh, int sw, int ph, int pw, tp_tensor **out) {
@@ -260,8 +267,17 @@ int tp_residual_block_new_ex(int in_ch, int out_ch, int stride, uint64_t seed, i
     TP_BEGIN
     TAPER_ASSERT(out, "tp_residual_block_new_ex: null argument");
     TAPER_ASSERT(in_ch > 0 && out_ch > 0 && stride > 0, "ResidualBlock: in_channels, out_channels and stride must be positive");
-    const bool exact = exact_stride_flag("tp_residual_block_new_ex", flags);
-    *out = new tp_module{std::make_shared<ResidualBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed, exact)};
+    known_flags("tp_residual_block_new_ex", flags);
+    *out = new tp_module{std::make_shared<ResidualBlock>((size_t)in_ch, (size_t)out_ch, (size_t)stride, seed, (flags & TP_CONV_EXACT_STRIDE) != 0,
+                                                         (flags & TP_CONV_EXACT_POINTWISE) != 0)};
+    TP_END
+}
+int tp_bottleneck_block_new(int in_ch, int mid_ch, int out_ch, int stride, uint64_t seed, tp_module **out) {
+    TP_BEGIN
+    TAPER_ASSERT(out, "tp_bottleneck_block_new: null argument");
+    TAPER_ASSERT(in_ch > 0 && mid_ch > 0 && out_ch > 0 && stride > 0,
+                 "BottleneckBlock: in_channels, mid_channels, out_channels and stride must be positive");
+    *out = new tp_module{std::make_shared<BottleneckBlock>((size_t)in_ch, (size_t)mid_ch, (size_t)out_ch, (size_t)stride, seed)};
     TP_END
 }
 int tp_module_num_buffers(const tp_module *m, int *out) { TP_BEGIN *out = (int)m->m->buffers().size(); TP_END }
@@ -291,9 +307,9 @@ int tp_conv2d_new_ex(int ic, int oc, int kh, int kw, int sh, int sw, int ph, int
                      tp_module **out) {
     TP_BEGIN
     TAPER_ASSERT(out, "tp_conv2d_new_ex: null argument");
-    const bool exact = exact_stride_flag("tp_conv2d_new_ex", flags);
+    known_flags("tp_conv2d_new_ex", flags);
     auto c = std::make_shared<Conv2d>((size_t)ic, (size_t)oc, std::make_pair(kh, kw), std::make_pair(sh, sw), std::make_pair(ph, pw),
-                                      bias != 0, seed, 1, exact);
+                                      bias != 0, seed, 1, (flags & TP_CONV_EXACT_STRIDE) != 0, (flags & TP_CONV_EXACT_POINTWISE) != 0);
     c->fuse_relu = relu != 0;
     *out = new tp_module{c};
     TP_END

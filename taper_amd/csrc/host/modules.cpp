@@ -549,8 +549,18 @@ std::vector<Tensor> Linear::parameters() const {  // nn.rs:71-77
 }
 
 Conv2d::Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> s, std::pair<int, int> p,
-               bool with_bias, uint64_t seed, size_t g, bool exact)
-    : stride(s), padding(p), groups(g), exact_stride(exact) {  // nn.rs:190-244
+               bool with_bias, uint64_t seed, size_t g, bool exact, bool pointwise)
+    : stride(s), padding(p), groups(g), exact_stride(exact), exact_pointwise(pointwise) {  // nn.rs:190-244
+    TAPER_ASSERT(!(exact_stride && exact_pointwise), "Conv2d: exact_stride and exact_pointwise exclude each other (a kernel is 3x3 or 1x1)");
+    if (exact_pointwise) {
+        TAPER_ASSERT(kernel == std::make_pair(1, 1), "Conv2d exact_pointwise: the kernel must be 1x1 (got " + std::to_string(kernel.first) + "x" +
+                                                         std::to_string(kernel.second) + ")");
+        TAPER_ASSERT(s == std::make_pair(1, 1) || s == std::make_pair(2, 2), "Conv2d exact_pointwise: the stride must be (1, 1) or (2, 2) (got (" +
+                                                                                 std::to_string(s.first) + ", " + std::to_string(s.second) + "))");
+        TAPER_ASSERT(p == std::make_pair(0, 0), "Conv2d exact_pointwise: the padding must be (0, 0) (got (" + std::to_string(p.first) + ", " +
+                                                    std::to_string(p.second) + "))");
+        TAPER_ASSERT(g == 1, "Conv2d exact_pointwise: groups must be 1 (got " + std::to_string(g) + ")");
+    }
     if (exact_stride) {
         TAPER_ASSERT(kernel == std::make_pair(3, 3), "Conv2d exact_stride: the kernel must be 3x3 (got " + std::to_string(kernel.first) + "x" +
                                                          std::to_string(kernel.second) + ")");
@@ -572,7 +582,7 @@ Conv2d::Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pai
 Tensor Conv2d::forward(const Tensor &x) const { return forward_with(x, weight, bias); }
 
 Tensor Conv2d::forward_with(const Tensor &x, const Tensor &weight, const Tensor &bias) const {
-    if (groups == 1) return x.conv2d(weight, bias, stride, padding, dilation, fuse_relu, exact_stride);   // nn.rs:280-288
+    if (groups == 1) return x.conv2d(weight, bias, stride, padding, dilation, fuse_relu, exact_stride, exact_pointwise);   // nn.rs:280-288
     // nn.rs:289-332: slices are fresh tensors without tape nodes, so nothing upstream of a grouped
     // convolution (and none of its own parameters) ever receives a gradient -- reproduced as is
     TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] % groups == 0, "Input channels must be divisible by groups");

@@ -581,6 +581,7 @@ void check_quantizable(const Module &m, bool batchnorm) {
     const auto *cv = dynamic_cast<const Conv2d *>(&m);
     if (const auto *bb = dynamic_cast<const BasicBlock *>(&m)) cv = &bb->conv;
     if (cv && cv->exact_stride) throw Error("exact-stride Conv2d: quantized twins are a follow-up");
+    if (cv && cv->exact_pointwise) throw Error("exact-pointwise Conv2d: quantized twins are a follow-up");
     if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const QATModule *>(&m) || dynamic_cast<const ReLU *>(&m) ||
         dynamic_cast<const Sigmoid *>(&m) || dynamic_cast<const MaxPool2d *>(&m) || dynamic_cast<const AvgPool2d *>(&m) ||
         dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m) ||

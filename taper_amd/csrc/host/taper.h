@@ -163,10 +163,13 @@ class Tensor {
     // exact_stride (not in the reference): the call must be 3x3, stride (2, 2), padding (1, 1), dilation (1, 1) and runs the exact strided
     // convolution (th_conv3x3_s2_fwd) instead of the reference's general gather (Q9); under full_backward its weight and input take
     // gradients by the stride-1 rules (th_conv3x3_s2_bwd_weight / _bwd_input).  Any other geometry with the flag is refused by name.
+    // exact_pointwise (not in the reference): the call must be 1x1, stride (1, 1) or (2, 2), padding (0, 0), dilation (1, 1) and runs the
+    // exact pointwise convolution (th_conv1x1_exact_fwd) instead of the reference's 1x1 reinterpretation (Q4); gradients as for exact_stride
+    // (th_conv1x1_exact_bwd_weight / _bwd_input).  Any other geometry with the flag, and both flags together, are refused by name.
     Tensor conv2d(const Tensor &weight, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                  std::pair<int, int> dilation, bool relu = false, bool exact_stride = false) const;
+                  std::pair<int, int> dilation, bool relu = false, bool exact_stride = false, bool exact_pointwise = false) const;
     Tensor conv2d_relu(const Tensor &weight, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                       std::pair<int, int> dilation, bool exact_stride = false) const;
+                       std::pair<int, int> dilation, bool exact_stride = false, bool exact_pointwise = false) const;
     // Conv2dReLU (3x3, stride 1) + MaxPool2d(2, 2) as ONE launch that writes only the pooled tensor (th_conv3x3_pool2_fwd).
     // Trainer-internal: valid in faithful mode (Q2: the conv's only gradient is its bias, taken from the pooled tensors)
     // when nobody else reads the conv output.  conv2d_relu_maxpool2_supported tells whether the pair qualifies.
@@ -347,8 +350,15 @@ class Conv2d : public Module {  // nn.rs:180-354
     // the exact strided convolution with both gradients (Tensor::conv2d's flag): 3x3, stride (2, 2), padding (1, 1), one group -- anything
     // else with the flag throws in the constructor.  Constructor state, not checkpoint content.
     bool exact_stride = false;
+    // the exact pointwise convolution with both gradients (Tensor::conv2d's flag): 1x1, stride (1, 1) or (2, 2), padding (0, 0), one group --
+    // anything else with the flag, and both flags, throw in the constructor.  Constructor state, not checkpoint content.
+    bool exact_pointwise = false;
     Conv2d(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride, std::pair<int, int> padding,
-           bool with_bias, uint64_t seed, size_t groups = 1, bool exact_stride = false);
+           bool with_bias, uint64_t seed, size_t groups = 1, bool exact_stride = false, bool exact_pointwise = false);
+    // Conv2d(in, out, 1x1, stride (s, s), no padding, no bias) with exact_pointwise: the projection and the bottleneck convs of the blocks
+    static Conv2d pointwise(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed) {
+        return Conv2d(in_ch, out_ch, {1, 1}, {(int)stride, (int)stride}, {0, 0}, false, seed, 1, false, true);
+    }
     Tensor forward(const Tensor &x) const override;
     // nn.rs:280-332 with the given weight / bias (the quantized twin passes its dequantized tensors)
     Tensor forward_with(const Tensor &x, const Tensor &w, const Tensor &b) const;
@@ -359,8 +369,8 @@ class Conv2d : public Module {  // nn.rs:180-354
 class Conv2dReLU : public Conv2d {  // nn.rs:433-490
    public:
     Conv2dReLU(size_t in_ch, size_t out_ch, std::pair<int, int> kernel, std::pair<int, int> stride,
-               std::pair<int, int> padding, bool with_bias, uint64_t seed, bool exact_stride = false)
-        : Conv2d(in_ch, out_ch, kernel, stride, padding, with_bias, seed, 1, exact_stride) {
+               std::pair<int, int> padding, bool with_bias, uint64_t seed, bool exact_stride = false, bool exact_pointwise = false)
+        : Conv2d(in_ch, out_ch, kernel, stride, padding, with_bias, seed, 1, exact_stride, exact_pointwise) {
         fuse_relu = true;
     }
 };
@@ -464,8 +474,9 @@ class BasicBlock : public Module {
 
 // A ResNet-style block (no upstream counterpart): conv3x3(in, out, stride, pad 1) -> BatchNorm2d + ReLU -> conv3x3(out, out, 1, pad 1) ->
 // BatchNorm2d.forward_add(., shortcut) with the ReLU after the add.  The shortcut is the block's input when in == out and stride == 1,
-// else conv3x3(in, out, stride, pad 1) -> BatchNorm2d (no ReLU).  The projection is a 3x3 convolution, not torchvision's 1x1: the float
-// 1x1 path keeps the reference's row-scrambling reinterpretation and is not a usable projection.  No conv carries a bias:
+// else conv3x3(in, out, stride, pad 1) -> BatchNorm2d (no ReLU).  By default the projection is a 3x3 convolution, not torchvision's 1x1: the
+// default float 1x1 path keeps the reference's row-scrambling reinterpretation and is not a usable projection; with
+// pointwise_shortcut it is the exact pointwise convolution (Conv2d::pointwise).  No conv carries a bias:
 // in front of a normalisation its gradient is zero analytically, and Adam turns the rounding noise into steps.
 // Seeds: conv1 seed, conv2 seed + 1, the projection seed + 2.
 class ResidualBlock : public Module {
@@ -479,12 +490,37 @@ class ResidualBlock : public Module {
     // zero arguments throw before the device is touched
     // exact_stride: handed to every conv of the block whose stride is 2 (conv1 and the projection: Conv2d::exact_stride) -- the block to
     // train with; nothing changes at stride 1; any other stride with the flag is refused by name
-    ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride = false);
+    // pointwise_shortcut: the projection is Conv2d::pointwise(in, out, stride) -> BatchNorm2d (the 1x1 projection every ResNet uses: a ninth
+    // of the 3x3's arithmetic and weights), same seed + 2, no bias; strides 1 and 2 alone; with an identity shortcut it changes nothing
+    ResidualBlock(size_t in_ch, size_t out_ch, size_t stride, uint64_t seed, bool exact_stride = false, bool pointwise_shortcut = false);
     Tensor forward(const Tensor &x) const override;
     std::vector<BatchNorm2d *> batchnorms();            // bn1, bn2, [the shortcut's]
     std::vector<Tensor> parameters() const override;   // conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, [shortcut conv w, gamma beta]
     std::vector<Tensor> buffers() const override;      // the running pairs in the same order
     const char *name() const override { return "ResidualBlock"; }
+};
+
+// The bottleneck block of the deeper ResNets (no upstream counterpart): pointwise(in, mid) -> BatchNorm2d + ReLU -> conv3x3(mid, mid, stride,
+// pad 1; the exact strided convolution at stride 2) -> BatchNorm2d + ReLU -> pointwise(mid, out) -> BatchNorm2d.forward_add(., shortcut) with
+// the ReLU after the add.  The shortcut is the block's input when in == out and stride == 1, else pointwise(in, out, stride) -> BatchNorm2d.
+// Every 1x1 is the exact pointwise convolution; no conv carries a bias.  Seeds: seed .. seed + 3 in that order.  Strides 1 and 2 alone.
+class BottleneckBlock : public Module {
+   public:
+    Conv2d conv1;
+    BatchNorm2d bn1;
+    Conv2d conv2;
+    BatchNorm2d bn2;
+    Conv2d conv3;
+    BatchNorm2d bn3;
+    std::unique_ptr<Conv2d> shortcut_conv;       // null: the identity shortcut
+    std::unique_ptr<BatchNorm2d> shortcut_bn;
+    // zero arguments and a stride other than 1 or 2 throw before the device is touched
+    BottleneckBlock(size_t in_ch, size_t mid_ch, size_t out_ch, size_t stride, uint64_t seed);
+    Tensor forward(const Tensor &x) const override;
+    std::vector<BatchNorm2d *> batchnorms();            // bn1, bn2, bn3, [the shortcut's]
+    std::vector<Tensor> parameters() const override;   // conv1 w, bn1 gamma beta, conv2 w, bn2 gamma beta, conv3 w, bn3 gamma beta, [shortcut conv w, gamma beta]
+    std::vector<Tensor> buffers() const override;      // the running pairs in the same order
+    const char *name() const override { return "BottleneckBlock"; }
 };
 
 class Sequential : public Module {  // nn.rs:130-162
@@ -502,8 +538,10 @@ class Sequential : public Module {  // nn.rs:130-162
     const char *name() const override { return "Sequential"; }
 };
 
-// The BatchNorm2d layers of a model (a Sequential's, a BasicBlock's and a ResidualBlock's, or the module itself), in order
+// The BatchNorm2d layers of a model (a Sequential's, a BasicBlock's, a ResidualBlock's and a BottleneckBlock's, or the module itself), in order
 void batchnorm_modules(Module &m, std::vector<BatchNorm2d *> *out);
+// whether `m` holds a Conv2d with exact_pointwise (itself, in a Sequential or in a block): such a model trains in the Layered step form
+bool holds_exact_pointwise(const Module &m);
 // train() / eval() of every BatchNorm2d and every Dropout inside `m`
 void set_training(Module &m, bool on);
 

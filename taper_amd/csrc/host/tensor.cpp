@@ -834,7 +834,7 @@ Tensor Tensor::argmax(int dim) const { return max(dim).second; }
 static void pooled_bias_grad(const Tensor &bias, const float *dy, const float *mask_y, int n, int c, int hw, bool avg, const float *cnt = nullptr);
 
 Tensor Tensor::conv2d(const Tensor &w, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                      std::pair<int, int> dilation, bool relu, bool exact_stride) const {  // tensor.rs:1221-1285 (+1379-1389)
+                      std::pair<int, int> dilation, bool relu, bool exact_stride, bool exact_pointwise) const {  // tensor.rs:1221-1285 (+1379-1389)
     TAPER_ASSERT(shape_.size() == 4, "Input must be 4D: [N, C_in, H, W]");
     TAPER_ASSERT(w.shape_.size() == 4, "Weight must be 4D: [C_out, C_in, K_h, K_w]");
     const int n = (int)shape_[0], c_in = (int)shape_[1], h = (int)shape_[2], wd = (int)shape_[3];
@@ -849,7 +849,18 @@ Tensor Tensor::conv2d(const Tensor &w, const Tensor &bias, std::pair<int, int> s
     const float *bp = bias.defined() ? bias.dptr() : nullptr;
     Tensor out = empty({(size_t)n, (size_t)c_out, (size_t)h_out, (size_t)w_out});
     const int pad = padding.first;
-    if (exact_stride) {   // the exact strided convolution (not in the reference: its strided path is the general gather below, Q9)
+    TAPER_ASSERT(!(exact_stride && exact_pointwise), "conv2d: exact_stride and exact_pointwise exclude each other (a kernel is 3x3 or 1x1)");
+    if (exact_pointwise) {   // the exact pointwise convolution (not in the reference: its 1x1 path is the reinterpretation below, Q4)
+        TAPER_ASSERT(k_h == 1 && k_w == 1, "conv2d exact_pointwise: the kernel must be 1x1 (got " + std::to_string(k_h) + "x" + std::to_string(k_w) + ")");
+        TAPER_ASSERT(stride == std::make_pair(1, 1) || stride == std::make_pair(2, 2),
+                     "conv2d exact_pointwise: the stride must be (1, 1) or (2, 2) (got (" + std::to_string(stride.first) + ", " +
+                         std::to_string(stride.second) + "))");
+        TAPER_ASSERT(padding == std::make_pair(0, 0), "conv2d exact_pointwise: the padding must be (0, 0) (got (" + std::to_string(padding.first) +
+                                                          ", " + std::to_string(padding.second) + "))");
+        TAPER_ASSERT(dilation == std::make_pair(1, 1), "conv2d exact_pointwise: the dilation must be (1, 1) (got (" + std::to_string(dilation.first) +
+                                                           ", " + std::to_string(dilation.second) + "))");
+        TH(th_conv1x1_exact_fwd(c, dptr(), w.dptr(), bp, out.dptr(), n, c_in, h, wd, c_out, stride.first, /*taper layout*/ 0, relu ? 1 : 0));
+    } else if (exact_stride) {   // the exact strided convolution (not in the reference: its strided path is the general gather below, Q9)
         TAPER_ASSERT(k_h == 3 && k_w == 3, "conv2d exact_stride: the kernel must be 3x3 (got " + std::to_string(k_h) + "x" + std::to_string(k_w) + ")");
         TAPER_ASSERT(stride == std::make_pair(2, 2), "conv2d exact_stride: the stride must be (2, 2) (got (" + std::to_string(stride.first) + ", " +
                                                          std::to_string(stride.second) + "))");
@@ -874,13 +885,13 @@ Tensor Tensor::conv2d(const Tensor &w, const Tensor &bias, std::pair<int, int> s
     const bool fb = full_backward();
     const bool bias_grad = bias.defined() && bias.requires_grad_;
     const bool w_grad = fb && w.requires_grad_;
-    const bool x_grad = fb && requires_grad_ && ((is3 && pad == 1) || exact_stride);
+    const bool x_grad = fb && requires_grad_ && ((is3 && pad == 1) || exact_stride || exact_pointwise);
     if (bias_grad || w_grad || x_grad) {
         out.requires_grad_ = true;
         out.grad_->wants_pooled = relu && bias_grad && !w_grad && !x_grad && PoolBiasScope::active();
         out.grad_->relu_output = relu && (w_grad || x_grad);   // full backward: a max-pool behind this layer may fold the ReLU's mask into its scatter
         Tensor x = *this, wt = w, b = bias, r = out;
-        Tape::push(out, true, [x, wt, b, r, n, c_in, h, wd, c_out, h_out, w_out, pad, relu, bias_grad, w_grad, x_grad, is3, exact_stride]() {
+        Tape::push(out, true, [x, wt, b, r, n, c_in, h, wd, c_out, h_out, w_out, pad, relu, bias_grad, w_grad, x_grad, is3, exact_stride, exact_pointwise, sp = stride.first]() {
             th_ctx *c = Device::ctx();
             if (r.grad_->pooled_dy && !r.grad_->has) {
                 // the max-pool behind this layer left its OUTPUT's gradient: db = sum of the pooled gradients whose
@@ -917,14 +928,20 @@ Tensor Tensor::conv2d(const Tensor &w, const Tensor &bias, std::pair<int, int> s
                 if (ps) TH(th_bias_grad_plane_sums(c, ps->d, db, n, c_out, none ? 0 : 1));
                 else TH(th_bias_grad_nchw_masked(c, gy, nullptr, db, n, c_out, h_out * w_out, none ? 0 : 1));
             }
-            if (w_grad && exact_stride) {
+            if (w_grad && exact_pointwise) {
+                float *dw = wt.grad_for_write(&none);
+                TH(th_conv1x1_exact_bwd_weight(c, x.dptr(), gy, dw, n, c_in, h, wd, c_out, sp, 0, none ? 0 : 1));
+            } else if (w_grad && exact_stride) {
                 float *dw = wt.grad_for_write(&none);
                 TH(th_conv3x3_s2_bwd_weight(c, x.dptr(), gy, dw, n, c_in, h, wd, c_out, 0, none ? 0 : 1));
             } else if (w_grad && is3) {
                 float *dw = wt.grad_for_write(&none);
                 TH(th_conv3x3_bwd_weight(c, x.dptr(), gy, dw, n, c_in, h, wd, c_out, pad, 0, none ? 0 : 1));
             }
-            if (x_grad && exact_stride) {
+            if (x_grad && exact_pointwise) {
+                float *dx = x.grad_for_write(&none);
+                TH(th_conv1x1_exact_bwd_input(c, gy, wt.dptr(), dx, n, c_in, h, wd, c_out, sp, 0, none ? 0 : 1));
+            } else if (x_grad && exact_stride) {
                 float *dx = x.grad_for_write(&none);
                 TH(th_conv3x3_s2_bwd_input(c, gy, wt.dptr(), dx, n, c_in, h, wd, c_out, 0, none ? 0 : 1));
             } else if (x_grad) {
@@ -937,8 +954,8 @@ Tensor Tensor::conv2d(const Tensor &w, const Tensor &bias, std::pair<int, int> s
 }
 
 Tensor Tensor::conv2d_relu(const Tensor &w, const Tensor &bias, std::pair<int, int> stride, std::pair<int, int> padding,
-                           std::pair<int, int> dilation, bool exact_stride) const {
-    return conv2d(w, bias, stride, padding, dilation, true, exact_stride);
+                           std::pair<int, int> dilation, bool exact_stride, bool exact_pointwise) const {
+    return conv2d(w, bias, stride, padding, dilation, true, exact_stride, exact_pointwise);
 }
 
 // Bias gradient of a bias-only Conv2dReLU from pooled tensors (see GradSlot).  Inside a fused-update step it is the last backward

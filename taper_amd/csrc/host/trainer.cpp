@@ -331,6 +331,8 @@ StepPlan Trainer::plan_step(size_t batch, int64_t n_rows) const {
         p.fused_adam = false;
         return p;
     }
+    // the exact pointwise convolution belongs to no fused form (the conv chain's stages are 3x3 rows): such a model trains layer by layer
+    if (holds_exact_pointwise(*model)) return take(StepForm::Layered, nl, {});
     Linear *last = (fuse_head && nl) ? linear(nl - 1) : nullptr;
     Linear *hidden = (last && fuse_head >= 2 && seq->fuse && nl >= 3 && relu(nl - 2)) ? linear(nl - 3) : nullptr;
     Linear *hidden0 = (hidden && nl >= 5 && relu(nl - 4)) ? linear(nl - 5) : nullptr;   // a three-layer classifier: th_mlp3_xent, two launches
