@@ -547,6 +547,29 @@ int th_conv2d_q8q8_fwd_codes_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch,
                                     const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
                                     const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
                                     int per_channel, const float *d_affine);
+/* ---- a skip connection in the epilogue of a static convolution ----
+ * The two affine products with a residual r added in f32 behind the affine and in front of the ReLU and the codec, where
+ * th_bn_residual_fwd adds it in the float model: with v the product's value (bias included, WITHOUT its ReLU) and {a, b} the channel's pair,
+ *     y = ((v * a) + b) + r   (one multiply, two adds, each rounded once in this order, never contracted), then max(y, 0) with relu
+ *                             (NaN -> 0 there), then the store (f32 form) or the codec with *d_yscale (codes form) as in the twin.
+ * Exactly one of the two residual forms is given:
+ *     d_res    f32 [n][c_out][h_out][w_out], the output's shape:                  r = d_res[b][co][oh][ow]
+ *     d_res_q  int8 codes [n][h_out][w_out][cpitch_r], channel-last as th_quantize_act_nhwc_int8 and the codes forms write them, with
+ *              the device scalar d_res_scale:                                     r = (float)d_res_q[b][oh][ow][co] * *d_res_scale
+ *              (bytes c_out .. cpitch_r - 1 of a pixel may hold anything: they reach no stored value)
+ * Nothing of the residual is read for a pixel or a channel that is not stored.  Refused before a launch: everything the _affine twins
+ * refuse, a null d_affine, both residual pointers set or neither, and with d_res_q a null d_res_scale, a cpitch_r that is no multiple of
+ * 16 or below c_out, or a d_res_q off a 16-byte boundary.  The forms (th_debug_qconv_plan) are the twins'.  Neither call allocates,
+ * synchronises or reads back; both can be captured into a graph. */
+int th_conv2d_q8q8_fwd_residual(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                const int8_t *d_qb, const float *d_bparams, int relu, float *d_y, int per_channel, const float *d_affine,
+                                const float *d_res, const int8_t *d_res_q, int cpitch_r, const float *d_res_scale);
+int th_conv2d_q8q8_fwd_codes_residual(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                      const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                      const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
+                                      int per_channel, const float *d_affine, const float *d_res, const int8_t *d_res_q, int cpitch_r,
+                                      const float *d_res_scale);
 /* The max-pool on channel-last codes [n][h][w][cpitch] -> [n][h_out][w_out][cpitch], h_out = (h + 2 pad_h - k_h) / s_h + 1: every byte the
  * maximum over the in-image taps from -128 (the code of the float pool's -inf start), bytes c .. cpitch - 1 written 0, d_ypixsum the sum
  * over the c channels.  The codec never decreases in its argument, so this is the code of th_maxpool2d_fwd's result on finite values.

@@ -232,11 +232,26 @@ int tp_module_quantize_static_chain(const tp_module *m, const tp_tensor *const *
  * channel-last codes the conv (or the pool) writes with its scale.  LINKS alone is valid (Linear links only) and combines with the three
  * flags above.  Calibration, packing, tensors, scales and every output bit are those of the same flags without LINKS; only the launches
  * differ, and tp_qmodule_storage_bytes counts the re-laid rows of a Linear behind a Flatten link.  The value is 16: bit 8 stays an unknown
- * bit and is refused, like -1. */
+ * bit and is refused, like -1.
+ * TP_QBLOCKS (32; needs CONVS, refused by name without it) quantizes residual models.  Without it every refusal stands:
+ * ResidualBlock, BottleneckBlock and every exact_stride / exact_pointwise conv are refused with their messages.  With it the exact convs
+ * (3x3 stride 2 pad 1; 1x1 stride 1 or 2) are static convs like the stride-1 3x3, bare, in a BasicBlock or in a block, and a ResidualBlock /
+ * BottleneckBlock whose convs are all such convolutions gets a twin: its main branch as static stages with each BatchNorm2d in its
+ * conv's epilogue, and the skip connection r added in f32 in the last conv's epilogue (th_conv2d_q8q8_fwd_residual / _codes_residual),
+ *     y = max(((v * a) + b) + r, 0)   (each operation rounded once, in this order).
+ * Identity shortcut: r = (float)code * scale from the codes of the block's input as its first conv reads them.  Projected shortcut: the
+ * projection is one more static stage on the same codes (its calibrated scale equals the first conv's bit for bit), its BatchNorm2d in
+ * its epilogue, no ReLU, and r is its f32 map.  A block that holds a default strided or 1x1 conv (no convolution: SURVEY Q4 / Q9) is
+ * refused by name before anything is allocated: build it with exact_stride / pointwise_shortcut.  With CHAIN a block is a stage of the
+ * enclosing Sequential's run and the boundaries inside its main branch are links (the 128-channel rule applies; the identity residual
+ * is no boundary); the scales, tensors and every output bit are those of the same flags without CHAIN / LINKS.  tp_qmodule_tensor
+ * lists conv1, conv2, [conv3], [projection]; the scales follow that order; tp_qmodule_affine lists bn1, bn2, [bn3], [the shortcut's].
+ * tp_module_quantize keeps refusing blocks; blocks wider than 128 channels at a link run through f32; int8 training is out of scope. */
 #define TP_QSTATIC_CONVS 1
 #define TP_QSTATIC_CHAIN 2
 #define TP_QSTATIC_PER_CHANNEL 4
 #define TP_QSTATIC_LINKS 16
+#define TP_QBLOCKS 32
 int tp_module_quantize_static_ex(const tp_module *m, const tp_tensor *const *calib, int n_calib, int flags, tp_qmodule **out);
 /* tp_module_quantize_static_ex with the rule that turns the calibration tensors into each static layer's activation scale.  `flags`: the
  * TP_QSTATIC_* flags above, their rules unchanged; every twin form, the BatchNorm folds and the QAT inner layers combine with either

@@ -277,7 +277,8 @@ def accuracy(pred, targets) -> float:
 
 
 _QSTATIC_CONVS, _QSTATIC_CHAIN, _QSTATIC_PER_CHANNEL, _QSTATIC_LINKS = 1, 2, 4, 16      # include/taper_host.h's TP_QSTATIC_* flags
-_CALIB_MINMAX, _CALIB_PERCENTILE = 0, 1                                                 # ... and its TP_CALIB_* methods
+_QBLOCKS = 32                                                                           # ... its TP_QBLOCKS (residual models)
+_CALIB_MINMAX, _CALIB_PERCENTILE = 0, 1                                               # ... and its TP_CALIB_* methods
 
 
 # -- src/nn.rs, src/activation.rs ------------------------------------------------
@@ -379,6 +380,21 @@ class Module:
         flags = ((_QSTATIC_CONVS if convs or chain else 0) | (_QSTATIC_CHAIN if chain else 0) | (_QSTATIC_PER_CHANNEL if per_channel else 0)
                  | (_QSTATIC_LINKS if links else 0))
         return self._quantize_static(host.tp_module_quantize_static_cal, "quantize_static_calibrated", calib, flags, _CALIB_PERCENTILE,
+                                     int(round(float(percentile) * 1e4)), int(bins))
+
+    def quantize_static_residual(self, calib, chain=True, per_channel=False, links=False, percentile=None, bins=2048):
+        """The static conv twin of a residual model (TP_QBLOCKS with TP_QSTATIC_CONVS): the exact strided 3x3 and the exact 1x1 convs are
+        static like the stride-1 3x3, and a ResidualBlock / BottleneckBlock built from such convs runs its main branch as static stages
+        with the skip connection added in f32 inside the last conv's epilogue, y = max(((v * a) + b) + r, 0): r from the codes of the
+        block's input (identity shortcut) or from the projection's f32 map.  `chain`: a block is a stage of the enclosing Sequential's
+        run and the boundaries inside it are links; `per_channel`, `links` and `percentile` / `bins` combine as in the calls above
+        (percentile=None: min / max calibration).  The same scales, tensors and output bits with and without `chain` / `links`.  A block
+        with a default strided or 1x1 conv is refused by name: build it with exact_stride / pointwise_shortcut."""
+        flags = (_QSTATIC_CONVS | _QBLOCKS | (_QSTATIC_CHAIN if chain else 0) | (_QSTATIC_PER_CHANNEL if per_channel else 0)
+                 | (_QSTATIC_LINKS if links else 0))
+        if percentile is None:
+            return self._quantize_static(host.tp_module_quantize_static_ex, "quantize_static_residual", calib, flags)
+        return self._quantize_static(host.tp_module_quantize_static_cal, "quantize_static_residual", calib, flags, _CALIB_PERCENTILE,
                                      int(round(float(percentile) * 1e4)), int(bins))
 
     def _quantize_static(self, entry, name, calib, *flags):
@@ -523,9 +539,10 @@ class Conv2d(Module):
     """exact_stride: the layer is the exact 3x3 convolution with stride (2, 2) and padding (1, 1) (one group), and under
     set_full_backward(True) its weight and its input take gradients like a stride-1 layer's; the constructor refuses any other geometry
     with the flag by name.  Without it a strided Conv2d keeps the reference's general gather: not a convolution, no gradient.
-    The flag is constructor state (a checkpoint holds the parameters alone); quantize* refuse such a layer.
+    The flag is constructor state (a checkpoint holds the parameters alone); quantize* refuse such a layer, except
+    quantize_static_residual, where it is a static conv.
     exact_pointwise: the layer is the exact 1x1 convolution with stride (1, 1) or (2, 2) and no padding (one group), with the same
-    gradients, constructor state and quantize* refusal.  Without it a 1x1 Conv2d keeps the reference's reinterpretation."""
+    gradients, constructor state and quantize* refusal (quantize_static_residual takes it).  Without it a 1x1 Conv2d keeps the reference's reinterpretation."""
 
     def __init__(self, in_ch, out_ch, kernel_size, stride=None, padding=None, dilation=None, groups=None, bias=True,
                  seed=1, _relu=False, exact_stride=False, exact_pointwise=False):

@@ -372,7 +372,7 @@ static void quantize_static_into(const char *fn, const tp_module *m, const tp_te
     for (int i = 0; i < n_calib; ++i) c.push_back(calib && calib[i] ? calib[i]->t : Tensor());
     QuantizeOptions o;
     o.convs = (flags & TP_QSTATIC_CONVS) != 0, o.chain = (flags & TP_QSTATIC_CHAIN) != 0, o.per_channel = (flags & TP_QSTATIC_PER_CHANNEL) != 0;
-    o.links = (flags & TP_QSTATIC_LINKS) != 0;
+    o.links = (flags & TP_QSTATIC_LINKS) != 0, o.blocks = (flags & TP_QBLOCKS) != 0;
     o.calibration = cal;
     auto h = std::make_unique<tp_qmodule>();
     h->q = quantize_static(*m->m, c, o);
@@ -384,8 +384,9 @@ static void quantize_static_into(const char *fn, const tp_module *m, const tp_te
 }
 // the flag rules of every call that takes TP_QSTATIC_* flags
 static void check_qstatic_flags(const std::string &fn, int flags) {
-    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL | TP_QSTATIC_LINKS)) == 0, fn + ": unknown flag bits");
+    TAPER_ASSERT((flags & ~(TP_QSTATIC_CONVS | TP_QSTATIC_CHAIN | TP_QSTATIC_PER_CHANNEL | TP_QSTATIC_LINKS | TP_QBLOCKS)) == 0, fn + ": unknown flag bits");
     TAPER_ASSERT(!(flags & TP_QSTATIC_CHAIN) || (flags & TP_QSTATIC_CONVS), fn + ": TP_QSTATIC_CHAIN needs TP_QSTATIC_CONVS");
+    TAPER_ASSERT(!(flags & TP_QBLOCKS) || (flags & TP_QSTATIC_CONVS), fn + ": TP_QBLOCKS needs TP_QSTATIC_CONVS");
 }
 int tp_module_quantize_static(const tp_module *m, const tp_tensor *const *calib, int n_calib, tp_qmodule **out) {
     TP_BEGIN

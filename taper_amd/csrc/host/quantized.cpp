@@ -270,13 +270,24 @@ struct QEpilogue {
     bool relu = false;
     const QBatchNorm *bn = nullptr;
 };
+// a block's shortcut in the last conv's epilogue: an f32 map of the output's shape (a projected shortcut), or the codes the
+// block's first conv read with their scale (the identity shortcut); exactly one when set
+struct QResidual {
+    const Tensor *map = nullptr;
+    const QCodes *codes = nullptr;
+    const float *scale = nullptr;
+    explicit operator bool() const { return map || codes; }
+};
 class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: the same with the ReLU fused)
    public:
     // The integer product is a convolution, so it stands in for the float layer only where the float path is one: 3x3, stride 1, one
     // group, no dilation (th_conv3x3_fwd, with the weight buffer read as [c_in k_h k_w][c_out]: tensor.rs:1262).  The float 1x1 and general
     // paths keep the reference's scrambled gathers (tensor.rs:1799-1801, 1931): a twin of those stays weight-only, on the same kernels.
-    static bool can_be_static(const Conv2d &c) {
+    // exact (QuantizeOptions::blocks): the exact strided 3x3 and the exact pointwise convs are convolutions as well, on the same
+    // weight_layout 0 buffer, so the product stands in for them through the same re-lay
+    static bool can_be_static(const Conv2d &c, bool exact = false) {
         const Shape &ws = c.weight.shape();
+        if (exact && (c.exact_stride || c.exact_pointwise)) return true;   // (the constructor fixed their geometry: one group, no dilation)
         return c.groups == 1 && c.dilation == std::make_pair(1, 1) && c.stride == std::make_pair(1, 1) && ws[2] == 3 && ws[3] == 3;
     }
     // o.convs: the static int8 twin (quantize_static with convs) -- the weight codes re-laid once channel-last for the product (an internal
@@ -284,11 +295,11 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
     // (static only): one weight pair per effective output channel co, whose elements lie at (ci taps + tap) c_out + co of the buffer
     QConv(const Conv2d &c, int qtype, QuantizeOptions o = {})
         : geom_(std::make_shared<Conv2d>(c)),
-          w_(o.convs && o.per_channel && can_be_static(c) ? quantize_channels(c.weight, c.weight.shape()[0], 1, c.weight.shape()[0]) : quantize_tensor(c.weight, qtype)) {
+          w_(o.convs && o.per_channel && can_be_static(c, o.blocks) ? quantize_channels(c.weight, c.weight.shape()[0], 1, c.weight.shape()[0]) : quantize_tensor(c.weight, qtype)) {
         if (c.bias.defined()) b_ = std::make_unique<QTensor>(quantize_tensor(c.bias, qtype));
         geom_->weight = Tensor();   // the twin keeps the geometry only, not the source's f32 storage
         geom_->bias = Tensor();
-        if (!o.convs || !can_be_static(c)) return;
+        if (!o.convs || !can_be_static(c, o.blocks)) return;
         const Shape &ws = w_.shape;   // [c_out, c_in, k_h, k_w]
         cpitch_ = (size_t)th_qconv_i8_cpitch((int)ws[1]);
         relaid_ = Buffer::alloc(ws[0] * ws[2] * ws[3] * cpitch_ / 4);
@@ -312,8 +323,8 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
         QCodes codes;
     };
     QDest dest(bool sums) const { return QDest{act_.scale(), cpitch_, sums}; }   // this layer as the destination of the product ahead
-    // the integer product on codes made with this layer's scale
-    Output product(const QCodes &in, QEpilogue e, QDest d = {}) const {
+    // the integer product on codes made with this layer's scale; `r`: a block's shortcut, added behind e.bn and in front of the ReLU
+    Output product(const QCodes &in, QEpilogue e, QDest d = {}, QResidual r = {}) const {
         const Shape &ws = w_.shape;
         TAPER_ASSERT(in.c == ws[1] && in.cpitch == cpitch_, "QuantizedConv2d: input must be [batch, in_channels, h, w]");
         const int sh = geom_->stride.first, sw = geom_->stride.second, ph = geom_->padding.first, pw = geom_->padding.second;
@@ -328,6 +339,23 @@ class QConv : public QuantizedModule {   // nn.rs:336-429 (Conv2dReLU, 481-504: 
                      reinterpret_cast<const int8_t *>(relaid_->d), (int)ws[0], (int)ws[2], (int)ws[3], sh, sw, ph, pw, w_.params->d, b.i8(), b.params, fold, tail...));
         };
         Output out;
+        if (r) {   // th_conv2d_q8q8_fwd_residual / _codes_residual: the affine entries' lists, then the residual's four
+            TAPER_ASSERT(e.bn, "QuantizedConv2d: a residual needs a BatchNorm2d in the epilogue");
+            const bool fits = r.map ? r.map->shape() == Shape{in.n, ws[0], ho, wo} : r.codes->n == in.n && r.codes->c == ws[0] && r.codes->h == ho && r.codes->w == wo;
+            TAPER_ASSERT(fits, "QuantizedConv2d: the residual's shape differs from the output's");
+            const float *map = r.map ? r.map->dptr() : nullptr;
+            const int8_t *codes = r.codes ? r.codes->codes() : nullptr;
+            const int cpitch_r = r.codes ? (int)r.codes->cpitch : 0;
+            if (!d) {
+                out.y = Tensor::empty({in.n, ws[0], ho, wo});
+                run(th_conv2d_q8q8_fwd_residual, out.y.dptr(), pc, e.bn->pairs(), map, codes, cpitch_r, r.scale);
+            } else {
+                QCodes &q = out.codes = QCodes::alloc(in.n, ws[0], ho, wo, d.pitch);
+                run(th_conv2d_q8q8_fwd_codes_residual, d.scale, q.codes(), (int)q.cpitch, d.sums ? q.pixsum() : nullptr, pc, e.bn->pairs(), map, codes, cpitch_r,
+                    r.scale);
+            }
+            return out;
+        }
         if (!d) {
             out.y = Tensor::empty({in.n, ws[0], ho, wo});
             if (e.bn) run(th_conv2d_q8q8_fwd_affine, out.y.dptr(), pc, e.bn->pairs());
@@ -400,6 +428,92 @@ QCodes max_pool_codes(const QCodes &in, const MaxPool2d &mp) {
     return out;
 }
 
+// A ResidualBlock or a BottleneckBlock as its twin sees it: the main branch's conv + BatchNorm2d pairs in order, and the projection's
+// pair (null: the identity shortcut).  Empty for any other module.
+struct BlockView {
+    const char *name = nullptr;
+    std::vector<std::pair<const Conv2d *, const BatchNorm2d *>> main;
+    const Conv2d *proj = nullptr;
+    const BatchNorm2d *proj_bn = nullptr;
+    explicit operator bool() const { return name != nullptr; }
+    std::vector<const Conv2d *> convs() const {   // in the order of the block's parameters()
+        std::vector<const Conv2d *> out;
+        for (const auto &p : main) out.push_back(p.first);
+        if (proj) out.push_back(proj);
+        return out;
+    }
+};
+BlockView block_view(const Module &m) {
+    BlockView v;
+    if (auto *rb = dynamic_cast<const ResidualBlock *>(&m)) {
+        v.name = "ResidualBlock";
+        v.main = {{&rb->conv1, &rb->bn1}, {&rb->conv2, &rb->bn2}};
+        v.proj = rb->shortcut_conv.get(), v.proj_bn = rb->shortcut_bn.get();
+    } else if (auto *nb = dynamic_cast<const BottleneckBlock *>(&m)) {
+        v.name = "BottleneckBlock";
+        v.main = {{&nb->conv1, &nb->bn1}, {&nb->conv2, &nb->bn2}, {&nb->conv3, &nb->bn3}};
+        v.proj = nb->shortcut_conv.get(), v.proj_bn = nb->shortcut_bn.get();
+    }
+    return v;
+}
+
+// The twin of a ResidualBlock or a BottleneckBlock (QuantizeOptions::blocks): the main branch as a run of static stages, each
+// BatchNorm2d in its conv's epilogue, and the skip connection added in f32 in the last conv's epilogue behind its BatchNorm2d and in
+// front of the ReLU -- where th_bn_residual_fwd adds it in the float block.  The block reads codes made with conv1's scale.  Identity
+// shortcut: those codes are the residual (th_conv2d_q8q8_fwd_residual's d_res_q with conv1's scale) in every form of the twin.
+// Projected shortcut: the projection is one more static stage on the same codes (its scale is conv1's bit for bit: both observed the
+// same tensor), its BatchNorm2d in its epilogue, no ReLU, f32 out; the last stage takes that map (d_res).  With `chain` every boundary
+// inside the main branch whose producing conv has at most th_qconv_i8_chain_max_cout() output channels is a link.
+class QBlock : public QuantizedModule {
+   public:
+    QBlock(const BlockView &v, int qtype, QuantizeOptions o) {
+        for (const auto &p : v.main) main_.push_back(Part{std::make_unique<QConv>(*p.first, qtype, o), std::make_unique<QBatchNorm>(*p.second)});
+        if (v.proj) proj_ = Part{std::make_unique<QConv>(*v.proj, qtype, o), std::make_unique<QBatchNorm>(*v.proj_bn)};
+        for (size_t i = 0; i + 1 < main_.size(); ++i) link_.push_back(o.chain && main_[i].conv->out_channels() <= (size_t)th_qconv_i8_chain_max_cout());
+        for (const Part &p : main_) TAPER_ASSERT(p.conv->is_static(), std::string(v.name) + ": every conv of a block twin must be static");
+    }
+    const QConv &head() const { return *main_[0].conv; }   // the conv whose scale the block's input codes are made with
+    const QConv &conv(size_t i) const { return *main_[i].conv; }
+    const QConv *proj() const { return proj_.conv.get(); }
+    size_t out_channels() const { return main_.back().conv->out_channels(); }
+    // the block on the codes of its input (made with head()'s scale), into f32 or the next stage's codes
+    QConv::Output run(const QCodes &in, QDest d = {}) const {
+        Tensor shortcut;
+        if (proj_.conv) shortcut = proj_.conv->product(in, QEpilogue{proj_.bn->fuse_relu(), proj_.bn.get()}).y;
+        QCodes cur = in;
+        for (size_t i = 0; i + 1 < main_.size(); ++i) {
+            const Part &p = main_[i];
+            const QConv &next = *main_[i + 1].conv;
+            const QEpilogue e{p.bn->fuse_relu(), p.bn.get()};
+            cur = link_[i] ? p.conv->product(cur, e, next.dest(/*sums=*/true)).codes : next.encode(p.conv->product(cur, e).y);
+        }
+        const Part &last = main_.back();
+        const QResidual r = proj_.conv ? QResidual{&shortcut, nullptr, nullptr} : QResidual{nullptr, &in, head().act().scale()};
+        return last.conv->product(cur, QEpilogue{last.bn->fuse_relu(), last.bn.get()}, d, r);
+    }
+    Tensor forward(const Tensor &x) const override { return run(head().encode(x)).y; }   // alone: one codec, then the stages
+    void tensors(std::vector<const QTensor *> *out) const override { each([&](const Part &p) { p.conv->tensors(out); }); }
+    void act_scales(std::vector<const float *> *out) const override { each([&](const Part &p) { p.conv->act_scales(out); }); }
+    void calibrations(std::vector<ActCalibration> *out) const override { each([&](const Part &p) { p.conv->calibrations(out); }); }
+    void affines(std::vector<std::pair<const float *, size_t>> *out) const override { each([&](const Part &p) { p.bn->affines(out); }); }
+    int chain_links() const override { return (int)std::count(link_.begin(), link_.end(), true); }   // the inner boundaries crossed in int8
+    void each_act(const std::function<void(const ActScale &)> &f) const { each([&](const Part &p) { f(p.conv->act()); }); }
+
+   private:
+    struct Part {
+        std::unique_ptr<QConv> conv;
+        std::unique_ptr<QBatchNorm> bn;
+    };
+    template <class F>
+    void each(F f) const {   // conv1, conv2, [conv3], [projection]: the order of the source's parameters()
+        for (const Part &p : main_) f(p);
+        if (proj_.conv) f(proj_);
+    }
+    std::vector<Part> main_;
+    Part proj_;
+    std::vector<bool> link_;   // link_[i]: main_[i]'s product writes main_[i + 1]'s codes
+};
+
 class QSequential : public QuantizedModule {   // nn.rs:153-177
    public:
     std::vector<std::unique_ptr<QuantizedModule>> layers;
@@ -407,8 +521,11 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
     // its own leaves the layer standing: the ReLU comes first there); `fold.relu` = the ReLU folded in behind both -- the BatchNorm's own
     // or a ReLU layer; with `chain`, whether a link starts here -- `pool` (or nullptr) and the static conv `next`, the run's next stage,
     // that takes the codes.
+    // A block's twin is a stage as well: `block` instead of `conv`, nothing folded (its tail holds its own BatchNorm2d and
+    // ReLU); it reads the codes made with its first conv's scale, so as `next` it is that conv.
     struct Stage {
         const QConv *conv = nullptr;
+        const QBlock *block = nullptr;
         QEpilogue fold;
         const MaxPool2d *pool = nullptr;
         const QConv *next = nullptr;
@@ -440,6 +557,9 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
             auto *c = j < layers.size() ? dynamic_cast<const QConv *>(layers[j].get()) : nullptr;
             return c && c->is_static() ? c : nullptr;
         };
+        auto blk = [&](size_t j) { return j < layers.size() ? dynamic_cast<const QBlock *>(layers[j].get()) : nullptr; };
+        // the conv that reads the codes a stage at layer j takes: a static conv itself, a block's first conv
+        auto head = [&](size_t j) -> const QConv * { return stat(j) ? stat(j) : blk(j) ? &blk(j)->head() : nullptr; };
         auto slin = [&](size_t j) {
             auto *l = j < layers.size() ? dynamic_cast<QLinear *>(layers[j].get()) : nullptr;
             return l && l->is_static() ? l : nullptr;
@@ -459,26 +579,31 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
             } else if ((s.lin = dynamic_cast<const QLinear *>(layers[i].get()))) {
                 s.relu = pass(i + 1) && pass(i + 1)->is_relu();   // Linear + ReLU: one launch, the ReLU in its epilogue
                 i += s.relu ? 2 : 1;
-            } else if (stat(i)) {   // conv + ReLU: the ReLU in the product's epilogue
-                for (const QConv *cv = stat(i); cv; cv = s.run.back().next) {
+            } else if (head(i)) {   // conv + ReLU: the ReLU in the product's epilogue
+                for (const QConv *hd = head(i); hd; hd = s.run.back().next) {
                     Stage st;
-                    st.conv = cv;
                     size_t after = i + 1;   // the first layer behind everything the stage folds
-                    if (!cv->own_relu() && after < layers.size() && (st.fold.bn = dynamic_cast<const QBatchNorm *>(layers[after].get()))) {
-                        st.fold.relu = st.fold.bn->fuse_relu();
-                        ++after;
-                    }
-                    if (pass(after) && pass(after)->is_relu()) {   // (behind a BatchNorm with a ReLU of its own: the same ReLU a second time)
-                        st.fold.relu = true;
-                        ++after;
+                    if ((st.block = blk(i))) {
+                        // (a block folds nothing: a ReLU layer behind it would be its own ReLU a second time, and runs as a layer)
+                    } else {
+                        const QConv *cv = st.conv = hd;
+                        if (!cv->own_relu() && after < layers.size() && (st.fold.bn = dynamic_cast<const QBatchNorm *>(layers[after].get()))) {
+                            st.fold.relu = st.fold.bn->fuse_relu();
+                            ++after;
+                        }
+                        if (pass(after) && pass(after)->is_relu()) {   // (behind a BatchNorm with a ReLU of its own: the same ReLU a second time)
+                            st.fold.relu = true;
+                            ++after;
+                        }
                     }
                     i = after;
-                    if (chain && cv->out_channels() <= (size_t)th_qconv_i8_chain_max_cout()) {
+                    const size_t c = st.block ? st.block->out_channels() : st.conv->out_channels();
+                    if (chain && c <= (size_t)th_qconv_i8_chain_max_cout()) {
                         size_t j = after;
                         if (pass(j) && pass(j)->max_pool()) st.pool = pass(j++)->max_pool();
                         QLinear *fl = links && pass(j) && pass(j)->flatten() && pass(j)->flatten()->start_dim == 1 ? slin(j + 1) : nullptr;
-                        const size_t c = cv->out_channels(), cpitch = (size_t)th_qconv_i8_cpitch((int)c);
-                        if ((st.next = stat(j))) {
+                        const size_t cpitch = (size_t)th_qconv_i8_cpitch((int)c);
+                        if ((st.next = head(j))) {
                             i = j;   // a link: the run goes on there
                         } else if (fl && fl->in_features() % c == 0 && fl->in_features() / c * cpitch <= (size_t)th_q8q8_max_k()) {
                             fl->link_flatten(c, fl->in_features() / c, cpitch);   // a Flatten link: the Linears take over from there
@@ -518,13 +643,14 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
             } else if (s.plain) {
                 x = s.plain->forward(x);
             } else if (!s.run.empty()) {   // a run: one codec, then codes from product to product (pooled buffers, each returned when `cur` moves on)
-                QCodes cur = s.run[0].conv->encode(x);
+                QCodes cur = (s.run[0].block ? s.run[0].block->head() : *s.run[0].conv).encode(x);
                 for (const Stage &st : s.run) {
                     const bool last = !st.next;
+                    auto produce = [&](QDest d) { return st.block ? st.block->run(cur, d) : st.conv->product(cur, st.fold, d); };
                     if (last && !s.flat) {
-                        x = st.conv->product(cur, st.fold).y;
+                        x = produce({}).y;
                     } else {
-                        QCodes out = st.conv->product(cur, st.fold, last ? s.lrun[0].lin->dest() : st.next->dest(/*sums=*/!st.pool)).codes;
+                        QCodes out = produce(last ? s.lrun[0].lin->dest() : st.next->dest(/*sums=*/!st.pool)).codes;
                         cur = st.pool ? max_pool_codes(out, *st.pool) : out;
                     }
                 }
@@ -560,6 +686,8 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
         int links = 0;
         for (const Step &s : steps_) {
             if (s.plain) links += s.plain->chain_links();
+            for (const Stage &st : s.run)
+                if (st.block) links += st.block->chain_links();   // the links inside a block's main branch
             links += (s.run.empty() ? 0 : (int)s.run.size() - 1) + (s.flat ? 1 : 0) + (s.lrun.empty() ? 0 : (int)s.lrun.size() - 1);
         }
         return links;
@@ -571,17 +699,25 @@ class QSequential : public QuantizedModule {   // nn.rs:153-177
 };
 
 // nn.rs:15: every module without a quantize() of its own (Dropout among them) panics.  batchnorm: whether BatchNorm2d and BasicBlock
-// have one -- in the static twins; the weight-only quantize() keeps the reference's refusal
-void check_quantizable(const Module &m, bool batchnorm) {
+// have one -- in the static twins; the weight-only quantize() keeps the reference's refusal.  blocks (QuantizeOptions::blocks,
+// DESIGN 6t): the exact convs, and a ResidualBlock / BottleneckBlock whose convs are all convolutions, have one as well
+void check_quantizable(const Module &m, bool batchnorm, bool blocks = false) {
     if (auto *s = dynamic_cast<const Sequential *>(&m)) {
-        for (const auto &l : s->layers) check_quantizable(*l, batchnorm);
+        for (const auto &l : s->layers) check_quantizable(*l, batchnorm, blocks);
         return;
     }
-    // the exact strided convolution has no packed twin yet (the int8 product of a strided conv stands in for the general gather, Q9)
+    if (const BlockView v = block_view(m); v && blocks) {
+        for (const Conv2d *c : v.convs())
+            if (!QConv::can_be_static(*c, /*exact=*/true))
+                throw Error(std::string(v.name) + ": the block holds a default strided or 1x1 Conv2d, whose float path is no convolution (SURVEY Q4 / Q9): " +
+                            "build the block with exact_stride / pointwise_shortcut to quantize it");
+        return;
+    }
+    // without `blocks` the exact convs keep their refusal (the int8 product of a default strided conv stands in for the general gather, Q9)
     const auto *cv = dynamic_cast<const Conv2d *>(&m);
     if (const auto *bb = dynamic_cast<const BasicBlock *>(&m)) cv = &bb->conv;
-    if (cv && cv->exact_stride) throw Error("exact-stride Conv2d: quantized twins are a follow-up");
-    if (cv && cv->exact_pointwise) throw Error("exact-pointwise Conv2d: quantized twins are a follow-up");
+    if (cv && cv->exact_stride && !blocks) throw Error("exact-stride Conv2d: quantized twins are a follow-up");
+    if (cv && cv->exact_pointwise && !blocks) throw Error("exact-pointwise Conv2d: quantized twins are a follow-up");
     if (dynamic_cast<const Linear *>(&m) || dynamic_cast<const Conv2d *>(&m) || dynamic_cast<const QATModule *>(&m) || dynamic_cast<const ReLU *>(&m) ||
         dynamic_cast<const Sigmoid *>(&m) || dynamic_cast<const MaxPool2d *>(&m) || dynamic_cast<const AvgPool2d *>(&m) ||
         dynamic_cast<const AdaptiveAvgPool2d *>(&m) || dynamic_cast<const Flatten *>(&m) ||
@@ -627,6 +763,7 @@ std::unique_ptr<QuantizedModule> quantize_checked(const Module &m, int qtype, Qu
     if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) return std::make_unique<QBatchNorm>(*bn);
     if (auto *lin = dynamic_cast<const Linear *>(&l)) return std::make_unique<QLinear>(*lin, qtype, o, /*keep_packed=*/nested && o.links && o.chain);
     if (auto *c = dynamic_cast<const Conv2d *>(&l)) return std::make_unique<QConv>(*c, qtype, o);
+    if (const BlockView v = block_view(l); v && o.blocks) return std::make_unique<QBlock>(v, qtype, o);
     std::shared_ptr<Module> p;
     if (!(p = copy_of<ReLU>(l)) && !(p = copy_of<Sigmoid>(l)) && !(p = copy_of<MaxPool2d>(l)) && !(p = copy_of<AvgPool2d>(l)) &&
         !(p = copy_of<AdaptiveAvgPool2d>(l)) && !(p = copy_of<Flatten>(l)))
@@ -640,6 +777,8 @@ void layers_of(const Module &m, std::vector<const L *> *out) {
     for (const Module *l : leaves_of(m)) {
         if (auto *p = dynamic_cast<const L *>(l)) out->push_back(p);
         else if (l != &m) layers_of(*l, out);
+        else if constexpr (std::is_same_v<L, Conv2d>)   // a block is one leaf: its convs are its twin's
+            for (const Conv2d *c : block_view(*l).convs()) out->push_back(c);
     }
 }
 
@@ -659,16 +798,42 @@ Tensor calibrate(const Module &m, const QuantizedModule &q, const Tensor &x, boo
         return h;
     }
     const Module &l = *leaves[0];
-    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) {
-        TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == bn->num_features, "BatchNorm2d: expected a 4-D input [N, num_features, H, W]");
+    // a BatchNorm2d in eval mode, by the kernels themselves; with `residual` the skip connection added in the same map (th_bn_residual_fwd)
+    auto bn_eval = [](const BatchNorm2d &bn, const Tensor &x, const Tensor *residual) {
+        TAPER_ASSERT(x.shape().size() == 4 && x.shape()[1] == bn.num_features, "BatchNorm2d: expected a 4-D input [N, num_features, H, W]");
+        TAPER_ASSERT(!residual || residual->shape() == x.shape(), "BatchNorm2d: the residual's shape differs from the input's");
         const size_t hw = x.shape()[2] * x.shape()[3];
         TAPER_ASSERT(x.shape()[0] <= 0x7fffffffu && hw <= 0x7fffffffu, "BatchNorm2d: input too large");
         Tensor y = Tensor::empty(x.shape());
-        auto saved = Buffer::alloc(2 * bn->num_features);
-        TH(th_batchnorm2d_fwd(Device::ctx(), x.dptr(), bn->gamma.dptr(), bn->beta.dptr(), y.dptr(), bn->running_mean.dptr(), bn->running_var.dptr(), saved->d,
-                              saved->d + bn->num_features, (int)x.shape()[0], (int)bn->num_features, (int)hw, bn->eps, bn->momentum, /*training=*/0,
-                              bn->fuse_relu ? 1 : 0));
+        auto saved = Buffer::alloc(2 * bn.num_features);
+        const int n = (int)x.shape()[0], c = (int)bn.num_features, relu = bn.fuse_relu ? 1 : 0;
+        if (residual)
+            TH(th_bn_residual_fwd(Device::ctx(), x.dptr(), residual->dptr(), bn.gamma.dptr(), bn.beta.dptr(), y.dptr(), bn.running_mean.dptr(),
+                                  bn.running_var.dptr(), saved->d, saved->d + bn.num_features, n, c, (int)hw, bn.eps, bn.momentum, /*training=*/0, relu));
+        else
+            TH(th_batchnorm2d_fwd(Device::ctx(), x.dptr(), bn.gamma.dptr(), bn.beta.dptr(), y.dptr(), bn.running_mean.dptr(), bn.running_var.dptr(), saved->d,
+                                  saved->d + bn.num_features, n, c, (int)hw, bn.eps, bn.momentum, /*training=*/0, relu));
         return y;
+    };
+    if (auto *bn = dynamic_cast<const BatchNorm2d *>(&l)) return bn_eval(*bn, x, nullptr);
+    if (const BlockView v = block_view(l)) {   // the float block, every conv of its twin shown its input; conv1 and the projection see the same tensor
+        auto &qb = dynamic_cast<const QBlock &>(q);
+        auto see = [&](const QConv &qc, const Tensor &t) { hist_bins ? qc.act().observe_hist(t, hist_bins) : qc.act().observe(t, first); };
+        auto conv = [&](const Conv2d &cv, const Tensor &t) { return cv.forward_with(t, plain(cv.weight), plain(cv.bias)); };
+        Tensor shortcut = x, h = x;
+        for (size_t i = 0; i < v.main.size(); ++i) {
+            see(qb.conv(i), h);
+            if (i + 1 < v.main.size()) {
+                h = bn_eval(*v.main[i].second, conv(*v.main[i].first, h), nullptr);
+                continue;
+            }
+            if (v.proj) {
+                see(*qb.proj(), x);
+                shortcut = bn_eval(*v.proj_bn, conv(*v.proj, x), nullptr);
+            }
+            h = bn_eval(*v.main[i].second, conv(*v.main[i].first, h), &shortcut);
+        }
+        return h;
     }
     if (auto *lin = dynamic_cast<const Linear *>(&l)) {
         const ActScale &act = dynamic_cast<const QLinear &>(q).act();
@@ -691,6 +856,8 @@ void each_act_scale(const QuantizedModule &q, const std::function<void(const Act
         if (l->is_static()) f(l->act());
     } else if (auto *c = dynamic_cast<const QConv *>(&q)) {
         if (c->is_static()) f(c->act());
+    } else if (auto *b = dynamic_cast<const QBlock *>(&q)) {
+        b->each_act(f);
     }
 }
 
@@ -720,7 +887,8 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
     o.linears = true;
     o.convs = o.convs || o.chain;
     // every refusal before anything is allocated
-    check_quantizable(m, /*batchnorm=*/true);
+    TAPER_ASSERT(!o.blocks || o.convs, "quantize_static: blocks needs convs (a block's twin is a run of static convs)");
+    check_quantizable(m, /*batchnorm=*/true, o.blocks);
     const Calibration &cal = o.calibration;
     const bool percentile = cal.method == CalibMethod::Percentile;
     TAPER_ASSERT(percentile || cal.method == CalibMethod::MinMax, "quantize_static: unknown calibration method " + std::to_string((int)cal.method));
@@ -742,7 +910,7 @@ std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vec
         layers_of(m, &cvs);
         for (const Conv2d *c : cvs) {
             const Shape &ws = c->weight.shape();
-            TAPER_ASSERT(!QConv::can_be_static(*c) || ws[1] * ws[2] * ws[3] <= max_k,
+            TAPER_ASSERT(!QConv::can_be_static(*c, o.blocks) || ws[1] * ws[2] * ws[3] <= max_k,
                          "quantize_static: a Conv2d with in_channels * k_h * k_w = " + std::to_string(ws[1] * ws[2] * ws[3]) + above);
         }
     }

@@ -638,9 +638,24 @@ std::unique_ptr<QuantizedModule> quantize(const Module &m, QType qtype, bool ena
 // channels add nothing; integer sums have no order).  Such a weight's storage_bytes() counts the re-laid rows, tensors() still gives the
 // packed codes.  Anything else at a boundary (a Sigmoid, a nested Sequential, another Flatten, an AvgPool, a wider conv) is no link and runs
 // as before.  chain_links() counts every int8 boundary: conv -> conv, Flatten, Linear -> Linear.
-// (linears: set by quantize_static itself -- every Linear static; quantize() leaves all five off)
+// blocks (with convs): residual models.  Without it every refusal stands: ResidualBlock, BottleneckBlock and every exact_stride /
+// exact_pointwise conv are refused by name.  With it the exact convs (3x3 stride 2 pad 1; 1x1 stride 1 or 2) are static convs like the
+// stride-1 3x3 -- they are convolutions on the same weight_layout 0 buffer, so the same re-lay and product stand in for them, bare, in a
+// BasicBlock or in a block -- and a ResidualBlock / BottleneckBlock whose convs are all such convolutions gets a twin: its main branch
+// as static stages (each BatchNorm2d in its conv's epilogue), the skip connection added in f32 in the last conv's epilogue behind the
+// BatchNorm2d's affine and in front of the ReLU and the codec (th_conv2d_q8q8_fwd_residual / _codes_residual):
+//     y = max(((v * a) + b) + r, 0)
+// Identity shortcut: r = (float)code * scale from the codes of the block's input as conv1 reads them, in every form.  Projected shortcut:
+// the projection is a static stage on those same codes (conv1 and the projection observe the same tensor, so their scales are equal bit
+// for bit), its BatchNorm2d in its epilogue, no ReLU, f32 out, and r is that map.  A block holding a default strided or 1x1 conv (no
+// convolution: SURVEY Q4 / Q9) is refused by name before anything is allocated.  With chain a block is a stage of the enclosing
+// Sequential's run (it takes the codes the stage in front writes and writes the next stage's), and every boundary inside its main branch
+// behind a conv of at most th_qconv_i8_chain_max_cout() channels is a link; chain_links() counts those too (the identity residual is no
+// boundary).  tensors() / act_scales(): conv1, conv2, [conv3], [projection]; affines(): bn1, bn2, [bn3], [the shortcut's].  The weight-only
+// quantize() of blocks, blocks wider than 128 channels at a link (they run, through f32) and int8 training are out of scope.
+// (linears: set by quantize_static itself -- every Linear static; quantize() leaves all six off)
 struct QuantizeOptions {
-    bool linears = false, convs = false, chain = false, per_channel = false, links = false;
+    bool linears = false, convs = false, chain = false, per_channel = false, links = false, blocks = false;
     Calibration calibration;   // combines with every member above: only the value of each layer's scale differs
 };
 std::unique_ptr<QuantizedModule> quantize_static(const Module &m, const std::vector<Tensor> &calib, QuantizeOptions o = {});

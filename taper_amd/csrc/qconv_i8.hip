@@ -12,6 +12,8 @@
 //   th_conv2d_q8q8_fwd_pc, th_conv2d_q8q8_fwd_codes_pc: both with one {mw, sw} per output channel, a template flag of the kernel
 //   th_conv2d_q8q8_fwd_affine, th_conv2d_q8q8_fwd_codes_affine: both with a frozen BatchNorm2d behind the bias, y = v a[co] + b[co], then the
 //                              ReLU: one more template flag, the pairs {a, b} staged beside the weight pairs
+//   th_conv2d_q8q8_fwd_residual, th_conv2d_q8q8_fwd_codes_residual: the affine twins with a skip connection's value added behind the affine and in
+//                              front of the ReLU: an f32 NCHW map of the output's shape, or channel-last codes with their scale
 //   th_maxpool2d_nhwc_int8     the max-pool on channel-last codes (the codec is monotone: the maximum of the codes is the code of the maximum)
 //
 // With both operands channel-last a 16-byte piece of K is 16 consecutive channels of one tap: M = n h_out w_out output pixels, N = c_out,
@@ -83,6 +85,10 @@ struct QcArgs {
     QWindow win;
     int cpitch, c_out, M, relu, tiles_n;
     const float *affine;   // AFFINE: {a, b} per output channel (null otherwise)
+    const float *res;      // RES == 1: the f32 residual [n][c_out][h_out][w_out]
+    const int8_t *res_q;   // RES == 2: the residual's codes [n][h_out][w_out][cpitch_r] with the scale *res_scale
+    const float *res_scale;
+    int cpitch_r;
 };
 
 // A workgroup owns 128 output pixels (any run of the n h_out w_out list: it may span map rows and images) by 32 NT channels; wave v
@@ -99,7 +105,13 @@ struct QcArgs {
 // the epilogue reads them from there -- 16 NT dependent loads from memory a lane cost 2.6 - 7.5 us a layer, measured; this costs 0.0 - 0.6.
 // AFFINE: a frozen BatchNorm2d behind the layer: the value is q8_value without its ReLU, then __fadd_rn(__fmul_rn(v, a), b) with
 // the channel's {a, b}, then the ReLU.  The workgroup's 32 NT pairs are staged like the weight pairs, behind them and the same barrier.
-template <int NT, bool CODES, bool PC, bool AFFINE = false>
+// RES (with AFFINE): a skip connection's value r is added behind the affine and in front of the ReLU (affine_residual_value).
+// 1: r is read from an f32 map of the output's shape at the f32 store's address pattern, 32 consecutive pixels of one channel plane a wave
+// access, a tile's 16 values requested before the first is used (each loaded next to its use cost 3 - 11 us a call, measured).
+// 2: r = __fmul_rn((float)qr, *res_scale) with qr the code at byte co of the pixel's row of a channel-last map; an accumulator
+// group's four channels are one word of that row, at byte 8 (reg >> 2) + 4 (lane >> 5) of the tile -- four dword loads a tile, the words
+// the codes form's swaps would gather.  A pixel past M and a word whose first channel is past c_out are not read.
+template <int NT, bool CODES, bool PC, bool AFFINE = false, int RES = 0>
 __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     __shared__ uint4 lds_x[2][kQcPix * 4];          // 16 KB
     __shared__ uint4 lds_w[2][kQcChan * NT * 4];    // 4 / 8 / 16 KB
@@ -198,9 +210,31 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
     if (live) a.win.for_taps(o.oh, o.ow, [&](int ih, int iw) { rs += ps[ih * a.win.w + iw]; });
     const float sx = a.xscale[0], mw = PC ? 0.f : a.wparams[0], sw = PC ? 0.f : a.wparams[1], rterm = q8_rterm(mw, rs), sy = CODES ? a.yscale[0] : 0.f;
     float *yp = CODES ? nullptr : a.y + ((size_t)o.img * a.c_out + col0 + 4 * h) * hw_out + o.p;   // the f32 form: this pixel in the lane's first channel plane
+    const float *rp = nullptr;      // RES == 1: this pixel in the residual's plane of the lane's first channel
+    const uint32_t *rrow = nullptr; // RES == 2: the word at byte col0 + 4 h of this pixel's row of residual codes
+    float sr = 0.f;
+    if constexpr (RES == 1) rp = a.res + ((size_t)o.img * a.c_out + col0 + 4 * h) * hw_out + o.p;
+    if constexpr (RES == 2) {
+        rrow = (const uint32_t *)(a.res_q + (size_t)(live ? m : 0) * a.cpitch_r + col0 + 4 * h);
+        sr = a.res_scale[0];
+    }
     int sum = 0;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
+        uint32_t rw[4] = {0, 0, 0, 0};   // RES == 2: the lane's four words of this tile
+        if constexpr (RES == 2) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                if (live && col0 + 32 * j + 8 * g + 4 * h < a.c_out) rw[g] = rrow[8 * j + 2 * g];
+        }
+        float rv[16];   // RES == 1: the lane's 16 values of this tile, all requested before the first is used
+        if constexpr (RES == 1) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int c = 32 * j + (e & 3) + 8 * (e >> 2);
+                rv[e] = live && col0 + c + 4 * h < a.c_out ? rp[(size_t)c * hw_out] : 0.f;
+            }
+        }
         int q[16];   // CODES: the lane's channels of this tile through the activation codec with the next layer's scale; past c_out the code 0
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -209,7 +243,13 @@ __global__ __launch_bounds__(256) void qconv_i8_kernel(QcArgs a) {
             if (co >= a.c_out) continue;
             float v = q8_value(acc[j][e], rs, PC ? q8_rterm(pairs[co - col0].x, rs) : rterm, sx, PC ? pairs[co - col0].y : sw, a.qb != nullptr,
                                [&] { return dequant_int8(a.qb[co], a.bparams[1], a.bparams[0]); }, AFFINE ? 0 : a.relu);
-            if constexpr (AFFINE) v = affine_value(v, ab[co - col0].x, ab[co - col0].y, a.relu);
+            if constexpr (AFFINE && RES == 0) v = affine_value(v, ab[co - col0].x, ab[co - col0].y, a.relu);
+            if constexpr (RES != 0) {
+                float r;   // (a pixel past M read nothing: its value is stored nowhere)
+                if constexpr (RES == 1) r = rv[e];
+                else r = __fmul_rn((float)(int)(int8_t)((rw[e >> 2] >> (8 * (e & 3))) & 0xFF), sr);
+                v = affine_residual_value(v, ab[co - col0].x, ab[co - col0].y, r, a.relu);
+            }
             if constexpr (CODES) {
                 q[e] = act_code(v, sy);
                 sum += q[e];
@@ -256,13 +296,19 @@ static const char *qconv_plan(int n, int c_in, int h, int w, int c_out, int k_h,
     return nullptr;
 }
 
-// the kernel of a plan's NT and a call's form: one lookup over (nt, codes, pc, affine)
+// the kernel of a plan's NT and a call's form: one lookup over (nt, codes, pc, affine), or over (nt, codes, pc, res) for a residual
 using QcKernel = void (*)(QcArgs);
-template <bool CODES, bool PC, bool AFFINE>
+template <bool CODES, bool PC, bool AFFINE, int RES = 0>
 static QcKernel qconv_kernel_of(int nt) {
-    return nt == 1 ? qconv_i8_kernel<1, CODES, PC, AFFINE> : nt == 2 ? qconv_i8_kernel<2, CODES, PC, AFFINE> : qconv_i8_kernel<4, CODES, PC, AFFINE>;
+    return nt == 1 ? qconv_i8_kernel<1, CODES, PC, AFFINE, RES> : nt == 2 ? qconv_i8_kernel<2, CODES, PC, AFFINE, RES> : qconv_i8_kernel<4, CODES, PC, AFFINE, RES>;
 }
-static QcKernel qconv_kernel(int nt, bool codes, bool pc, bool affine) {
+static QcKernel qconv_kernel(int nt, bool codes, bool pc, bool affine, int res) {
+    if (res) {
+        static constexpr QcKernel (*of_res[2][2][2])(int) = {
+            {{qconv_kernel_of<false, false, true, 1>, qconv_kernel_of<false, false, true, 2>}, {qconv_kernel_of<false, true, true, 1>, qconv_kernel_of<false, true, true, 2>}},
+            {{qconv_kernel_of<true, false, true, 1>, qconv_kernel_of<true, false, true, 2>}, {qconv_kernel_of<true, true, true, 1>, qconv_kernel_of<true, true, true, 2>}}};
+        return of_res[codes][pc][res - 1](nt);
+    }
     static constexpr QcKernel (*of[2][2][2])(int) = {
         {{qconv_kernel_of<false, false, false>, qconv_kernel_of<false, false, true>}, {qconv_kernel_of<false, true, false>, qconv_kernel_of<false, true, true>}},
         {{qconv_kernel_of<true, false, false>, qconv_kernel_of<true, false, true>}, {qconv_kernel_of<true, true, false>, qconv_kernel_of<true, true, true>}}};
@@ -346,8 +392,8 @@ int th_pack_conv_weight_taper_int8(th_ctx *ctx, const int8_t *d_src, int c_out, 
 
 // One call of a product, as its entry point fills it: fn = the entry point's name for the messages; codes, pc, affine = its form (pc:
 // d_wparams holds a pair per output channel; affine: d_affine holds {a, b} per output channel); then the arguments in the prototypes'
-// order -- the 21 that every entry point takes (QC_SHARED), the f32 form's output, the codes form's four, d_affine.  What a form does not
-// take stays null / 0 and is not read.
+// order -- the 21 that every entry point takes (QC_SHARED), the f32 form's output, the codes form's four, d_affine, and with
+// `residual` the skip connection's four (exactly one of d_res, d_res_q).  What a form does not take stays null / 0 and is not read.
 struct QcCall {
     const char *fn;
     bool codes, pc, affine;
@@ -369,6 +415,11 @@ struct QcCall {
     int cpitch_y = 0;
     int *d_ypixsum = nullptr;
     const float *d_affine = nullptr;
+    bool residual = false;
+    const float *d_res = nullptr;
+    const int8_t *d_res_q = nullptr;
+    int cpitch_r = 0;
+    const float *d_res_scale = nullptr;
 };
 #define QC_SHARED ctx, d_qx, cpitch, d_pixsum, d_xscale, n, c_in, h, w, d_qw, c_out, k_h, k_w, s_h, s_w, pad_h, pad_w, d_wparams, d_qb, d_bparams, relu
 
@@ -389,10 +440,20 @@ static int qconv_run(const QcCall &c) {
         TH_REQUIRE(((uintptr_t)c.d_qy & 15) == 0, "%s: the output code pointer must be 16-byte aligned", c.fn);
         TH_REQUIRE(c.cpitch_y % 16 == 0 && c.cpitch_y >= c.c_out, "%s: cpitch_y %d must be a multiple of 16 and at least c_out %d", c.fn, c.cpitch_y, c.c_out);
     }
+    if (c.residual) {
+        TH_REQUIRE((c.d_res != nullptr) != (c.d_res_q != nullptr), "%s: exactly one of d_res (an f32 residual) and d_res_q (a residual in codes) must be set", c.fn);
+        if (c.d_res_q) {
+            TH_REQUIRE(c.d_res_scale, "%s: null d_res_scale with a residual in codes", c.fn);
+            TH_REQUIRE(c.cpitch_r % 16 == 0 && c.cpitch_r >= c.c_out, "%s: cpitch_r %d must be a multiple of 16 and at least c_out %d", c.fn, c.cpitch_r, c.c_out);
+            TH_REQUIRE(((uintptr_t)c.d_res_q & 15) == 0, "%s: the residual code pointer must be 16-byte aligned", c.fn);
+        }
+    }
+    const int res = !c.residual ? 0 : c.d_res ? 1 : 2;
     if (c.n == 0) return 0;
     const QcArgs a{c.d_qx, c.d_qw, c.d_pixsum, c.d_xscale, c.d_wparams, c.d_qb, c.d_bparams, c.d_y, c.d_yscale, c.d_qy, c.d_ypixsum, c.cpitch_y, p.win, c.cpitch, c.c_out,
-                   c.n * p.win.h_out * p.win.w_out, c.relu, p.tiles_n, c.affine ? c.d_affine : nullptr};
-    hipLaunchKernelGGL(qconv_kernel(p.nt, c.codes, c.pc, c.affine), dim3(p.grid), dim3(256), 0, c.ctx->stream, a);
+                   c.n * p.win.h_out * p.win.w_out, c.relu, p.tiles_n, c.affine ? c.d_affine : nullptr, res == 1 ? c.d_res : nullptr, res == 2 ? c.d_res_q : nullptr, res == 2 ? c.d_res_scale : nullptr,
+                   res == 2 ? c.cpitch_r : 0};
+    hipLaunchKernelGGL(qconv_kernel(p.nt, c.codes, c.pc, c.affine, res), dim3(p.grid), dim3(256), 0, c.ctx->stream, a);
     TH_LAUNCH_CHECK();
     return 0;
 }
@@ -434,6 +495,22 @@ int th_conv2d_q8q8_fwd_codes_affine(th_ctx *ctx, const int8_t *d_qx, int cpitch,
                                     const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
                                     int per_channel, const float *d_affine) {
     return qconv_run({"th_conv2d_q8q8_fwd_codes_affine", true, per_channel != 0, true, QC_SHARED, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum, d_affine});
+}
+
+int th_conv2d_q8q8_fwd_residual(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams, const int8_t *d_qb,
+                                const float *d_bparams, int relu, float *d_y, int per_channel, const float *d_affine, const float *d_res, const int8_t *d_res_q,
+                                int cpitch_r, const float *d_res_scale) {
+    return qconv_run({"th_conv2d_q8q8_fwd_residual", false, per_channel != 0, true, QC_SHARED, d_y, nullptr, nullptr, 0, nullptr, d_affine, true, d_res, d_res_q,
+                      cpitch_r, d_res_scale});
+}
+
+int th_conv2d_q8q8_fwd_codes_residual(th_ctx *ctx, const int8_t *d_qx, int cpitch, const int *d_pixsum, const float *d_xscale, int n, int c_in, int h, int w,
+                                      const int8_t *d_qw, int c_out, int k_h, int k_w, int s_h, int s_w, int pad_h, int pad_w, const float *d_wparams,
+                                      const int8_t *d_qb, const float *d_bparams, int relu, const float *d_yscale, int8_t *d_qy, int cpitch_y, int *d_ypixsum,
+                                      int per_channel, const float *d_affine, const float *d_res, const int8_t *d_res_q, int cpitch_r, const float *d_res_scale) {
+    return qconv_run({"th_conv2d_q8q8_fwd_codes_residual", true, per_channel != 0, true, QC_SHARED, nullptr, d_yscale, d_qy, cpitch_y, d_ypixsum, d_affine, true,
+                      d_res, d_res_q, cpitch_r, d_res_scale});
 }
 #undef QC_SHARED
 

@@ -84,4 +84,11 @@ __device__ __forceinline__ float affine_value(float v, float a, float b, int rel
     return relu ? (y > 0.f ? y : 0.f) : y;
 }
 
+// The same with a skip connection's value r added behind the affine and in front of the ReLU, where th_bn_residual_fwd adds
+// it in the float model: one more add, rounded once.
+__device__ __forceinline__ float affine_residual_value(float v, float a, float b, float r, int relu) {
+    const float y = __fadd_rn(__fadd_rn(__fmul_rn(v, a), b), r);
+    return relu ? (y > 0.f ? y : 0.f) : y;
+}
+
 }  // namespace th
