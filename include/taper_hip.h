@@ -266,6 +266,11 @@ int th_mlp_tail(th_ctx *ctx, const float *d_x, const float *d_h, const float *d_
  * OPERAND wave (everything the gradient products need, requested meanwhile): 576 threads per workgroup, same bits.  on = 0: the 320-thread
  * launch whatever the shape -- the form tests and tools compare with.  Default 1. */
 int th_mlp_tail_set_split(th_ctx *ctx, int on);
+/* 1 where th_mlp_tail(ctx, ..) takes that split form.  There -- and only there -- a gradient whose fused update runs in the launch may go
+ * unstored: d_dw1 == NULL beside w1_fuse, d_db1 == NULL beside b1_fuse (b1 still trains; without b1_fuse a null d_db1 means what it always
+ * meant, no db1).  For a caller that drops the slot once the update has consumed the value (a Trainer step that ends in zero_grad()): the
+ * stores are a quarter of the launch's bytes.  Same p / m / v, loss, hit count, dW2, db2 and step log, bit for bit. */
+int th_mlp_tail_drops_grads(th_ctx *ctx, int batch, int in_features, int hidden);
 
 /* A three-layer classifier -- Linear + ReLU, Linear + ReLU, Linear, softmax cross-entropy (the tail of examples/train_mnist_cnn.rs:53-61
  * behind the global average pool; examples/train_mnist.rs:40-48 behind the images) -- forward AND backward in TWO launches: everything but

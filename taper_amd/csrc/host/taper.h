@@ -255,6 +255,9 @@ struct StepLogSink {
     // data parallel (Trainer-internal): the gradient launch of mlp_tail_cross_entropy / conv_chain_head_cross_entropy exchanges its sums
     // with this communicator's peers itself (th_mlp_tail_dp / th_wide_head_grads_dp) -- what its fused epilogues apply is the mean
     const class Communicator *exchange = nullptr;
+    // Trainer-internal: nothing behind the step's launches reads a gradient whose Adam update ran in a launch's epilogue -- no exchange, no
+    // shared parameter, and the step ends in zero_grad() -- so a launch that can leave such a gradient unstored may (mlp_tail_cross_entropy)
+    bool drop_applied_grads = false;
 };
 // Classifier head = last Linear + cross-entropy as ONE launch (th_linear_xent_head), with the
 // backward products for loss.backward() from the root computed in the same launch.  Trainer-internal:

@@ -403,6 +403,10 @@ void Trainer::enqueue_compute(const StepPlan &plan, float *d_xb, float *d_yb, si
     Tape::reset();
     StepLogSink sink{metrics_->d, (int64_t)metrics_cap_, state, (int64_t)batch, plan.fused_adam ? optimizer->d_tick() : nullptr,
                      plan.exchange ? comm.get() : nullptr};
+    // this function ends in zero_grad(), so a gradient an epilogue has applied is dead unless a communicator reads the gradient arena
+    // (reduce_grads, step_reduced, the in-launch exchange) or a second use of the parameter adds to the slot -- and a model with a shared
+    // parameter never takes this form: plan_step trains it layer by layer (has_shared_parameter)
+    sink.drop_applied_grads = plan.form == StepForm::MlpTail && plan.fused_adam && !comm;
     Adam *adam = optimizer.get();
     auto *seq = dynamic_cast<Sequential *>(model.get());
     Linear *const *L = plan.linear;

@@ -91,10 +91,22 @@ __device__ long long g_tail_prof_op[256][8];
         }                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                    \
     } while (0)
+// mlp_tail_split_kernel's true entry: a wall-clock read in front of any argument use (TAIL_ENTRY_READ, the kernel's first statement), kept
+// where the two stamping waves use no other slot -- slot 5 of the logit wave's table, slot 2 of the operand wave's (tools/prof_tail.py: `args`)
+#define TAIL_ENTRY_READ()                                                                     \
+    const long long t_entry_ = wall_clock64();                                                \
+    __builtin_amdgcn_sched_barrier(0)
+#define TAIL_STAMP_ENTRY()                                                                    \
+    do {                                                                                      \
+        if (threadIdx.x == 0 && blockIdx.x < 256) g_tail_prof_all[blockIdx.x][5] = t_entry_;  \
+        if (threadIdx.x == 256 && blockIdx.x < 256) g_tail_prof_op[blockIdx.x][2] = t_entry_; \
+    } while (0)
 __global__ void tail_prof_mark_kernel(int i) { g_tail_prof[0][i] = g_tail_prof[1][i] = wall_clock64(); }
 #else
 #define TAIL_STAMP(i) do { } while (0)
 #define TAIL_STAMP_OP(i) do { } while (0)
+#define TAIL_ENTRY_READ() do { } while (0)
+#define TAIL_STAMP_ENTRY() do { } while (0)
 #endif
 
 // (the step-log slot, step_log_slot() of step_log_dev.h: the lead head workgroup forms it in its prologue, under the operand loads)
@@ -524,7 +536,7 @@ template <int NW, bool SPLIT = false>
 __device__ __forceinline__ void tail_helper_wave(const TailArgs &a, bool head_role, bool lead, bool any_w, bool any_b, float *h_step,
                                                  const float (*sc)[36]) {
     const int lane = threadIdx.x & 63;
-    if constexpr (SPLIT) __syncthreads();   // mlp_tail_split_kernel's barrier 0 (W2's image is whole), at once: its logit waves wait for it
+    // (SPLIT: mlp_tail_split_kernel's helper has met barrier 0 in the kernel, in front of the argument fetch this function's first lines need)
     // the counter / learning rate of the workgroup's fused update: plain scalar loads (nobody writes the counter in this launch)
     float step = 0.f;
     if (head_role ? any_b : any_w) {
@@ -943,8 +955,27 @@ __global__ __launch_bounds__(64 * (NW + tail_helper_waves(KS, NW, DPNR))) void m
 // sum in wave order, the dW1 store, the fused Adam element from p / m / v words the wave requested itself (the logit wave right behind
 // the image's read-back, so they are in flight under its MFMAs and softmax).  The head role's finish stays on the operand waves.
 // Measured in profiles/mlp_tail_split.md and profiles/mlp_tail_pairs.md.
+// Its arguments are its own (profiles/mlp_tail_args.md): what a wave's FIRST round of loads and the role choice need -- five pointers and six
+// counts, sixteen dwords -- is the argument block's first 64-byte line, so a wave meets one cold scalar wait and then issues; everything
+// else (TailRest) lies behind it and is fetched under the vector loads in flight, where it is first used.  (As one TailArgs the kernel
+// forced 23 fields spread over five lines into SGPRs in front of its first load.)
+struct TailRest {
+    float *loss, *ncorrect, *dw1, *db1, *dw2, *db2;
+    float *metrics;
+    int64_t capacity;
+    int64_t *state;
+    int64_t advance;
+    AdamDev w1_adam, b1_adam;
+    const float *w1;                     // dX role (its 32-column groups are the dW1 role's: `groups`)
+    float *dx;
+};
+constexpr int kTailRestOffset = 5 * sizeof(float *) + 6 * sizeof(int);   // the leading scalars fill the first line exactly
+static_assert(kTailRestOffset == 64 && alignof(TailRest) == 8, "TailRest must begin the argument block's second 64-byte line");
+
 template <int KS, int TN, bool HAS_DX>
-__global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
+__global__ __launch_bounds__(576) void mlp_tail_split_kernel(const float *h, const float *w2, const float *targets, const float *b2,
+                                                             const float *x, int batch, int in_features, int c, int n_head, int n_dw, int groups,
+                                                             TailRest /* read through take_rest() */) {
     constexpr int NW = 4;
     static_assert(tail_helper_waves(KS, NW, 0) != 0, "the split form replaces exactly the instances that have the helper wave");
     constexpr unsigned HID = 16 * KS;
@@ -954,17 +985,44 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     __shared__ float rowv[NW][2][16];
     __shared__ float sc[NW][36];
     __shared__ float4 wimg[KS][64];                  // W2 as the logits' A operand, fetched once per workgroup: [k-slice][lane]
-    asm volatile("" ::"s"(a.x), "s"(a.h), "s"(a.w2), "s"(a.b2), "s"(a.targets), "s"(a.batch), "s"(a.in_f), "s"(a.c), "s"(a.dw1),
-                 "s"(a.db1), "s"(a.w1_adam.p), "s"(a.w1_adam.m), "s"(a.w1_adam.v), "s"(a.w1_adam.t), "s"(a.w1_adam.lr),
-                 "s"(a.b1_adam.p), "s"(a.b1_adam.t), "s"(a.b1_adam.lr), "s"(a.n_dw), "s"(a.n_head), "s"(a.groups), "s"(a.metrics),
-                 "s"(a.state));
+    TAIL_ENTRY_READ();
+    // ONE batch of scalar loads for the leading line (left alone the compiler sinks each count's s_load into the block that first uses it)
+    asm volatile("" ::"s"(h), "s"(w2), "s"(targets), "s"(b2), "s"(x), "s"(batch), "s"(in_features), "s"(c), "s"(n_head), "s"(n_dw), "s"(groups));
+    // the body speaks of its arguments as the other kernels of this file do (the fields nobody reads here cost nothing)
+    static_assert(TN == 2, "the dX role's 32-column groups are the dW1 role's");
+    TailArgs a{};
+    a.x = x; a.h = h; a.w2 = w2; a.b2 = b2; a.targets = targets;
+    a.batch = batch; a.in_f = in_features; a.hid = HID; a.c = c;
+    a.n_dw = n_dw; a.n_head = n_head; a.tiles_m = KS; a.groups = a.xgroups = groups;
+    // ... and takes the rest of the block where a wave calls this, behind its first round of loads: a kernel argument read as such is
+    // an invariant load, which the compiler hoists to the roles' common entry -- a second cold wait in front of every wave's first load
+    bool any_w = false, any_b = false;
+    auto take_rest = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        auto *r = reinterpret_cast<const __attribute__((address_space(4))) TailRest *>(
+            (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + kTailRestOffset);
+        asm volatile("" : "+s"(r));
+        a.loss = r->loss; a.ncorrect = r->ncorrect; a.dw1 = r->dw1; a.db1 = r->db1; a.dw2 = r->dw2; a.db2 = r->db2;
+        a.metrics = r->metrics; a.capacity = r->capacity; a.state = r->state; a.advance = r->advance;
+        a.w1_adam.p = r->w1_adam.p; a.w1_adam.m = r->w1_adam.m; a.w1_adam.v = r->w1_adam.v; a.w1_adam.t = r->w1_adam.t; a.w1_adam.lr = r->w1_adam.lr;
+        a.w1_adam.beta1 = r->w1_adam.beta1; a.w1_adam.beta2 = r->w1_adam.beta2; a.w1_adam.eps = r->w1_adam.eps; a.w1_adam.wd = r->w1_adam.wd;
+        a.b1_adam.p = r->b1_adam.p; a.b1_adam.m = r->b1_adam.m; a.b1_adam.v = r->b1_adam.v; a.b1_adam.t = r->b1_adam.t; a.b1_adam.lr = r->b1_adam.lr;
+        a.b1_adam.beta1 = r->b1_adam.beta1; a.b1_adam.beta2 = r->b1_adam.beta2; a.b1_adam.eps = r->b1_adam.eps; a.b1_adam.wd = r->b1_adam.wd;
+        a.w1 = r->w1; a.dx = r->dx;
+        any_w = a.w1_adam.p != nullptr;
+        any_b = a.b1_adam.p != nullptr;   // (with or without a slot for db1: mlp_tail_launch)
+    };
     const int t = threadIdx.x, lane = t & 63, r16 = lane & 15, g4 = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int bid = blockIdx.x;
     TAIL_STAMP(0);
     TAIL_STAMP_OP(0);
+    TAIL_STAMP_ENTRY();
     if (HAS_DX && bid >= a.n_head + a.n_dw) {
-        if (wave < NW) tail_dx_role<KS, NW>(a, bid - a.n_head - a.n_dw);   // (no barriers in this role: operand waves and helper just leave)
+        if (wave < NW) {   // (no barriers in this role: operand waves and helper just leave)
+            take_rest();   // (W1 and dX: first used behind the softmax)
+            tail_dx_role<KS, NW>(a, bid - a.n_head - a.n_dw);
+        }
         return;
     }
     const bool head_role = bid < a.n_head;
@@ -982,8 +1040,9 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     const int C = a.c, B = a.batch;
     const unsigned in_f = (unsigned)a.in_f;
     const bool lead = head_role && tile_m == 0;
-    const bool any_w = a.w1_adam.p != nullptr, any_b = a.db1 && a.b1_adam.p != nullptr;
     if (wave == 2 * NW) {
+        __syncthreads();   // barrier 0 (W2's image is whole), at once: the logit waves wait for it
+        take_rest();
         tail_helper_wave<NW, true>(a, head_role, lead, any_w, any_b, &h_step, sc);
         return;
     }
@@ -993,7 +1052,6 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
     // dW1 role: the PAIR finishes the block, one 16-column tile per wave -- operand wave 4 + e element e of every lane's C/D quad (row
     // 4 g4 + e of the tile) in tile 0, logit wave e the same element in tile 1; each requests the p / m / v word it finishes itself.
     // (Three inlined copies -- operand wave, logit wave, logit wave without rows: paths that join again share their waits, see below)
-    static_assert(TN == 2, "one tile per wave of a pair");
     auto pair_offset = [&](int tn) { return ((tile_m * 16 + g4 * 4 + j) * in_f + grp * 16 * TN + r16) * 4u + tn * 64; };
     // behind barrier 2: the deterministic cross-wave sum of tile tn, element j (+ fused Adam, optim.rs:99-110)
     auto finish_tile = [&](int tn, unsigned e_off, float e_p, float e_m, float e_v) __attribute__((always_inline)) {
@@ -1001,7 +1059,8 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
         float out = red[0][tn][lane][j];
 #pragma unroll
         for (int w = 1; w < NW; ++w) out += red[w][tn][lane][j];
-        *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off) = out;
+        // (no slot: the caller drops the gradient once the update below has consumed it -- workgroup-uniform)
+        if (a.dw1) *reinterpret_cast<float *>(reinterpret_cast<char *>(a.dw1) + e_off) = out;
         if (any_w) {
             const AdamDev &ad = a.w1_adam;
             const AdamMV x = adam_moments(ad, e_p, e_m, e_v, out);
@@ -1028,6 +1087,7 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
                 if (q * NW + j < KS) wimg[q * NW + j][lane] = wsl[q];
         };
         if (!rows_here) {   // (a path of its own to its end: behind a merge, the wait for the slices is a wait for every load of the longer path)
+            take_rest();
             put_slices();
             __syncthreads();                         // barrier 0
             __syncthreads();                         // barrier 1
@@ -1052,6 +1112,7 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
                 for (int s = 0; s < 4; ++s) b2v[s] = ldg_b(a.b2, (unsigned)min(g4 * 4 + s, C - 1) * 4u);
             }
             TAIL_STAMP(1);
+            take_rest();   // (first used behind barrier 0: the fused update's pointers)
             const unsigned e_off = pair_offset(1);
             put_slices();
             __syncthreads();                         // barrier 0: the image is whole
@@ -1145,6 +1206,7 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
                 for (int s = 0; s < 4; ++s) xv[tn][s] = ldg_b(a.x, x_off + s * in_f * 4u + tn * 64);
             }
         }
+        take_rest();
         // epilogue operands of tile 0 (tile 1's are its logit wave's)
         const unsigned e_off = pair_offset(0);
         float e_p = 0.f, e_m = 0.f, e_v = 0.f;
@@ -1189,6 +1251,7 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) hm[s] = ldg_b(a.h, hm_off + s * HID * 4);
     }
+    take_rest();
     const int te = t - 64 * NW;                      // thread among the operand waves: who finishes what, as thread t of the 320-thread form
     const unsigned b1_off = (tile_m * 16 + (te & 15)) * 4u;
     float bp_ = 0.f, bm_ = 0.f, bv_ = 0.f;
@@ -1245,12 +1308,12 @@ __global__ __launch_bounds__(576) void mlp_tail_split_kernel(TailArgs a) {
         for (int w = 1; w < NW; ++w) sum += red[w][0][lane][j];
         if (cls < C) a.dw2[cls * HID + hcol] = sum;
     }
-    if (a.db1 && te < 16) {
+    if ((a.db1 || any_b) && te < 16) {
         float out = sc[0][te];
 #pragma unroll
         for (int w = 1; w < NW; ++w) out += sc[w][te];
         const int ix = tile_m * 16 + te;
-        a.db1[ix] = out;
+        if (a.db1) a.db1[ix] = out;   // (no slot: as for dW1)
         if (any_b) {
             const AdamDev &ad = a.b1_adam;
             const AdamPMV x = adam_next(ad, bp_, bm_, bv_, out, b_step);
@@ -1315,12 +1378,25 @@ extern "C" int th_mlp_tail_dp_supported(const th_comm *comm, th_ctx *ctx, int ba
     return 1;
 }
 
+// the launches that take the split form -- whole tiles, one chunk, an instance with a helper wave -- unless the context asks for the
+// 320-thread one (th_mlp_tail_set_split).  Only this form tests its gradient slots: there d_dw1 / d_db1 may be null beside a fused update
+static bool tail_split_form(const th_ctx *ctx, int batch, int in_features, int hidden) {
+    return tail_whole_tiles(batch, in_features, hidden) && batch <= 64 && tail_helper_waves(hidden / 16, 4, 0) != 0 && ctx->tail_split;
+}
+extern "C" int th_mlp_tail_drops_grads(th_ctx *ctx, int batch, int in_features, int hidden) {
+    return ctx && tail_split_form(ctx, batch, in_features, hidden) ? 1 : 0;
+}
+
 // the split form of the instances with a helper wave (mlp_tail_split_kernel): 4 logit + 4 operand waves + the helper
 template <int KS, int TN>
 static void tail_launch_split(bool dx, int grid, hipStream_t stream, const TailArgs &a) {
     if constexpr (tail_helper_waves(KS, 4, 0) != 0) {
-        if (dx) hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, true>), dim3(grid), dim3(576), 0, stream, a);
-        else hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, false>), dim3(grid), dim3(576), 0, stream, a);
+        const TailRest rest{a.loss, a.ncorrect, a.dw1, a.db1, a.dw2, a.db2, a.metrics, a.capacity, a.state, a.advance,
+                            a.w1_adam, a.b1_adam, a.w1, a.dx};
+        if (dx) hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, true>), dim3(grid), dim3(576), 0, stream, a.h, a.w2, a.targets, a.b2, a.x,
+                                   a.batch, a.in_f, a.c, a.n_head, a.n_dw, a.groups, rest);
+        else hipLaunchKernelGGL((mlp_tail_split_kernel<KS, TN, false>), dim3(grid), dim3(576), 0, stream, a.h, a.w2, a.targets, a.b2, a.x,
+                                a.batch, a.in_f, a.c, a.n_head, a.n_dw, a.groups, rest);
     }
 }
 
@@ -1329,7 +1405,7 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
                            float *d_ncorrect, float *d_dw1, float *d_db1, float *d_dw2, float *d_db2, const float *d_w1, float *d_dx,
                            float *d_metrics, int64_t metrics_capacity, int64_t *d_state, int64_t advance,
                            const th_adam_fuse *w1_fuse, const th_adam_fuse *b1_fuse, int32_t *d_tick) {
-    TH_REQUIRE(ctx && d_x && d_h && d_w2 && d_targets && d_loss && d_dw1, "th_mlp_tail: null argument");
+    TH_REQUIRE(ctx && d_x && d_h && d_w2 && d_targets && d_loss, "th_mlp_tail: null argument");
     TH_REQUIRE(th_mlp_tail_supported(batch, in_features, hidden, classes, 0),
                "th_mlp_tail: needs batch <= 512, hidden <= 256 and a multiple of 4, classes <= 16 (got %d, %d, %d)", batch, hidden, classes);
     TH_REQUIRE(!d_dx || (d_w1 && tail_whole_tiles(batch, in_features, hidden)),
@@ -1337,7 +1413,10 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
     TH_REQUIRE(!d_dx || !(w1_fuse && w1_fuse->d_p), "th_mlp_tail: with d_dx the launch reads W1, its update must be deferred (th_adam_slice)");
     TH_REQUIRE((((uintptr_t)d_h | (uintptr_t)d_w2) & 15) == 0, "th_mlp_tail: d_h and d_w2 must be 16-byte aligned");
     TH_REQUIRE_STEP_LOG("th_mlp_tail");
-    TH_REQUIRE(!(b1_fuse && b1_fuse->d_p) || d_db1, "th_mlp_tail: fused b1 update needs d_db1");
+    // a gradient whose fused update runs in this launch may go unstored (a caller that drops it afterwards): the split form only
+    const bool drop_ok = !comm && th_mlp_tail_drops_grads(ctx, batch, in_features, hidden);
+    TH_REQUIRE(d_dw1 || (drop_ok && w1_fuse && w1_fuse->d_p), "th_mlp_tail: d_dw1 may be null only with w1_fuse, where th_mlp_tail_drops_grads");
+    TH_REQUIRE(!(b1_fuse && b1_fuse->d_p) || d_db1 || drop_ok, "th_mlp_tail: fused b1 update needs d_db1 (null only where th_mlp_tail_drops_grads)");
     constexpr int TN = 2;   // input tiles per dW1 workgroup
     TailArgs a{};
     a.x = d_x; a.h = d_h; a.w2 = d_w2; a.b2 = d_b2; a.targets = d_targets;
@@ -1373,7 +1452,7 @@ static int mlp_tail_launch(th_comm *comm, th_ctx *ctx, const float *d_x, const f
         return 0;
     }
     // ... and of its 4-wave instances up to hidden 128, the split form unless the context asks for the 320-thread one (th_mlp_tail_set_split)
-    const bool split = exact && nw == 4 && tail_helper_waves(hidden / 16, nw, 0) != 0 && ctx->tail_split;
+    const bool split = tail_split_form(ctx, batch, in_features, hidden);
 #define TH_TAIL_LAUNCH(KS)                                                                                            \
     do {                                                                                                              \
         if (split) tail_launch_split<KS, TN>(d_dx != nullptr, grid, ctx->stream, a);                                  \

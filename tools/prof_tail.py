@@ -27,7 +27,9 @@ above) stamps TWO waves per workgroup: lane 0 of logit wave 0 and lane 0 of oper
   lg_sync   logit wave: stamp 6 - 4 (barrier 1, then at barrier 2 for the operand waves)
   lg_behind logit wave: stamp 2 - 6 (dW1 workgroups: wave-ordered sums, stores, fused Adam of tile 1; 0 where it finishes nothing)
   parked    logit wave's stamp 4 from the earlier stamp 0 of the two waves (entry -> dlogits parked)
-(lg_sync / lg_behind only from a build that stamps them.)
+  lg_args / op_args                    stamp 0 - the wave's true entry (a wall-clock read in front of any argument use): the argument fetch
+  lg_entry_issued / op_entry_issued    stamp 1 - the true entry (entry -> the last of the wave's loads requested)
+(lg_sync / lg_behind, and the four columns from the true entry, only from a build that stamps them.)
 body / end are the workgroup's stamp 7 -- the latest of its logit wave's, its operand wave's and, in the lead, the helper's -- from the
 earlier stamp 0 of the two waves.
 
@@ -114,6 +116,8 @@ def split_row(s, o):
         s = s.copy()
         s[:, 2] = own_end
         cols += [("lg_sync", s, 6, 4), ("lg_behind", s, 2, 6)]
+    if s[:, 5].any() and o[:, 2].any():   # a build that stamps the kernel's true entry (slot 5 of the logit wave's table, slot 2 of the operand wave's)
+        cols += [("lg_args", s, 0, 5), ("lg_entry_issued", s, 1, 5), ("op_args", o, 0, 2), ("op_entry_issued", o, 1, 2)]
     for name, tab, hi, lo in cols:
         d = tab[:, hi] - tab[:, lo]
         row.update({f"lead_{name}": d[0], f"head_{name}": np.median(d[1:N_HEAD]), f"dw_{name}": np.median(d[dw])})
